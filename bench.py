@@ -11,10 +11,11 @@ Default workload `c3` = the configuration BASELINE.json's metric is quoted on, N
   (default: sub-groups of 2 + 2 + 1 on three HIP streams).
   A "step" is one lock-step step: every fold model that still has a batch takes one optimisation step on it (zero-grad,
   forward, Cox partial likelihood on the labelled patients + gate entropy, backward, clip, Adam -- one replayed HIP graph per
-  sub-group).  The timed region is WHOLE EPOCHS of the 5-fold job (135 steps each: 134 full batches + the ragged tail of every
-  fold, entropy-only batches included) -- at least one epoch, more if --steps asks for more; `value` = training patients
-  processed / wall time.  The cohort is resident in HBM before the timed region; each step's batches are gathered
-  device-to-device by one launch fed by one small index copy.  `--h2d` adds the host-resident variant.
+  sub-group).  The timed region is exactly --steps lock-step steps of the 5-fold job, epoch after epoch (135 steps per epoch:
+  134 full batches + the ragged tail of every fold, entropy-only batches included; default: one whole epoch), after whole
+  warm-up epochs; `value` = training patients processed / wall time.  The cohort is resident in HBM before the timed region;
+  each step's batches are gathered device-to-device by one launch fed by one small index copy.  `--full --h2d` adds the
+  host-resident variant.
 
 Other workloads: `--workload c2` (BASELINE configs[1]: MultiModalSurvivalNet, 109 complete patients, fold models in flight
 configurable -- round 1's headline), `--workload c5` (BASELINE config 5: RNA-seq-only model, batch 2048).
@@ -28,11 +29,22 @@ is fixed, at N = 4 the ranks hold 2/1/1/1 fold models, at N = 8 three ranks idle
 repetition of the 5-fold CV, per-GPU work fixed: weak scaling) is reported beside it as `repeated_kfold_patients_per_s`.
 `--mode ddp` = BASELINE config 4's data-parallel step (one model, global batch N*B, gradient all-reduce over RCCL).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run sets up, warms up, times the steps and prints that
+line; `--full` adds the side legs (c3: single chain, validation, host-resident epoch, 2 x 10 fold models, the repeated K-fold at
+N > 1) and
   "roofline":     dominant kernel family, algorithmic FLOPs / measured average launch duration vs the fp32 MFMA peak
   "cpu_baseline": the CPU oracle (torch fp32 restatement of the same model/loop) timed on this box's host cores.
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computes in its last step, as DIR/<name>.npy (rank 0's
+models): that step is run once more on the same batches through the same entry point, from the seeded initial state of the models
+(a trained state after hundreds of steps is not reproducible: fp32 atomics, DESIGN.md "Determinism"), and per model its loss (and
+gate entropy), a fixed seeded sample of the raw weight gradient and of the parameters it produced, and the float buffers are
+written; then the trained state is put back.  The inputs are seeded: the same arguments give the same inputs, and the same
+outputs to rounding, on every run.  The gradient sample is what sees the backward's magnitudes: after a first Adam step from zero
+moments each weight has moved by about lr * sign(gradient).  Errors that only show after more than one step are not seen (see
+dump_outputs).
 """
 import argparse
+import itertools
 import json
 import math
 import os
@@ -308,6 +320,66 @@ def cpu_baseline_final(cohort, train_idx, steps, B):
                 sample=f"{steps} training steps (batch {B}) of the torch-fp32 CPU oracle after 1 warm-up step, {dt:.1f} s")
 
 
+# ---- --dump-outputs: what the timed steps computed ----------------------------------------------------------------------------
+# The fused steps accumulate weight gradients with fp32 atomics (DESIGN.md "Determinism"): one step agrees run to run to rounding, but
+# a training trajectory of hundreds of steps drifts apart.  So the dump is the timed path's LAST step recomputed from a fixed state:
+# after the timed steps the models are set back to their seeded initial state, that step runs once more on the same batches through
+# the same entry point (same sub-groups), what it computed is written, and the trained state is put back.
+# What the dump can tell apart: the forward (losses; BatchNorm running statistics = buffers), the backward (the raw weight gradient,
+# magnitudes included: grads_sample) and the direction of the optimiser update (params_sample -- a first Adam step from zero moments
+# moves every weight by about lr * sign(gradient), so the parameters alone do NOT see gradient magnitudes).  What it cannot: anything
+# that only shows after more than one step from the initial state (Adam's moment accumulation and bias correction past step 1, the
+# trained trajectory itself).
+def save_state(engines):
+    """Everything a training step reads and writes of each engine (as SurvivalEngine's own roll-back around graph capture)."""
+    with torch.no_grad():
+        return [[e.flat.clone(), e.m.clone(), e.v.clone(), e.step_count.clone(), e.rng.clone(), e.acc.clone(),
+                 [b.clone() for b in e.model.buffers()]] for e in engines]
+
+
+def load_state(engines, state):
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for e, st in zip(engines, state):
+            e.flat.copy_(st[0]); e.m.copy_(st[1]); e.v.copy_(st[2]); e.step_count.copy_(st[3]); e.rng.copy_(st[4]); e.acc.copy_(st[5])
+            for b, b0 in zip(e.model.buffers(), st[6]):
+                b.copy_(b0)
+            e.sync_packs()          # the weights changed outside the fused step: rebuild the derived conv2 packs
+    torch.cuda.synchronize()
+
+
+DUMP_FLOATS = 6 << 20            # at most 24 MB each of parameter and gradient samples in all
+DUMP_PER_MODEL = 1 << 20
+
+
+def dump_outputs(out_dir, engines, losses):
+    """The replayed last step's results: `losses` ([n_models][k], float64) -> losses.npy; every model's parameters after the step and
+    the step's raw weight gradient (the engine's gradient buffer, before clipping and weight decay; the next step zeroes it), both
+    flattened in torch order and sampled at one fixed seeded set of positions (all of them when few enough) -> params_sample.npy and
+    grads_sample.npy [n_models][S] float32, those positions -> params_sample_index.npy; the float buffers (BatchNorm running
+    statistics), whole -> buffers.npy [n_models][nb]."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()            # (the step ran on worker streams)
+    with torch.no_grad():
+        params = [torch.cat([p.detach().reshape(-1).float() for p in e.model.parameters()]) for e in engines]
+        grads = [torch.cat([g.reshape(-1).float() for g in e.gviews]) for e in engines]
+        bufs = [torch.cat([b.detach().reshape(-1).float() for b in e.model.buffers() if b.is_floating_point()] or [torch.zeros(0)]).cpu()
+                for e in engines]
+    n = params[0].numel()
+    if any(t.numel() != n for t in params + grads):
+        raise ValueError("dump_outputs: models of one shape expected")
+    S = min(n, DUMP_PER_MODEL, DUMP_FLOATS // len(params))
+    idx = np.arange(n) if S == n else np.sort(np.random.default_rng(0).permutation(n)[:S])
+    it = torch.as_tensor(idx, device=params[0].device)
+    np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, dtype=np.float64))
+    np.save(os.path.join(out_dir, "params_sample.npy"), np.stack([t[it].cpu().numpy() for t in params]).astype(np.float32))
+    np.save(os.path.join(out_dir, "grads_sample.npy"), np.stack([t[it].cpu().numpy() for t in grads]).astype(np.float32))
+    np.save(os.path.join(out_dir, "params_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "buffers.npy"), np.stack([t.numpy() for t in bufs]).astype(np.float32))
+
+
 # ---- workload c3: BASELINE config 3 (the metric's configuration) -------------------------------------------------------------
 def run_config3(args, world, rank, dev):
     import numpy as np
@@ -337,6 +409,7 @@ def run_config3(args, world, rank, dev):
         torch.manual_seed(42 + k)
         ms.append(models.PartialModalityNet(rna_dim=5005).to(dev).train())
     group = FoldGroupEngine(ms, lr=1e-4, weight_decay=1e-4, adamw=False, gate_entropy_weight=0.01)
+    init_state = save_state(group.engines) if args.dump_outputs else None      # the seeded initial state, before any step
     conc = args.lockstep_streams
     steps_per_epoch = max(len(l) for l in train_loaders)
     patients_per_epoch = sum(len(t) for t in train_sets)
@@ -359,18 +432,41 @@ def run_config3(args, world, rank, dev):
     n_warm = max(1, math.ceil(args.warmup / steps_per_epoch))       # whole epochs: every sub-group / ragged-tail graph gets captured
     for _ in range(n_warm):
         epoch(mine)
-    n_ep = max(1, math.ceil(args.steps / steps_per_epoch))
-    last = []
+    n_steps = steps_per_epoch if args.steps is None else args.steps
+    last, last_batch = [], {}
 
-    def run_epochs():
-        for _ in range(n_ep):
-            last[:] = epoch(mine)
-    dt, _ = timed(run_epochs)
-    value = n_ep * patients_per_epoch / dt          # the whole job's training patients (all folds, all ranks) per second
+    def keep_last(it, g):
+        for b in it:
+            last_batch[g] = b
+            yield b
+
+    def run_steps():
+        """exactly n_steps lock-step steps: whole epochs, then the first steps of one more epoch (each a fresh shuffle)"""
+        left = n_steps
+        while left > 0:
+            k = min(left, steps_per_epoch)
+            last[:] = epoch(mine, [keep_last(itertools.islice(l, k), g) for g, l in enumerate(train_loaders)])
+            left -= k
+    dt, _ = timed(run_steps)
+    q, r = divmod(n_steps, steps_per_epoch)
+    patients_timed = q * patients_per_epoch + sum(min(r * B, len(t)) for t in train_sets)
+    value = patients_timed / dt                     # the whole job's training patients (all folds, all ranks) per second
+    if args.dump_outputs:
+        k_last = (n_steps - 1) % steps_per_epoch + 1                    # position of the last timed step in its epoch
+        took = [len(train_loaders[g]) >= k_last for g in mine]           # the fold models that took a batch in it
+        trained = save_state(group.engines)
+        load_state(group.engines, init_state)
+        # all of this rank's folds as members (an exhausted one with no batch), so that the sub-groups are those of the timed step
+        res = train_epoch_lockstep(group, [[last_batch[g]] if t else [] for g, t in zip(mine, took)], "partial", members=mine,
+                                   concurrent=conc)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, [group.engines[g] for g, t in zip(mine, took) if t],
+                         [[float(a), float(b)] for (a, b), t in zip(res, took) if t])
+        load_state(group.engines, trained)
     if args.timed_only:
         if rank == 0:
-            print(f"timed-only: {value:.1f} patients/s, {dt / (n_ep * steps_per_epoch) * 1e3:.3f} ms per lock-step step, "
-                  f"{dt / n_ep:.3f} s per epoch", flush=True)
+            print(f"timed-only: {value:.1f} patients/s, {dt / n_steps * 1e3:.3f} ms per lock-step step, "
+                  f"{dt / n_steps * steps_per_epoch:.3f} s per epoch", flush=True)
         D.barrier()
         return
     from multimodal_survival_prediction_amd.training import subgroup_sizes
@@ -378,44 +474,52 @@ def run_config3(args, world, rank, dev):
     import torch.distributed as tdist
     backend = tdist.get_backend() if tdist.is_initialized() else None
 
-    # side leg at N > 1: repeated K-fold (rank r = repetition r of the 5-fold CV on the same cohort, KFold random_state 42 + r, all K
-    # fold models of this rank in lock-step): per-GPU work fixed as N grows = weak scaling, no collective
-    repeated = None
-    if world > 1:
-        rep_loaders = cv_loaders(42 + rank)[0]
-        epoch(None, rep_loaders)                                     # capture the full-group graphs
-        dtr, _ = timed(lambda: epoch(None, rep_loaders))
-        repeated = world * patients_per_epoch / dtr
-    # one fold model alone on the GPU (what a rank with a single fold of config 3 runs)
-    n1 = max(20, min(steps_per_epoch, args.steps // 3))
-    idx1 = train_loaders[0].idx
+    def side_legs():
+        """--full: the figures beside the metric, each timed on its own after the headline steps."""
+        # side leg at N > 1: repeated K-fold (rank r = repetition r of the 5-fold CV on the same cohort, KFold random_state 42 + r, all K
+        # fold models of this rank in lock-step): per-GPU work fixed as N grows = weak scaling, no collective
+        repeated = None
+        if world > 1:
+            rep_loaders = cv_loaders(42 + rank)[0]
+            epoch(None, rep_loaders)                                     # capture the full-group graphs
+            dtr, _ = timed(lambda: epoch(None, rep_loaders))
+            repeated = world * patients_per_epoch / dtr
+        # one fold model alone on the GPU (what a rank with a single fold of config 3 runs)
+        n1 = max(20, min(steps_per_epoch, n_steps // 3))
+        idx1 = train_loaders[0].idx
 
-    def chain(n):
-        for i in range(n):
-            group.train_step_indexed(train_loaders[0].view, idx1[(i % (len(idx1) // B)) * B:][:B].view(1, B), members=(0,),
-                                     skip_if_unusable=False)
-    chain(3)
-    dt1, _ = timed(lambda: chain(n1))
-    dt1 /= n1
-    # validation (reported separately): validate_lockstep over the K validation splits
-    validate_lockstep(group, val_loaders, "partial", dev, concurrent=args.validation_streams)
-    dtv, val = timed(lambda: validate_lockstep(group, val_loaders, "partial", dev, concurrent=args.validation_streams))
-    n_val = sum(len(l.idx) for l in val_loaders)
-    for e_ in group.engines:
-        e_.model.train()
-    # host-resident variant (the reference moves every batch host -> device, final_multimodal.py:244-247)
-    h2d = run_h2d_epoch(args, group, cohort_cpu, train_sets, B, dev, timed, conc) if args.h2d else None
-    # the same kernels with the chip filled: 2 concurrent groups x 10 lock-step fold models (four cross-validations in flight)
-    many = None
-    if args.many_folds:
-        many = run_many(args, cohort, train_sets, B, dev, timed, models, FoldGroupEngine)
+        def chain(n):
+            for i in range(n):
+                group.train_step_indexed(train_loaders[0].view, idx1[(i % (len(idx1) // B)) * B:][:B].view(1, B), members=(0,),
+                                         skip_if_unusable=False)
+        chain(3)
+        dt1, _ = timed(lambda: chain(n1))
+        dt1 /= n1
+        # validation (reported separately, SURVEY 8d): validate_lockstep over the K validation splits
+        validate_lockstep(group, val_loaders, "partial", dev, concurrent=args.validation_streams)
+        dtv, val = timed(lambda: validate_lockstep(group, val_loaders, "partial", dev, concurrent=args.validation_streams))
+        n_val = sum(len(l.idx) for l in val_loaders)
+        for e_ in group.engines:
+            e_.model.train()
+        # host-resident variant (SURVEY 8d: the reference moves every batch host -> device, final_multimodal.py:244-247)
+        h2d = run_h2d_epoch(args, group, cohort_cpu, train_sets, B, dev, timed, conc) if args.h2d else None
+        # the same kernels with the chip filled: 2 concurrent groups x 10 lock-step fold models (four cross-validations in flight)
+        many = None
+        if args.many_folds:
+            many = run_many(args, cohort, train_sets, B, dev, timed, models, FoldGroupEngine)
+        return {"repeated_kfold_patients_per_s": repeated,
+                "single_chain_patients_per_s": B / dt1, "single_chain_ms_per_step": dt1 * 1e3,
+                "validation_patients_per_s": n_val / dtv,
+                "h2d": h2d, "many_folds": many,
+                "val_loss_cindex": [[float(a), float(b)] for a, b in val]}
+    side = side_legs() if args.full else None
 
     if rank == 0:
         out = {
             "metric": "patients/sec per epoch (training epoch of the K-fold job: fwd + Cox + gate entropy + bwd + clip + Adam; HBM-resident "
                       "cohort, batches gathered on the device inside the timed region -- the same epoch fed from pinned host memory over PCIe: config.h2d)",
-            "value": value, "unit": "patients/s", "n_gpus": world, "steps": n_ep * steps_per_epoch,
-            "warmup": n_warm * steps_per_epoch, "ms_per_step": dt / (n_ep * steps_per_epoch) * 1e3, "higher_is_better": True,
+            "value": value, "unit": "patients/s", "n_gpus": world, "steps": n_steps,
+            "warmup": n_warm * steps_per_epoch, "ms_per_step": dt / n_steps * 1e3, "higher_is_better": True,
             "scaling": None if world == 1 else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {
                 "workload": ("BASELINE config 3, N=1 leg" if world == 1 else "BASELINE config 3, one 5-fold CV sharded over %d GPUs" % world) +
@@ -423,32 +527,34 @@ def run_config3(args, world, rank, dev):
                             "(%d CT / %d RNA-seq / %d clinical / %d labelled), PartialModalityNet (DenseNet121-3D CT %dx%dx%d + RNA-seq 5005 + "
                             "clinical, softmax gate + 0.01 x gate entropy), %d-fold CV over the labelled patients with all %d unlabelled "
                             "patients in every training split (%d training patients per epoch over the folds), batch %d, Adam lr 1e-4 wd "
-                            "1e-4, clip 1.0; %d whole epoch(s) timed, ragged tails and entropy-only batches included"
+                            "1e-4, clip 1.0; %d lock-step step(s) timed (%.3g epochs), ragged tails and entropy-only batches included"
                             % (args.patients, int(cohort_cpu["mask"][:, 0].sum()), int(cohort_cpu["mask"][:, 1].sum()),
                                int(cohort_cpu["mask"][:, 2].sum()), len(survival), dims[0], dims[1], dims[2], K, len(non_survival),
-                               patients_per_epoch, B, n_ep),
+                               patients_per_epoch, B, n_steps, n_steps / steps_per_epoch),
                 "step": "one lock-step step of the K-fold job: every fold model takes one batch (<= %d x %d patients)" % (K, B),
-                "steps_requested": args.steps, "warmup_requested": args.warmup, "epochs_timed": n_ep, "steps_per_epoch": steps_per_epoch,
-                "train_patients_per_epoch": patients_per_epoch, "seconds_per_epoch": dt / n_ep,
+                "steps_requested": args.steps, "warmup_requested": args.warmup, "epochs_timed": n_steps / steps_per_epoch,
+                "steps_per_epoch": steps_per_epoch, "train_patients_per_epoch": patients_per_epoch, "train_patients_timed": patients_timed,
+                "seconds_per_epoch": dt / n_steps * steps_per_epoch,
                 "global_batch": K * B,
                 "parallelism": (f"1 GPU: the {K} fold models in lock-step as sub-groups of {'+'.join(map(str, sub_groups))} on "
                                 f"{len(sub_groups)} HIP stream(s), one step graph per sub-group" if world == 1 else
                                 f"kfold-shard x{world}: ONE {K}-fold CV, fold k on rank k mod {world} (rank 0 holds {len(mine)} fold model(s), "
                                 f"{max(0, world - K)} rank(s) idle), no data-path collective (torch.distributed backend {backend}); value = the "
-                                f"CV's training patients / max-over-ranks epoch time"),
+                                f"CV's training patients / max-over-ranks time of the timed steps"),
                 "fold_models_in_flight": K, "lockstep_streams": conc,
                 "rccl_ranks_seen": (tdist.get_world_size() if backend == "nccl" else 0),
-                "repeated_kfold_patients_per_s": repeated,
-                "single_chain_patients_per_s": B / dt1, "single_chain_ms_per_step": dt1 * 1e3,
-                "validation_patients_per_s": n_val / dtv,
-                "h2d": h2d, "many_folds": many,
                 "hip_graph": True, "bn": "per-model batch statistics", "cox": "per-batch risk sets, Efron ties = torchsurv's rule (identical to Breslow on the cohort's distinct times)",
                 "train_loss_last_epoch": [[float(a), float(b)] for a, b in last],
-                "val_loss_cindex": [[float(a), float(b)] for a, b in val]},
+                "train_loss_last_epoch_steps": (n_steps - 1) % steps_per_epoch + 1,       # the last pass of the timed steps: a partial
+                                                                                         # epoch unless --steps is a multiple of an epoch
+                "train_loss_what": "per fold model (Cox loss over usable batches, gate entropy), mean over the last pass of the timed "
+                                   "steps = train_loss_last_epoch_steps steps of its epoch"},
         }
-        out["roofline"] = roofline_block(B, dims, dev, sub_groups)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_partial(cohort_cpu, torch.as_tensor(train_sets[0]), args.cpu_steps, B)
+        if args.full:
+            out["config"].update(side)
+            out["roofline"] = roofline_block(B, dims, dev, sub_groups)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_partial(cohort_cpu, torch.as_tensor(train_sets[0]), args.cpu_steps, B)
         print(json.dumps(out), flush=True)
     D.barrier()
 
@@ -512,6 +618,7 @@ def run_config5(args, dev):
     torch.manual_seed(0)
     net = models.RNASeqSurvivalModel(input_dim=5005).to(dev).train()
     fo = FusedOptimizer(net, lr=1e-4, weight_decay=1e-3, adamw=True, max_norm=0.0)
+    init_state = save_state([fo.engine]) if args.dump_outputs else None
     rng = np.random.default_rng(0)
     rna = torch.tensor(rng.normal(0, 1, (B, 5005)).astype(np.float32), device=dev)
     t = torch.tensor((rng.exponential(1000, B) + 1 + np.arange(B) * 1e-3).astype(np.float32), device=dev)
@@ -527,6 +634,14 @@ def run_config5(args, dev):
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    mean_loss = fo.engine.epoch_stats()["sum_loss"] / (args.steps + max(args.warmup, 3))
+    if args.dump_outputs:                      # the step's batch is the same every step: replay it from the initial state
+        trained = save_state([fo.engine])
+        load_state([fo.engine], init_state)
+        fo.engine.reset_epoch_stats()
+        step()
+        dump_outputs(args.dump_outputs, [fo.engine], [[fo.engine.epoch_stats()["sum_loss"]]])
+        load_state([fo.engine], trained)
     if args.timed_only:
         print(f"timed-only (config 5): {B / dt:.1f} patients/s, {dt * 1e3:.3f} ms/step", flush=True)
         return
@@ -535,7 +650,10 @@ def run_config5(args, dev):
            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": f"BASELINE config 5: RNASeqSurvivalModel (5005-1024-512-256-1), batch {B}, Cox over the {B}-patient risk set, "
                                   "AdamW lr 1e-4 wd 1e-3", "global_batch": B, "parallelism": "single GPU, one step graph",
-                      "hip_graph": not args.no_graph, "mean_train_loss": fo.engine.epoch_stats()["sum_loss"] / (args.steps + max(args.warmup, 3))}}
+                      "hip_graph": not args.no_graph, "mean_train_loss": mean_loss}}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     P = fo.engine.plans[(B,)]
     q, lib = P.big_lin[True][0], _lib.load_library()
     P.big_stats.zero_()
@@ -607,6 +725,7 @@ def run_config2(args, world, rank, dev):
     from multimodal_survival_prediction_amd import ops as _ops
     streams = _ops.worker_streams(dev, F)
     gb = B * world if ddp else B                                  # patients per step handled by one model
+    init_state = save_state(engines) if args.dump_outputs else None
 
     def batch_of(m, k):
         order = orders[m]
@@ -652,6 +771,24 @@ def run_config2(args, world, rank, dev):
     if G > 1 and args.steps % (F * G):
         run(args.steps, F)                                        # the exact timed schedule once, untimed: captures the ragged tail's sub-group graph
     dt = timed(args.steps, F)
+    if args.dump_outputs:                      # the last launch of the timed schedule again, from the initial state (every rank: ddp)
+        u_last, left = -1, args.steps
+        while left > 0:
+            u_last += 1; m_last = min(G, left); left -= m_last
+        f = u_last % F
+        mine = engines[f * G:f * G + m_last]
+        trained, n_sync = save_state(engines), getattr(engines[0], "sync_collectives", None)
+        load_state(engines, init_state)
+        for e in mine:
+            e.reset_epoch_stats()
+        launch(u_last, F, m_last)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, mine,
+                         [[e.epoch_stats()["sum_loss"] / max(e.epoch_stats()["n_batches"], 1)] for e in mine])
+        load_state(engines, trained)
+        if n_sync is not None:
+            engines[0].sync_collectives = n_sync          # (the replay's collectives are not the timed steps')
     if args.timed_only:
         if rank == 0:
             print(f"timed-only: {world * args.steps * B / dt:.1f} patients/s, {dt / args.steps * 1e3:.3f} ms/step", flush=True)
@@ -679,9 +816,10 @@ def run_config2(args, world, rank, dev):
                        "concurrent_folds": F, "fold_group": G, "fold_models_in_flight": F * G,
                        "hip_graph": not args.no_graph, "mean_train_loss": stats["sum_loss"] / max(stats["n_batches"], 1)},
         }
-        out["roofline"] = roofline_block(B, dims, dev, (G,))
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_final(cohort_cpu, torch.as_tensor(folds[0][0]), args.cpu_steps, B)
+        if args.full:
+            out["roofline"] = roofline_block(B, dims, dev, (G,))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_final(cohort_cpu, torch.as_tensor(folds[0][0]), args.cpu_steps, B)
         print(json.dumps(out), flush=True)
     D.barrier()
 
@@ -738,7 +876,7 @@ def _spawn_ranks(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="c3: lock-step steps (rounded up to whole epochs, default one epoch); "
+    ap.add_argument("--steps", type=int, default=None, help="timed steps -- c3: lock-step steps of the K-fold job (default one epoch); "
                                                             "c2/c5: optimisation steps (default 240 / 200)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--batch", type=int, default=4)
@@ -753,12 +891,16 @@ def main():
                     help="c3: the folds step as this many lock-step sub-groups on as many HIP streams (default 3: 5 folds = 2 + 2 + 1; round 2 ran 3 + 2); "
                          "more than 3 need GPU_MAX_HW_QUEUES >= streams + 1 in the environment, else two streams share a hardware queue")
     ap.add_argument("--validation-streams", type=int, default=2, help="c3: sub-groups / streams of the validation pass")
-    ap.add_argument("--h2d", action="store_true", default=True, help="c3: also time the epoch with the cohort in pinned host memory")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the side legs of the workload, roofline, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computes (replayed from the seeded initial state) as DIR/<name>.npy")
+    ap.add_argument("--h2d", action="store_true", default=True, help="c3 --full: also time the epoch with the cohort in pinned host memory")
     ap.add_argument("--no-h2d", dest="h2d", action="store_false")
-    ap.add_argument("--many-folds", action="store_true", default=True, help="c3: also time 2 x 10 fold models in flight")
+    ap.add_argument("--many-folds", action="store_true", default=True, help="c3 --full: also time 2 x 10 fold models in flight")
     ap.add_argument("--no-many-folds", dest="many_folds", action="store_false")
-    ap.add_argument("--cpu-steps", type=int, default=6)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-steps", type=int, default=6, help="--full: batches of the CPU oracle's timed sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU oracle out")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--timed-only", action="store_true", help="profiling aid: stop after the timed region (no extra legs, no JSON)")
     ap.add_argument("--roofline-only", action="store_true",
@@ -814,9 +956,11 @@ def main():
                          "diagnostics may run on it, never a bench line")
     if args.mode == "ddp":
         args.workload = "c2"
-    dflt = {"c3": (1, 1), "c2": (240, 20), "c5": (200, 10)}[args.workload]
+    dflt = {"c3": (None, 1), "c2": (240, 20), "c5": (200, 10)}[args.workload]         # c3: None = one epoch
     args.steps = dflt[0] if args.steps is None else args.steps
     args.warmup = dflt[1] if args.warmup is None else args.warmup
+    if (args.steps is not None and args.steps < 1) or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.roofline_only:
         from multimodal_survival_prediction_amd.training import subgroup_sizes
         sub = (subgroup_sizes(args.folds, args.lockstep_streams) if args.workload == "c3"

@@ -1,6 +1,6 @@
 """BASELINE config 5: RNA-seq-only model (5005 -> 1024 -> 512 -> 256 -> 1), batch 2048, one full training step per replay
 (zero-grad, forward, O(B^2) Cox partial likelihood, backward, AdamW) as a captured HIP graph.  Profiling aid (tools/prof_c5.sh):
-prints one JSON line with the GPU rate only; the judged line with roofline and cpu_baseline is `python bench.py --workload c5`."""
+prints one JSON line with the GPU rate only; the judged line with roofline and cpu_baseline is `python bench.py --workload c5 --full`."""
 import argparse
 import json
 import os

@@ -1,7 +1,7 @@
 #!/bin/bash
 # concurrency analysis of the default bench (2 groups): in-situ kernel time per queue vs wall
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd /tmp; export TMPDIR=/tmp
-rm -rf /tmp/ov; rocprofv3 --kernel-trace --output-format csv -d /tmp/ov -- python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline "$@" > /tmp/ov.log 2>&1
+rm -rf /tmp/ov; rocprofv3 --kernel-trace --output-format csv -d /tmp/ov -- python3 $R/bench.py --steps 60 --warmup 10 --full --no-cpu-baseline "$@" > /tmp/ov.log 2>&1
 python3 - <<'PY'
 import csv,glob,collections
 f=glob.glob('/tmp/ov/*/*_kernel_trace.csv')[0]
