@@ -84,6 +84,11 @@ typedef struct MmsDnOpts {
     int trans_prepass;     /* transitions: 0 = AvgPool3d(relu(norm(x))) by its own launch into the workspace (mms_pool_act), the 1x1x1 convolution
                               and its weight gradient read that pooled operand; -1 = pooled while loading, inside both GEMMs (each of the N / 16-32
                               column tiles of a row tile re-reads and re-normalises the 8 source voxels: rounds 1-3) */
+    int fuse_layers;       /* dense block 3's forward with conv2 of layer l and conv1 of layer l + 1 in ONE launch (csrc/dn_c3s.hip; the conv1
+                              workgroups wait inside the launch for the conv2 ones): 0 = wherever the block runs the small-grid kernels
+                              (<= 128 rows, <= 4 models per launch, one statistic replica, no SyncBN / statistics hook, persist_b3 off),
+                              -1 = never.  A caller that may have more such launches in flight than the chip holds passes -1
+                              (ops.persistent_opts); a wait that times out raises the drivers' error word (mms_dn121_region "b4_err") */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.

@@ -9,109 +9,19 @@
 // four waves (16-channel groups dealt round robin, v_mfma_f32_16x16x4_f32, two accumulators each) and summed through LDS.  One memory round trip before the MFMAs, none between
 // them, no cross-workgroup hand-off; statistics as everywhere (fp64 column sums, one atomic pair per column and workgroup).
 #include "dn_ops.h"
+#include "dn_c1s.h"
 #include <stdlib.h>
 
 namespace {
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 // C1S_NP: operand pieces (float4) per thread and panel -- 16 at K <= 1024 (228 VGPRs), 8 at K <= 512 (156 VGPRs: such a wave still fits
-// on a SIMD that holds two waves of another stream's block-1 kernels, see mms_c3s_fwd)
+// on a SIMD that holds two waves of another stream's block-1 kernels, see mms_c3s_fwd).  The tile itself: dn_c1s.h (shared with the
+// fused block-3 launch of dn_c3s.hip).
 template <int C1S_NP>
 __global__ __launch_bounds__(256) void conv1s_fwd_kernel(const Grp<Conv1FwdP> grp) {
-    const Conv1FwdP& p = grp.p[blockIdx.z];
-    const float* __restrict__ x = p.x;                 // kernel arguments read once (dn_c3s.hip: left in the kernarg segment they are
-    const float* __restrict__ w = p.w;                 // re-read inside every predicated block)
-    const int M = p.M, K = p.K, N = p.N, ldx = p.ldx;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, h = lane >> 4;
-    const int m0 = blockIdx.x * 16, n0 = blockIdx.y * 16;
-    const int P = K + 4;                               // LDS row pitch (floats)
-    float* As = smem;                                  // [16][P]  relu(bn1(x)) panel
-    float* cmean = As + 16 * P;                        // [K] BatchNorm1 constants
-    float* csc = cmean + K;
-    float* cbeta = csc + K;
-
-    // ---- one batch of loads: the activation panel (clamped addresses, branch-free), this wave's weight fragments, the BatchNorm
-    // statistics / parameters.  The weights go straight into the MFMA register layout (lane (li, h), group g: W[n0 + li][16 g + 4 h ..
-    // + 3]) -- only the activation panel, which needs the BatchNorm transform, is staged: half the LDS of a two-panel layout, so a
-    // second workgroup -- or the other streams' workgroups -- fits beside this one on a CU (the step-ablation runs of
-    // profiles/r03_step_ablation.txt: the kernels with the largest LDS footprints cost the step the most per microsecond of their own).
-    const int kq = K >> 2, total = 16 * kq;            // float4 pieces of the panel
-    const int ng16 = K >> 4;
-    float4 ra[C1S_NP], rb[C1S_NP];
-#pragma unroll
-    for (int i = 0; i < C1S_NP; ++i) {
-        if (256 * i < total) {                         // workgroup-uniform
-            const int idx = tid + 256 * i, ic = idx < total ? idx : total - 1;
-            const int r = ic / kq, k4 = (ic - r * kq) * 4;
-            const int mr = m0 + r < M ? m0 + r : M - 1;
-            ra[i] = *(const float4*)(x + (size_t)mr * ldx + k4);
-        }
-    }
-    const float* wr = w + (size_t)(n0 + li < N ? n0 + li : N - 1) * K + 4 * h;
-#pragma unroll
-    for (int i = 0; i < C1S_NP; ++i) {
-        if (wave + 4 * i < ng16) rb[i] = *(const float4*)(wr + 16 * (wave + 4 * i));      // wave-uniform
-    }
-    bn_consts_to_lds<4>(p.bn, K, tid, cmean, csc, cbeta);
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < C1S_NP; ++i) {
-        if (256 * i < total) {
-            const int idx = tid + 256 * i;
-            if (idx < total) {
-                const int r = idx / kq, k4 = (idx - r * kq) * 4;
-                const float z = m0 + r < M ? 1.f : 0.f;
-                const float4 v = ra[i];
-                *(float4*)&As[r * P + k4] = make_float4(z * fmaxf(bn_apply(v.x, cmean[k4], csc[k4], cbeta[k4]), 0.f),
-                                                        z * fmaxf(bn_apply(v.y, cmean[k4 + 1], csc[k4 + 1], cbeta[k4 + 1]), 0.f),
-                                                        z * fmaxf(bn_apply(v.z, cmean[k4 + 2], csc[k4 + 2], cbeta[k4 + 2]), 0.f),
-                                                        z * fmaxf(bn_apply(v.w, cmean[k4 + 3], csc[k4 + 3], cbeta[k4 + 3]), 0.f));
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- the K range: 16-channel groups g = wave, wave + 4, ...; element e of lane (row, h) is k = 16 g + 4 h + e for both operands
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    const float* ar = As + li * P + 4 * h;
-    const float zb = n0 + li < N ? 1.f : 0.f;
-#pragma unroll
-    for (int i = 0; i < C1S_NP; i += 2) {
-        const int g = wave + 4 * i;
-        if (g < ng16) {                                // wave-uniform
-            const bool two = g + 4 < ng16;
-            const float4 a0 = *(const float4*)(ar + 16 * g);
-            const float4 a1 = two ? *(const float4*)(ar + 16 * (g + 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 b0 = rb[i];
-            const float4 b1 = two ? rb[i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-            acc0 = MFMA16(a0.x, zb * b0.x, acc0); acc1 = MFMA16(a1.x, zb * b1.x, acc1);
-            acc0 = MFMA16(a0.y, zb * b0.y, acc0); acc1 = MFMA16(a1.y, zb * b1.y, acc1);
-            acc0 = MFMA16(a0.z, zb * b0.z, acc0); acc1 = MFMA16(a1.z, zb * b1.z, acc1);
-            acc0 = MFMA16(a0.w, zb * b0.w, acc0); acc1 = MFMA16(a1.w, zb * b1.w, acc1);
-        }
-    }
-    __syncthreads();                                   // the panels are dead: Cs aliases them
-    float* Cs = smem;                                  // [4 waves][16][17]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Cs[(wave * 16 + 4 * h + r) * 17 + li] = acc0[r] + acc1[r];      // C/D: column = lane & 15, row = 4 (lane >> 4) + r
-    __syncthreads();
-    double* red = (double*)(smem + 4 * 16 * 17);       // [2][16][16] (offset 4352 bytes: 8-byte aligned)
-    const int r = tid >> 4, c = tid & 15, m = m0 + r, n = n0 + c;
-    const float v = (Cs[r * 17 + c] + Cs[(16 + r) * 17 + c]) + (Cs[(32 + r) * 17 + c] + Cs[(48 + r) * 17 + c]);
-    const bool ok = m < M && n < N;
-    if (ok) p.y[(size_t)m * p.ldy + n] = v;
-    if (p.osum == nullptr) return;
-    red[r * 16 + c] = ok ? (double)v : 0.0;
-    red[256 + r * 16 + c] = ok ? (double)v * v : 0.0;
-    __syncthreads();
-    if (tid < 16 && n0 + tid < N) {
-        double s = 0, q = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s += red[i * 16 + tid]; q += red[256 + i * 16 + tid]; }
-        atomicAdd(&stat_rep(p.osum, p.srep, p.sstride)[n0 + tid], s);
-        atomicAdd(&stat_rep(p.osumsq, p.srep, p.sstride)[n0 + tid], q);
-    }
+    conv1s_fwd_tile<C1S_NP, false>(grp.p[blockIdx.z], blockIdx.x, blockIdx.y, smem);
 }
 
 // ---- backward-data of the same layers when ONE workgroup can own every row of its channels (M <= 128: dense block 3 of 64x64x32

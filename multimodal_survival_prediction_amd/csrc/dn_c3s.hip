@@ -17,6 +17,7 @@
 //     (= conv input) channels, nothing to sum.  With few row tiles in the launch the output channels are split over blockIdx.y too (JN = 1).
 // Summation order is fixed: results are deterministic and independent of the group size.
 #include "dn_ops.h"
+#include "dn_c1s.h"
 #include <stdlib.h>
 
 namespace {
@@ -102,19 +103,17 @@ __device__ __forceinline__ void c3s_place(int& tile, int& half, int& model) {
 }
 
 // ---- forward: out[m][co] = sum_tap sum_cin relu(bn2(y1))[m + off(tap)][cin] * W[co][tap][cin] --------------------------------------
-template <int JN, int D, bool FRAG>
-__global__ __launch_bounds__(256) void conv3s_fwd_kernel(const Grp<Conv3FwdP> grp) {
+// One workgroup's tile.  PUB (the producers of the fused block-3 launch below): the slab columns are stored write-through and the
+// workgroup publishes them and its statistics on `flag` (dn_c1s.h hx_publish).
+template <int JN, int D, bool FRAG, bool PUB>
+__device__ __forceinline__ void conv3s_fwd_tile(const Conv3FwdP& p, int tile_, int half_, float* smem, unsigned* flag) {
     // every kernel argument the prologue needs, read ONCE into registers: left as references into the kernarg segment the compiler
     // re-loads them (s_load + wait) inside each predicated load below -- 30 serial scalar round trips, 3.3 us before the first MFMA
-    int tile_, half_, model_;
-    c3s_place(tile_, half_, model_);
-    const Conv3FwdP& p = grp.p[model_];
     const float* __restrict__ y1 = p.y1;
     const float* __restrict__ wp = p.wp;
     const int* __restrict__ coords = p.coords;
     const int M = p.M;
     const Dims3 g = p.g;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, h = lane >> 4;
     const int m0 = tile_ * C3S_TM, co0 = JN == 1 ? 16 * half_ : 0;
     const int W = g.W, HW = g.H * g.W, halo = HW + W + 1, nrows = C3S_TM + 2 * halo;
@@ -196,12 +195,17 @@ __global__ __launch_bounds__(256) void conv3s_fwd_kernel(const Grp<Conv3FwdP> gr
         const int r = rg * RPT + i, m = m0 + r;
         const float v = (Cs[r * CP + c] + Cs[(16 + r) * CP + c]) + (Cs[(32 + r) * CP + c] + Cs[(48 + r) * CP + c]);
         if (m < p.M) {
-            p.out[(size_t)m * p.ldo + co0 + c] = v;
+            if (PUB) pstore(&p.out[(size_t)m * p.ldo + co0 + c], v);
+            else p.out[(size_t)m * p.ldo + co0 + c] = v;
             s += v; q2 += (double)v * v;
         }
     }
     C3S_STAMP(4);
-    if (p.osum == nullptr) { C3S_TS_FLUSH(); return; }
+    if (p.osum == nullptr) {
+        if (PUB) hx_publish(flag);
+        C3S_TS_FLUSH();
+        return;
+    }
     red[rg * NC + c] = s; red[(NRG + rg) * NC + c] = q2;
     __syncthreads();
     if (tid < NC) {
@@ -212,7 +216,15 @@ __global__ __launch_bounds__(256) void conv3s_fwd_kernel(const Grp<Conv3FwdP> gr
         atomicAdd(&stat_rep(p.osumsq, p.srep, p.sstride)[co0 + tid], b);
     }
     C3S_STAMPW(5);
+    if (PUB) hx_publish(flag);
     C3S_TS_FLUSH();
+}
+template <int JN, int D, bool FRAG>
+__global__ __launch_bounds__(256) void conv3s_fwd_kernel(const Grp<Conv3FwdP> grp) {
+    int tile_, half_, model_;
+    c3s_place(tile_, half_, model_);
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    conv3s_fwd_tile<JN, D, FRAG, false>(grp.p[model_], tile_, half_, smem, nullptr);
 }
 
 // ---- backward-data: dbn2[m][cin] = [a2 > 0] * sum_tap sum_co dz[m - off(tap)][co] * W[cin][tap][co]; BatchNorm2-backward sums -------
@@ -351,7 +363,79 @@ int launch_bwd(const Conv3BwdDataP* pp, int ng, hipStream_t s) {
     return mms_check_launch();
 }
 
+// ---- dense block 3's forward with ONE launch boundary per layer: conv2 of layer l (producers: the one-tile form above, 16-row tiles x
+// two 16-column halves per model, ring 6, fragment-ordered weights) and conv1 of layer l + 1 (consumers: dn_c1s.h conv1s_fwd_tile,
+// 16 x 16 tiles of its 128 outputs) in one 1-D grid, the producers of every model first.  A consumer does everything that does not depend
+// on layer l's output -- its prologue loads and the MFMAs over the channels < K - 32 -- before it waits for its model's producers (all of
+// them: the 32 new channels' batch statistics span every row).  Each BatchNorm reduction keeps its launch boundary; only the boundary
+// between layers becomes a one-way in-launch wait.  Forward progress: the caller keeps the waiting workgroups of all its streams
+// co-resident with room for the producers (ops.persistent_opts); a wait that still times out raises the error word instead of hanging.
+struct C3C1FwdArgs {
+    Conv3FwdP c3[MMS_FUSE_MAXG];
+    Conv1FwdP c1[MMS_FUSE_MAXG];
+    unsigned* flag[MMS_FUSE_MAXG];
+    unsigned* err[MMS_FUSE_MAXG];
+    int ng, nprod, ctm, ctn;                   // models; producers per model; consumer tiles per model (rows x columns)
+};
+// Two waves per SIMD (256 VGPRs, no AGPRs, no scratch at C1S_NP = 16) with <= 78 KB of LDS: two workgroups per CU -- the residency
+// rule of ops.persistent_opts counts on it.  (The unfused conv1s_fwd_kernel<16> takes 256 + 12 AGPRs: one per CU.)
+template <int C1S_NP>
+__global__ __launch_bounds__(256, 2) void c3s_c1s_fwd_kernel(const C3C1FwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int f = blockIdx.x, np = a.nprod * a.ng;
+    if (f < np) {                              // (model, half) pairs dealt as c3s_place deals them
+        const int pairs = 2 * a.ng, pr = f % pairs;
+        conv3s_fwd_tile<1, 6, true, true>(a.c3[pr >> 1], f / pairs, pr & 1, smem, a.flag[pr >> 1]);
+    } else {
+        const int q = f - np, per = a.ctm * a.ctn, model = q / per, t = q - model * per;
+        conv1s_fwd_tile<C1S_NP, true>(a.c1[model], t % a.ctm, t / a.ctm, smem, a.flag[model], (unsigned)a.nprod, a.err[model]);
+    }
+}
+
 }  // namespace
+
+// Driver-internal launcher of the fused form (dn_net.hip decides when; dn_ops.h).  p3[g]: conv2 of layer l, p1[g]: conv1 of layer l + 1
+// reading layer l's output as its last 32 input channels; flags[g]: a zeroed arrival word per (model, launch); errs[g]: the error word.
+int mms_c3s_c1s_fwd(const Conv3FwdP* p3, const Conv1FwdP* p1, unsigned* const* flags, unsigned* const* errs, int ng, hipStream_t s) {
+    if (!p3 || !p1 || !flags || !errs || ng < 1 || ng > MMS_FUSE_MAXG) return MMS_ERR_ARG;
+    const int M = p3->M, K = p1->K;
+    const Dims3 gd = p3->g;
+    if (M < 1 || M > 256 || K < 64 || K > 1024 || K % 32 || 16 + 2 * (gd.H * gd.W + gd.W + 1) > MMS_C3S_MAXROWS) return MMS_ERR_ARG;
+    C3C1FwdArgs a;
+    for (int g = 0; g < ng; ++g) {
+        const Conv3FwdP& q3 = p3[g];
+        const Conv1FwdP& q1 = p1[g];
+        const bool train = q3.osum != nullptr;
+        if (q3.M != M || q3.g.D != gd.D || q3.g.H != gd.H || q3.g.W != gd.W || !q3.wfrag || q3.partial || q3.srep > 1 ||
+            q1.M != M || q1.K != K || q1.N != 128 || q1.pool || q1.srep > 1 || q1.bn.nrep > 1 || q1.ldx % 4 ||
+            q1.x + (K - 32) != q3.out || q1.ldx != q3.ldo || (((uintptr_t)q1.x | (uintptr_t)q1.w) & 15) ||
+            (q1.bn.train != 0) != train || (train && (q1.bn.sum + (K - 32) != q3.osum || q1.bn.sumsq + (K - 32) != q3.osumsq)) ||
+            !flags[g] || !errs[g]) return MMS_ERR_ARG;
+        a.c3[g] = q3; a.c1[g] = q1; a.flag[g] = flags[g]; a.err[g] = errs[g];
+    }
+    a.ng = ng; a.ctm = (M + 15) / 16; a.ctn = 128 / 16; a.nprod = 2 * a.ctm;
+    const int nrows = C3S_TM + 2 * (gd.H * gd.W + gd.W + 1);
+    int smem = nrows * C3S_FP * (int)sizeof(float);
+    if (smem < 12800) smem = 12800;                                  // (conv3s_fwd_tile's epilogue)
+    const int smem1 = (16 * (K + 4) + 3 * K) * (int)sizeof(float);   // (conv1s_fwd_tile: >= its epilogue's 8448 bytes at K >= 64)
+    if (smem < smem1) smem = smem1;
+    constexpr int smax = (16 * 1028 + 3 * 1024) * (int)sizeof(float);
+    static_assert(smax >= MMS_C3S_MAXROWS * C3S_FP * (int)sizeof(float), "LDS limit of the fused launch");
+    static std::once_flag attr_once;
+    std::call_once(attr_once, [] {
+        hipFuncSetAttribute((const void*)(void (*)(const C3C1FwdArgs))c3s_c1s_fwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, smax);
+        hipFuncSetAttribute((const void*)(void (*)(const C3C1FwdArgs))c3s_c1s_fwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, smax);
+    });
+    const dim3 grid((a.nprod + a.ctm * a.ctn) * ng);
+    if (K <= 512) {
+        const auto kern = c3s_c1s_fwd_kernel<8>;
+        MMS_LAUNCH(kern, grid, dim3(256), smem, s, a);
+    } else {
+        const auto kern = c3s_c1s_fwd_kernel<16>;
+        MMS_LAUNCH(kern, grid, dim3(256), smem, s, a);
+    }
+    return mms_check_launch();
+}
 
 #ifdef C3S_TIMING
 extern "C" int mms_c3s_timing_buffer(void* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(c3s_ts_buf), &buf, sizeof(buf)) == hipSuccess ? MMS_OK : MMS_ERR_LAUNCH; }

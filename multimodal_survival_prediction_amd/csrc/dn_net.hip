@@ -45,6 +45,7 @@ struct Plan {
     int cl_rt[NB], cl_rpc[NB], cl_ncl[NB];
     size_t cl_xa[NB], cl_xb[NB], cl_gst[NB], cl_tab[NB], cl_zero_begin, cl_ga, cl_gz;
     size_t b4_err;
+    size_t hx;                      // arrival words of the fused block-3 forward launches, one per dense layer (inside the per-step zeroed region)
     size_t bb_y0, bb_y1[NLAYER], bb_in[NLAYER], bb_tr[3], bb_head;   // backward (s1 | s2)
     size_t total;
 };
@@ -116,6 +117,7 @@ bool make_plan(Plan& P, int B, int D, int H, int W) {
     for (int i = 0; i < NLAYER; ++i) P.bb_in[i] = take((size_t)P.R[blk_of[i]] * 2 * 1024 * 8);
     for (int i = 0; i < 3; ++i) P.bb_tr[i] = take((size_t)P.R[i] * 2 * 1024 * 8);
     P.bb_head = take((size_t)2 * 1024 * 8);
+    P.hx = take(256);
     P.cl_zero_begin = o;
     P.cl_ga = take((size_t)2 * 8 * 256 * 8);          // backward of a single-cluster block 4: hand-off A by layer parity, the dz broadcast
     P.cl_gz = take((size_t)512 * 8);
@@ -251,6 +253,7 @@ extern "C" int mms_dn121_region(int B, int D, int H, int W, const char* name, in
     if (!strcmp(name, "tpool") && index >= 0 && index < 3) return set(P.tpool[index], (size_t)P.M[index + 1] * CTOT[index] * 4);
     if (!strcmp(name, "stats")) return set(P.stats_begin, P.stats_end - P.stats_begin);
     if (!strcmp(name, "b4_err")) return set(P.b4_err, 1024);
+    if (!strcmp(name, "hx")) return set(P.hx, 256);
     return MMS_ERR_ARG;
 }
 
@@ -362,6 +365,17 @@ static bool conv3_frag_block(const Plan& P, int b, int ng, const MmsDnOpts& o) {
     // (the cluster kernels read the classic forward pack: with packed primary storage that is the parameter itself, always there)
     return b < NB - 1 && mms_conv3_small_jn(P.M[b], ng, P.g[b], o) != 0 && (o.w2_packed || !cluster_block(P, b, o, 0));
 }
+// Whether dense block b's forward runs conv2 of layer l and conv1 of layer l + 1 as ONE launch (dn_c3s.hip mms_c3s_c1s_fwd; the block's
+// 2 L launches become L + 1): MmsDnOpts.fuse_layers >= 0, block 3, and the launches it merges run the small-grid forms whose roles the
+// fused kernel holds -- the one-tile conv2 kernel (JN = 1, ring 6) on fragment-ordered weights, the whole-K conv1 kernel -- with one
+// statistic replica, <= 128 rows and <= MMS_FUSE_MAXG models.  (Caller: not under SyncBN / a statistics hook; residency is the caller's.)
+static bool fuse_block(const Plan& P, int b, int ng, const MmsDnOpts& o) {
+    if (o.fuse_layers < 0 || b != 2 || ng > MMS_FUSE_MAXG || P.M[b] > 128 || P.R[b] != 1 || cluster_block(P, b, o, 0)) return false;
+    if (mms_conv3_small_jn(P.M[b], ng, P.g[b], o) != 1 || !conv3_frag_block(P, b, ng, o) || (o.c3s_ring > 0 && o.c3s_ring != 6)) return false;
+    Conv1FwdP q{};
+    q.M = P.M[b]; q.N = 128; q.K = CTOT[b] - 32; q.ldx = CTOT[b];
+    return mms_conv1_small_ok(q, ng, o);
+}
 static uint64_t conv3_fragmask(const Plan& P, int ng, const MmsDnOpts& o) {
     uint64_t m = 0;
     int l = 0;
@@ -441,6 +455,11 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
         FOR_G regs[g] = at<void>(cx[g].ws, P.cl_zero_begin);
         TRY(mms_zero_regions_group(regs, ng, P.stats_end - P.cl_zero_begin, s));
     }
+    if (!train && cl_ok && fuse_block(P, 2, ng, o)) {       // the fused block-3 launches' arrival words (training: the zero-fill above)
+        void* regs[MMS_MAX_GROUP];
+        FOR_G regs[g] = at<void>(cx[g].ws, P.hx);
+        TRY(mms_zero_regions_group(regs, ng, 256, s));
+    }
     int l = 0;
     for (int b = 0; b < NB; ++b) {
         int C = C0[b];
@@ -456,36 +475,55 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
             TRYS(32, mms_cl_fwd_group(q, ng, s));
             l += LAYERS[b];
             C += 32 * LAYERS[b];
-        } else
-        for (int i = 0; i < LAYERS[b]; ++i, ++l, C += 32) {
-            const int ip = IDX.layer[l];
-            Conv1FwdP c1[MMS_MAX_GROUP];
-            Conv3FwdP c3[MMS_MAX_GROUP];
+        } else {
             const int ns3 = conv3_nsplit(P.M[b], ng, P.partial_rows, P.g[b], o);
-            // conv1 at small M is a chain of dependent K-steps on a handful of workgroups: one K-step per workgroup instead
-            int ks1 = 1;
-            if (o.conv1_ksplit >= 0 && (long)((P.M[b] + 31) / 32) * 4 * ng <= 128 && C >= 256 && (long)((C + 127) / 128) * P.M[b] <= P.partial_rows)
-                ks1 = (C + 127) / 128;
-            FOR_G {
-                const Ctx& c = cx[g];
-                float* slab = at<float>(c.ws, P.slab[b]);
-                c1[g] = Conv1FwdP{slab, CTOT[b], P.M[b], C, c.prm[ip + 2], 128, at<float>(c.ws, P.y1[l]), 128,
-                                  mk_bn(c.ws, P.st_slab[b], CTOT[b], c.prm, ip, c.buf, IDX.bn_layer1[l], P.M[b] * bw, train, P.R[b]),
-                                  st(c.ws, P.st_y1[l], 128, 0, false), st(c.ws, P.st_y1[l], 128, 0, true), 0, Dims3{0, 0, 0}};
-                c1[g].srep = P.R[b]; c1[g].sstride = 2 * 128;
-                if (ks1 > 1) { c1[g].partial = at<float>(c.ws, P.partial); c1[g].ksplit = ks1; c1[g].counters = at<unsigned>(c.ws, P.counters); }
-                const bool frag3 = conv3_frag_block(P, b, ng, o);
-                const float* wp3 = !packed ? at<float>(c.ws, P.wpf[l]) : (frag3 ? c.prm[NPARAM + 2 * l + 1] : c.prm[ip + 5]);
-                c3[g] = Conv3FwdP{at<float>(c.ws, P.y1[l]), at<int>(c.ws, P.coords[b]), P.g[b], P.M[b], wp3,
-                                  slab + C, CTOT[b], mk_bn(c.ws, P.st_y1[l], 128, c.prm, ip + 3, c.buf, IDX.bn_layer2[l], P.M[b] * bw, train, P.R[b]),
-                                  st(c.ws, P.st_slab[b], CTOT[b], C, false), st(c.ws, P.st_slab[b], CTOT[b], C, true),
-                                  ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
-                c3[g].srep = P.R[b]; c3[g].sstride = 2 * CTOT[b]; c3[g].wfrag = conv3_frag_block(P, b, ng, o) ? 1 : 0;
+            const bool frag3 = conv3_frag_block(P, b, ng, o);
+            // conv1 of layer l_ (C_ input channels) of model c
+            auto mk_c1 = [&](const Ctx& c, int l_, int C_) {
+                const int ip = IDX.layer[l_];
+                Conv1FwdP q{at<float>(c.ws, P.slab[b]), CTOT[b], P.M[b], C_, c.prm[ip + 2], 128, at<float>(c.ws, P.y1[l_]), 128,
+                            mk_bn(c.ws, P.st_slab[b], CTOT[b], c.prm, ip, c.buf, IDX.bn_layer1[l_], P.M[b] * bw, train, P.R[b]),
+                            st(c.ws, P.st_y1[l_], 128, 0, false), st(c.ws, P.st_y1[l_], 128, 0, true), 0, Dims3{0, 0, 0}};
+                q.srep = P.R[b]; q.sstride = 2 * 128;
+                // conv1 at small M is a chain of dependent K-steps on a handful of workgroups: one K-step per workgroup instead
+                if (o.conv1_ksplit >= 0 && (long)((P.M[b] + 31) / 32) * 4 * ng <= 128 && C_ >= 256 && (long)((C_ + 127) / 128) * P.M[b] <= P.partial_rows) {
+                    q.partial = at<float>(c.ws, P.partial); q.ksplit = (C_ + 127) / 128; q.counters = at<unsigned>(c.ws, P.counters);
+                }
+                return q;
+            };
+            // dense block 3 (fuse_block): conv2 of layer l and conv1 of layer l + 1 as ONE launch -- the first conv1 and the last conv2
+            // of the block stay single launches, 25 launches instead of 48
+            const bool fuse = cl_ok && fuse_block(P, b, ng, o);
+            for (int i = 0; i < LAYERS[b]; ++i, ++l, C += 32) {
+                const int ip = IDX.layer[l];
+                Conv1FwdP c1[MMS_MAX_GROUP];
+                Conv3FwdP c3[MMS_MAX_GROUP];
+                FOR_G {
+                    const Ctx& c = cx[g];
+                    c1[g] = mk_c1(c, l, C);
+                    const float* wp3 = !packed ? at<float>(c.ws, P.wpf[l]) : (frag3 ? c.prm[NPARAM + 2 * l + 1] : c.prm[ip + 5]);
+                    c3[g] = Conv3FwdP{at<float>(c.ws, P.y1[l]), at<int>(c.ws, P.coords[b]), P.g[b], P.M[b], wp3,
+                                      at<float>(c.ws, P.slab[b]) + C, CTOT[b],
+                                      mk_bn(c.ws, P.st_y1[l], 128, c.prm, ip + 3, c.buf, IDX.bn_layer2[l], P.M[b] * bw, train, P.R[b]),
+                                      st(c.ws, P.st_slab[b], CTOT[b], C, false), st(c.ws, P.st_slab[b], CTOT[b], C, true),
+                                      ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
+                    c3[g].srep = P.R[b]; c3[g].sstride = 2 * CTOT[b]; c3[g].wfrag = frag3 ? 1 : 0;
+                }
+                if (!fuse || i == 0) {          // (fused: this layer's conv1 ran in the previous layer's launch)
+                    TRYS(b, mms_conv1_fwd_group(c1, ng, &o, s));
+                    SYNC(at<double>(cx[0].ws, P.st_y1[l]), P.R[b], 2 * 128, 128, 128);
+                }
+                if (fuse && i + 1 < LAYERS[b]) {
+                    Conv1FwdP n1[MMS_MAX_GROUP];
+                    unsigned* fl[MMS_MAX_GROUP];
+                    unsigned* er[MMS_MAX_GROUP];
+                    FOR_G { n1[g] = mk_c1(cx[g], l + 1, C + 32); fl[g] = at<unsigned>(cx[g].ws, P.hx) + l; er[g] = at<unsigned>(cx[g].ws, P.b4_err); }
+                    TRYS(4 + b, mms_c3s_c1s_fwd(c3, n1, fl, er, ng, s));
+                } else {
+                    TRYS(4 + b, mms_conv3_fwd_group(c3, ng, &o, s));
+                    SYNC(at<double>(cx[0].ws, P.st_slab[b]) + C, P.R[b], 2 * CTOT[b], 32, CTOT[b]);
+                }
             }
-            TRYS(b, mms_conv1_fwd_group(c1, ng, &o, s));
-            SYNC(at<double>(cx[0].ws, P.st_y1[l]), P.R[b], 2 * 128, 128, 128);
-            TRYS(4 + b, mms_conv3_fwd_group(c3, ng, &o, s));
-            SYNC(at<double>(cx[0].ws, P.st_slab[b]) + C, P.R[b], 2 * CTOT[b], 32, CTOT[b]);
         }
         if (b < 3) {
             const int ip = IDX.trans[b];

@@ -64,6 +64,10 @@ bool mms_conv1_small_bwd_ok(const Conv1BwdP& p, const MmsDnOpts& o);
 int mms_c1s_bwd(const Conv1BwdP* pp, int ng, hipStream_t s);
 int mms_c3s_fwd(const Conv3FwdP* pp, int ng, const MmsDnOpts& o, hipStream_t s);
 int mms_c3s_bwd_data(const Conv3BwdDataP* pp, int ng, const MmsDnOpts& o, hipStream_t s);
+// conv2 of dense layer l + conv1 of layer l + 1 as ONE launch with an in-launch hand-off (dn_c3s.hip; dense block 3's forward, dn_net.hip
+// fuse_block): at most MMS_FUSE_MAXG models per launch (the two parameter blocks per model travel in the kernarg segment)
+#define MMS_FUSE_MAXG 4
+int mms_c3s_c1s_fwd(const Conv3FwdP* p3, const Conv1FwdP* p1, unsigned* const* flags, unsigned* const* errs, int ng, hipStream_t s);
 
 // ---- dense blocks 3 / 4 as one launch per pass (dn_cl.hip, dn_b4.hip); internal to the network drivers ---------------------------
 struct B4Layer {               // device table entry, one per dense layer (built by mms_dn121_init)

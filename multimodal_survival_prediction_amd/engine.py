@@ -901,8 +901,9 @@ class SurvivalEngine:
                     P.b4_err = P.ws[off.value:off.value + 4].view(torch.int32)
                 if int(P.b4_err.item()) != 0:
                     P.b4_err.zero_()
-                    raise RuntimeError("mmsurv: a hand-off of the block-4 persistent kernel timed out (too many persistent launches in "
-                                       "flight at once?); the results since the last check are invalid -- rerun with dn_opts={'persist_b4': -1}")
+                    raise RuntimeError("mmsurv: an in-launch hand-off (block-4 persistent kernel or fused block-3 forward) timed out (too many "
+                                       "such launches in flight at once?); the results since the last check are invalid -- rerun with "
+                                       "dn_opts={'persist_b4': -1, 'fuse_layers': -1}")
 
     def epoch_stats(self):
         """-> dict(sum_loss, n_usable, sum_entropy, n_batches) (one device->host sync); checks the block-4 time-out word (check_b4)."""

@@ -304,6 +304,17 @@ def cluster_workgroups(B, dims):
     return tuple(out)
 
 
+def fused_layer_workgroups(B, dims):
+    """(producers, consumers) per model of the fused block-3 forward launch (csrc/dn_c3s.hip mms_c3s_c1s_fwd: conv2 of layer l as
+    16-row tiles x two 16-column halves, conv1 of layer l + 1 as 16 x 16 tiles of its 128 outputs; the rule of csrc/dn_net.hip
+    fuse_block); (0, 0) = more than 128 rows, never fused."""
+    M = B * max(1, (dims[0] >> 4) * (dims[1] >> 4) * (dims[2] >> 4))
+    if M > 128:
+        return (0, 0)
+    tiles = -(-M // 16)
+    return (2 * tiles, 8 * tiles)
+
+
 def persistent_opts(base, device, ng, B, dims):
     """MmsDnOpts for a driver call of ng lock-step models: `base` with persist_b3 / persist_b4 switched to the per-layer path (-1) where
     the persistent launches of all worker streams could not be co-resident -- their workgroups hand data to each other inside the
@@ -319,6 +330,15 @@ def persistent_opts(base, device, ng, B, dims):
         kw["persist_b3"] = -1
     if base.persist_b4 >= 0 and w4 * ng * max_worker_streams() > cus:
         kw["persist_b4"] = -1
+    # fused block-3 forward (fuse_layers): its conv1 workgroups wait inside the launch for its conv2 ones.  Every worker stream may have
+    # one such launch in flight, and one block-4 persistent launch; the fused kernel holds two workgroups per CU (256 VGPRs, 78 KB of
+    # LDS), a block-4 cluster workgroup is counted as one of them.  The waiting workgroups of all streams must leave room for one
+    # launch's producers (3 streams x 2 models -> 3 x 2 x (64 + 8) + 2 x 16 = 464 <= 512).
+    fp, fc = fused_layer_workgroups(B, dims)
+    if base.fuse_layers >= 0 and fc:
+        b4 = w4 if kw.get("persist_b4", base.persist_b4) >= 0 else 0
+        if max_worker_streams() * ng * (fc + b4) + ng * fp > 2 * cus:
+            kw["fuse_layers"] = -1
     return dn_opts(base, **kw) if kw else base
 
 
