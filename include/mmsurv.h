@@ -455,6 +455,46 @@ typedef struct MixP {
     float* dbias[4];
 } MixP;
 
+/* Gated mixture of modality experts (SimMLM_SurvivalNet, R/scripts/analysis/generate_km_curves.py:158-281), F = feature width:
+ *   expert hazards  hz[:, 1 + e] = wx_e . f_e + bx_e   on the UNMASKED features f_e (e = image, rna, clinical);
+ *   gate input      gin = [f_0 m_0 | f_1 m_1 | f_2 m_2 | m]  (3F + 3 columns) -> gate MLP 3F+3 -> 128 -> Dropout -> 64 (mms_linear_*) -> h2;
+ *   gate            g = softmax(W3 h2 + b3 with the logits of modalities whose mask == 0 set to -inf);
+ *   mixture         fused = sum_e g_e f_e m_e;   ensemble hazard hz[:, 0] = we . fused + be.
+ * The forward runs in two stages around the gate MLP (stage 0: expert heads + gate input, valid_x; stage 1: gate output layer,
+ * masked softmax, mixture, ensemble head); the backward in the reverse order (stage 1: ensemble head, mixture and gate gradients ->
+ * dh2; stage 0: expert heads, and the gradient of the unmasked features = own Cox-head gradient + (mixture + gate-input gradient) * m_e).
+ * A row whose mask is all zero: gate weights and ensemble hazard are NaN in the forward, as torch computes them; the backward
+ * defines that row's gate and mixture gradients (and its share of the ensemble head's weight gradient) as 0, where torch would
+ * spread NaN into every gate parameter gradient.  One workgroup per model; M <= 32 rows; weight gradients are summed over the
+ * rows inside the workgroup (no atomics) and ADDED to dw*. */
+typedef struct MoeP {
+    int M; int F;                   // rows (1..32), feature width (positive multiple of 4)
+    int stage;                      // 0 or 1 (see above)
+    const float* feats; int ldf;    // [M][ldf] unmasked expert features: image | rna | clinical at columns 0, F, 2F
+    const float* mask; int ldm;     // [M][ldm] modality flags in columns 0..2
+    const float* valid;             // optional [M] has_survival (null = every row)
+    float* valid_x;                 // optional [4][M] out (forward stage 0): the Cox terms' sets -- row 0 (ensemble): valid && some
+                                    // mask != 0 (a row without any modality has a NaN ensemble hazard and is left out), row 1 + e: valid && mask_e != 0
+    float* gin; int ldg;            // [M][ldg] gate input, 3F + 3 columns (forward stage 0 output)
+    const float* h2; int ldh2;      // [M][ldh2] gate hidden after its second ReLU, 64 columns
+    const float* w3; const float* b3;           // gate output layer [3][64], [3]
+    const float* wx[3]; const float* bx[3];     // expert Cox heads [F], [1]
+    const float* we; const float* be;           // ensemble Cox head [F], [1]
+    float* hz; int ldhz;            // [M][ldhz] column 0 ensemble hazard, 1..3 expert hazards
+    float* gate;                    // [M][3] gate weights
+    float* fused;                   // [M][F] mixture (saved for the backward)
+    /* backward */
+    const float* dhz; int lddhz;    // [M][lddhz] gradient wrt the four hazard columns
+    const float* dgate_ext;         // optional [M][3] gradient wrt the gate weights
+    float* dh2; int lddh2;          // stage 1 out: gradient wrt h2 (overwritten)
+    const float* dgin; int lddg;    // stage 0 in: gradient wrt the gate input (first 3F columns read)
+    float* dfeats; int lddf;        // stage 0 out: gradient wrt the unmasked features (overwritten)
+    float* dw3; float* db3; float* dwx[3]; float* dbx[3]; float* dwe; float* dbe;   // accumulated (+=)
+    /* optional objective (backward stage 1): loss_out = {out_0[0] + expert_weight (out_1[0] + out_2[0] + out_3[0]), out_0[1]} over the
+       CoxP.out blocks [4][2] of the ensemble and the three expert terms */
+    const float* cox_outs; float expert_weight; float* loss_out;
+} MoeP;
+
 /* Batch assembly (the DataLoader collate + `.to(device)` of R/scripts/training/final_multimodal.py:228-247): row idx[b] of each
  * source array -> row b of its destination, all sources of all models of a fold group in ONE launch.  The sources live in HBM
  * (device-resident cohort) or in PINNED HOST memory (hipHostMalloc / torch pin_memory: the kernel then reads the rows over PCIe --
@@ -524,6 +564,8 @@ int mms_bn1d_bwd_apply(const LinBigP* p, hipStream_t s);
 int mms_missing_mix_fwd(const MixP* p, hipStream_t s);        /* R/scripts/training/flexible_multimodal.py:243-250 */
 int mms_missing_mix_bwd(const MixP* p, hipStream_t s);
 int mms_cox_fwd_bwd(const CoxP* p, hipStream_t s);
+int mms_moe_fwd(const MoeP* p, hipStream_t s);                 /* R/scripts/analysis/generate_km_curves.py:262-281 (MoeP above) */
+int mms_moe_bwd(const MoeP* p, hipStream_t s);
 int mms_cindex_counts(const CindexP* p, hipStream_t s);
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */
@@ -620,6 +662,8 @@ int mms_linear_bwd_group(const LinearBwdP* p, int ng, hipStream_t s);
 int mms_gate_fwd_group(const GateP* p, int ng, hipStream_t s);
 int mms_gate_bwd_group(const GateP* p, int ng, hipStream_t s);
 int mms_cox_fwd_bwd_group(const CoxP* p, int ng, hipStream_t s);
+int mms_moe_fwd_group(const MoeP* p, int ng, hipStream_t s);   /* SimMLM heads: MoeP.stage of the forward */
+int mms_moe_bwd_group(const MoeP* p, int ng, hipStream_t s);   /* ... and of the backward */
 int mms_grad_sumsq_group(const AdamP* p, int ng, hipStream_t s);
 int mms_clip_adam_group(const AdamP* p, int ng, hipStream_t s);
 int mms_w2_pack_group(const AdamP* p, int ng, hipStream_t s);

@@ -108,6 +108,21 @@ def head_program(model):
             lins.append(_Lin(mods[i], src, dst, False, pro_bn=pro_bn, pro_drop=pro_drop, need_dx=n > 0))
         bufs["hz"] = 1
         return dict(kind=kind, width=0, ct_cols=0, lins=lins, gate=None, bufs=bufs, encoder=None, n_pre=0)
+    if kind == "SimMLM_SurvivalNet":           # generate_km_curves.py:158-281: experts -> masked gate MLP -> mixture (MoeP, include/mmsurv.h)
+        F = model.feature_dim
+        r, c, g = model.expert_rnaseq.encoder, model.expert_clinical.encoder, model.gating.gate
+        lins = [
+            _Lin(r[0], ("rna", 0), ("r1", 0), False, need_dx=False),
+            _Lin(r[4], ("r1", 0), ("feats", F), True, pro_bn=r[1], pro_drop=r[3]),
+            _Lin(c[0], ("clin", 0), ("c1", 0), True, need_dx=False),
+            _Lin(c[2], ("c1", 0), ("feats", 2 * F), True),
+            _Lin(g[0], ("gin", 0), ("g1", 0), True),                   # (the first stage of mms_moe_fwd fills gin)
+            _Lin(g[3], ("g1", 0), ("g2", 0), True, pro_drop=g[2]),     # g2 feeds the second stage (gate output layer, softmax, mixture)
+        ]
+        bufs = dict(rna=r[0].in_features, clin=c[0].in_features, r1=512, c1=64, feats=3 * F, gin=3 * F + 3, g1=128, g2=64, hz=4)
+        experts = [model.expert_image.cox_head, model.expert_rnaseq.cox_head, model.expert_clinical.cox_head]
+        return dict(kind=kind, width=3 * F, ct_cols=0, lins=lins, gate=None, bufs=bufs, encoder=model.expert_image.encoder, n_pre=4,
+                    enc_width=F, moe=dict(F=F, out=g[5], experts=experts, ensemble=model.ensemble_cox))
     raise TypeError("unsupported model %s" % kind)
 
 
@@ -118,8 +133,10 @@ class _Plan:
 
 class SurvivalEngine:
     def __init__(self, model, adamw=None, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0,
-                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None, _slots=None):
-        """dn_opts: launch-shape options of the encoder drivers (dict of MmsDnOpts fields, include/mmsurv.h; None = defaults).
+                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None, expert_weight=0.1, _slots=None):
+        """expert_weight: lambda of SimMLM_SurvivalNet's training objective (project-defined)
+        L = cox(ensemble; has_survival) + lambda * sum_m cox(h_m; has_survival and mask_m); ignored by the other models.
+        dn_opts: launch-shape options of the encoder drivers (dict of MmsDnOpts fields, include/mmsurv.h; None = defaults).
         _slots (used by FoldGroupEngine): dict(gflat=[n] fp32, sumsq=[1] fp64, entropy=[1] fp32) views of group-wide
         buffers, so the per-step zeroing of a whole fold group is three memsets."""
         self.lib = _lib.load_library()
@@ -147,6 +164,7 @@ class SurvivalEngine:
         self.step_count = torch.zeros(1, device=self.device)
         self.rng = torch.tensor([0x5EED, 0], dtype=torch.int32, device=self.device)
         self.ent_weight = gate_entropy_weight
+        self.expert_weight = float(expert_weight)
         from . import losses
         self.tie_mode = ops.TIE_MODES[cox_ties or losses.default_ties()]    # CoxP.tie_mode of the fused step's loss
         self.side_stream = torch.cuda.Stream(device=self.device)
@@ -247,7 +265,7 @@ class SurvivalEngine:
         D, H, W = dims if P.has_enc else (1, 1, 1)
         P.ct = torch.zeros(B, 1, D, H, W, device=dev)
         P.big = B > 32                 # rows beyond the one-lane-per-column head kernels: MFMA GEMM path (mms_linear_big_*)
-        if P.big and (P.has_enc or prog["gate"] is not None or prog.get("mix") is not None):
+        if P.big and (P.has_enc or prog["gate"] is not None or prog.get("mix") is not None or prog.get("moe") is not None):
             raise RuntimeError("batches of more than 32 rows are supported for the encoder-less RNASeqSurvivalModel only "
                                "(the reference trains the imaging models at batch 4-16)")
         # row pitch padded to a multiple of 4 floats so that the 5005-wide RNA rows are 16-B aligned (float4 operand loads)
@@ -345,12 +363,18 @@ class SurvivalEngine:
                 M.seg_begin[i], M.seg_width[i] = b0, w
                 M.bias[i], M.dbias[i] = bias.data_ptr(), gmap[id(bias)].data_ptr()
             P.mix = M
+        P.moe = None
+        if prog.get("moe") is not None:
+            self._plan_moe(P, gmap)
         hz = P.buf["hz"]
-        P.cox = _S()["CoxP"](hz.data_ptr(), 1, P.time.data_ptr(), P.event.data_ptr(), P.valid.data_ptr(), B, 1.0,
-                             P.lse.data_ptr(), P.dbuf["hz"].data_ptr(), 1, P.cox_out.data_ptr(), self.tie_mode, P.tie_frac.data_ptr())
+        # (SimMLM: the ensemble term's set leaves out rows without any modality, whose ensemble hazard is NaN)
+        ens_valid = P.valid_x[0] if P.moe is not None else P.valid
+        P.cox = _S()["CoxP"](hz.data_ptr(), hz.stride(0), P.time.data_ptr(), P.event.data_ptr(), ens_valid.data_ptr(), B, 1.0,
+                             P.lse.data_ptr(), P.dbuf["hz"].data_ptr(), P.dbuf["hz"].stride(0), P.cox_out.data_ptr(), self.tie_mode,
+                             P.tie_frac.data_ptr())
         # validation: the batch's Cox value only (no gradient), (loss | usable) kept per batch for validate_*'s bookkeeping
         P.cox_eval_out = torch.zeros(2, device=self.device)
-        P.cox_eval = _S()["CoxP"](hz.data_ptr(), 1, P.time.data_ptr(), P.event.data_ptr(), P.valid.data_ptr(), B, 1.0,
+        P.cox_eval = _S()["CoxP"](hz.data_ptr(), hz.stride(0), P.time.data_ptr(), P.event.data_ptr(), ens_valid.data_ptr(), B, 1.0,
                                   P.lse.data_ptr(), None, 1, P.cox_eval_out.data_ptr(), self.tie_mode, P.tie_frac.data_ptr())
         book = dict(acc=self.acc, cox_out=P.cox_out, entropy=self.entropy, rng=self.rng)   # per-step bookkeeping, in-kernel
         w2 = self.w2 if (self.w2 is not None and self.w2["fragmask"] is not None) else None
@@ -363,6 +387,58 @@ class SurvivalEngine:
         P.graphs = {}
         self.plans[key] = P
         return P
+
+    def _plan_moe(self, P, gmap):
+        """MoeP blocks (include/mmsurv.h) of SimMLM_SurvivalNet: the two forward and two backward stages around the gate MLP, and the
+        four Cox terms of the fused step (ensemble | image | rna | clinical) for ONE mms_cox_fwd_bwd_group launch."""
+        mo, B, dev, S = self.prog["moe"], P.B, self.device, _S()
+        F = mo["F"]
+        P.gatew = torch.zeros(B, 3, device=dev)
+        P.fused = torch.zeros(B, F, device=dev)
+        P.valid_x = torch.ones(4, B, device=dev)          # Cox sets of the ensemble and the three experts (MoeP.valid_x)
+        P.cox_outs = torch.zeros(4, 2, device=dev)
+        P.lse4, P.frac4 = torch.zeros(4, B, device=dev), torch.zeros(4, B, device=dev)
+        fe, dfe, hz, dhz = P.buf["feats"], P.dbuf["feats"], P.buf["hz"], P.dbuf["hz"]
+        gin, dgin, h2, dh2 = P.buf["gin"], P.dbuf["gin"], P.buf["g2"], P.dbuf["g2"]
+        out, ens = mo["out"], mo["ensemble"]
+
+        def block(stage):
+            q = S["MoeP"]()
+            q.M, q.F, q.stage = B, F, stage
+            q.feats, q.ldf, q.mask, q.ldm = fe.data_ptr(), fe.stride(0), P.mask.data_ptr(), P.mask.stride(0)
+            q.valid, q.valid_x = P.valid.data_ptr(), P.valid_x.data_ptr()
+            q.gin, q.ldg, q.h2, q.ldh2 = gin.data_ptr(), gin.stride(0), h2.data_ptr(), h2.stride(0)
+            q.w3, q.b3 = out.weight.data_ptr(), out.bias.data_ptr()
+            for e, L in enumerate(mo["experts"]):
+                q.wx[e], q.bx[e] = L.weight.data_ptr(), L.bias.data_ptr()
+                q.dwx[e], q.dbx[e] = gmap[id(L.weight)].data_ptr(), gmap[id(L.bias)].data_ptr()
+            q.we, q.be = ens.weight.data_ptr(), ens.bias.data_ptr()
+            q.hz, q.ldhz, q.gate, q.fused = hz.data_ptr(), hz.stride(0), P.gatew.data_ptr(), P.fused.data_ptr()
+            q.dhz, q.lddhz, q.dh2, q.lddh2 = dhz.data_ptr(), dhz.stride(0), dh2.data_ptr(), dh2.stride(0)
+            q.dgin, q.lddg, q.dfeats, q.lddf = dgin.data_ptr(), dgin.stride(0), dfe.data_ptr(), dfe.stride(0)
+            q.dw3, q.db3 = gmap[id(out.weight)].data_ptr(), gmap[id(out.bias)].data_ptr()
+            q.dwe, q.dbe = gmap[id(ens.weight)].data_ptr(), gmap[id(ens.bias)].data_ptr()
+            # the objective's value for the step's bookkeeping (AdamP.cox_out): written by the backward's stage 1 (on the autograd path
+            # too, where nothing reads it)
+            q.cox_outs, q.expert_weight, q.loss_out = P.cox_outs.data_ptr(), self.expert_weight, P.cox_out.data_ptr()
+            return q
+        P.moe = [block(0), block(1)]
+        P.moe_bwd = [block(0), block(1)]
+        lam = self.expert_weight
+        cox = (S["CoxP"] * 4)()
+        for c in range(4):
+            valid = P.valid_x[c]
+            cox[c] = S["CoxP"](hz[:, c].data_ptr(), hz.stride(0), P.time.data_ptr(), P.event.data_ptr(), valid.data_ptr(), B,
+                               1.0 if c == 0 else lam, P.lse4[c].data_ptr(), dhz[:, c].data_ptr(), dhz.stride(0), P.cox_outs[c].data_ptr(),
+                               self.tie_mode, P.frac4[c].data_ptr())
+        P.cox4 = cox
+
+    def _cox_step(self, P):
+        """The fused step's loss: one Cox term, or SimMLM's four (one launch; their sum is formed by the backward's mms_moe_bwd)."""
+        if P.moe is not None:
+            _lib.check(self.lib.mms_cox_fwd_bwd_group(P.cox4, 4, ops.stream()), "mms_cox_fwd_bwd_group")
+        else:
+            _lib.check(self.lib.mms_cox_fwd_bwd(ctypes.byref(P.cox), ops.stream()), "mms_cox_fwd_bwd")
 
     def _plan_big(self, P, gmap):
         """LinBigP blocks (include/mmsurv.h) of the large-batch Linear chain.  BatchNorm1d statistics of a buffer live in one
@@ -457,6 +533,8 @@ class SurvivalEngine:
         n_pre = prog["n_pre"]
         for i in range(n_pre):
             _lib.check(lib.mms_linear_fwd(ctypes.byref(lf[i]), st), "mms_linear_fwd")
+        if P.moe is not None:
+            _lib.check(lib.mms_moe_fwd(ctypes.byref(P.moe[0]), st), "mms_moe_fwd")
         if P.gate is not None:
             self.entropy.zero_()
             _lib.check(lib.mms_gate_fwd(ctypes.byref(P.gate), st), "mms_gate_fwd")
@@ -464,6 +542,8 @@ class SurvivalEngine:
             _lib.check(lib.mms_missing_mix_fwd(ctypes.byref(P.mix), st), "mms_missing_mix_fwd")
         for i in range(n_pre, len(lf)):
             _lib.check(lib.mms_linear_fwd(ctypes.byref(lf[i]), st), "mms_linear_fwd")
+        if P.moe is not None:
+            _lib.check(lib.mms_moe_fwd(ctypes.byref(P.moe[1]), st), "mms_moe_fwd")
 
     def _backward_from_dhz(self, P):
         """dbuf['hz'] holds dL/dhazard; accumulates every parameter gradient into gflat."""
@@ -484,12 +564,16 @@ class SurvivalEngine:
                     if L.pro_bn is not None:
                         _lib.check(lib.mms_bn1d_bwd_apply(ctypes.byref(q), st), "mms_bn1d_bwd_apply")
             return
+        if P.moe is not None:
+            _lib.check(lib.mms_moe_bwd(ctypes.byref(P.moe_bwd[1]), st), "mms_moe_bwd")
         for i in range(len(P.lin_bwd) - 1, n_pre - 1, -1):
             _lib.check(lib.mms_linear_bwd(ctypes.byref(P.lin_bwd[i]), st), "mms_linear_bwd")
         if P.gate is not None:
             _lib.check(lib.mms_gate_bwd(ctypes.byref(P.gate), st), "mms_gate_bwd")
         if P.mix is not None:
             _lib.check(lib.mms_missing_mix_bwd(ctypes.byref(P.mix), st), "mms_missing_mix_bwd")
+        if P.moe is not None:
+            _lib.check(lib.mms_moe_bwd(ctypes.byref(P.moe_bwd[0]), st), "mms_moe_bwd")
         for i in range(n_pre - 1, -1, -1):
             _lib.check(lib.mms_linear_bwd(ctypes.byref(P.lin_bwd[i]), st), "mms_linear_bwd")
 
@@ -572,7 +656,7 @@ class SurvivalEngine:
             self.gflat.zero_()
             self.sumsq.zero_()
             self._forward(P, True)
-            _lib.check(lib.mms_cox_fwd_bwd(ctypes.byref(P.cox), st), "mms_cox_fwd_bwd")
+            self._cox_step(P)
             self._backward_from_dhz(P)
             if part == "grad":
                 return
@@ -623,7 +707,7 @@ class SurvivalEngine:
             srcs.append((cohort["image"].view(cohort["image"].shape[0], -1), P.ct.view(P.B, -1), None, flags.get("image")))
         if "clin" in P.buf:
             srcs.append((cohort["clinical"], P.buf["clin"], None))
-        if P.gate is not None:
+        if P.gate is not None or P.moe is not None:
             srcs.append((cohort["mask"], P.mask, None))
         if P.mix is not None:            # [has_image, has_rnaseq] = the first columns of the cohort's modality mask
             srcs.append((cohort["mask"], P.mask2, P.mask2.shape[1]))
@@ -656,6 +740,9 @@ class SurvivalEngine:
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None, bn_world=ddp_world if (sync_bn and ddp_world > 1) else 1)
         self.load_batch(P, ct, rna, clinical, mask, time, event, valid)
         self.sync_packs()
+        if ddp_world > 1 and P.moe is not None:
+            raise RuntimeError("SimMLM_SurvivalNet: the data-parallel step (ddp_world > 1) is not implemented for this model; "
+                               "train its folds as a fold group or one per process instead")
         if ddp_world > 1 and sync_bn:
             self._ddp_step_syncbn(P, ddp_world)
             return
@@ -882,7 +969,7 @@ class SurvivalEngine:
             P.graphs["eval"].replay()
         else:
             self._forward(P, False)
-        return P.buf["hz"][:, 0], (P.gatew if P.gate is not None else None)
+        return P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)
 
     def reset_epoch_stats(self):
         self.acc.zero_()

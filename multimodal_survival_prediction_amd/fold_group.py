@@ -103,6 +103,12 @@ class FoldGroupEngine:
         GP.lin_fwd = {t: [_arr([P.lin_fwd[t][i] for P in Ps]) for i in range(nl)] for t in (True, False)}
         GP.lin_bwd = [_arr([P.lin_bwd[i] for P in Ps]) for i in range(nl)]
         GP.gate = _arr([P.gate for P in Ps]) if Ps[0].gate is not None else None
+        GP.moe = GP.moe_bwd = GP.cox4 = None
+        if Ps[0].moe is not None:        # SimMLM: the two stages of each pass; the 4 x ng Cox terms in launches of <= MMS_MAX_GROUP blocks
+            GP.moe = [_arr([P.moe[s] for P in Ps]) for s in (0, 1)]
+            GP.moe_bwd = [_arr([P.moe_bwd[s] for P in Ps]) for s in (0, 1)]
+            terms = [P.cox4[c] for P in Ps for c in range(4)]
+            GP.cox4 = [(_arr(terms[i:i + 8]), len(terms[i:i + 8])) for i in range(0, len(terms), 8)]
         GP.cox = _arr([P.cox for P in Ps])
         GP.cox_eval = _arr([P.cox_eval for P in Ps])
         GP.adam = {True: _arr([P.adam_skip for P in Ps]), False: _arr([P.adam for P in Ps])}
@@ -131,12 +137,16 @@ class FoldGroupEngine:
         n_pre = prog["n_pre"]
         for i in range(n_pre):
             _lib.check(lib.mms_linear_fwd_group(lf[i], ng, st), "mms_linear_fwd_group")
+        if GP.moe is not None:
+            _lib.check(lib.mms_moe_fwd_group(GP.moe[0], ng, st), "mms_moe_fwd_group")
         if GP.gate is not None:
             _lib.check(lib.mms_gate_fwd_group(GP.gate, ng, st), "mms_gate_fwd_group")
         if GP.mix is not None:
             _lib.check(lib.mms_missing_mix_fwd_group(GP.mix, ng, st), "mms_missing_mix_fwd_group")
         for i in range(n_pre, len(lf)):
             _lib.check(lib.mms_linear_fwd_group(lf[i], ng, st), "mms_linear_fwd_group")
+        if GP.moe is not None:
+            _lib.check(lib.mms_moe_fwd_group(GP.moe[1], ng, st), "mms_moe_fwd_group")
 
     @staticmethod
     def _sync_packs(GP):
@@ -159,7 +169,12 @@ class FoldGroupEngine:
         prog = GP.eng[0].prog
         self._zero(GP)
         self._forward(GP, True)
-        _lib.check(lib.mms_cox_fwd_bwd_group(GP.cox, ng, st), "mms_cox_fwd_bwd_group")
+        if GP.cox4 is not None:
+            for arr, n in GP.cox4:
+                _lib.check(lib.mms_cox_fwd_bwd_group(arr, n, st), "mms_cox_fwd_bwd_group")
+            _lib.check(lib.mms_moe_bwd_group(GP.moe_bwd[1], ng, st), "mms_moe_bwd_group")
+        else:
+            _lib.check(lib.mms_cox_fwd_bwd_group(GP.cox, ng, st), "mms_cox_fwd_bwd_group")
         n_pre = prog["n_pre"]
         for i in range(len(GP.lin_bwd) - 1, n_pre - 1, -1):
             _lib.check(lib.mms_linear_bwd_group(GP.lin_bwd[i], ng, st), "mms_linear_bwd_group")
@@ -167,6 +182,8 @@ class FoldGroupEngine:
             _lib.check(lib.mms_gate_bwd_group(GP.gate, ng, st), "mms_gate_bwd_group")
         if GP.mix is not None:
             _lib.check(lib.mms_missing_mix_bwd_group(GP.mix, ng, st), "mms_missing_mix_bwd_group")
+        if GP.moe is not None:
+            _lib.check(lib.mms_moe_bwd_group(GP.moe_bwd[0], ng, st), "mms_moe_bwd_group")
         for i in range(n_pre - 1, -1, -1):
             _lib.check(lib.mms_linear_bwd_group(GP.lin_bwd[i], ng, st), "mms_linear_bwd_group")
         if GP.has_enc:
@@ -325,7 +342,7 @@ class FoldGroupEngine:
             self._graph(GP, "eval", lambda: self._forward(GP, False)).replay()
         else:
             self._forward(GP, False)
-        return [(P.buf["hz"][:, 0], (P.gatew if P.gate is not None else None)) for P in GP.Ps]
+        return [(P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)) for P in GP.Ps]
 
     def reset_epoch_stats(self):
         for e in self.engines:

@@ -185,3 +185,103 @@ class RNASeqSurvivalModel(nn.Module):
 
     def forward(self, rnaseq):
         return _run(self, None, rnaseq, None, None)[0].unsqueeze(1)
+
+
+# ---- SimMLM_SurvivalNet (generate_km_curves.py:158-281): gated mixture of modality experts -----------------------------------
+class _MoeExpert(nn.Module):
+    """Parameter holder with the reference's ModalityExpert names (encoder, [pool,] cox_head); never called."""
+
+    def __init__(self, modality, input_dim=None, output_dim=128):
+        super().__init__()
+        self.modality_type = modality
+        if modality == "image":
+            self.encoder = _ct_encoder(output_dim)
+            self.use_monai = USE_MONAI
+            self.pool = nn.AdaptiveAvgPool3d(1)
+        elif modality == "rnaseq":
+            self.encoder = nn.Sequential(nn.Linear(input_dim, 512), nn.BatchNorm1d(512), nn.ReLU(), nn.Dropout(0.3),
+                                         nn.Linear(512, output_dim), nn.ReLU())
+        else:
+            self.encoder = nn.Sequential(nn.Linear(input_dim, 64), nn.ReLU(), nn.Linear(64, output_dim), nn.ReLU())
+        self.cox_head = nn.Linear(output_dim, 1)
+
+
+class _MoeGate(nn.Module):
+    def __init__(self, feature_dim=128, num_modalities=3):
+        super().__init__()
+        self.gate = nn.Sequential(nn.Linear(feature_dim * num_modalities + num_modalities, 128), nn.ReLU(), nn.Dropout(0.2),
+                                  nn.Linear(128, 64), nn.ReLU(), nn.Linear(64, num_modalities))
+
+
+class _MoeNet(torch.autograd.Function):
+    """forward/backward of SimMLM_SurvivalNet on the engine's eager path; backward takes gradients on all five outputs."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, ct, rna, clinical, mask):
+        eng = engine_of(model)
+        P = eng.plan(rna.shape[0], tuple(ct.shape[-3:]))
+        eng.load_batch(P, ct, rna, clinical, mask)
+        eng._forward(P, model.training)
+        ctx.eng, ctx.P, ctx.train = eng, P, model.training
+        hz = P.buf["hz"]
+        return hz[:, 0].clone(), hz[:, 1].clone(), hz[:, 2].clone(), hz[:, 3].clone(), P.gatew.clone()
+
+    @staticmethod
+    def backward(ctx, d0, d1, d2, d3, dgate):
+        if not ctx.train:
+            raise RuntimeError("backward through an eval-mode forward is not supported (BN batch statistics)")
+        eng, P = ctx.eng, ctx.P
+        if eng.params[0].grad is None:
+            eng.gflat.zero_()
+            eng.attach_grads()
+        dh = P.dbuf["hz"]
+        for c, d in enumerate((d0, d1, d2, d3)):
+            if d is None:
+                dh[:, c].zero_()
+            else:
+                dh[:, c].copy_(d)
+        ext = dgate.contiguous() if dgate is not None else None
+        P.moe_bwd[1].dgate_ext = ext.data_ptr() if ext is not None else None
+        eng._backward_from_dhz(P)
+        P.moe_bwd[1].dgate_ext = None
+        return None, None, None, None, None, None
+
+
+class SimMLM_SurvivalNet(nn.Module):
+    """generate_km_curves.py:158-281: one expert per modality (CT, RNA-seq, clinical), each with its own Cox head; a gate MLP on the
+    masked features and the mask with a -inf masked softmax; the ensemble Cox head reads the gate-weighted SUM of the masked
+    expert features.  Sub-module names and parameter creation order are the reference's (a seeded construction draws its weights).
+    forward(image, rnaseq, clinical, mask) -> (ensemble_hazard [B], {'image', 'rnaseq', 'clinical'}: hazards [B], gate_weights [B, 3]).
+    A row whose mask is all zero yields NaN gate weights and ensemble hazard (as in torch); its gate / mixture gradient is defined as 0
+    (include/mmsurv.h MoeP)."""
+
+    def __init__(self, rna_dim=5005, clinical_dim=1, feature_dim=128):
+        super().__init__()
+        # the heads read feature rows of width feature_dim; the fallback encoder's last convolution is fixed at 128 channels in the
+        # reference (its ModalityExpert ignores output_dim there), so the fallback branch exists at 128 only
+        if feature_dim % 4 != 0 or feature_dim <= 0:
+            raise ValueError("feature_dim must be a positive multiple of 4 (16-byte aligned feature columns)")
+        if not USE_MONAI and feature_dim != 128:
+            raise ValueError("the fallback CT encoder (USE_MONAI = False) produces 128 features: feature_dim must be 128")
+        self.expert_image = _MoeExpert("image", output_dim=feature_dim)
+        self.expert_rnaseq = _MoeExpert("rnaseq", input_dim=rna_dim, output_dim=feature_dim)
+        self.expert_clinical = _MoeExpert("clinical", input_dim=clinical_dim, output_dim=feature_dim)
+        self.gating = _MoeGate(feature_dim=feature_dim, num_modalities=3)
+        self.ensemble_cox = nn.Linear(feature_dim, 1)
+        self.feature_dim = feature_dim
+        self.use_monai = USE_MONAI
+
+    def forward(self, image, rnaseq, clinical, mask):
+        if not rnaseq.is_cuda or not image.is_cuda:
+            raise RuntimeError("SimMLM_SurvivalNet (HIP): inputs must be on an MI355X device; there is no CPU fallback")
+        anchor = next(self.parameters())
+        if torch.is_grad_enabled() and self.training:
+            h, hi, hr, hc, g = _MoeNet.apply(anchor, self, image, rnaseq, clinical, mask)
+        else:
+            eng = engine_of(self)
+            P = eng.plan(rnaseq.shape[0], tuple(image.shape[-3:]))
+            eng.load_batch(P, image, rnaseq, clinical, mask)
+            eng._forward(P, self.training)
+            hz = P.buf["hz"]
+            h, hi, hr, hc, g = hz[:, 0].clone(), hz[:, 1].clone(), hz[:, 2].clone(), hz[:, 3].clone(), P.gatew.clone()
+        return h, {'image': hi, 'rnaseq': hr, 'clinical': hc}, g

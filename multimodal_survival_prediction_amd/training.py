@@ -17,11 +17,12 @@ class FusedOptimizer:
     """Handle for the engine-resident Adam/AdamW state (drop-in where the scripts build `optim.Adam(...)`)."""
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-4, adamw=False, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0,
-                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None):
+                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None, expert_weight=0.1):
         # (a model that already belongs to a FoldGroupEngine keeps that engine: this object is then just the handle
         # the LR schedulers talk to -- pass the same hyper-parameters to the group's constructor)
         self.engine = engine_of(model, lr=lr, weight_decay=weight_decay, adamw=adamw, betas=betas, eps=eps,
-                                max_norm=max_norm, gate_entropy_weight=gate_entropy_weight, cox_ties=cox_ties, dn_opts=dn_opts)
+                                max_norm=max_norm, gate_entropy_weight=gate_entropy_weight, cox_ties=cox_ties, dn_opts=dn_opts,
+                                expert_weight=expert_weight)
         self.param_groups = [dict(lr=lr, weight_decay=weight_decay)]
 
     def set_lr(self, lr):
@@ -155,6 +156,53 @@ def validate_partial(model, loader, device):
     return (total / nb if nb > 0 else 0), c
 
 
+# ---- SimMLM_SurvivalNet (generate_km_curves.py:158-281; the reference ships no training loop for it) ------------------------
+def train_epoch_simmlm(model, loader, optimizer, device):
+    """One epoch of the project-defined objective L = cox(ensemble; has_survival) + lambda sum_m cox(h_m; has_survival and mask_m)
+    (lambda = the engine's expert_weight), fused step per batch; a batch whose ensemble term is unusable takes no step.
+    -> mean of L over the usable batches."""
+    if not isinstance(optimizer, FusedOptimizer):
+        raise TypeError("train_epoch_simmlm drives the fused step; pass a FusedOptimizer")
+    model.train()
+    eng = optimizer.engine
+    eng.reset_epoch_stats()
+    for batch in loader:
+        label = batch['label']
+        valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
+        eng.train_step(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'], time=label[:, 0],
+                       event=label[:, 1], valid=valid, skip_if_unusable=True)
+    st = eng.epoch_stats()
+    return st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0
+
+
+def validate_simmlm(model, loader, device):
+    """-> (mean ensemble Cox loss over the usable batches, C-index of the ensemble hazard over their labelled patients); the batch
+    rule of validate_partial over the labelled patients WITH at least one modality (a row whose mask is all zero has a NaN ensemble
+    hazard: it is left out, as it is left out of the training objective)."""
+    model.eval()
+    eng = engine_of(model)
+    total, nb, hs, ts, es = 0.0, 0, [], [], []
+    for batch in loader:
+        label = _t(batch['label'], device)
+        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'])
+        smask = _simmlm_rows(batch, device)
+        if int(smask.sum()) > 0:
+            h, t, e = hz[smask].clone(), label[smask, 0], label[smask, 1]
+            if h.shape[0] >= 2 and float(e.sum()) > 0:
+                total += losses.cox_loss(h, e, t).item()
+                nb += 1
+                hs.append(h); ts.append(t); es.append(e)
+    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
+    eng.check_b4()
+    return (total / nb if nb > 0 else 0), c
+
+
+def _simmlm_rows(batch, device):
+    """labelled patients with at least one modality (the ensemble term's set)"""
+    smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
+    return smask & (_t(batch['mask'], device) != 0).any(1)
+
+
 # ---- simple_fusion.py -------------------------------------------------------------------------------------------
 def train_epoch_simple(model, loader, optimizer, device):
     if not isinstance(optimizer, FusedOptimizer):
@@ -282,7 +330,7 @@ def _train_kwargs(style, batch):
     if style == "rnaseq":
         return dict(rna=batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1))
     valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
-    if style == "partial":
+    if style in ("partial", "simmlm"):
         label = batch['label']
         return dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], mask=batch['mask'], time=label[:, 0],
                     event=label[:, 1], valid=valid)
@@ -298,6 +346,11 @@ def _train_kwargs(style, batch):
 
 
 _SKIP_UNUSABLE = {"final": True, "partial": False, "simple": True, "flexible": True, "rnaseq": False}
+
+
+def _skip_unusable(style):
+    """the reference scripts' rule (_SKIP_UNUSABLE); "simmlm" (train_epoch_simmlm): a batch whose ensemble term is unusable takes no step"""
+    return True if style == "simmlm" else _SKIP_UNUSABLE[style]
 
 
 def _lockstep(loaders, members):
@@ -336,7 +389,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
                 by.setdefault((len(b["index"]), id(b["gather"])), []).append((g, b))
             for items in by.values():
                 group.train_step_indexed(items[0][1]["gather"], torch.stack([torch.as_tensor(b["index"]) for _, b in items]),
-                                         members=tuple(g for g, _ in items), skip_if_unusable=_SKIP_UNUSABLE[style])
+                                         members=tuple(g for g, _ in items), skip_if_unusable=_skip_unusable(style))
             pos = {g: b for g, b in pos.items() if "gather" not in b}
         by_size = {}
         for g, batch in pos.items():
@@ -346,7 +399,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
                 by_size.setdefault(n, []).append((g, kw))
         for items in by_size.values():           # a ragged last batch forms its own (sub-)group step
             group.train_step([kw for _, kw in items], members=tuple(g for g, _ in items),
-                             skip_if_unusable=_SKIP_UNUSABLE[style])
+                             skip_if_unusable=_skip_unusable(style))
 
     _run_subgroups(group, loaders, members, concurrent, advance)
     if concurrent > 1:
@@ -488,7 +541,7 @@ def validate_lockstep(group, loaders, style, device, members=None, concurrent=1)
         for g, batch in pos.items():
             if style == "final":
                 kw = dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'])
-            elif style == "partial":
+            elif style in ("partial", "simmlm"):
                 kw = dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], mask=batch['mask'])
             elif style == "rnaseq":
                 kw = dict(rna=batch['rnaseq'])
@@ -508,9 +561,10 @@ def validate_lockstep(group, loaders, style, device, members=None, concurrent=1)
                     label = _t(batch['label'], device)
                     h, t, e = hz.clone(), label[:, 0], label[:, 1]
                     a["total"] += losses.cox_loss(h, e, t).item(); a["nb"] += 1
-                elif style == "partial":
+                elif style in ("partial", "simmlm"):
                     label = _t(batch['label'], device)
-                    smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
+                    smask = (torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device) if style == "partial"
+                             else _simmlm_rows(batch, device))
                     if int(smask.sum()) == 0:
                         continue
                     h, t, e = hz[smask].clone(), label[smask, 0], label[smask, 1]

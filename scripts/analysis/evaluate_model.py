@@ -38,6 +38,7 @@ MODELS = {
     "partial": ("PartialModalityNet", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=608, complete=False), 608, 3, 8),
     "simple": ("SimpleFusionModel", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=88, complete=True), 88, 3, 8),
     "flexible": ("FlexibleMultimodalModel", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=608, complete=False), 608, 3, 16),
+    "simmim": ("SimMLM_SurvivalNet", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=608, complete=False), 608, 3, 8),
     "rnaseq": ("RNASeqSurvivalModel", lambda c: dict(input_dim=c["rnaseq"].shape[1]), dict(seed=427, complete=True, dims=(32, 32, 32)), 240, 3, 16),
 }
 
@@ -54,11 +55,14 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
     cls, ctor, ckw, n_default, folds_default, batch_default = MODELS[kind]
     n_folds, batch_size = n_folds or env_int("MMS_FOLDS", folds_default), batch_size or env_int("MMS_BATCH_SIZE", batch_default)
     n = env_int("MMS_PATIENTS", n_default)
-    if kind == "partial":
+    if kind in ("partial", "simmim"):
         cohort = load_or_make_cohort(device, n=n, **ckw)                 # data/processed/* under MMS_DATA_ROOT when present
     else:
         cohort = data.cohort_to(data.make_cohort(n=n, **ckw), device)
-    labelled = torch.nonzero(cohort["has_survival"].cpu()).reshape(-1).numpy()
+    keep = cohort["has_survival"].cpu().bool()
+    if kind == "simmim":              # simmlm_training.py's cohort: labelled patients with at least one modality
+        keep &= (cohort["mask"].cpu() != 0).any(1)
+    labelled = torch.nonzero(keep).reshape(-1).numpy()
     _, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
     idx = labelled[val]
     model = getattr(models, cls)(**ctor(cohort))
@@ -71,7 +75,7 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
         ct, rna, clin, mask = cohort["image"][j], cohort["rnaseq"][j], cohort["clinical"][j], cohort["mask"][j]
         if kind == "final":
             hz, _ = eng.forward_eval(ct, rna, clin)
-        elif kind == "partial":
+        elif kind in ("partial", "simmim"):
             hz, _ = eng.forward_eval(ct, rna, clin, mask=mask)
         elif kind == "simple":
             hz, _ = eng.forward_eval(ct, rna)

@@ -14,6 +14,7 @@ RESULTS_FILES = {          # display name -> file written by scripts/training/<e
     "Simple Fusion": "results/simple_fusion/cv_results.json",
     "Flexible Multimodal": "results/flexible_multimodal/cv_results.json",
     "Final Multimodal": "results/final/cv_results.json",
+    "SimMLM": "results/simmim/cv_results.json",              # scripts/training/simmlm_training.py
 }
 
 
