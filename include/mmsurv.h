@@ -675,6 +675,24 @@ int mms_dn121_backward_group(int ng, void* const* ws, int B, int D, int H, int W
                              const void* const* const* params, const float* const* dout, int lddout,
                              void* const* const* grads, const MmsDnOpts* opts, hipStream_t s);
 
+/* Fallback CT encoder in lock-step (csrc/fb_group.hip): fp32-MFMA group forms of the mms_fb_* ops on the same parameter blocks.  All
+ * members share one shape.  Taken: Cin = 1 (has_bn = 0) or Cin in {32, 64, 96, 128}; Cout a multiple of 32; out = ceil(in / 2);
+ * x / dy 16-byte aligned for Cin > 1; bwd_x needs has_bn; bwd_w splits the rows over FbConvP.msplit (1..1024) workgroups per tile.
+ * Anything else -- ng outside 1..MMS_MAX_GROUP, a NULL pointer the op uses -- is MMS_ERR_ARG and nothing is launched. */
+int mms_fb_conv_fwd_group(const FbConvP* p, int ng, hipStream_t s);
+int mms_fb_conv_bwd_w_group(const FbConvP* p, int ng, hipStream_t s);
+int mms_fb_conv_bwd_x_group(const FbConvP* p, int ng, hipStream_t s);
+int mms_fb_pool_fwd_group(const FbPoolP* p, int ng, hipStream_t s);
+int mms_fb_pool_bwd_group(const FbPoolP* p, int ng, hipStream_t s);
+/* whole-encoder drivers (arguments as mms_fb_forward / _backward, one entry per member; ws[g]: mms_fb_workspace_bytes, initialised by
+ * mms_fb_init).  No copies and no synchronisation: capturable into a HIP graph. */
+int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
+                         const void* const* const* params, const void* const* const* buffers, float* const* out,
+                         int ldo, int train, hipStream_t s);
+int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
+                          const void* const* const* params, const float* const* dout, int lddout,
+                          void* const* const* grads, hipStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,10 +80,9 @@ class FoldGroupEngine:
                                "RNA-seq-only folds one engine at a time (SurvivalEngine.train_step)")
         eng = [self.engines[i] for i in members]
         Ps = [e.plan(B, dims) for e in eng]
-        if any(P.fallback and P.has_enc for P in Ps):
-            raise NotImplementedError("fold groups drive the DenseNet121-3D encoder; the 3-conv fallback encoder has no "
-                                      "group entry points (train those folds one at a time)")
         GP = _GroupPlan()
+        # 3-conv fallback encoder (models.USE_MONAI = False): the mms_fb_*_group drivers; none of the DenseNet launch options apply
+        GP.fallback = bool(Ps[0].has_enc and Ps[0].fallback)
         GP.members, GP.eng, GP.Ps, GP.B, GP.dims = members, eng, Ps, B, (tuple(dims) if dims is not None else ())
         prog = eng[0].prog
         GP.ng = len(eng)
@@ -125,8 +124,12 @@ class FoldGroupEngine:
         prog = GP.eng[0].prog
         if GP.has_enc:
             B, (D, H, W) = GP.B, GP.dims
-            _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
-                                                   1 if train else 0, self._opts_arg(GP), st), "mms_dn121_forward_group")
+            if GP.fallback:
+                _lib.check(lib.mms_fb_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                                                    1 if train else 0, st), "mms_fb_forward_group")
+            else:
+                _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                                                       1 if train else 0, self._opts_arg(GP), st), "mms_dn121_forward_group")
         self._forward_heads(GP, train)
 
     def _forward_heads(self, GP, train):
@@ -152,6 +155,8 @@ class FoldGroupEngine:
     def _sync_packs(GP):
         """Derived conv2 packs of every member current (SurvivalEngine.sync_packs: a no-op unless the weights were changed outside the
         fused step since the last call)."""
+        if GP.fallback:        # (no derived weight state on this encoder)
+            return
         for e in GP.eng:
             e.sync_packs()
 
@@ -188,8 +193,12 @@ class FoldGroupEngine:
             _lib.check(lib.mms_linear_bwd_group(GP.lin_bwd[i], ng, st), "mms_linear_bwd_group")
         if GP.has_enc:
             B, (D, H, W) = GP.B, GP.dims
-            _lib.check(lib.mms_dn121_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, self._opts_arg(GP), st),
-                       "mms_dn121_backward_group")
+            if GP.fallback:
+                _lib.check(lib.mms_fb_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, st),
+                           "mms_fb_backward_group")
+            else:
+                _lib.check(lib.mms_dn121_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, self._opts_arg(GP), st),
+                           "mms_dn121_backward_group")
         ad = GP.adam[bool(skip_if_unusable)]
         _lib.check(lib.mms_grad_sumsq_group(ad, ng, st), "mms_grad_sumsq_group")
         _lib.check(lib.mms_clip_adam_group(ad, ng, st), "mms_clip_adam_group")
