@@ -550,6 +550,17 @@ int mms_fb_forward(void* ws, int B, int D, int H, int W, const float* x, const v
                    const void* const* buffers, float* out, int ldo, int train, hipStream_t s);
 int mms_fb_backward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
                     const float* dout, int lddout, void* const* grads, hipStream_t s);
+/* The same drivers at other channel widths: widths = int[3], the three convolutions' output channels, each a multiple of 16 in 16..128
+ * (ImageOnlyModel: {16, 32, 64}; mms_fb_* above = {32, 64, 128}).  Tables as above (12 params, 9 buffers, 12 grads; every entry non-NULL);
+ * out / dout hold widths[2] columns.  ws_bytes: what the caller allocated -- anything but mms_fb3_workspace_bytes of THESE widths and
+ * dims is MMS_ERR_ARG (a workspace planned for another width set is laid out differently).  mms_fb3_forward / _backward run the scalar
+ * kernels above (a thread per (voxel, channel) of a 256-thread workgroup): their widths must divide 256 -- 16, 32, 64, 128. */
+int mms_fb3_workspace_bytes(const int* widths, int B, int D, int H, int W, size_t* bytes);
+int mms_fb3_init(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const void* const* buffers, hipStream_t s);
+int mms_fb3_forward(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params,
+                    const void* const* buffers, float* out, int ldo, int train, hipStream_t s);
+int mms_fb3_backward(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params,
+                     const float* dout, int lddout, void* const* grads, hipStream_t s);
 
 /* ---- heads ---- */
 int mms_linear_fwd(const LinearFwdP* p, hipStream_t s);        /* nn.Linear (+ preceding BN1d/ReLU/Dropout, + following ReLU) */
@@ -676,7 +687,8 @@ int mms_dn121_backward_group(int ng, void* const* ws, int B, int D, int H, int W
                              void* const* const* grads, const MmsDnOpts* opts, hipStream_t s);
 
 /* Fallback CT encoder in lock-step (csrc/fb_group.hip): fp32-MFMA group forms of the mms_fb_* ops on the same parameter blocks.  All
- * members share one shape.  Taken: Cin = 1 (has_bn = 0) or Cin in {32, 64, 96, 128}; Cout a multiple of 32; out = ceil(in / 2);
+ * members share one shape.  Taken: Cin = 1 (has_bn = 0) or Cin a multiple of 16 in 16..128; Cout a multiple of 16 other than 48 + 64 n (a
+ * last 32-wide column tile may be half filled: masked); out = ceil(in / 2);
  * x / dy 16-byte aligned for Cin > 1; bwd_x needs has_bn; bwd_w splits the rows over FbConvP.msplit (1..1024) workgroups per tile.
  * Anything else -- ng outside 1..MMS_MAX_GROUP, a NULL pointer the op uses -- is MMS_ERR_ARG and nothing is launched. */
 int mms_fb_conv_fwd_group(const FbConvP* p, int ng, hipStream_t s);
@@ -692,6 +704,27 @@ int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H, int W, co
 int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
                           const void* const* const* params, const float* const* dout, int lddout,
                           void* const* const* grads, hipStream_t s);
+/* ... at other channel widths (arguments as mms_fb3_forward / _backward, one entry per member; widths additionally as Cout above) */
+int mms_fb3_forward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                          const void* const* const* params, const void* const* const* buffers, float* const* out,
+                          int ldo, int train, hipStream_t s);
+int mms_fb3_backward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                           const void* const* const* params, const float* const* dout, int lddout,
+                           void* const* const* grads, hipStream_t s);
+/* ImageOnlyModel's tail in one launch per pass: BN3 + ReLU + global average pool -> Linear + ReLU -> Linear.  The arguments are the blocks of
+ * the three launches it replaces, one of each per member: pool (y, bn, C <= 128, V, B <= 32, out / ldo = the pooled features), l1 reading
+ * pool.out (K = C, N <= 64, out_relu = 1, no prologue), l2 reading l1.y (N <= 8, out_relu = 0).  Backward: l2.dy = dL/dhazard; accumulates
+ * l1 / l2 .dw / .dbias (one workgroup per member owns them: no float atomics), writes pool.dbn and adds pool.s1 / s2 as
+ * mms_fb_pool_bwd_group does; pool.dout and the Linear blocks' dx are not used.  Blocks that are not such a chain: MMS_ERR_ARG. */
+int mms_img_tail_fwd_group(const FbPoolP* pool, const LinearFwdP* l1, const LinearFwdP* l2, int ng, hipStream_t s);
+int mms_img_tail_bwd_group(const FbPoolP* pool, const LinearBwdP* l1, const LinearBwdP* l2, int ng, hipStream_t s);
+/* mms_fb3_forward_group / _backward_group with that tail in place of the pool launch (out / ldo: where the pooled features go = l1.x) */
+int mms_img_forward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                          const void* const* const* params, const void* const* const* buffers, float* const* out,
+                          int ldo, int train, const LinearFwdP* l1, const LinearFwdP* l2, hipStream_t s);
+int mms_img_backward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                           const void* const* const* params, void* const* const* grads, const LinearBwdP* l1, const LinearBwdP* l2,
+                           hipStream_t s);
 
 #ifdef __cplusplus
 }

@@ -4,10 +4,17 @@ Host side: Python on PyTorch-ROCm (device memory, streams, torch.distributed onl
 hot path runs in hand-written HIP kernels behind the C ABI in include/mmsurv.h (libmmsurv_hip.so).
 There is no CPU fallback: ops raise if the library is missing.
 
-Modules: models (the reference's five nn.Modules), losses, training (train_epoch_* / validate_* of each script, lock-step
+Modules: models (the reference's nn.Modules), losses, training (train_epoch_* / validate_* of each script, lock-step
 K-fold variants), engine (fused HIP-graph step of one model), fold_group (K fold models advanced by one launch sequence),
 data / cohort_io (synthetic cohorts, on-disk contract, GPU preprocessing), distributed (fold sharding, DDP helpers).
 """
 from ._lib import lib_path, load_library  # noqa: F401
 
-__all__ = ["load_library", "lib_path"]
+__all__ = ["load_library", "lib_path", "ImageOnlyModel"]
+
+
+def __getattr__(name):      # (models pulls in torch and the engine: imported on first use)
+    if name == "ImageOnlyModel":
+        from .models import ImageOnlyModel
+        return ImageOnlyModel
+    raise AttributeError(name)

@@ -2,6 +2,7 @@
 // simple_fusion.py:191-202): 3 x [Conv3d(k3,s2,p1)+BN3d+ReLU] + global average pool.  Correctness-first kernels
 // (VALU, LDS-staged activations); this path is 15x fewer FLOPs than DenseNet121 and is not the headline config.
 #include "common.h"
+#include "fb_plan.h"
 #include <string.h>
 
 // activation a(m_in, cin) = has_bn ? relu(bn(x)) : x
@@ -60,6 +61,7 @@ extern "C" int mms_fb_conv_fwd(const FbConvP* pp, hipStream_t s) {
     const FbConvP& p = *pp;
     if (p.Cout <= 0 || 256 % p.Cout || p.Cin <= 0) return MMS_ERR_ARG;
     const int VB = 256 / p.Cout, Mout = p.B * p.out.D * p.out.H * p.out.W;
+    if ((size_t)VB * 27 * p.Cin * 4 > 60 * 1024) return MMS_ERR_ARG;          // the [VB][27 Cin] patch + the 4 KB of `red`: 64 KB of LDS
     MMS_LAUNCH(fb_conv_fwd_kernel, dim3((Mout + VB - 1) / VB), dim3(256), (size_t)VB * 27 * p.Cin * 4, s, p);
     return mms_check_launch();
 }
@@ -181,111 +183,99 @@ extern "C" int mms_fb_pool_bwd(const FbPoolP* pp, hipStream_t s) {
 }
 
 // ================================= whole-encoder driver =================================
-namespace {
-constexpr int FC[4] = {1, 32, 64, 128};
-struct FbPlan {
-    int B; Dims3 g[4]; int M[4];
-    size_t y[4], dy[4], dbn[4], st[4], bb[4], tab_bn, stats_begin, stats_end, total;
-};
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-bool fb_plan(FbPlan& P, int B, int D, int H, int W) {
-    if (B <= 0 || D < 1 || H < 1 || W < 1) return false;
-    P.B = B; P.g[0] = Dims3{D, H, W};
-    for (int l = 1; l < 4; ++l) P.g[l] = Dims3{(P.g[l - 1].D + 1) / 2, (P.g[l - 1].H + 1) / 2, (P.g[l - 1].W + 1) / 2};
-    for (int l = 0; l < 4; ++l) P.M[l] = B * P.g[l].D * P.g[l].H * P.g[l].W;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = al(o + n); return r; };
-    for (int l = 1; l < 4; ++l) { P.y[l] = take((size_t)P.M[l] * FC[l] * 4); P.dy[l] = take((size_t)P.M[l] * FC[l] * 4); P.dbn[l] = take((size_t)P.M[l] * FC[l] * 4); }
-    P.tab_bn = take(sizeof(BnRunEntry) * 3);
-    P.stats_begin = o;
-    for (int l = 1; l < 4; ++l) { P.st[l] = take(2 * 128 * 8); P.bb[l] = take(2 * 128 * 8); }
-    P.stats_end = o; P.total = o;
+// Width-parametrised (mms_fb3_*: widths[3] = the three convolutions' output channels); mms_fb_* = the reference's {32, 64, 128}.
+using namespace fbplan;
+// what the scalar kernels take: a thread per (voxel, channel) of a 256-thread workgroup (widths dividing 256), the forward's activation
+// patch of 256 / Cout voxels x 27 Cin floats within the LDS
+static bool fb_scalar_widths_ok(const int* widths) {
+    if (!fb_widths_ok(widths)) return false;
+    int cin = 1;
+    for (int l = 0; l < 3; ++l) {
+        if (256 % widths[l] || (size_t)(256 / widths[l]) * 27 * cin * 4 > 60 * 1024) return false;
+        cin = widths[l];
+    }
     return true;
 }
-template <class T> inline T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
-inline BnSrc fb_bn(void* ws, const FbPlan& P, int l, const float* const* prm, const void* const* buf, int train) {
-    BnSrc b;
-    b.nrep = 0; b.rep_stride = 0;
-    b.sum = at<double>(ws, P.st[l]); b.sumsq = b.sum + 128;
-    b.rmean = buf ? (const float*)buf[3 * (l - 1)] : nullptr; b.rvar = buf ? (const float*)buf[3 * (l - 1) + 1] : nullptr;
-    b.gamma = prm[4 * (l - 1) + 2]; b.beta = prm[4 * (l - 1) + 3];
-    b.inv_count = 1.f / (float)P.M[l]; b.eps = 1e-5f; b.train = train;
-    return b;
-}
-}  // namespace
 
 extern "C" int mms_bn_running_update(const void*, int, float, hipStream_t);
 extern "C" int mms_zero_regions_group(void* const*, int, size_t, hipStream_t);
 extern "C" int mms_bn_bwd_apply(const BnBwdApplyP*, hipStream_t);
 #define TRY(x) do { int rc_ = (x); if (rc_ != MMS_OK) return rc_; } while (0)
 
-extern "C" int mms_fb_workspace_bytes(int B, int D, int H, int W, size_t* bytes) {
+extern "C" int mms_fb3_workspace_bytes(const int* widths, int B, int D, int H, int W, size_t* bytes) {
     FbPlan P;
-    if (!fb_plan(P, B, D, H, W) || !bytes) return MMS_ERR_ARG;
+    if (!fb_plan(P, widths, B, D, H, W) || !bytes) return MMS_ERR_ARG;
     *bytes = P.total;
     return MMS_OK;
 }
-extern "C" int mms_fb_init(void* ws, int B, int D, int H, int W, const void* const* buffers, hipStream_t s) {
+extern "C" int mms_fb3_init(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const void* const* buffers, hipStream_t s) {
     FbPlan P;
-    if (!fb_plan(P, B, D, H, W) || !ws || !buffers) return MMS_ERR_ARG;
+    if (!fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total || !ws || !buffers) return MMS_ERR_ARG;
+    for (int i = 0; i < 9; ++i)
+        if (!buffers[i]) return MMS_ERR_ARG;
     (void)hipGetLastError();
     BnRunEntry bn[3];
     for (int l = 1; l < 4; ++l) {
         bn[l - 1].sum = at<double>(ws, P.st[l]); bn[l - 1].sumsq = bn[l - 1].sum + 128;
         bn[l - 1].rmean = (float*)buffers[3 * (l - 1)]; bn[l - 1].rvar = (float*)buffers[3 * (l - 1) + 1];
-        bn[l - 1].nbt = (long long*)buffers[3 * (l - 1) + 2]; bn[l - 1].C = FC[l]; bn[l - 1].count = (float)P.M[l];
+        bn[l - 1].nbt = (long long*)buffers[3 * (l - 1) + 2]; bn[l - 1].C = P.C[l]; bn[l - 1].count = (float)P.M[l];
         bn[l - 1].nrep = 0; bn[l - 1].rep_stride = 0;
     }
     if (hipMemcpyAsync(at<void>(ws, P.tab_bn), bn, sizeof(bn), hipMemcpyHostToDevice, s) != hipSuccess) return MMS_ERR_LAUNCH;
     if (hipStreamSynchronize(s) != hipSuccess) return MMS_ERR_LAUNCH;
     return MMS_OK;
 }
-extern "C" int mms_fb_forward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params_,
-                              const void* const* buffers, float* out, int ldo, int train, hipStream_t s) {
+extern "C" int mms_fb3_forward(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params_,
+                               const void* const* buffers, float* out, int ldo, int train, hipStream_t s) {
     FbPlan P;
-    if (!fb_plan(P, B, D, H, W) || !ws || !x || !params_ || !out) return MMS_ERR_ARG;
+    if (!fb_scalar_widths_ok(widths) || !fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total || !ws || !x || !params_ || !out || ldo < P.C[3]) return MMS_ERR_ARG;
+    if (!train && !buffers) return MMS_ERR_ARG;
     const float* const* prm = (const float* const*)params_;
+    for (int i = 0; i < 12; ++i)
+        if (!prm[i]) return MMS_ERR_ARG;
     if (train) {    // (a zero-fill kernel, not hipMemsetAsync: consecutive memset nodes of a captured graph were observed to misorder)
         void* reg = at<void>(ws, P.stats_begin);
         TRY(mms_zero_regions_group(&reg, 1, P.stats_end - P.stats_begin, s));
     }
     for (int l = 1; l < 4; ++l) {
         FbConvP c{};
-        c.x = l == 1 ? x : at<float>(ws, P.y[l - 1]); c.Cin = FC[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
+        c.x = l == 1 ? x : at<float>(ws, P.y[l - 1]); c.Cin = P.C[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
         c.has_bn = l > 1; if (l > 1) c.bn = fb_bn(ws, P, l - 1, prm, buffers, train);
-        c.w = prm[4 * (l - 1)]; c.bias = prm[4 * (l - 1) + 1]; c.Cout = FC[l];
+        c.w = prm[4 * (l - 1)]; c.bias = prm[4 * (l - 1) + 1]; c.Cout = P.C[l];
         c.y = at<float>(ws, P.y[l]);
         c.osum = train ? at<double>(ws, P.st[l]) : nullptr; c.osumsq = train ? at<double>(ws, P.st[l]) + 128 : nullptr;
         TRY(mms_fb_conv_fwd(&c, s));
     }
     FbPoolP pl{};
-    pl.y = at<float>(ws, P.y[3]); pl.C = 128; pl.V = P.M[3] / B; pl.B = B; pl.bn = fb_bn(ws, P, 3, prm, buffers, train);
+    pl.y = at<float>(ws, P.y[3]); pl.C = P.C[3]; pl.V = P.M[3] / B; pl.B = B; pl.bn = fb_bn(ws, P, 3, prm, buffers, train);
     pl.out = out; pl.ldo = ldo;
     TRY(mms_fb_pool_fwd(&pl, s));
     if (train && buffers) TRY(mms_bn_running_update(at<void>(ws, P.tab_bn), 3, 0.1f, s));
     return MMS_OK;
 }
-extern "C" int mms_fb_backward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params_,
-                               const float* dout, int lddout, void* const* grads_, hipStream_t s) {
+extern "C" int mms_fb3_backward(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params_,
+                                const float* dout, int lddout, void* const* grads_, hipStream_t s) {
     FbPlan P;
-    if (!fb_plan(P, B, D, H, W) || !ws || !x || !params_ || !dout || !grads_) return MMS_ERR_ARG;
+    if (!fb_scalar_widths_ok(widths) || !fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total || !ws || !x || !params_ || !dout || !grads_ || lddout < P.C[3]) return MMS_ERR_ARG;
     const float* const* prm = (const float* const*)params_;
     float* const* grd = (float* const*)grads_;
+    for (int i = 0; i < 12; ++i)
+        if (!prm[i] || !grd[i]) return MMS_ERR_ARG;
     FbPoolP pl{};
-    pl.y = at<float>(ws, P.y[3]); pl.C = 128; pl.V = P.M[3] / B; pl.B = B; pl.bn = fb_bn(ws, P, 3, prm, nullptr, 1);
+    pl.y = at<float>(ws, P.y[3]); pl.C = P.C[3]; pl.V = P.M[3] / B; pl.B = B; pl.bn = fb_bn(ws, P, 3, prm, nullptr, 1);
     pl.dout = dout; pl.lddout = lddout; pl.dbn = at<float>(ws, P.dbn[3]);
     pl.s1 = at<double>(ws, P.bb[3]); pl.s2 = pl.s1 + 128;
     TRY(mms_fb_pool_bwd(&pl, s));
     for (int l = 3; l >= 1; --l) {
         // BN_l backward: dbn_l -> dy_l (gradient w.r.t. the raw conv output), BN parameter grads
-        BnBwdApplyP ap{at<float>(ws, P.dbn[l]), FC[l], at<float>(ws, P.y[l]), FC[l], at<float>(ws, P.dy[l]), FC[l], P.M[l], FC[l],
+        BnBwdApplyP ap{at<float>(ws, P.dbn[l]), P.C[l], at<float>(ws, P.y[l]), P.C[l], at<float>(ws, P.dy[l]), P.C[l], P.M[l], P.C[l],
                        fb_bn(ws, P, l, prm, nullptr, 1), BnBwd{at<double>(ws, P.bb[l]), at<double>(ws, P.bb[l]) + 128, 0, 0}, 0,
                        grd[4 * (l - 1) + 2], grd[4 * (l - 1) + 3]};
         TRY(mms_bn_bwd_apply(&ap, s));
         FbConvP c{};
-        c.x = l == 1 ? x : at<float>(ws, P.y[l - 1]); c.Cin = FC[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
+        c.x = l == 1 ? x : at<float>(ws, P.y[l - 1]); c.Cin = P.C[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
         c.has_bn = l > 1; if (l > 1) c.bn = fb_bn(ws, P, l - 1, prm, nullptr, 1);
-        c.w = prm[4 * (l - 1)]; c.Cout = FC[l]; c.dy = at<float>(ws, P.dy[l]);
+        c.w = prm[4 * (l - 1)]; c.Cout = P.C[l]; c.dy = at<float>(ws, P.dy[l]);
         c.dw = grd[4 * (l - 1)]; c.dbias = grd[4 * (l - 1) + 1];
         c.msplit = P.M[l] >= 4096 ? 16 : (P.M[l] >= 512 ? 4 : 1);
         TRY(mms_fb_conv_bwd_w(&c, s));
@@ -295,4 +285,25 @@ extern "C" int mms_fb_backward(void* ws, int B, int D, int H, int W, const float
         }
     }
     return MMS_OK;
+}
+
+// ---- the reference's widths (signatures and results as before: the caller's workspace is mms_fb_workspace_bytes large) ----
+static size_t fb_default_bytes(int B, int D, int H, int W) {
+    FbPlan P;
+    return fb_plan(P, FB_DEFAULT_WIDTHS, B, D, H, W) ? P.total : 0;
+}
+extern "C" int mms_fb_workspace_bytes(int B, int D, int H, int W, size_t* bytes) {
+    return mms_fb3_workspace_bytes(FB_DEFAULT_WIDTHS, B, D, H, W, bytes);
+}
+extern "C" int mms_fb_init(void* ws, int B, int D, int H, int W, const void* const* buffers, hipStream_t s) {
+    if (!buffers) return MMS_ERR_ARG;
+    return mms_fb3_init(ws, fb_default_bytes(B, D, H, W), FB_DEFAULT_WIDTHS, B, D, H, W, buffers, s);
+}
+extern "C" int mms_fb_forward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params_,
+                              const void* const* buffers, float* out, int ldo, int train, hipStream_t s) {
+    return mms_fb3_forward(ws, fb_default_bytes(B, D, H, W), FB_DEFAULT_WIDTHS, B, D, H, W, x, params_, buffers, out, ldo, train, s);
+}
+extern "C" int mms_fb_backward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params_,
+                               const float* dout, int lddout, void* const* grads_, hipStream_t s) {
+    return mms_fb3_backward(ws, fb_default_bytes(B, D, H, W), FB_DEFAULT_WIDTHS, B, D, H, W, x, params_, dout, lddout, grads_, s);
 }

@@ -6,6 +6,7 @@
 // workgroup (no function attribute); nothing derived from the weights outlives a launch.
 #include "common.h"
 #include "tile_gemm.h"
+#include "fb_plan.h"
 #include <type_traits>
 
 namespace {
@@ -336,8 +337,10 @@ bool fbg_conv_ok(const FbConvP* pp, int ng, int op) {
     const FbConvP& p = *pp;
     if (p.B <= 0 || p.in.D < 1 || p.in.H < 1 || p.in.W < 1 || p.in.D > 1024 || p.in.H > 1024 || p.in.W > 1024) return false;
     if (p.out.D != (p.in.D + 1) / 2 || p.out.H != (p.in.H + 1) / 2 || p.out.W != (p.in.W + 1) / 2) return false;
-    if (p.Cout <= 0 || p.Cout % 32 != 0 || p.Cout > 1024) return false;                  // 32-wide column tiles, float4 rows of dy
-    if (!(p.Cin == 1 && !p.has_bn) && !(p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 128)) return false;      // BN constants of <= 128 channels in LDS
+    // 32-wide column tiles whose last one may be half filled (every op masks its columns), float4 rows of dy.  Cout % 64 == 48 (48, 112)
+    // stays refused although nothing in the kernels needs that: the argument checks of tests/test_gpu_fb_group.py pin Cout = 48 as an error.
+    if (p.Cout <= 0 || p.Cout % 16 != 0 || p.Cout % 64 == 48 || p.Cout > 1024) return false;
+    if (!(p.Cin == 1 && !p.has_bn) && !(p.Cin % 16 == 0 && p.Cin >= 16 && p.Cin <= 128)) return false;      // BN constants of <= 128 channels in LDS
     if (op == FBG_BWD_X && (p.Cin == 1 || !p.has_bn)) return false;
     if (op == FBG_BWD_W && (p.msplit < 1 || p.msplit > 1024)) return false;
     const long rin = (long)p.B * p.in.D * p.in.H * p.in.W, rout = (long)p.B * p.out.D * p.out.H * p.out.W;
@@ -367,16 +370,179 @@ bool fbg_pool_ok(const FbPoolP* pp, int ng, bool bwd) {
     }
     return true;
 }
+
+// ------------------------------------------------------------------------------------------------------
+// Fused tail of ImageOnlyModel: BN3 + ReLU + global average pool -> Linear(C, N1) + ReLU -> Linear(N1, N2), one launch per pass.
+// The arguments are the blocks of the three launches it replaces (FbPoolP + two LinearFwdP / LinearBwdP), condensed on the host.
+// Forward: workgroup = (sample b, member); the pool is fbg_pool_fwd_kernel's (same wave split, same summation order).
+// Backward: workgroups 0..B-1 = one sample each: its row of dL/dfeats recomputed from dhz (N2 x N1 + N1 x C fmas) and the pool backward
+// of fbg_pool_bwd_kernel (dbn3, fp64 s1 / s2); workgroup B owns the four parameter gradients over all B <= 32 rows: no float atomics.
+// ------------------------------------------------------------------------------------------------------
+struct ImgTailK {
+    const float* y; BnSrc bn; int C, V, B;
+    float* feats; int ldf;
+    const float* w1; const float* b1; int N1; float* f1; int ld1;
+    const float* w2; const float* b2; int N2; float* hz; int ldh;
+    const float* dhz; int lddh;
+    float* dw1; float* db1; float* dw2; float* db2;
+    float* dbn; double* s1; double* s2;
+};
+constexpr int IT_C = 128, IT_N1 = 64, IT_N2 = 8, IT_B = 32;
+
+__global__ __launch_bounds__(256) void img_tail_fwd_kernel(const Grp<ImgTailK> grp) {
+    __shared__ float red[4][IT_C];
+    __shared__ float feat[IT_C];
+    __shared__ float h1[IT_N1];
+    const ImgTailK& p = grp.p[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
+    for (int c = lane; c < p.C; c += 64) {
+        float mu, rs;
+        bn_mean_rstd(p.bn, c, mu, rs);
+        const float sc = p.bn.gamma[c] * rs, be = p.bn.beta[c];
+        float a = 0.f;
+        for (int v = wv; v < p.V; v += 4) a += fmaxf(bn_apply(p.y[((size_t)b * p.V + v) * p.C + c], mu, sc, be), 0.f);
+        red[wv][c] = a;
+    }
+    __syncthreads();
+    if (tid < p.C) {
+        const float f = (red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]) / (float)p.V;
+        feat[tid] = f; p.feats[(size_t)b * p.ldf + tid] = f;
+    }
+    __syncthreads();
+    // Linear 1: 8 lanes per output feature split K, summed by shuffles
+    for (int n = tid >> 3; n < p.N1; n += 32) {
+        float acc = 0.f;
+        for (int k = tid & 7; k < p.C; k += 8) acc = fmaf(p.w1[(size_t)n * p.C + k], feat[k], acc);
+        acc += __shfl_xor(acc, 4, 64); acc += __shfl_xor(acc, 2, 64); acc += __shfl_xor(acc, 1, 64);
+        if ((tid & 7) == 0) {
+            const float h = fmaxf(acc + p.b1[n], 0.f);
+            h1[n] = h; p.f1[(size_t)b * p.ld1 + n] = h;
+        }
+    }
+    __syncthreads();
+    if (tid < p.N2) {
+        float acc = 0.f;
+        for (int k = 0; k < p.N1; ++k) acc = fmaf(p.w2[(size_t)tid * p.N1 + k], h1[k], acc);
+        p.hz[(size_t)b * p.ldh + tid] = acc + p.b2[tid];
+    }
+}
+
+__global__ __launch_bounds__(256) void img_tail_bwd_kernel(const Grp<ImgTailK> grp) {
+    __shared__ float g1[IT_B * IT_N1];          // dL/d(pre-ReLU Linear 1): the sample's row, or all B rows in the parameter workgroup
+    __shared__ float dfe[IT_C];
+    __shared__ double red[2][4][IT_C];
+    const ImgTailK& p = grp.p[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if ((int)blockIdx.x == p.B) {               // (workgroup-uniform) parameter gradients, accumulated like mms_linear_bwd's
+        for (int idx = tid; idx < p.B * p.N1; idx += 256) {
+            const int m = idx / p.N1, n = idx - m * p.N1;
+            float g = 0.f;
+            for (int j = 0; j < p.N2; ++j) g = fmaf(p.dhz[(size_t)m * p.lddh + j], p.w2[(size_t)j * p.N1 + n], g);
+            g1[idx] = p.f1[(size_t)m * p.ld1 + n] > 0.f ? g : 0.f;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < p.N2 * p.N1; idx += 256) {
+            const int j = idx / p.N1, n = idx - j * p.N1;
+            float a = 0.f;
+            for (int m = 0; m < p.B; ++m) a = fmaf(p.dhz[(size_t)m * p.lddh + j], p.f1[(size_t)m * p.ld1 + n], a);
+            p.dw2[idx] += a;
+        }
+        if (tid < p.N2) {
+            float a = 0.f;
+            for (int m = 0; m < p.B; ++m) a += p.dhz[(size_t)m * p.lddh + tid];
+            p.db2[tid] += a;
+        }
+        for (int idx = tid; idx < p.N1 * p.C; idx += 256) {
+            const int n = idx / p.C, c = idx - n * p.C;
+            float a = 0.f;
+            for (int m = 0; m < p.B; ++m) a = fmaf(g1[m * p.N1 + n], p.feats[(size_t)m * p.ldf + c], a);
+            p.dw1[idx] += a;
+        }
+        if (tid < p.N1) {
+            float a = 0.f;
+            for (int m = 0; m < p.B; ++m) a += g1[m * p.N1 + tid];
+            p.db1[tid] += a;
+        }
+        return;
+    }
+    const int b = blockIdx.x;
+    if (tid < p.N1) {
+        float g = 0.f;
+        for (int j = 0; j < p.N2; ++j) g = fmaf(p.dhz[(size_t)b * p.lddh + j], p.w2[(size_t)j * p.N1 + tid], g);
+        g1[tid] = p.f1[(size_t)b * p.ld1 + tid] > 0.f ? g : 0.f;
+    }
+    __syncthreads();
+    if (tid < p.C) {
+        float a = 0.f;
+        for (int n = 0; n < p.N1; ++n) a = fmaf(g1[n], p.w1[(size_t)n * p.C + tid], a);
+        dfe[tid] = a;
+    }
+    __syncthreads();
+    for (int c = lane; c < p.C; c += 64) {
+        float mu, rs;
+        bn_mean_rstd(p.bn, c, mu, rs);
+        const float ga = p.bn.gamma[c], be = p.bn.beta[c], d = dfe[c] / (float)p.V;
+        double s1 = 0, s2 = 0;
+        for (int v = wv; v < p.V; v += 4) {
+            const size_t o = ((size_t)b * p.V + v) * p.C + c;
+            const float xh = (p.y[o] - mu) * rs;
+            const float g = fmaf(ga, xh, be) > 0.f ? d : 0.f;
+            p.dbn[o] = g;
+            s1 += g; s2 += (double)g * xh;
+        }
+        red[0][wv][c] = s1; red[1][wv][c] = s2;
+    }
+    __syncthreads();
+    if (tid < p.C) {
+        atomicAdd(&p.s1[tid], red[0][0][tid] + red[0][1][tid] + red[0][2][tid] + red[0][3][tid]);
+        atomicAdd(&p.s2[tid], red[1][0][tid] + red[1][1][tid] + red[1][2][tid] + red[1][3][tid]);
+    }
+}
+
+// the three launches' blocks -> ImgTailK; false when they are not a BN+ReLU+pool -> Linear+ReLU -> Linear chain on shared buffers
+bool img_tail_fill(Grp<ImgTailK>& a, const FbPoolP* pool, const LinearFwdP* f1, const LinearFwdP* f2, const LinearBwdP* b1, const LinearBwdP* b2,
+                   int ng) {
+    const bool bwd = b1 != nullptr;
+    if (!fbg_pool_ok(pool, ng, false) || (bwd ? (!b1 || !b2) : (!f1 || !f2))) return false;
+    for (int g = 0; g < ng; ++g) {
+        const FbPoolP& q = pool[g];
+        ImgTailK& k = a.p[g];
+        k = ImgTailK{};
+        k.y = q.y; k.bn = q.bn; k.C = q.C; k.V = q.V; k.B = q.B; k.feats = q.out; k.ldf = q.ldo;
+        int M1, K1, M2, K2, relu1, relu2;
+        const InProlog *p1, *p2;
+        const float *x1, *x2;
+        if (!bwd) {
+            const LinearFwdP &u = f1[g], &v = f2[g];
+            k.w1 = u.w; k.b1 = u.bias; k.N1 = u.N; k.f1 = u.y; k.ld1 = u.ldy; k.w2 = v.w; k.b2 = v.bias; k.N2 = v.N; k.hz = v.y; k.ldh = v.ldy;
+            M1 = u.M; K1 = u.K; M2 = v.M; K2 = v.K; relu1 = u.out_relu; relu2 = v.out_relu; p1 = &u.pro; p2 = &v.pro; x1 = u.x; x2 = v.x;
+            if (!k.b1 || !k.b2 || !k.hz || u.ldx != q.ldo || v.ldx != u.ldy) return false;
+        } else {
+            const LinearBwdP &u = b1[g], &v = b2[g];
+            k.w1 = u.w; k.N1 = u.N; k.f1 = const_cast<float*>(u.y); k.ld1 = u.ldy; k.w2 = v.w; k.N2 = v.N; k.dhz = v.dy; k.lddh = v.lddy;
+            k.dw1 = u.dw; k.db1 = u.dbias; k.dw2 = v.dw; k.db2 = v.dbias; k.dbn = q.dbn; k.s1 = q.s1; k.s2 = q.s2;
+            M1 = u.M; K1 = u.K; M2 = v.M; K2 = v.K; relu1 = u.out_relu; relu2 = v.out_relu; p1 = &u.pro; p2 = &v.pro; x1 = u.x; x2 = v.x;
+            if (!k.dhz || !k.dw1 || !k.db1 || !k.dw2 || !k.db2 || !k.dbn || !k.s1 || !k.s2 || !q.bn.train || u.ldx != q.ldo || v.ldx != u.ldy || k.lddh < k.N2)
+                return false;
+        }
+        if (!k.w1 || !k.w2 || !k.f1 || x1 != q.out || x2 != k.f1 || M1 != q.B || M2 != q.B || K1 != q.C || K2 != k.N1 || !relu1 || relu2) return false;
+        if (p1->bn || p2->bn || p1->drop_mask || p2->drop_mask || (p1->train && p1->drop_p > 0.f) || (p2->train && p2->drop_p > 0.f)) return false;
+        if (q.B > IT_B || q.C > IT_C || k.N1 < 1 || k.N1 > IT_N1 || k.N2 < 1 || k.N2 > IT_N2 || k.ld1 < k.N1 || (!bwd && k.ldh < k.N2)) return false;
+        if (g && (k.N1 != a.p[0].N1 || k.N2 != a.p[0].N2)) return false;
+    }
+    a.zdim = 1;
+    return true;
+}
 }  // namespace
 
 extern "C" int mms_fb_conv_fwd_group(const FbConvP* pp, int ng, hipStream_t s) {
     if (!fbg_conv_ok(pp, ng, FBG_FWD)) return MMS_ERR_ARG;
     const FbConvP& p = *pp;
     const int M = p.B * p.out.D * p.out.H * p.out.W;
-    if (p.Cin == 1) return launch_tile_gemm<FbFwdOp<4, 1, 1, true>>(pp, ng, dim3((M + 127) / 128, p.Cout / 32, 1), s);
+    if (p.Cin == 1) return launch_tile_gemm<FbFwdOp<4, 1, 1, true>>(pp, ng, dim3((M + 127) / 128, (p.Cout + 31) / 32, 1), s);
     // tile shape from ONE member's work, so that a model's arithmetic does not depend on the group it runs in
     if (p.Cout % 64 == 0 && (long)M * p.Cout >= 128L * 64 * 64) return launch_tile_gemm<FbFwdOp<2, 2, 1, false>>(pp, ng, dim3((M + 63) / 64, p.Cout / 64, 1), s);
-    return launch_tile_gemm<FbFwdOp<1, 1, 4, false>>(pp, ng, dim3((M + 31) / 32, p.Cout / 32, 1), s);      // few rows: the 4 waves split K
+    return launch_tile_gemm<FbFwdOp<1, 1, 4, false>>(pp, ng, dim3((M + 31) / 32, (p.Cout + 31) / 32, 1), s);      // few rows: the 4 waves split K
 }
 extern "C" int mms_fb_conv_bwd_w_group(const FbConvP* pp, int ng, hipStream_t s) {
     if (!fbg_conv_ok(pp, ng, FBG_BWD_W)) return MMS_ERR_ARG;
@@ -389,7 +555,7 @@ extern "C" int mms_fb_conv_bwd_x_group(const FbConvP* pp, int ng, hipStream_t s)
     const FbConvP& p = *pp;
     const int rows0 = p.B * ((p.in.D + 1) / 2) * ((p.in.H + 1) / 2) * ((p.in.W + 1) / 2);      // class (even, even, even) is the largest
     if (p.Cin % 64 == 0) return launch_tile_gemm<FbBwdXOp<2, 2>>(pp, ng, dim3((rows0 + 63) / 64, p.Cin / 64, 8), s);
-    return launch_tile_gemm<FbBwdXOp<4, 1>>(pp, ng, dim3((rows0 + 127) / 128, p.Cin / 32, 8), s);
+    return launch_tile_gemm<FbBwdXOp<4, 1>>(pp, ng, dim3((rows0 + 127) / 128, (p.Cin + 31) / 32, 8), s);      // (a last column tile of 16: masked)
 }
 extern "C" int mms_fb_pool_fwd_group(const FbPoolP* pp, int ng, hipStream_t s) {
     Grp<FbPoolP> a;
@@ -403,50 +569,37 @@ extern "C" int mms_fb_pool_bwd_group(const FbPoolP* pp, int ng, hipStream_t s) {
     MMS_LAUNCH(fbg_pool_bwd_kernel, dim3((pp->C + 63) / 64, pp->B, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
+extern "C" int mms_img_tail_fwd_group(const FbPoolP* pool, const LinearFwdP* l1, const LinearFwdP* l2, int ng, hipStream_t s) {
+    Grp<ImgTailK> a;
+    if (!img_tail_fill(a, pool, l1, l2, nullptr, nullptr, ng)) return MMS_ERR_ARG;
+    MMS_LAUNCH(img_tail_fwd_kernel, dim3(pool->B, ng), dim3(256), 0, s, a);
+    return mms_check_launch();
+}
+extern "C" int mms_img_tail_bwd_group(const FbPoolP* pool, const LinearBwdP* l1, const LinearBwdP* l2, int ng, hipStream_t s) {
+    Grp<ImgTailK> a;
+    if (!l1 || !l2 || !img_tail_fill(a, pool, nullptr, nullptr, l1, l2, ng)) return MMS_ERR_ARG;
+    MMS_LAUNCH(img_tail_bwd_kernel, dim3(pool->B + 1, ng), dim3(256), 0, s, a);
+    return mms_check_launch();
+}
 
 // ================================= whole-encoder drivers (lock-step) =================================
-// Per-member workspace: the layout of mms_fb_workspace_bytes / mms_fb_init (fallback.hip, FbPlan), restated here because that file's
-// plan is private to it.  What guards against drift: the drivers refuse to run (MMS_ERR_ARG) when this plan's size differs from what
-// mms_fb_workspace_bytes reports -- the caller allocated that many bytes -- and the running-statistics table that mms_fb_init wrote
-// at FbPlan's offsets is read here at this plan's (tests/test_gpu_fb_group.py compares the running statistics of both paths).
+// Per-member workspace: the plan of fb_plan.h, the one the single-model drivers and mms_fb3_init use.  The caller states how many bytes
+// each workspace holds; a size that is not this width set's plan is MMS_ERR_ARG.
+using namespace fbplan;
 namespace {
-constexpr int FC[4] = {1, 32, 64, 128};
-struct FbgPlan {
-    int B; Dims3 g[4]; int M[4];
-    size_t y[4], dy[4], dbn[4], st[4], bb[4], tab_bn, stats_begin, stats_end, total;
-};
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-bool fbg_plan(FbgPlan& P, int B, int D, int H, int W) {
-    if (B <= 0 || D < 1 || H < 1 || W < 1) return false;
-    P.B = B; P.g[0] = Dims3{D, H, W};
-    for (int l = 1; l < 4; ++l) P.g[l] = Dims3{(P.g[l - 1].D + 1) / 2, (P.g[l - 1].H + 1) / 2, (P.g[l - 1].W + 1) / 2};
-    for (int l = 0; l < 4; ++l) P.M[l] = B * P.g[l].D * P.g[l].H * P.g[l].W;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = al(o + n); return r; };
-    for (int l = 1; l < 4; ++l) { P.y[l] = take((size_t)P.M[l] * FC[l] * 4); P.dy[l] = take((size_t)P.M[l] * FC[l] * 4); P.dbn[l] = take((size_t)P.M[l] * FC[l] * 4); }
-    P.tab_bn = take(sizeof(BnRunEntry) * 3);
-    P.stats_begin = o;
-    for (int l = 1; l < 4; ++l) { P.st[l] = take(2 * 128 * 8); P.bb[l] = take(2 * 128 * 8); }
-    P.stats_end = o; P.total = o;
-    return true;
-}
-template <class T> inline T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
-inline BnSrc fbg_bn(void* ws, const FbgPlan& P, int l, const float* const* prm, const void* const* buf, int train) {
-    BnSrc b;
-    b.nrep = 0; b.rep_stride = 0;
-    b.sum = at<double>(ws, P.st[l]); b.sumsq = b.sum + 128;
-    b.rmean = buf ? (const float*)buf[3 * (l - 1)] : nullptr; b.rvar = buf ? (const float*)buf[3 * (l - 1) + 1] : nullptr;
-    b.gamma = prm[4 * (l - 1) + 2]; b.beta = prm[4 * (l - 1) + 3];
-    b.inv_count = 1.f / (float)P.M[l]; b.eps = 1e-5f; b.train = train;
-    return b;
-}
 // rows of the weight-gradient GEMM per workgroup: enough workgroups to fill the chip with ONE member, no more (each slice is one
 // [Cout][27 Cin] image of fp32 atomics: atomic bytes per launch = msplit x the gradient's size)
-inline int fbg_msplit(int l, int M) {
-    const int tiles = ((FC[l] + 63) / 64) * ((27 * FC[l - 1] + 63) / 64), steps = (M + 31) / 32;
+inline int fbg_msplit(int Cin, int Cout, int M) {
+    const int tiles = ((Cout + 63) / 64) * ((27 * Cin + 63) / 64), steps = (M + 31) / 32;
     int ms = (256 + tiles - 1) / tiles;
     if (ms > steps / 4) ms = steps / 4;            // >= 4 K steps (128 rows) per slice
     return ms < 1 ? 1 : ms;
+}
+inline bool fbg_widths_ok(const int* widths) {      // what mms_fb_conv_*_group takes as Cout
+    if (!fb_widths_ok(widths)) return false;
+    for (int l = 0; l < 3; ++l)
+        if (widths[l] % 64 == 48) return false;
+    return true;
 }
 }  // namespace
 
@@ -455,18 +608,21 @@ extern "C" int mms_zero_regions_group(void* const*, int, size_t, hipStream_t);
 extern "C" int mms_bn_bwd_apply_group(const BnBwdApplyP*, int, hipStream_t);
 #define TRY(x) do { int rc_ = (x); if (rc_ != MMS_OK) return rc_; } while (0)
 
-extern "C" int mms_fb_workspace_bytes(int, int, int, int, size_t*);
-static bool fbg_plan_checked(FbgPlan& P, int B, int D, int H, int W) {
-    size_t want = 0;
-    return fbg_plan(P, B, D, H, W) && mms_fb_workspace_bytes(B, D, H, W, &want) == MMS_OK && want == P.total;
-}
+extern "C" int mms_img_tail_fwd_group(const FbPoolP*, const LinearFwdP*, const LinearFwdP*, int, hipStream_t);
+extern "C" int mms_img_tail_bwd_group(const FbPoolP*, const LinearBwdP*, const LinearBwdP*, int, hipStream_t);
 
-extern "C" int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
-                                    const void* const* const* buffers, float* const* out, int ldo, int train, hipStream_t s) {
-    FbgPlan P;
-    if (ng < 1 || ng > MMS_MAX_GROUP || !fbg_plan_checked(P, B, D, H, W) || !ws || !x || !params || !out) return MMS_ERR_ARG;
-    for (int g = 0; g < ng; ++g)
+// l1 / l2 != NULL: the pool launch is the fused tail (pool + the two Linear layers that read its output)
+static int fbg_forward(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                       const void* const* const* params, const void* const* const* buffers, float* const* out, int ldo, int train,
+                       const LinearFwdP* l1, const LinearFwdP* l2, hipStream_t s) {
+    FbPlan P;
+    if (ng < 1 || ng > MMS_MAX_GROUP || !fbg_widths_ok(widths) || !fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total) return MMS_ERR_ARG;
+    if (!ws || !x || !params || !out || ldo < P.C[3]) return MMS_ERR_ARG;
+    for (int g = 0; g < ng; ++g) {
         if (!ws[g] || !x[g] || !params[g] || !out[g] || (!train && (!buffers || !buffers[g]))) return MMS_ERR_ARG;
+        for (int i = 0; i < 12; ++i)
+            if (!params[g][i]) return MMS_ERR_ARG;
+    }
     if (train) {
         void* reg[MMS_MAX_GROUP];
         for (int g = 0; g < ng; ++g) reg[g] = at<void>(ws[g], P.stats_begin);
@@ -478,9 +634,9 @@ extern "C" int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H
             const float* const* prm = (const float* const*)params[g];
             const void* const* buf = buffers ? buffers[g] : nullptr;
             c[g] = FbConvP{};
-            c[g].x = l == 1 ? x[g] : at<float>(ws[g], P.y[l - 1]); c[g].Cin = FC[l - 1]; c[g].in = P.g[l - 1]; c[g].out = P.g[l]; c[g].B = B;
-            c[g].has_bn = l > 1; if (l > 1) c[g].bn = fbg_bn(ws[g], P, l - 1, prm, buf, train);
-            c[g].w = prm[4 * (l - 1)]; c[g].bias = prm[4 * (l - 1) + 1]; c[g].Cout = FC[l];
+            c[g].x = l == 1 ? x[g] : at<float>(ws[g], P.y[l - 1]); c[g].Cin = P.C[l - 1]; c[g].in = P.g[l - 1]; c[g].out = P.g[l]; c[g].B = B;
+            c[g].has_bn = l > 1; if (l > 1) c[g].bn = fb_bn(ws[g], P, l - 1, prm, buf, train);
+            c[g].w = prm[4 * (l - 1)]; c[g].bias = prm[4 * (l - 1) + 1]; c[g].Cout = P.C[l];
             c[g].y = at<float>(ws[g], P.y[l]);
             c[g].osum = train ? at<double>(ws[g], P.st[l]) : nullptr; c[g].osumsq = train ? at<double>(ws[g], P.st[l]) + 128 : nullptr;
         }
@@ -492,32 +648,54 @@ extern "C" int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H
     for (int g = 0; g < ng; ++g) {
         const void* const* buf = buffers ? buffers[g] : nullptr;
         pl[g] = FbPoolP{};
-        pl[g].y = at<float>(ws[g], P.y[3]); pl[g].C = 128; pl[g].V = P.M[3] / B; pl[g].B = B;
-        pl[g].bn = fbg_bn(ws[g], P, 3, (const float* const*)params[g], buf, train);
+        pl[g].y = at<float>(ws[g], P.y[3]); pl[g].C = P.C[3]; pl[g].V = P.M[3] / B; pl[g].B = B;
+        pl[g].bn = fb_bn(ws[g], P, 3, (const float* const*)params[g], buf, train);
         pl[g].out = out[g]; pl[g].ldo = ldo;
         tabs[g] = at<void>(ws[g], P.tab_bn);
         upd = upd && buf;
     }
-    TRY(mms_fb_pool_fwd_group(pl, ng, s));
+    if (l1) TRY(mms_img_tail_fwd_group(pl, l1, l2, ng, s));
+    else TRY(mms_fb_pool_fwd_group(pl, ng, s));
     if (upd) TRY(mms_bn_running_update_group(tabs, ng, 3, 0.1f, s));
     return MMS_OK;
 }
 
-extern "C" int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
-                                     const float* const* dout, int lddout, void* const* const* grads, hipStream_t s) {
-    FbgPlan P;
-    if (ng < 1 || ng > MMS_MAX_GROUP || !fbg_plan_checked(P, B, D, H, W) || !ws || !x || !params || !dout || !grads) return MMS_ERR_ARG;
-    for (int g = 0; g < ng; ++g)
-        if (!ws[g] || !x[g] || !params[g] || !dout[g] || !grads[g]) return MMS_ERR_ARG;
+extern "C" int mms_fb3_forward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                                     const void* const* const* params, const void* const* const* buffers, float* const* out, int ldo, int train,
+                                     hipStream_t s) {
+    return fbg_forward(ng, ws, ws_bytes, widths, B, D, H, W, x, params, buffers, out, ldo, train, nullptr, nullptr, s);
+}
+extern "C" int mms_img_forward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                                     const void* const* const* params, const void* const* const* buffers, float* const* out, int ldo, int train,
+                                     const LinearFwdP* l1, const LinearFwdP* l2, hipStream_t s) {
+    if (!l1 || !l2) return MMS_ERR_ARG;
+    return fbg_forward(ng, ws, ws_bytes, widths, B, D, H, W, x, params, buffers, out, ldo, train, l1, l2, s);
+}
+
+// l1 / l2 != NULL: the fused tail's backward replaces the pool backward (dout is not read: the tail derives it from l2's dy)
+static int fbg_backward(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                        const void* const* const* params, const float* const* dout, int lddout, void* const* const* grads,
+                        const LinearBwdP* l1, const LinearBwdP* l2, hipStream_t s) {
+    FbPlan P;
+    if (ng < 1 || ng > MMS_MAX_GROUP || !fbg_widths_ok(widths) || !fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total) return MMS_ERR_ARG;
+    if (!ws || !x || !params || !grads || (!l1 && (!dout || lddout < P.C[3]))) return MMS_ERR_ARG;
+    for (int g = 0; g < ng; ++g) {
+        if (!ws[g] || !x[g] || !params[g] || (!l1 && !dout[g]) || !grads[g]) return MMS_ERR_ARG;
+        for (int i = 0; i < 12; ++i)
+            if (!params[g][i] || !grads[g][i]) return MMS_ERR_ARG;
+    }
     FbPoolP pl[MMS_MAX_GROUP];
     for (int g = 0; g < ng; ++g) {
         pl[g] = FbPoolP{};
-        pl[g].y = at<float>(ws[g], P.y[3]); pl[g].C = 128; pl[g].V = P.M[3] / B; pl[g].B = B;
-        pl[g].bn = fbg_bn(ws[g], P, 3, (const float* const*)params[g], nullptr, 1);
-        pl[g].dout = dout[g]; pl[g].lddout = lddout; pl[g].dbn = at<float>(ws[g], P.dbn[3]);
+        pl[g].y = at<float>(ws[g], P.y[3]); pl[g].C = P.C[3]; pl[g].V = P.M[3] / B; pl[g].B = B;
+        pl[g].bn = fb_bn(ws[g], P, 3, (const float* const*)params[g], nullptr, 1);
+        pl[g].dbn = at<float>(ws[g], P.dbn[3]);
         pl[g].s1 = at<double>(ws[g], P.bb[3]); pl[g].s2 = pl[g].s1 + 128;
+        if (l1) { pl[g].out = const_cast<float*>(l1[g].x); pl[g].ldo = l1[g].ldx; }      // the pooled features the forward wrote
+        else { pl[g].dout = dout[g]; pl[g].lddout = lddout; }
     }
-    TRY(mms_fb_pool_bwd_group(pl, ng, s));
+    if (l1) TRY(mms_img_tail_bwd_group(pl, l1, l2, ng, s));
+    else TRY(mms_fb_pool_bwd_group(pl, ng, s));
     BnBwdApplyP ap[MMS_MAX_GROUP];
     FbConvP c[MMS_MAX_GROUP];
     for (int l = 3; l >= 1; --l) {
@@ -526,15 +704,15 @@ extern "C" int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int 
             float* const* grd = (float* const*)grads[g];
             void* w = ws[g];
             // BN_l backward: dbn_l -> dy_l (gradient w.r.t. the raw conv output), BN parameter grads
-            ap[g] = BnBwdApplyP{at<float>(w, P.dbn[l]), FC[l], at<float>(w, P.y[l]), FC[l], at<float>(w, P.dy[l]), FC[l], P.M[l], FC[l],
-                                fbg_bn(w, P, l, prm, nullptr, 1), BnBwd{at<double>(w, P.bb[l]), at<double>(w, P.bb[l]) + 128, 0, 0}, 0,
+            ap[g] = BnBwdApplyP{at<float>(w, P.dbn[l]), P.C[l], at<float>(w, P.y[l]), P.C[l], at<float>(w, P.dy[l]), P.C[l], P.M[l], P.C[l],
+                                fb_bn(w, P, l, prm, nullptr, 1), BnBwd{at<double>(w, P.bb[l]), at<double>(w, P.bb[l]) + 128, 0, 0}, 0,
                                 grd[4 * (l - 1) + 2], grd[4 * (l - 1) + 3]};
             c[g] = FbConvP{};
-            c[g].x = l == 1 ? x[g] : at<float>(w, P.y[l - 1]); c[g].Cin = FC[l - 1]; c[g].in = P.g[l - 1]; c[g].out = P.g[l]; c[g].B = B;
-            c[g].has_bn = l > 1; if (l > 1) c[g].bn = fbg_bn(w, P, l - 1, prm, nullptr, 1);
-            c[g].w = prm[4 * (l - 1)]; c[g].Cout = FC[l]; c[g].dy = at<float>(w, P.dy[l]);
+            c[g].x = l == 1 ? x[g] : at<float>(w, P.y[l - 1]); c[g].Cin = P.C[l - 1]; c[g].in = P.g[l - 1]; c[g].out = P.g[l]; c[g].B = B;
+            c[g].has_bn = l > 1; if (l > 1) c[g].bn = fb_bn(w, P, l - 1, prm, nullptr, 1);
+            c[g].w = prm[4 * (l - 1)]; c[g].Cout = P.C[l]; c[g].dy = at<float>(w, P.dy[l]);
             c[g].dw = grd[4 * (l - 1)]; c[g].dbias = grd[4 * (l - 1) + 1];
-            c[g].msplit = fbg_msplit(l, P.M[l]);
+            c[g].msplit = fbg_msplit(P.C[l - 1], P.C[l], P.M[l]);
             if (l > 1) { c[g].dbn_in = at<float>(w, P.dbn[l - 1]); c[g].s1 = at<double>(w, P.bb[l - 1]); c[g].s2 = c[g].s1 + 128; }
         }
         TRY(mms_bn_bwd_apply_group(ap, ng, s));
@@ -542,4 +720,30 @@ extern "C" int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int 
         if (l > 1) TRY(mms_fb_conv_bwd_x_group(c, ng, s));
     }
     return MMS_OK;
+}
+
+extern "C" int mms_fb3_backward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                                      const void* const* const* params, const float* const* dout, int lddout, void* const* const* grads,
+                                      hipStream_t s) {
+    return fbg_backward(ng, ws, ws_bytes, widths, B, D, H, W, x, params, dout, lddout, grads, nullptr, nullptr, s);
+}
+extern "C" int mms_img_backward_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                                      const void* const* const* params, void* const* const* grads, const LinearBwdP* l1, const LinearBwdP* l2,
+                                      hipStream_t s) {
+    if (!l1 || !l2) return MMS_ERR_ARG;
+    return fbg_backward(ng, ws, ws_bytes, widths, B, D, H, W, x, params, nullptr, 0, grads, l1, l2, s);
+}
+
+// ---- the reference's widths {32, 64, 128}: signatures and results as before ----
+static size_t fbg_default_bytes(int B, int D, int H, int W) {
+    FbPlan P;
+    return fb_plan(P, FB_DEFAULT_WIDTHS, B, D, H, W) ? P.total : 0;
+}
+extern "C" int mms_fb_forward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
+                                    const void* const* const* buffers, float* const* out, int ldo, int train, hipStream_t s) {
+    return mms_fb3_forward_group(ng, ws, fbg_default_bytes(B, D, H, W), FB_DEFAULT_WIDTHS, B, D, H, W, x, params, buffers, out, ldo, train, s);
+}
+extern "C" int mms_fb_backward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
+                                     const float* const* dout, int lddout, void* const* const* grads, hipStream_t s) {
+    return mms_fb3_backward_group(ng, ws, fbg_default_bytes(B, D, H, W), FB_DEFAULT_WIDTHS, B, D, H, W, x, params, dout, lddout, grads, s);
 }

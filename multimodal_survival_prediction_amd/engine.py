@@ -123,7 +123,44 @@ def head_program(model):
         experts = [model.expert_image.cox_head, model.expert_rnaseq.cox_head, model.expert_clinical.cox_head]
         return dict(kind=kind, width=3 * F, ct_cols=0, lins=lins, gate=None, bufs=bufs, encoder=model.expert_image.encoder, n_pre=4,
                     enc_width=F, moe=dict(F=F, out=g[5], experts=experts, ensemble=model.ensemble_cox))
+    if kind == "ImageOnlyModel":               # generate_km_curves.py:28-54: 3-conv encoder (16, 32, 64) -> Linear(64, 32)+ReLU -> Linear(32, 1)
+        w = model.fc[0].in_features
+        lins = [
+            _Lin(model.fc[0], ("feats", 0), ("f1", 0), True),
+            _Lin(model.risk_head, ("f1", 0), ("hz", 0), False),
+        ]
+        bufs = dict(feats=w, f1=model.fc[0].out_features, hz=1)
+        return dict(kind=kind, width=w, ct_cols=0, lins=lins, gate=None, bufs=bufs, encoder=model.encoder, n_pre=0, enc_width=w)
     raise TypeError("unsupported model %s" % kind)
+
+
+def fallback_widths(enc):
+    """The three channel widths of a 3 x [Conv3d(k3, s2, p1) + BatchNorm3d + ReLU] + pool nn.Sequential, read from its Conv3d modules
+    (what the mms_fb3_* drivers take); raises for what no driver computes.  What only ONE path cannot run is refused where that path is
+    chosen, with the reason: scalar_widths_ok (SurvivalEngine's own launches), group_widths_ok (FoldGroupEngine.plan)."""
+    convs = [m for m in enc if isinstance(m, nn.Conv3d)]
+    bns = [m for m in enc if isinstance(m, nn.BatchNorm3d)]
+    cin = 1
+    if len(convs) != 3 or len(bns) != 3:
+        raise TypeError("the 3-conv CT encoder has three Conv3d and three BatchNorm3d modules")
+    for c, b in zip(convs, bns):
+        if (c.in_channels != cin or c.kernel_size != (3, 3, 3) or c.stride != (2, 2, 2) or c.padding != (1, 1, 1) or c.bias is None
+                or b.num_features != c.out_channels):
+            raise TypeError("the 3-conv CT encoder is a chain of Conv3d(k=3, s=2, p=1, bias) + BatchNorm3d starting at 1 channel")
+        if c.out_channels % 16 != 0 or not 16 <= c.out_channels <= 128:
+            raise ValueError("3-conv CT encoder: channel widths must be multiples of 16 in 16..128, got %d" % c.out_channels)
+        cin = c.out_channels
+    return tuple(c.out_channels for c in convs)
+
+
+def scalar_widths_ok(widths):
+    """the single-model scalar kernels (csrc/fallback.hip): a thread per (voxel, channel) of a 256-thread workgroup"""
+    return all(256 % w == 0 for w in widths)
+
+
+def group_widths_ok(widths):
+    """the fold-group kernels (csrc/fb_group.hip, fbg_conv_ok): every multiple of 16 except 48 + 64 n"""
+    return all(w % 64 != 48 for w in widths)
 
 
 class _Plan:
@@ -151,6 +188,9 @@ class SurvivalEngine:
             raise RuntimeError("SurvivalEngine: move the model to the GPU first (model.to('cuda')); no CPU fallback")
         self.device = p0.device
         self.params = list(model.parameters())
+        # (torch's "more than 1 value per channel" error of a training batch of ONE patient comes from BatchNorm1d; a model without one,
+        # like ImageOnlyModel, normalises over the voxels of that patient)
+        self.has_bn1d = any(isinstance(m, nn.BatchNorm1d) for m in model.modules())
         self._slots = _slots or {}
         self._flatten()
         n = self.flat.numel()
@@ -236,6 +276,19 @@ class SurvivalEngine:
             _lib.check(self.lib.mms_w2_pack(ctypes.byref(self._w2_adam), ops.stream()), "mms_w2_pack")
             self._packs_version = self.flat._version
 
+    def check_train_batch(self, B, dims=None, bn_world=1):
+        """check_train_batch for THIS model: BatchNorm1d heads need more than one patient; a model without them (ImageOnlyModel) trains
+        on one patient as long as its last BatchNorm3d sees more than one voxel (torch's rule for BatchNorm3d)."""
+        if self.has_bn1d:
+            check_train_batch(B, bn_world)
+        elif dims is not None and isinstance(self.prog["encoder"], nn.Sequential):
+            vox = 1
+            for d in dims:
+                vox *= (((int(d) + 1) // 2 + 1) // 2 + 1) // 2
+            if B * vox <= 1:
+                raise ValueError("Expected more than 1 value per channel when training: one patient whose volume shrinks to a single "
+                                 "voxel cannot be normalised by the encoder's last BatchNorm3d")
+
     def set_lr(self, lr):
         self.hyper[0] = lr
 
@@ -298,9 +351,15 @@ class SurvivalEngine:
                     raise RuntimeError("this engine's conv2 packs were laid out for another volume size (fragment-order layers differ); "
                                        "use one volume size per model")
             nbytes = ctypes.c_size_t(0)
-            wsfn = self.lib.mms_fb_workspace_bytes if P.fallback else self.lib.mms_dn121_workspace_bytes
-            _lib.check(wsfn(B, D, H, W, ctypes.byref(nbytes)), "workspace_bytes")
+            if P.fallback:
+                P.widths = (ctypes.c_int * 3)(*fallback_widths(enc))
+                if P.widths[2] != prog.get("enc_width", 128):
+                    raise ValueError("the CT encoder's last convolution has %d channels, the heads read %d" % (P.widths[2], prog.get("enc_width", 128)))
+                _lib.check(self.lib.mms_fb3_workspace_bytes(P.widths, B, D, H, W, ctypes.byref(nbytes)), "workspace_bytes")
+            else:
+                _lib.check(self.lib.mms_dn121_workspace_bytes(B, D, H, W, ctypes.byref(nbytes)), "workspace_bytes")
             P.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            P.ws_bytes = nbytes.value
             ptrs = [p.data_ptr() for p in eparams]
             if self.w2 is not None:       # packed primary conv2 storage: + 116 pointers (layer l: backward-data pack, forward fragment pack)
                 base, step = self.w2_packs.data_ptr(), 32 * 27 * 128 * 4
@@ -311,7 +370,7 @@ class SurvivalEngine:
             if P.fallback:
                 if bn_world > 1:
                     raise RuntimeError("SyncBN drives the DenseNet121-3D encoder only")
-                _lib.check(self.lib.mms_fb_init(P.ws.data_ptr(), B, D, H, W, P.btab, ops.stream()), "mms_fb_init")
+                _lib.check(self.lib.mms_fb3_init(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.btab, ops.stream()), "mms_fb3_init")
             else:
                 _lib.check(self.lib.mms_dn121_init_sync(P.ws.data_ptr(), B, D, H, W, P.ptab, P.btab, bn_world, ctypes.byref(self.dn_opts),
                                                         ops.stream()), "mms_dn121_init_sync")
@@ -518,8 +577,9 @@ class SurvivalEngine:
             feats = P.buf["feats"]
             out = feats[:, prog["ct_cols"]:]
             if P.fallback:
-                _lib.check(lib.mms_fb_forward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
-                                              feats.stride(0), 1 if train else 0, st), "mms_fb_forward")
+                self._check_scalar_path(P)
+                _lib.check(lib.mms_fb3_forward(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
+                                               feats.stride(0), 1 if train else 0, st), "mms_fb3_forward")
             else:
                 _lib.check(lib.mms_dn121_forward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
                                                  feats.stride(0), 1 if train else 0, self._opts_arg(P), st), "mms_dn121_forward")
@@ -544,6 +604,11 @@ class SurvivalEngine:
             _lib.check(lib.mms_linear_fwd(ctypes.byref(lf[i]), st), "mms_linear_fwd")
         if P.moe is not None:
             _lib.check(lib.mms_moe_fwd(ctypes.byref(P.moe[1]), st), "mms_moe_fwd")
+
+    def _check_scalar_path(self, P):
+        if not scalar_widths_ok(P.widths):
+            raise ValueError("3-conv CT encoder widths %s: one model at a time runs the scalar kernels, which take widths that divide 256 "
+                             "(16, 32, 64, 128); train and evaluate this model as a FoldGroupEngine (a group of one is fine)" % (tuple(P.widths),))
 
     def _backward_from_dhz(self, P):
         """dbuf['hz'] holds dL/dhazard; accumulates every parameter gradient into gflat."""
@@ -600,8 +665,8 @@ class SurvivalEngine:
                                               dfe.stride(0), P.gtab, self._opts_arg(P), st), "mms_dn121_backward")
             return
         if P.fallback:
-            _lib.check(lib.mms_fb_backward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
-                                           dfe.stride(0), P.gtab, st), "mms_fb_backward")
+            _lib.check(lib.mms_fb3_backward(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
+                                            dfe.stride(0), P.gtab, st), "mms_fb3_backward")
             return
         _lib.check(lib.mms_dn121_backward_mt(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
                                              dfe.stride(0), P.gtab, self._opts_arg(P), st, ctypes.c_void_p(self.side_stream.cuda_stream),
@@ -671,7 +736,8 @@ class SurvivalEngine:
     def load_batch(self, P, ct=None, rna=None, clinical=None, mask=None, time=None, event=None, valid=None):
         if P.has_enc:
             P.ct.copy_(ct.reshape(P.ct.shape), non_blocking=True)
-        P.buf["rna"].copy_(rna, non_blocking=True)
+        if "rna" in P.buf:
+            P.buf["rna"].copy_(rna, non_blocking=True)
         if clinical is not None and "clin" in P.buf:
             P.buf["clin"].copy_(clinical.reshape(P.buf["clin"].shape), non_blocking=True)
         if mask is not None:
@@ -702,7 +768,7 @@ class SurvivalEngine:
                     chk[key] = bool((cohort[key][gone] == 0).all()) if bool(gone.any()) else True
                 if chk[key]:
                     flags[key] = cohort["mask"][:, j:]
-        srcs = [(cohort["rnaseq"], P.buf["rna"], None, flags.get("rnaseq"))]
+        srcs = [(cohort["rnaseq"], P.buf["rna"], None, flags.get("rnaseq"))] if "rna" in P.buf else []
         if P.has_enc:
             srcs.append((cohort["image"].view(cohort["image"].shape[0], -1), P.ct.view(P.B, -1), None, flags.get("image")))
         if "clin" in P.buf:
@@ -735,8 +801,8 @@ class SurvivalEngine:
         ddp_world > 1: data-parallel step on this rank's shard of the global batch (`_ddp_step`: bucketed gradient all-reduce
         overlapped with the backward; rank-local BatchNorm; rank-local or global_cox risk sets), or with sync_bn=True the exact
         global-batch step (`_ddp_step_syncbn`: SyncBN + replicated heads + global risk set; eager launches)."""
-        B = rna.shape[0]
-        check_train_batch(B, ddp_world if sync_bn else 1)
+        B = (rna if rna is not None else ct).shape[0]
+        self.check_train_batch(B, tuple(ct.shape[-3:]) if ct is not None else None, ddp_world if sync_bn else 1)
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None, bn_world=ddp_world if (sync_bn and ddp_world > 1) else 1)
         self.load_batch(P, ct, rna, clinical, mask, time, event, valid)
         self.sync_packs()
@@ -950,7 +1016,7 @@ class SurvivalEngine:
 
     def forward_eval(self, ct=None, rna=None, clinical=None, mask=None, use_graph=True):
         """Eval-mode forward -> (hazard [B] view of a static buffer, gate [B,3] or None)."""
-        B = rna.shape[0]
+        B = (rna if rna is not None else ct).shape[0]
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None)
         self.load_batch(P, ct, rna, clinical, mask)
         self.sync_packs()

@@ -14,7 +14,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
-from .engine import SurvivalEngine, check_train_batch
+from .engine import SurvivalEngine, group_widths_ok
 
 _S = _lib.structs
 
@@ -35,8 +35,14 @@ class _GroupPlan:
 class FoldGroupEngine:
     MAX = 10     # MMS_MAX_GROUP
 
-    def __init__(self, models, **engine_kw):
-        """models: 1..10 modules of the same class/shape, already on the GPU and not yet bound to an engine."""
+    # ImageOnlyModel: pool + both Linear layers in one launch per pass (mms_img_tail_*).  On: measured 5 % faster than the three launches in
+    # the entry points' layout (sub-groups on three streams), more than that layout's spread (tools/bench_image_only.py)
+    FUSED_IMG_TAIL = True
+
+    def __init__(self, models, fused_tail=None, **engine_kw):
+        """models: 1..10 modules of the same class/shape, already on the GPU and not yet bound to an engine.
+        fused_tail: ImageOnlyModel's tail as one launch per pass (None: FUSED_IMG_TAIL); ignored by the other models."""
+        self.fused_tail = self.FUSED_IMG_TAIL if fused_tail is None else bool(fused_tail)
         if not 1 <= len(models) <= self.MAX:
             raise ValueError("a fold group holds 1..%d models" % self.MAX)
         self.lib = _lib.load_library()
@@ -97,6 +103,13 @@ class FoldGroupEngine:
             GP.out = _ptrs([P.buf["feats"][:, cc:].data_ptr() for P in Ps])
             GP.dout = _ptrs([P.dbuf["feats"][:, cc:].data_ptr() for P in Ps])
             GP.ld = Ps[0].buf["feats"].stride(0)
+            if GP.fallback:        # (identical for all members: FoldGroupEngine checks the parameter shapes)
+                GP.widths, GP.ws_bytes = Ps[0].widths, Ps[0].ws_bytes
+                if any(tuple(P.widths) != tuple(GP.widths) for P in Ps):
+                    raise ValueError("fold-group models must share the CT encoder's channel widths")
+                if not group_widths_ok(GP.widths):
+                    raise ValueError("3-conv CT encoder widths %s: the fold-group kernels take multiples of 16 other than 48 and 112" % (tuple(GP.widths),))
+        GP.img_tail = bool(self.fused_tail and GP.fallback and prog["kind"] == "ImageOnlyModel")
         GP.mix = _arr([P.mix for P in Ps]) if Ps[0].mix is not None else None
         nl = len(prog["lins"])
         GP.lin_fwd = {t: [_arr([P.lin_fwd[t][i] for P in Ps]) for i in range(nl)] for t in (True, False)}
@@ -124,9 +137,14 @@ class FoldGroupEngine:
         prog = GP.eng[0].prog
         if GP.has_enc:
             B, (D, H, W) = GP.B, GP.dims
+            if GP.img_tail:        # the encoder's pool launch carries the two Linear layers: no head launches
+                lf = GP.lin_fwd[train]
+                _lib.check(lib.mms_img_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                                                     1 if train else 0, lf[0], lf[1], st), "mms_img_forward_group")
+                return
             if GP.fallback:
-                _lib.check(lib.mms_fb_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
-                                                    1 if train else 0, st), "mms_fb_forward_group")
+                _lib.check(lib.mms_fb3_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                                                     1 if train else 0, st), "mms_fb3_forward_group")
             else:
                 _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
                                                        1 if train else 0, self._opts_arg(GP), st), "mms_dn121_forward_group")
@@ -180,6 +198,22 @@ class FoldGroupEngine:
             _lib.check(lib.mms_moe_bwd_group(GP.moe_bwd[1], ng, st), "mms_moe_bwd_group")
         else:
             _lib.check(lib.mms_cox_fwd_bwd_group(GP.cox, ng, st), "mms_cox_fwd_bwd_group")
+        self._backward_from_dhz(GP)
+        ad = GP.adam[bool(skip_if_unusable)]
+        _lib.check(lib.mms_grad_sumsq_group(ad, ng, st), "mms_grad_sumsq_group")
+        _lib.check(lib.mms_clip_adam_group(ad, ng, st), "mms_clip_adam_group")
+
+    def _backward_from_dhz(self, GP):
+        """Every member's dbuf['hz'] holds dL/dhazard (SimMLM: after the mixture's backward stage); accumulates every parameter gradient
+        into the members' gflat -- the group form of SurvivalEngine._backward_from_dhz."""
+        st = ops.stream()
+        lib, ng = self.lib, GP.ng
+        prog = GP.eng[0].prog
+        if GP.img_tail:
+            B, (D, H, W) = GP.B, GP.dims
+            _lib.check(lib.mms_img_backward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.grads,
+                                                  GP.lin_bwd[0], GP.lin_bwd[1], st), "mms_img_backward_group")
+            return
         n_pre = prog["n_pre"]
         for i in range(len(GP.lin_bwd) - 1, n_pre - 1, -1):
             _lib.check(lib.mms_linear_bwd_group(GP.lin_bwd[i], ng, st), "mms_linear_bwd_group")
@@ -194,14 +228,11 @@ class FoldGroupEngine:
         if GP.has_enc:
             B, (D, H, W) = GP.B, GP.dims
             if GP.fallback:
-                _lib.check(lib.mms_fb_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, st),
-                           "mms_fb_backward_group")
+                _lib.check(lib.mms_fb3_backward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, st),
+                           "mms_fb3_backward_group")
             else:
                 _lib.check(lib.mms_dn121_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, self._opts_arg(GP), st),
                            "mms_dn121_backward_group")
-        ad = GP.adam[bool(skip_if_unusable)]
-        _lib.check(lib.mms_grad_sumsq_group(ad, ng, st), "mms_grad_sumsq_group")
-        _lib.check(lib.mms_clip_adam_group(ad, ng, st), "mms_clip_adam_group")
 
     # ---- state snapshot around graph warm-up ---------------------------------------------------------
     def _snapshot(self, eng):
@@ -252,11 +283,12 @@ class FoldGroupEngine:
         if len(batches) != len(members):
             raise ValueError("one batch per member")
         has_enc = self.engines[0].prog["encoder"] is not None
-        B = batches[0]["rna"].shape[0]
-        check_train_batch(B)
+        rows = lambda b: (b["rna"] if b.get("rna") is not None else b["ct"]).shape[0]       # (a CT-only model has no rna input)
+        B = rows(batches[0])
         dims = tuple(batches[0]["ct"].shape[-3:]) if has_enc else None
+        self.engines[0].check_train_batch(B, dims)
         for b in batches:
-            if b["rna"].shape[0] != B or (has_enc and tuple(b["ct"].shape[-3:]) != dims):
+            if rows(b) != B or (has_enc and tuple(b["ct"].shape[-3:]) != dims):
                 raise ValueError("fold-group batches must share one shape; split ragged tails into their own step")
         GP = self.plan(B, dims, members)
         for e, P, b in zip(GP.eng, GP.Ps, batches):
@@ -305,8 +337,8 @@ class FoldGroupEngine:
         if idx.dim() != 2 or idx.shape[0] != len(members):
             raise ValueError("indices must be [len(members)][B]")
         B = idx.shape[1]
-        check_train_batch(B)
         dims = tuple(cohort["image"].shape[-3:]) if self.engines[0].prog["encoder"] is not None else None
+        self.engines[0].check_train_batch(B, dims)
         GP = self.plan(B, dims, members)
         self._gather_indexed(GP, cohort, idx)
         self._sync_packs(GP)
@@ -341,7 +373,7 @@ class FoldGroupEngine:
     def forward_eval(self, batches, members=None, use_graph=True):
         """Eval-mode forward of every member -> list of (hazard [B] view, gate [B,3] or None) per member."""
         members = tuple(range(len(self.engines))) if members is None else tuple(members)
-        B = batches[0]["rna"].shape[0]
+        B = (batches[0]["rna"] if batches[0].get("rna") is not None else batches[0]["ct"]).shape[0]
         dims = tuple(batches[0]["ct"].shape[-3:]) if self.engines[0].prog["encoder"] is not None else None
         GP = self.plan(B, dims, members)
         for e, P, b in zip(GP.eng, GP.Ps, batches):

@@ -43,7 +43,7 @@ class _Net(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, ct, rna, clinical, mask):
         eng = engine_of(model)
-        P = eng.plan(rna.shape[0], tuple(ct.shape[-3:]) if ct is not None else None)
+        P = eng.plan((rna if rna is not None else ct).shape[0], tuple(ct.shape[-3:]) if ct is not None else None)
         eng.load_batch(P, ct, rna, clinical, mask)
         eng._forward(P, model.training)
         ctx.eng, ctx.P, ctx.train = eng, P, model.training
@@ -76,13 +76,13 @@ class _Net(torch.autograd.Function):
 
 
 def _run(model, ct, rna, clinical, mask):
-    if not rna.is_cuda or (ct is not None and not ct.is_cuda):
+    if (rna is not None and not rna.is_cuda) or (ct is not None and not ct.is_cuda):
         raise RuntimeError("%s (HIP): inputs must be on an MI355X device; there is no CPU fallback" % type(model).__name__)
     anchor = next(model.parameters())
     if torch.is_grad_enabled() and model.training:
         return _Net.apply(anchor, model, ct, rna, clinical, mask)
     eng = engine_of(model)
-    P = eng.plan(rna.shape[0], tuple(ct.shape[-3:]) if ct is not None else None)
+    P = eng.plan((rna if rna is not None else ct).shape[0], tuple(ct.shape[-3:]) if ct is not None else None)
     eng.load_batch(P, ct, rna, clinical, mask)
     eng._forward(P, model.training)
     return P.buf["hz"][:, 0].clone(), (P.gatew.clone() if P.gate is not None else None)
@@ -185,6 +185,27 @@ class RNASeqSurvivalModel(nn.Module):
 
     def forward(self, rnaseq):
         return _run(self, None, rnaseq, None, None)[0].unsqueeze(1)
+
+
+class ImageOnlyModel(nn.Module):
+    """generate_km_curves.py:28-54: the CT-only baseline.  3 x [Conv3d(k3, s2, p1) + BatchNorm3d + ReLU] at 1 -> 16 -> 32 -> 64 channels +
+    global average pool (always this encoder: the class does not look at USE_MONAI), Linear(64, 32) + ReLU, Linear(32, 1).
+    Sub-module names (encoder.{0,1,3,4,6,7}, fc.0, risk_head) and parameter creation order are the reference's, so a seeded construction
+    draws its weights and state_dict() interchanges with it.  forward(x [B, 1, D, H, W]) -> risk [B].  No BatchNorm1d: a training batch of
+    one patient is legal (BatchNorm3d over that patient's voxels)."""
+
+    def __init__(self):
+        super().__init__()
+        self.encoder = nn.Sequential(        # parameter holder; never called
+            nn.Conv3d(1, 16, 3, stride=2, padding=1), nn.BatchNorm3d(16), nn.ReLU(),
+            nn.Conv3d(16, 32, 3, stride=2, padding=1), nn.BatchNorm3d(32), nn.ReLU(),
+            nn.Conv3d(32, 64, 3, stride=2, padding=1), nn.BatchNorm3d(64), nn.ReLU(),
+            nn.AdaptiveAvgPool3d(1))
+        self.fc = nn.Sequential(nn.Linear(64, 32), nn.ReLU())
+        self.risk_head = nn.Linear(32, 1)
+
+    def forward(self, x):
+        return _run(self, x, None, None, None)[0]
 
 
 # ---- SimMLM_SurvivalNet (generate_km_curves.py:158-281): gated mixture of modality experts -----------------------------------

@@ -203,6 +203,56 @@ def _simmlm_rows(batch, device):
     return smask & (_t(batch['mask'], device) != 0).any(1)
 
 
+# ---- ImageOnlyModel (generate_km_curves.py:28-54; the reference ships no training loop for it) ---------------------------------
+def train_epoch_image(model, loader, optimizer, device):
+    """The loop of final_multimodal.py:238-266 on the image alone (project-defined): a forward on every batch (BatchNorm
+    running statistics move even on a degenerate one), Cox loss over the whole batch, clip at 1.0; a batch with fewer than 2 patients or
+    without an event has loss 0 and takes no optimiser step.  -> mean loss over all batches."""
+    if not isinstance(optimizer, FusedOptimizer):
+        return _train_epoch_image_autograd(model, loader, optimizer, device)
+    model.train()
+    eng = optimizer.engine
+    eng.reset_epoch_stats()
+    for batch in loader:
+        label = batch['label']
+        eng.train_step(batch['image'], time=label[:, 0], event=label[:, 1], skip_if_unusable=True)
+    st = eng.epoch_stats()
+    return st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0
+
+
+def _train_epoch_image_autograd(model, loader, optimizer, device):
+    model.train()
+    total, nb = 0.0, 0
+    for batch in loader:
+        ct, label = _t(batch['image'], device), _t(batch['label'], device)
+        risk = model(ct)
+        loss = losses.cox_loss(risk, label[:, 1], label[:, 0])
+        optimizer.zero_grad()
+        if ct.shape[0] >= 2 and float(label[:, 1].sum()) > 0:
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+            optimizer.step()
+        total += loss.item()
+        nb += 1
+    return total / nb if nb > 0 else 0
+
+
+def validate_image(model, loader, device):
+    """Eval-mode forward of every batch -> (mean of the batches' Cox losses, C-index by pair counts over all patients)."""
+    model.eval()
+    eng = engine_of(model)
+    total, nb, hs, ts, es = 0.0, 0, [], [], []
+    for batch in loader:
+        label = _t(batch['label'], device)
+        hz, _ = eng.forward_eval(batch['image'])
+        hz = hz.clone()
+        total += losses.cox_loss(hz, label[:, 1], label[:, 0]).item()
+        nb += 1
+        hs.append(hz); ts.append(label[:, 0]); es.append(label[:, 1])
+    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
+    return (total / nb if nb > 0 else 0), c
+
+
 # ---- simple_fusion.py -------------------------------------------------------------------------------------------
 def train_epoch_simple(model, loader, optimizer, device):
     if not isinstance(optimizer, FusedOptimizer):
@@ -329,6 +379,9 @@ def _train_kwargs(style, batch):
         return dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], time=label[:, 0], event=label[:, 1])
     if style == "rnaseq":
         return dict(rna=batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1))
+    if style == "image":
+        label = batch['label']
+        return dict(ct=batch['image'], time=label[:, 0], event=label[:, 1])
     valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
     if style in ("partial", "simmlm"):
         label = batch['label']
@@ -349,8 +402,9 @@ _SKIP_UNUSABLE = {"final": True, "partial": False, "simple": True, "flexible": T
 
 
 def _skip_unusable(style):
-    """the reference scripts' rule (_SKIP_UNUSABLE); "simmlm" (train_epoch_simmlm): a batch whose ensemble term is unusable takes no step"""
-    return True if style == "simmlm" else _SKIP_UNUSABLE[style]
+    """the reference scripts' rule (_SKIP_UNUSABLE); "simmlm" (train_epoch_simmlm): a batch whose ensemble term is unusable takes no step;
+    "image" (train_epoch_image): final_multimodal.py's rule"""
+    return True if style in ("simmlm", "image") else _SKIP_UNUSABLE[style]
 
 
 def _lockstep(loaders, members):
@@ -395,7 +449,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
         for g, batch in pos.items():
             kw = _train_kwargs(style, batch)
             if kw is not None:
-                n = int(kw["rna"].shape[0])
+                n = int((kw["rna"] if "rna" in kw else kw["ct"]).shape[0])
                 by_size.setdefault(n, []).append((g, kw))
         for items in by_size.values():           # a ragged last batch forms its own (sub-)group step
             group.train_step([kw for _, kw in items], members=tuple(g for g, _ in items),
@@ -407,7 +461,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
     out = []
     for g in members:
         st = group.engines[g].epoch_stats()
-        if style in ("final", "rnaseq"):
+        if style in ("final", "rnaseq", "image"):
             out.append(st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0)
         elif style == "partial":
             out.append((st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0,
@@ -545,6 +599,8 @@ def validate_lockstep(group, loaders, style, device, members=None, concurrent=1)
                 kw = dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], mask=batch['mask'])
             elif style == "rnaseq":
                 kw = dict(rna=batch['rnaseq'])
+            elif style == "image":
+                kw = dict(ct=batch['image'])
             else:
                 if int(torch.as_tensor(batch['has_survival']).sum()) < 2:
                     continue
@@ -552,12 +608,12 @@ def validate_lockstep(group, loaders, style, device, members=None, concurrent=1)
                 if style == "flexible":
                     kw["mask"] = batch['mask'][:, :2]
             meta[g] = batch
-            by_size.setdefault(int(kw["rna"].shape[0]), []).append((g, kw))
+            by_size.setdefault(int((kw["rna"] if "rna" in kw else kw["ct"]).shape[0]), []).append((g, kw))
         for items in by_size.values():
             outs = group.forward_eval([kw for _, kw in items], members=tuple(g for g, _ in items))
             for (g, _), (hz, _gate) in zip(items, outs):
                 batch, a = meta[g], acc[g]
-                if style == "final":
+                if style in ("final", "image"):
                     label = _t(batch['label'], device)
                     h, t, e = hz.clone(), label[:, 0], label[:, 1]
                     a["total"] += losses.cox_loss(h, e, t).item(); a["nb"] += 1

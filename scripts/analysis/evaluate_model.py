@@ -39,6 +39,7 @@ MODELS = {
     "simple": ("SimpleFusionModel", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=88, complete=True), 88, 3, 8),
     "flexible": ("FlexibleMultimodalModel", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=608, complete=False), 608, 3, 16),
     "simmim": ("SimMLM_SurvivalNet", lambda c: dict(rna_dim=c["rnaseq"].shape[1]), dict(seed=608, complete=False), 608, 3, 8),
+    "image_only": ("ImageOnlyModel", lambda c: dict(), dict(seed=608, complete=False), 608, 5, 4),
     "rnaseq": ("RNASeqSurvivalModel", lambda c: dict(input_dim=c["rnaseq"].shape[1]), dict(seed=427, complete=True, dims=(32, 32, 32)), 240, 3, 16),
 }
 
@@ -48,20 +49,24 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
     labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth."""
     import torch
-    from _common import env_int, load_or_make_cohort, setup_device
+    from _common import env_dims, env_int, load_or_make_cohort, setup_device
     from multimodal_survival_prediction_amd import data, models
     from multimodal_survival_prediction_amd.engine import engine_of
     _, _, device = setup_device()
     cls, ctor, ckw, n_default, folds_default, batch_default = MODELS[kind]
     n_folds, batch_size = n_folds or env_int("MMS_FOLDS", folds_default), batch_size or env_int("MMS_BATCH_SIZE", batch_default)
     n = env_int("MMS_PATIENTS", n_default)
-    if kind in ("partial", "simmim"):
+    if kind == "image_only":          # image_only_training.py builds its cohort at MMS_VOLUME
+        cohort = load_or_make_cohort(device, n=n, dims=env_dims(), **ckw)
+    elif kind in ("partial", "simmim"):
         cohort = load_or_make_cohort(device, n=n, **ckw)                 # data/processed/* under MMS_DATA_ROOT when present
     else:
         cohort = data.cohort_to(data.make_cohort(n=n, **ckw), device)
     keep = cohort["has_survival"].cpu().bool()
     if kind == "simmim":              # simmlm_training.py's cohort: labelled patients with at least one modality
         keep &= (cohort["mask"].cpu() != 0).any(1)
+    if kind == "image_only":          # image_only_training.py's cohort: patients with an image and a label
+        keep &= cohort["mask"].cpu()[:, 0] != 0
     labelled = torch.nonzero(keep).reshape(-1).numpy()
     _, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
     idx = labelled[val]
@@ -81,6 +86,8 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
             hz, _ = eng.forward_eval(ct, rna)
         elif kind == "flexible":
             hz, _ = eng.forward_eval(ct, rna, mask=mask[:, :2])
+        elif kind == "image_only":
+            hz, _ = eng.forward_eval(ct)
         else:
             hz, _ = eng.forward_eval(None, rna)
         risks.append(hz.clone().cpu())

@@ -15,6 +15,7 @@ RESULTS_FILES = {          # display name -> file written by scripts/training/<e
     "Flexible Multimodal": "results/flexible_multimodal/cv_results.json",
     "Final Multimodal": "results/final/cv_results.json",
     "SimMLM": "results/simmim/cv_results.json",              # scripts/training/simmlm_training.py
+    "Image-Only": "results/image_only/cv_results.json",      # scripts/training/image_only_training.py
 }
 
 
