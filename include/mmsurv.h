@@ -89,6 +89,10 @@ typedef struct MmsDnOpts {
                               (<= 128 rows, <= 4 models per launch, one statistic replica, no SyncBN / statistics hook, persist_b3 off),
                               -1 = never.  A caller that may have more such launches in flight than the chip holds passes -1
                               (ops.persistent_opts); a wait that times out raises the drivers' error word (mms_dn121_region "b4_err") */
+    int wgrad_tab;         /* deferred weight gradients of dense blocks 2-4 (batch_w >= 0): 0 = every (model, layer) member of a block in ONE
+                              conv2 and ONE conv1 launch at the block's end, the members described by compact records over the layer tables
+                              mms_dn121_init wrote (mms_wgrad_tab_group; the parameter pointers of the call must be those given to
+                              mms_dn121_init); -1 = launches of at most MMS_MAX_GROUP by-value members (rounds 2-5) */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.
@@ -227,6 +231,36 @@ typedef struct Conv3BwdWP {
                                     // 2: [32][27][128] (cout, tap, cin) -- the PACKED PRIMARY layout of MmsDnOpts.w2_packed: the same
                                     //    512-byte runs, and the buffer IS the parameter's gradient (no scratch, no unpack)
 } Conv3BwdWP;
+
+/* Weight gradients of many (model, layer) members of ONE dense block as one launch per op (csrc/dn_bwd.hip): the members' parameter
+ * blocks (Conv3BwdWP / Conv1BwdP, has_bn_out = 1, pool = 0, N = 128, K = C0 + 32 * layer) are rebuilt on the device from a per-model
+ * header, the model's device table of layer entries, and a small per-member record -- so a launch carries up to
+ * MMS_WGRAD_MAX_MEMBERS members instead of the MMS_MAX_GROUP by-value blocks that fit the 4 KB kernel-argument segment.
+ * Layer entry = 15 pointers (csrc/dn_ops.h B4Layer, written by mms_dn121_init), of which these are read: [0] norm1 gamma, [1] norm1
+ * beta, [3] norm2 gamma, [4] norm2 beta, [11] y1 [M][128], [12] y1's (sum | sumsq) [2][128] (x srep replicas, stride 256 doubles),
+ * [13] masked gradient at norm2's output [M][128], [14] its BatchNorm-backward sums (s1 | s2) [2][128] (replicas likewise). */
+#define MMS_WGRAD_MAX_MODELS 5
+#define MMS_WGRAD_MAX_MEMBERS 90
+typedef struct MmsWgradModel {
+    const void* tab;            // device table of the block's layer entries
+    const float* slab;          // [M][ld] block activations (conv1's input: columns [0, K))
+    const float* dslab;         // [M][ld] their gradient (conv2's dz of layer l: columns [C0 + 32 l, + 32))
+    const int* coords;          // [M] packed voxel coordinates
+    const double* st_slab;      // (sum | sumsq) [2][ld] of the slab channels (x srep replicas, stride 2 ld doubles)
+    int M; Dims3 g; int srep;   // rows, the block's voxel grid, statistic replicas -- equal for every model of a launch
+} MmsWgradModel;
+typedef struct MmsWgradMember {
+    float* dw2;                 // conv2 weight gradient (layout: MmsWgradShape.dw_layout), accumulated with atomics
+    float* dw1;                 // conv1 weight gradient [128][K], accumulated with atomics
+    float* dgamma2; float* dbeta2;      // [128] norm2 parameter gradients, accumulated by one workgroup of the conv1 launch
+    int model; int layer;       // index into the launch's models, layer of the block (table index)
+} MmsWgradMember;
+typedef struct MmsWgradShape {
+    int ld; int C0;             // slab row pitch (the block's final channel count), input channels of layer 0
+    int ms3; int ms1;           // row chunks of the conv2 / conv1 launch (Conv3BwdWP.msplit / Conv1BwdP.msplit)
+    int dw_layout;              // Conv3BwdWP.dw_layout
+    int count;                  // rows the BatchNorm statistics were taken over (M x ranks)
+} MmsWgradShape;
 
 // 1x1 conv backward (dense conv1 and transition conv).
 //   dy[m][n]  = g2[n]*rstd2[n]*(dbn2[m][n] - s1[n]/M - yhat[m][n]*s2[n]/M)     (has_bn_out=1)
@@ -656,6 +690,11 @@ int mms_conv3_bwd_weight_group(const Conv3BwdWP* p, int ng, const MmsDnOpts* opt
 int mms_conv3_bwd_weight_msplit(int M, int members, const MmsDnOpts* opts);
 int mms_conv1_bwd_data_group(const Conv1BwdP* p, int ng, const MmsDnOpts* opts, hipStream_t s);
 int mms_conv1_bwd_weight_group(const Conv1BwdP* p, int ng, hipStream_t s);
+/* The table-fed form of the two weight-gradient launches above (MmsWgradModel): which = 1 conv2, 2 conv1, 3 both.  MMS_ERR_ARG and no
+   launch for nmembers outside 1..MMS_WGRAD_MAX_MEMBERS, nmodels outside 1..MMS_WGRAD_MAX_MODELS, models of unequal M / grid / replicas,
+   a member whose model or layer index is out of range (layers: K = C0 + 32 layer <= ld - 32), or a row chunk over 1024 rows. */
+int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, const MmsWgradMember* members, int nmembers,
+                        const MmsWgradShape* shape, int which, hipStream_t s);
 int mms_bn_bwd_apply_group(const BnBwdApplyP* p, int ng, hipStream_t s);
 int mms_head_bwd_group(const HeadBwdP* p, int ng, hipStream_t s);
 int mms_pool_bwd_group(const PoolBwdP* p, int ng, hipStream_t s);

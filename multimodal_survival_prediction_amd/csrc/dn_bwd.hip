@@ -998,6 +998,104 @@ extern "C" int mms_conv1_bwd_weight_group(const Conv1BwdP* pp, int ng, hipStream
 }
 MMS_SINGLE(mms_conv1_bwd_weight, Conv1BwdP)
 
+// ---- table-fed weight-gradient launches (include/mmsurv.h MmsWgradModel): every (model, layer) member of a dense block in one launch per op.
+// The by-value form above carries MMS_MAX_GROUP parameter blocks of 136 / 352 bytes; here a member is 40 bytes in the kernel argument, and a
+// workgroup rebuilds its member's Conv3BwdWP / Conv1BwdP -- field for field what the network driver builds on the host -- from the model's
+// header and layer table, then runs the same tile_gemm_body<Op>: same arithmetic, same bits.
+struct WgradTab {
+    MmsWgradModel mod[MMS_WGRAD_MAX_MODELS];
+    MmsWgradMember mem[MMS_WGRAD_MAX_MEMBERS];
+    MmsWgradShape sh;
+    float inv_count;
+};
+static_assert(sizeof(WgradTab) <= 4096, "kernel-argument segment");
+
+__device__ __forceinline__ BnSrc wgrad_bn(const double* st, int C, const float* gamma, const float* beta, float inv_count, int nrep) {
+    BnSrc b;
+    b.sum = st; b.sumsq = st + C; b.rmean = nullptr; b.rvar = nullptr; b.gamma = gamma; b.beta = beta;
+    b.inv_count = inv_count; b.eps = 1e-5f; b.train = 1; b.nrep = nrep; b.rep_stride = 2 * C;
+    return b;
+}
+
+__global__ __launch_bounds__(256) MMS_TGK_ATTR void wgrad_tab_conv3_kernel(const WgradTab t) {
+    int gi, z;                                     // member, chunk * 27 + tap
+    Conv3BwdWOp::zremap((int)blockIdx.z, 27 * t.sh.ms3, (int)gridDim.z, gi, z);
+    const MmsWgradMember& m = t.mem[gi];
+    const MmsWgradModel& md = t.mod[m.model];
+    const B4Layer& L = ((const B4Layer*)md.tab)[m.layer];
+    Conv3BwdWP p;
+    p.y1 = L.y1; p.coords = md.coords; p.g = md.g; p.M = md.M;
+    p.bn = wgrad_bn(L.st_y1, 128, L.g2, L.b2, t.inv_count, md.srep);
+    p.dz = md.dslab + t.sh.C0 + 32 * m.layer; p.lddz = t.sh.ld;
+    p.dw = m.dw2; p.msplit = t.sh.ms3; p.dw_layout = t.sh.dw_layout;
+    tile_gemm_body<Conv3BwdWOp>(p, z, 0);
+}
+
+// grid (2, K tiles of the widest member, ms1 x members): a narrower member's surplus workgroups leave before they touch memory
+__global__ __launch_bounds__(256) MMS_TGK_ATTR void wgrad_tab_conv1_kernel(const WgradTab t) {
+    const int gi = blockIdx.z / t.sh.ms1, z = blockIdx.z - gi * t.sh.ms1;
+    const MmsWgradMember& m = t.mem[gi];
+    const int K = t.sh.C0 + 32 * m.layer;
+    if ((int)blockIdx.y * 64 >= K) return;
+    const MmsWgradModel& md = t.mod[m.model];
+    const B4Layer& L = ((const B4Layer*)md.tab)[m.layer];
+    Conv1BwdP p = Conv1BwdP{};
+    p.dyraw = L.dmid; p.lddy = 128; p.y = L.y1; p.ldy = 128;
+    p.bn_out = wgrad_bn(L.st_y1, 128, L.g2, L.b2, t.inv_count, md.srep);
+    p.bb_out = BnBwd{L.bb_y1, L.bb_y1 + 128, md.srep, 2 * 128}; p.has_bn_out = 1;
+    p.M = md.M; p.N = 128;
+    p.x = md.slab; p.ldx = t.sh.ld; p.K = K;
+    p.bn_in = wgrad_bn(md.st_slab, t.sh.ld, L.g1, L.b1, t.inv_count, md.srep);
+    p.w = L.w1; p.dw = m.dw1;
+    p.msplit = t.sh.ms1; p.dgamma_out = m.dgamma2; p.dbeta_out = m.dbeta2;
+    tile_gemm_body<Conv1BwdWOp<false>>(p, z, blockIdx.x);
+}
+
+extern "C" int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, const MmsWgradMember* members, int nmembers,
+                                   const MmsWgradShape* shape, int which, hipStream_t s) {
+    if (!models || !members || !shape || nmodels < 1 || nmodels > MMS_WGRAD_MAX_MODELS || nmembers < 1 || nmembers > MMS_WGRAD_MAX_MEMBERS ||
+        which < 1 || which > 3) return MMS_ERR_ARG;
+    const MmsWgradShape& sh = *shape;
+    const MmsWgradModel& m0 = models[0];
+    if (m0.M <= 0 || sh.ms3 <= 0 || sh.ms1 <= 0 || sh.count <= 0 || sh.ld % 4 != 0 || sh.C0 % 32 != 0 || sh.C0 < 32 || sh.ld < sh.C0 + 32 ||
+        sh.dw_layout < 0 || sh.dw_layout > 2 || m0.srep < 1) return MMS_ERR_ARG;
+    if ((((m0.M + sh.ms3 - 1) / sh.ms3 + 31) & ~31) > 1024) return MMS_ERR_ARG;          // conv2: the row chunk must fit the LDS mask table
+    if ((long)sh.ms3 * 27 * nmembers > 65535 || (long)sh.ms1 * nmembers > 65535) return MMS_ERR_ARG;
+    for (int g = 0; g < nmodels; ++g) {
+        const MmsWgradModel& q = models[g];
+        if (!q.tab || !q.slab || !q.dslab || !q.coords || !q.st_slab) return MMS_ERR_ARG;
+        if (q.M != m0.M || q.srep != m0.srep || q.g.D != m0.g.D || q.g.H != m0.g.H || q.g.W != m0.g.W) return MMS_ERR_ARG;
+        if ((((uintptr_t)q.slab | (uintptr_t)q.dslab | (uintptr_t)q.st_slab) & 15) != 0) return MMS_ERR_ARG;     // 16-byte vector loads
+    }
+    int kmax = 0;
+    for (int i = 0; i < nmembers; ++i) {
+        const MmsWgradMember& q = members[i];
+        if (q.model < 0 || q.model >= nmodels || q.layer < 0 || sh.C0 + 32 * q.layer + 32 > sh.ld) return MMS_ERR_ARG;
+        if (((which & 1) && !q.dw2) || ((which & 2) && (!q.dw1 || !q.dgamma2 || !q.dbeta2))) return MMS_ERR_ARG;
+        if (sh.C0 + 32 * q.layer > kmax) kmax = sh.C0 + 32 * q.layer;
+    }
+    WgradTab t;
+    memset(&t, 0, sizeof(t));
+    for (int g = 0; g < nmodels; ++g) t.mod[g] = models[g];
+    for (int i = 0; i < nmembers; ++i) t.mem[i] = members[i];
+    t.sh = sh; t.inv_count = 1.0f / (float)sh.count;
+    if (which & 1) {
+        constexpr size_t smem = TileGemmCfg<Conv3BwdWOp>::smem_bytes();
+        static_assert(smem <= 64 * 1024, "no dynamic-LDS attribute needed");
+        MMS_LAUNCH(wgrad_tab_conv3_kernel, dim3(1, 1, 27 * sh.ms3 * nmembers), dim3(256), smem, s, t);
+        const int rc = mms_check_launch();
+        if (rc != MMS_OK) return rc;
+    }
+    if (which & 2) {
+        constexpr size_t smem = TileGemmCfg<Conv1BwdWOp<false>>::smem_bytes();
+        static_assert(smem <= 64 * 1024, "no dynamic-LDS attribute needed");
+        MMS_LAUNCH(wgrad_tab_conv1_kernel, dim3(2, (kmax + 63) / 64, sh.ms1 * nmembers), dim3(256), smem, s, t);
+        const int rc = mms_check_launch();
+        if (rc != MMS_OK) return rc;
+    }
+    return MMS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // BN backward apply into the gradient slab: dx[:, 0:C] (+)= g*rstd*(dbn - s1/M - xhat*s2/M)
 // ------------------------------------------------------------------------------------------------------

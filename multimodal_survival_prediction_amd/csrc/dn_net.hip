@@ -401,6 +401,7 @@ struct Ctx {
 struct Dp {
     int bn_world = 1; mms_sync_fn hook = nullptr; void* user = nullptr;
     int b_hi = NB - 1, b_lo = 0;
+    bool staged = false;            // a backward stage (mms_dn121_backward_stage)
 };
 #define SYNC(ptr, nrep, rstride, ncols, pstride) do { if (dp.hook) { int rc_ = dp.hook(dp.user, (ptr), (nrep), (long)(rstride), (ncols), (long)(pstride), s); \
     if (rc_ != MMS_OK) { fprintf(stderr, "mmsurv: statistics all-reduce hook failed (dn_net.hip:%d)\n", __LINE__); return MMS_ERR_LAUNCH; } } } while (0)
@@ -608,7 +609,22 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
     Conv1BwdP c1q[MMS_MAX_GROUP];
     int nq = 0;
     int nq_limit = MMS_MAX_GROUP;
+    // Round 6: in blocks 2-4 the queue holds compact member records over the layer tables mms_dn121_init wrote (mms_wgrad_tab_group,
+    // dn_bwd.hip), so ONE launch pair carries the whole block (24 x ng members in block 3) instead of one pair per MMS_MAX_GROUP members:
+    // those launches were latency-bound (270 workgroups: a third of one round of the chip), each costing a workgroup's own critical path
+    // whatever its member count.  The members' row chunks (msplit) are what the <= 10-member launches use, so the sums are the same.
+    // MmsDnOpts.wgrad_tab = -1 restores those; SyncBN, backward stages and block 1 keep them.
+    const bool wtab = batch_w && o.wgrad_tab >= 0 && !sync && !dp.staged && ng <= MMS_WGRAD_MAX_MODELS;
+    MmsWgradModel wmod[MMS_WGRAD_MAX_MODELS];
+    MmsWgradMember wmem[MMS_WGRAD_MAX_MEMBERS];
+    MmsWgradShape wsh{};
+    int nwq = 0;
     auto flush_w = [&](int b) -> int {
+        if (nwq > 0) {
+            TRYS(12 + b, mms_wgrad_tab_group(wmod, ng, wmem, nwq, &wsh, 1, s));
+            TRYS(16 + b, mms_wgrad_tab_group(wmod, ng, wmem, nwq, &wsh, 2, s));
+            nwq = 0;
+        }
         if (nq == 0) return MMS_OK;
         TRYS(12 + b, mms_conv3_bwd_weight_group(bwq, nq, &o, s));
         TRYS(16 + b, mms_conv1_bwd_weight_group(c1q, nq, s));
@@ -704,7 +720,18 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 TRYS(8 + b, mms_conv3_bwd_data_group(bd, ng, &o, s));
                 SYNC(at<double>(cx[0].ws, P.bb_y1[l]), P.R[b], 2 * 128, 128, 128);
             }
-            if (defer) {
+            if (defer && wtab && b > 0) {
+                if (nwq + ng > MMS_WGRAD_MAX_MEMBERS) TRY(flush_w(b));       // (a block of more members: cut greedily)
+                if (nwq == 0) {
+                    FOR_G wmod[g] = MmsWgradModel{at<B4Layer>(cx[g].ws, P.cl_tab[b]), at<float>(cx[g].ws, P.slab[b]), at<float>(cx[g].ws, P.dslab[b]),
+                                                  at<int>(cx[g].ws, P.coords[b]), at<double>(cx[g].ws, P.st_slab[b]), M, P.g[b], P.R[b]};
+                    wsh = MmsWgradShape{CTOT[b], C0[b], ms3, ms1, packed ? 2 : 1, M * bnw};
+                }
+                FOR_G {
+                    if (!mms_bn_aligned16(bw[g].bn)) return MMS_ERR_ARG;          // (as mms_conv3_bwd_weight_group checks)
+                    wmem[nwq++] = MmsWgradMember{bw[g].dw, c1[g].dw, c1[g].dgamma_out, c1[g].dbeta_out, g, i};
+                }
+            } else if (defer) {
                 if (nq + ng > nq_limit) TRY(flush_w(b));
                 FOR_G { bwq[nq] = bw[g]; c1q[nq] = c1[g]; ++nq; }
             } else {
@@ -833,7 +860,7 @@ extern "C" int mms_dn121_backward_stage(void* ws, int B, int D, int H, int W, co
                                         int bn_world, mms_sync_fn hook, void* user, const MmsDnOpts* opts, hipStream_t s) {
     if (bn_world < 1) return MMS_ERR_ARG;
     Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
-    Dp dp; dp.bn_world = bn_world; dp.hook = hook; dp.user = user; dp.b_hi = block_hi; dp.b_lo = block_lo;
+    Dp dp; dp.bn_world = bn_world; dp.hook = hook; dp.user = user; dp.b_hi = block_hi; dp.b_lo = block_lo; dp.staged = true;
     return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
 }
 

@@ -74,13 +74,11 @@ template <class Op> struct has_zremap<Op, decltype((void)&Op::zremap)> { static 
 #ifndef MMS_TGK_ATTR
 #define MMS_TGK_ATTR            // register-budget experiments: -DMMS_TGK_ATTR='__attribute__((amdgpu_waves_per_eu(4, 4)))'
 #endif
+// One workgroup's share of the GEMM: M tile bx, N tile blockIdx.y, the op's own z index, on the parameter block p.  Shared by
+// tile_gemm_kernel below (p = a by-value member of the kernel argument) and by kernels that rebuild p from a device table
+// (dn_bwd.hip wgrad_tab_*): the arithmetic is this function's, so both give the same bits for the same p.
 template <class Op>
-__global__ __launch_bounds__(256) MMS_TGK_ATTR void tile_gemm_kernel(const Grp<typename Op::Params> grp) {
-    int gi, z, bx = blockIdx.x;                            // model of the fold group, the op's own z index, the M tile
-    if constexpr (has_zremap<Op>::value) Op::zremap((int)blockIdx.z, grp.zdim, (int)gridDim.z, gi, z);
-    else if (grp.zdim == 1) { xcd_place(gi, bx); z = 0; }  // M-tiled launch: XCD-contiguous tile ranges, each model of a 2 / 4 / 8 group on its own XCDs
-    else { gi = blockIdx.z / grp.zdim; z = blockIdx.z - gi * grp.zdim; }
-    const typename Op::Params& p = grp.p[gi];
+__device__ __forceinline__ void tile_gemm_body(const typename Op::Params& p, const int z, const int bx) {
     constexpr int WM = Op::WM, WN = Op::WN, WK = Op::WK;
     static_assert(WM * WN * WK == 4, "4 waves per workgroup");
     typedef TileGemmCfg<Op> Cfg;
@@ -95,11 +93,6 @@ __global__ __launch_bounds__(256) MMS_TGK_ATTR void tile_gemm_kernel(const Grp<t
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     constexpr bool consumer = true;
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
-    // XCD-aware tile order (cdna_hip_programming.md T1): workgroups are dealt round-robin over the 8 XCDs, so give the
-    // blocks that share an XCD (equal blockIdx.x % 8) a CONTIGUOUS range of M tiles -- neighbouring tiles share halo rows /
-    // operand panels, and each XCD's L2 then holds one compact slice of the activations instead of a scatter of all of them.
-    // Placement only affects speed, never results.  (zdim == 1: done by xcd_place above, with the models of a fold group apart.)
-    if ((has_zremap<Op>::value || grp.zdim != 1) && (gridDim.x & 7) == 0) bx = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const int m0 = bx * TM, n0 = blockIdx.y * TN;
 
     Op op;
@@ -289,6 +282,20 @@ __global__ __launch_bounds__(256) MMS_TGK_ATTR void tile_gemm_kernel(const Grp<t
         __syncthreads();
     }
     op.epilogue(p, m0, n0, z, Cs, tid, consumer);
+}
+
+template <class Op>
+__global__ __launch_bounds__(256) MMS_TGK_ATTR void tile_gemm_kernel(const Grp<typename Op::Params> grp) {
+    int gi, z, bx = blockIdx.x;                            // model of the fold group, the op's own z index, the M tile
+    if constexpr (has_zremap<Op>::value) Op::zremap((int)blockIdx.z, grp.zdim, (int)gridDim.z, gi, z);
+    else if (grp.zdim == 1) { xcd_place(gi, bx); z = 0; }  // M-tiled launch: XCD-contiguous tile ranges, each model of a 2 / 4 / 8 group on its own XCDs
+    else { gi = blockIdx.z / grp.zdim; z = blockIdx.z - gi * grp.zdim; }
+    // XCD-aware tile order (cdna_hip_programming.md T1): workgroups are dealt round-robin over the 8 XCDs, so give the
+    // blocks that share an XCD (equal blockIdx.x % 8) a CONTIGUOUS range of M tiles -- neighbouring tiles share halo rows /
+    // operand panels, and each XCD's L2 then holds one compact slice of the activations instead of a scatter of all of them.
+    // Placement only affects speed, never results.  (zdim == 1: done by xcd_place above, with the models of a fold group apart.)
+    if ((has_zremap<Op>::value || grp.zdim != 1) && (gridDim.x & 7) == 0) bx = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    tile_gemm_body<Op>(grp.p[gi], z, bx);
 }
 
 template <class Op>
