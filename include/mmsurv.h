@@ -187,6 +187,10 @@ typedef struct PoolActP {
 } PoolActP;
 
 // ---- norm5 + relu + global-avg-pool + Linear(1024,128) ---------------------------------------------------
+// Any B.  B * C * 4 <= 64 KiB (B <= 16 at C = 1024): a workgroup pools all B samples into LDS and writes its four output columns,
+// grid (ceil(N / 4), 1, ng).  Above that the samples are split into chunks of floor(64 KiB / (C * 4)) over grid.y: a workgroup pools ITS
+// chunk and writes its four columns of those samples, grid (ceil(N / 4), ceil(B / chunk), ng).  Same BatchNorm constants and the same
+// order of additions per sample in both forms.  C * 4 <= 64 KiB (one sample's pooled row must fit).
 typedef struct HeadFwdP {
     const float* slab; int ld; int C; int B; int V;   // [B*V][ld], C channels, V voxels per sample
     BnSrc bn;
@@ -389,7 +393,9 @@ typedef struct LinearBwdP {
 } LinearBwdP;
 
 /* Gated late fusion (R/scripts/training/partial_modality_training.py:257-271): feats [M][288] = ct|rna|clin,
- * mask [M][3]; masked = feats*mask; gate = softmax(W2 relu(W1 [masked|mask] + b1) + b2); fused = masked*gate. */
+ * mask [M][3]; masked = feats*mask; gate = softmax(W2 relu(W1 [masked|mask] + b1) + b2); fused = masked*gate.
+ * Any M, one workgroup per row.  mms_gate_bwd at M > 32: row-tiled form -- a workgroup owns 8 consecutive rows, keeps its share of
+ * dw1 / db1 / dw2 / db2 in registers over them and flushes once (1/8 of the per-row form's fp32 atomics); same values per row. */
 typedef struct GateP {
     const float* feats; const float* mask; int M;
     const float* w1; const float* b1; const float* w2; const float* b2;   // [64][291],[64],[3][64],[3]
@@ -457,7 +463,11 @@ typedef struct AdamP {
  * or dropout only).  fp32 MFMA GEMMs on the tile core; BatchNorm1d batch statistics travel like the BatchNorm3d ones: the
  * producing launch accumulates (sum, sumsq) of its output in fp64 (osum/osumsq), the consuming launch normalises in its
  * operand prologue (bn: sum/sumsq over the M rows).  Backward of one layer: mms_linear_big_bwd_w (dW, db), mms_linear_big_bwd_x
- * (gradient wrt P's output, through dropout/ReLU -> dbn + the two BN-backward column sums), mms_bn1d_bwd_apply (dx, dgamma, dbeta). */
+ * (gradient wrt P's output, through dropout/ReLU -> dbn + the two BN-backward column sums), mms_bn1d_bwd_apply (dx, dgamma, dbeta).
+ * x, y, dy, dbn, dx may be column windows of wider buffers (pointer = base + column offset, ld = the buffer's pitch): the multimodal
+ * heads write [ct | rna | clinical] into one feature buffer.  float4 operand loads need 16-byte aligned rows (offset and pitch multiples
+ * of 4 floats, pitch >= offset + roundup4(K)); anything else takes the scalar loaders.  mms_linear_big_bwd_x: K % 4 == 0; w 16-byte
+ * aligned -> float4 loads, 4-byte aligned -> 16-byte loads the hardware splits (a weight behind an odd-sized tensor in a flat buffer). */
 typedef struct LinBigP {
     const float* x; int ldx; int M; int K;
     const float* w; const float* bias; int N;      // torch Linear: weight [N][K], bias [N]

@@ -867,15 +867,21 @@ MMS_SINGLE(mms_pool_fwd, PoolFwdP)
 // ------------------------------------------------------------------------------------------------------
 // head: norm5 + relu + global average pool + Linear(C, N)
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void head_fwd_kernel(const Grp<HeadFwdP> grp) {
+// CHUNKED = false: one workgroup row pools all B samples into LDS (B * C floats <= 64 KiB); grid (N / 4, 1, ng).
+// CHUNKED = true (any B): grid.y splits the samples into chunks of `chunk`; a workgroup pools ITS chunk and writes its four output columns
+// for those samples.  Per sample the constants, the order of additions over the voxels and the dot product are those of the other form.
+template <bool CHUNKED>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const Grp<HeadFwdP> grp, const int chunk) {
     const HeadFwdP& p = grp.p[blockIdx.z];
-    extern __shared__ float pooled[];   // [B][C]
+    extern __shared__ float pooled[];   // [nb][C]
     const int tid = threadIdx.x;
+    const int b_lo = CHUNKED ? (int)blockIdx.y * chunk : 0;                                  // first sample of this workgroup
+    const int nb = CHUNKED ? (p.B - b_lo < chunk ? p.B - b_lo : chunk) : p.B;               // its samples
     // pooled[b][c] = mean over the sample's V voxels of relu(norm5(x)).  A thread owns 4 channels (tid + 256 j) of a 1024-channel chunk:
     // their BatchNorm constants are requested together, then the rows in batches of 8 -- 1 + rows / 8 memory round trips per chunk
     // (one (b, c) element per trip was B * C / 256 x (constants + V rows) serial round trips: 31 us per launch).
     const float invV = 1.f / (float)p.V;
-    const int rows = p.B * p.V;
+    const int rbase = b_lo * p.V, rows = nb * p.V;
     for (int c0 = 0; c0 < p.C; c0 += 1024) {
         float mu[4], sc[4], be[4];
 #pragma unroll
@@ -893,7 +899,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const Grp<HeadFwdP> grp) 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int c = c0 + tid + 256 * j, r = r0 + i;
-                    x[i][j] = (r < rows && c < p.C) ? p.slab[(size_t)r * p.ld + c] : 0.f;
+                    x[i][j] = (r < rows && c < p.C) ? p.slab[(size_t)(rbase + r) * p.ld + c] : 0.f;
                 }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -909,7 +915,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const Grp<HeadFwdP> grp) 
                             if (c < p.C) {
                                 const float a = accb[j] * invV;
                                 pooled[b * p.C + c] = a;
-                                if (blockIdx.x == 0 && p.pooled) p.pooled[b * p.C + c] = a;
+                                if (blockIdx.x == 0 && p.pooled) p.pooled[(size_t)(b_lo + b) * p.C + c] = a;
                             }
                             accb[j] = 0.f;
                         }
@@ -922,18 +928,18 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const Grp<HeadFwdP> grp) 
     const int n = blockIdx.x * 4 + (tid >> 6), lane = tid & 63;
     if (n >= p.N) return;
     const float bias = p.bias[n];
-    for (int b0 = 0; b0 < p.B; b0 += 4) {          // the weight row is read once per 4 samples
+    for (int b0 = 0; b0 < nb; b0 += 4) {          // the weight row is read once per 4 samples
         float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int c = lane; c < p.C; c += 64) {
             const float wv = p.w[(size_t)n * p.C + c];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) if (b0 + i < p.B) a[i] = fmaf(wv, pooled[(b0 + i) * p.C + c], a[i]);
+            for (int i = 0; i < 4; ++i) if (b0 + i < nb) a[i] = fmaf(wv, pooled[(b0 + i) * p.C + c], a[i]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float v = wave_sum(a[i]);
-            if (lane == 0 && b0 + i < p.B) p.out[(b0 + i) * p.ldo + n] = v + bias;
+            if (lane == 0 && b0 + i < nb) p.out[(size_t)(b_lo + b0 + i) * p.ldo + n] = v + bias;
         }
     }
 }
@@ -942,13 +948,21 @@ extern "C" int mms_head_fwd_group(const HeadFwdP* pp, int ng, hipStream_t s) {
     Grp<HeadFwdP> a;
     if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
     const HeadFwdP& p = *pp;
-    size_t smem = (size_t)p.B * p.C * sizeof(float);
-    if (smem > 64 * 1024 || p.B <= 0) return MMS_ERR_ARG;
+    if (p.B <= 0 || p.C <= 0 || p.V <= 0 || p.N <= 0) return MMS_ERR_ARG;
+    const size_t row = (size_t)p.C * sizeof(float), smem = (size_t)p.B * row;
+    if (row > 64 * 1024) return MMS_ERR_ARG;             // one sample's pooled row must fit
     for (int g = 1; g < ng; ++g) {
         const HeadFwdP& q = pp[g];
         if (q.B != p.B || q.C != p.C || q.N != p.N || q.V != p.V) return MMS_ERR_ARG;
     }
-    MMS_LAUNCH(head_fwd_kernel, dim3((p.N + 3) / 4, 1, ng), dim3(256), smem, s, a);
+    if (smem <= 64 * 1024) {
+        MMS_LAUNCH(head_fwd_kernel<false>, dim3((p.N + 3) / 4, 1, ng), dim3(256), smem, s, a, p.B);
+        return mms_check_launch();
+    }
+    // more samples than one workgroup's LDS holds: sample chunks over grid.y (16 samples at C = 1024)
+    const int chunk = (int)(64 * 1024 / row);
+    if ((p.B + chunk - 1) / chunk > 65535) return MMS_ERR_ARG;
+    MMS_LAUNCH(head_fwd_kernel<true>, dim3((p.N + 3) / 4, (p.B + chunk - 1) / chunk, ng), dim3(256), (size_t)chunk * row, s, a, chunk);
     return mms_check_launch();
 }
 MMS_SINGLE(mms_head_fwd, HeadFwdP)

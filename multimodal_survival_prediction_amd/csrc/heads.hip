@@ -400,6 +400,79 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const Grp<GateP> grp) {
         p.dfeats[(size_t)m * GATE_F + i] = (p.dfused[(size_t)m * GATE_F + i] * g[sg] + dG) * p.mask[m * 3 + sg];
     }
 }
+// Row-tiled backward for M > 32: a workgroup owns GATE_TR consecutive rows, keeps its share of dw1 / db1 / dw2 / db2 in registers over
+// those rows and flushes once -- 1 / GATE_TR of the atomics of the kernel above (which issues 64 x 291 + 64 x 4 + 3 per row).  Thread t owns
+// column t of dw1 (all 64 hidden units) and, for t < GATE_IN - 256, column 256 + t; threads t < 64 own db1[t] and dw2[.][t]; thread 0 db2.
+// Per row the arithmetic (dgate, entropy term, dgate_ext, dfeats) is that of gate_bwd_kernel.
+#define GATE_TR 8
+__global__ __launch_bounds__(256) void gate_bwd_tiled_kernel(const Grp<GateP> grp) {
+    const GateP& p = grp.p[blockIdx.z];
+    __shared__ float G[GATE_IN + 1], h[64], g[3], dl[3], dhp[64], red[4][3];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int m_lo = blockIdx.x * GATE_TR, m_hi = m_lo + GATE_TR < p.M ? m_lo + GATE_TR : p.M;
+    const bool two = t < GATE_IN - 256;
+    float a0[64], a1[64];
+#pragma unroll
+    for (int j = 0; j < 64; ++j) { a0[j] = 0.f; a1[j] = 0.f; }
+    float ab1 = 0.f, aw2[3] = {0.f, 0.f, 0.f}, ab2[3] = {0.f, 0.f, 0.f};
+    for (int m = m_lo; m < m_hi; ++m) {
+        __syncthreads();                 // the previous row's readers of G / dhp / g are done
+        for (int i = t; i < GATE_IN; i += 256)
+            G[i] = i < GATE_F ? p.feats[(size_t)m * GATE_F + i] * p.mask[m * 3 + gate_seg(i)] : p.mask[m * 3 + (i - GATE_F)];
+        if (t < 64) h[t] = p.hidden[m * 64 + t];
+        if (t < 3) g[t] = p.gate[m * 3 + t];
+        __syncthreads();
+        float part[3] = {0.f, 0.f, 0.f};
+        for (int i = t; i < GATE_F; i += 256) part[gate_seg(i)] += p.dfused[(size_t)m * GATE_F + i] * G[i];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { float v = wave_sum(part[c]); if (lane == 0) red[wave][c] = v; }
+        __syncthreads();
+        if (t == 0) {
+            float dg[3], dot = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dg[c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+                if (p.ent_weight != 0.f) dg[c] += p.ent_weight / (float)p.M * (logf(g[c] + 1e-8f) + g[c] / (g[c] + 1e-8f));
+                if (p.dgate_ext) dg[c] += p.dgate_ext[m * 3 + c];
+                dot += g[c] * dg[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { dl[c] = g[c] * (dg[c] - dot); ab2[c] += dl[c]; }
+        }
+        __syncthreads();
+        if (t < 64) {
+            float dh = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { dh = fmaf(dl[c], p.w2[c * 64 + t], dh); aw2[c] = fmaf(dl[c], h[t], aw2[c]); }
+            dhp[t] = h[t] > 0.f ? dh : 0.f;
+            ab1 += dhp[t];
+        }
+        __syncthreads();
+        const float g0 = G[t], g1 = two ? G[256 + t] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 64; ++j) { const float d = dhp[j]; a0[j] = fmaf(d, g0, a0[j]); a1[j] = fmaf(d, g1, a1[j]); }
+        for (int i = t; i < GATE_F; i += 256) {
+            float dG = 0.f;
+            for (int j = 0; j < 64; ++j) dG = fmaf(dhp[j], p.w1[j * GATE_IN + i], dG);
+            const int sg = gate_seg(i);
+            p.dfeats[(size_t)m * GATE_F + i] = (p.dfused[(size_t)m * GATE_F + i] * g[sg] + dG) * p.mask[m * 3 + sg];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 64; ++j) {
+        atomicAdd(&p.dw1[j * GATE_IN + t], a0[j]);
+        if (two) atomicAdd(&p.dw1[j * GATE_IN + 256 + t], a1[j]);
+    }
+    if (t < 64) {
+        atomicAdd(&p.db1[t], ab1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) atomicAdd(&p.dw2[c * 64 + t], aw2[c]);
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) atomicAdd(&p.db2[c], ab2[c]);
+    }
+}
 // gate_entropy_loss(gate) = mean_b sum_k g log(g + 1e-8)  (partial_modality_training.py:322-331), value and gradient
 __global__ void gate_entropy_kernel(const float* gate, int M, float scale, float* loss, float* dgate) {
     const int m = blockIdx.x * 64 + threadIdx.x;
@@ -435,7 +508,8 @@ extern "C" int mms_gate_fwd_group(const GateP* pp, int ng, hipStream_t s) {
 extern "C" int mms_gate_bwd_group(const GateP* pp, int ng, hipStream_t s) {
     Grp<GateP> a;
     if (!gate_group(a, pp, ng)) return MMS_ERR_ARG;
-    MMS_LAUNCH(gate_bwd_kernel, dim3(pp->M, 1, ng), dim3(256), 0, s, a);
+    if (pp->M > 32) MMS_LAUNCH(gate_bwd_tiled_kernel, dim3((pp->M + GATE_TR - 1) / GATE_TR, 1, ng), dim3(256), 0, s, a);
+    else MMS_LAUNCH(gate_bwd_kernel, dim3(pp->M, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
 MMS_SINGLE(mms_gate_fwd, GateP)

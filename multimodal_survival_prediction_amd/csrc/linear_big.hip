@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + r32 + 32 * i, n = n0 + r32 + 32 * i;
-            ra[i] = (m < p.M && k + 3 < p.ldx) ? tail4(*(const float4*)(p.x + (size_t)m * p.ldx + k), k, p.K) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ra[i] = (m < p.M && k < p.K) ? tail4(*(const float4*)(p.x + (size_t)m * p.ldx + k), k, p.K) : make_float4(0.f, 0.f, 0.f, 0.f);
             rb[i] = (n < p.N && k < p.K) ? ld4_row(p.w + (size_t)n * p.K, k, p.K) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int mb = blockIdx.z * mc, me = mb + mc < p.M ? mb + mc : p.M;
     if (mb >= me) return;
     const int c4 = (tid & 31) * 4, r8 = tid >> 5;
-    const bool nok = n0 + c4 < p.N, kok = k0 + c4 + 3 < p.ldx;
+    const bool nok = n0 + c4 < p.N, kok = k0 + c4 < p.K;      // (x_aligned: the pitch covers roundup4(K); never past it -- x may be a column window)
     DpreRaw ra[4];
     float4 rb[4];
     auto gload = [&](int r0) __attribute__((always_inline)) {
@@ -437,7 +437,10 @@ static int lbw_msplit(const LinBigP& p) {
 // ---------------------------------------------------------------------------------------------------------------------
 // backward-data:  dP[m][k] = sum_n dpre[m][n] * W[n][k]  ->  through dropout and ReLU:  dbn[m][k], plus the BatchNorm-backward
 // column sums s1 = sum_m dbn, s2 = sum_m dbn * (x - mean)      (K % 4 == 0: every hidden width)
+// WA16: the weight is 16-byte aligned (float4 loads); otherwise 16-byte loads from 4-byte aligned addresses, as in the forward -- a
+// weight that follows an odd-sized tensor in the flat parameter buffer (PartialModalityNet's fusion layers after the 64 x 291 gate).
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool WA16>
 struct LinBigBwdXOp {
     typedef LinBigP Params;
     static constexpr int WM = 2, WN = 2, WK = 1, AMODE = LD_K4, BMODE = LD_R4;
@@ -457,7 +460,9 @@ struct LinBigBwdXOp {
     __device__ float4 a_tx(const Params& p, int, const ARaw& r, int, int, bool ok) const { return ok ? dpre_tx(p, r) : r.g; }
     __device__ float4 b_ld(const Params& p, int, int k, int n, bool& ok) const {      // B(cols k..k+3, n) = W[n][k..k+3]
         ok = n < p.N && k < p.K;
-        return ok ? *(const float4*)(p.w + (size_t)n * p.K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!ok) return make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (WA16) return *(const float4*)(p.w + (size_t)n * p.K + k);
+        else return ld4u(p.w + (size_t)n * p.K + k);
     }
     __device__ float4 b_tx(const Params&, int, const float4& v, int, int, bool) const { return v; }
     __device__ void epilogue(const Params& p, int m0, int k0, int, const float* Cs, int tid, bool) {
@@ -561,8 +566,9 @@ extern "C" int mms_linear_big_bwd_w(const LinBigP* pp, hipStream_t s) {
 extern "C" int mms_linear_big_bwd_x(const LinBigP* pp, hipStream_t s) {
     if (!pp || !args_ok(*pp) || !pp->dy || !pp->dbn || pp->lddy < pp->N || pp->lddbn < pp->K) return MMS_ERR_ARG;
     const LinBigP& p = *pp;
-    if (!w_aligned(p) || (p.has_bn && (!p.s1 || !p.s2))) return MMS_ERR_ARG;
-    return launch_tile_gemm<LinBigBwdXOp>(pp, 1, dim3((p.M + 63) / 64, (p.K + 63) / 64, 1), s);
+    if ((p.K & 3) != 0 || !w_vec(p) || (p.has_bn && (!p.s1 || !p.s2))) return MMS_ERR_ARG;
+    const dim3 g((p.M + 63) / 64, (p.K + 63) / 64, 1);
+    return w_aligned(p) ? launch_tile_gemm<LinBigBwdXOp<true>>(pp, 1, g, s) : launch_tile_gemm<LinBigBwdXOp<false>>(pp, 1, g, s);
 }
 
 extern "C" int mms_bn1d_bwd_apply(const LinBigP* pp, hipStream_t s) {

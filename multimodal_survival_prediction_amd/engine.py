@@ -318,9 +318,13 @@ class SurvivalEngine:
         D, H, W = dims if P.has_enc else (1, 1, 1)
         P.ct = torch.zeros(B, 1, D, H, W, device=dev)
         P.big = B > 32                 # rows beyond the one-lane-per-column head kernels: MFMA GEMM path (mms_linear_big_*)
-        if P.big and (P.has_enc or prog["gate"] is not None or prog.get("mix") is not None or prog.get("moe") is not None):
-            raise RuntimeError("batches of more than 32 rows are supported for the encoder-less RNASeqSurvivalModel only "
-                               "(the reference trains the imaging models at batch 4-16)")
+        if P.big and prog.get("moe") is not None:
+            raise RuntimeError("SimMLM_SurvivalNet: batches are limited to 32 rows (its mixture-of-experts kernels, csrc/moe.hip, hold one "
+                               "model's rows in LDS arrays of 32); got %d -- train and evaluate it at a batch size of at most 32" % B)
+        if P.big and heads_only:
+            raise RuntimeError("the SyncBN data-parallel step replicates the heads on the GLOBAL batch with the small-batch head kernels, "
+                               "limited to 32 rows; got %d global rows -- lower the per-rank batch or the number of ranks, or train "
+                               "large batches on one GPU (SurvivalEngine.train_step)" % B)
         # row pitch padded to a multiple of 4 floats so that the 5005-wide RNA rows are 16-B aligned (float4 operand loads)
         P.buf = {k: torch.zeros(B, (w + 3) & ~3, device=dev)[:, :w] if P.big and w > 1 else torch.zeros(B, w, device=dev)
                  for k, w in prog["bufs"].items()}
@@ -501,10 +505,12 @@ class SurvivalEngine:
 
     def _plan_big(self, P, gmap):
         """LinBigP blocks (include/mmsurv.h) of the large-batch Linear chain.  BatchNorm1d statistics of a buffer live in one
-        fp64 array per plan: [sum | sumsq | s1 | s2] x columns, zeroed once per training step."""
+        fp64 array per plan: [sum | sumsq | s1 | s2] x columns, zeroed once per training step.  A layer's (buffer, column offset) source /
+        destination is a pointer into the buffer with the buffer's pitch (the multimodal heads write [ct | rna | clinical] into `feats`)."""
         prog, B, dev = self.prog, P.B, self.device
         S, ptr = _S()["LinBigP"], ops.ptr
-        widths = {L.src[0]: L.lin.in_features for L in prog["lins"] if L.pro_bn is not None}
+        # (keyed by (buffer, column offset): two layers that read different columns of one buffer get slots of their own)
+        widths = {L.src: L.lin.in_features for L in prog["lins"] if L.pro_bn is not None}
         off, o = {}, 0
         for name, k in widths.items():
             off[name] = o
@@ -515,9 +521,12 @@ class SurvivalEngine:
         P.big_lin = {True: [], False: []}
         for i, L in enumerate(prog["lins"]):
             (xs, xo), (ys, yo) = L.src, L.dst
-            if xo or yo:
-                raise RuntimeError("large-batch path: column-offset buffers are not supported")
-            x, y = P.buf[xs], P.buf[ys]
+            # column offsets are pointer offsets with the buffer's pitch; the float4 operand loads want 16-byte aligned rows
+            for what, name, co in (("source", xs, xo), ("destination", ys, yo)):
+                if co % 4 != 0 or (co and P.buf[name].stride(0) % 4 != 0):
+                    raise RuntimeError("large-batch path: %s column offset %d of buffer '%s' (pitch %d floats) of layer %d is not 16-byte "
+                                       "aligned; feature widths must be multiples of 4" % (what, co, name, P.buf[name].stride(0), i))
+            x, y = P.buf[xs][:, xo:], P.buf[ys][:, yo:]
             K, N = L.lin.in_features, L.lin.out_features
             for train in (True, False):
                 q = S()
@@ -530,25 +539,25 @@ class SurvivalEngine:
                 bn = L.pro_bn
                 if bn is not None:
                     q.has_bn = 1
-                    q.bn.sum, q.bn.sumsq = st(xs, 0).data_ptr(), st(xs, 1).data_ptr()
+                    q.bn.sum, q.bn.sumsq = st(L.src, 0).data_ptr(), st(L.src, 1).data_ptr()
                     q.bn.rmean, q.bn.rvar = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
                     q.bn.gamma, q.bn.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
                     q.bn.inv_count, q.bn.eps, q.bn.train, q.bn.nrep, q.bn.rep_stride = 1.0 / B, float(bn.eps), q.train, 1, 0
                     q.rmean, q.rvar, q.nbt = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
                     q.momentum = float(bn.momentum)
-                if train and ys in widths:           # a BatchNorm1d follows: the forward accumulates its batch statistics
-                    q.osum, q.osumsq = st(ys, 0).data_ptr(), st(ys, 1).data_ptr()
+                if train and L.dst in widths:        # a BatchNorm1d follows: the forward accumulates its batch statistics
+                    q.osum, q.osumsq = st(L.dst, 0).data_ptr(), st(L.dst, 1).data_ptr()
                 if train:
-                    dy = P.dbuf[ys]
+                    dy = P.dbuf[ys][:, yo:]
                     q.dy, q.lddy = dy.data_ptr(), dy.stride(0)
                     q.dw, q.dbias = gmap[id(L.lin.weight)].data_ptr(), gmap[id(L.lin.bias)].data_ptr()
                     tiles = ((N + 63) // 64) * ((K + 63) // 64)
                     q.msplit = max(1, min((512 + tiles - 1) // tiles, (B + 63) // 64))
                     if L.need_dx:
-                        dx = P.dbuf[xs]
+                        dx = P.dbuf[xs][:, xo:]
                         if bn is not None:
                             q.dbn, q.lddbn = P.big_dbn.data_ptr(), P.big_dbn.stride(0)
-                            q.s1, q.s2 = st(xs, 2).data_ptr(), st(xs, 3).data_ptr()
+                            q.s1, q.s2 = st(L.src, 2).data_ptr(), st(L.src, 3).data_ptr()
                             q.dx, q.lddx = dx.data_ptr(), dx.stride(0)
                             q.dgamma, q.dbeta = gmap[id(bn.weight)].data_ptr(), gmap[id(bn.bias)].data_ptr()
                         else:
@@ -586,7 +595,15 @@ class SurvivalEngine:
         if P.big:
             if train:
                 P.big_stats.zero_()
-            for q in P.big_lin[train]:
+            bl, n_pre = P.big_lin[train], prog["n_pre"]
+            for q in bl[:n_pre]:
+                _lib.check(lib.mms_linear_big_fwd(ctypes.byref(q), st), "mms_linear_big_fwd")
+            if P.gate is not None:
+                self.entropy.zero_()
+                _lib.check(lib.mms_gate_fwd(ctypes.byref(P.gate), st), "mms_gate_fwd")
+            if P.mix is not None:
+                _lib.check(lib.mms_missing_mix_fwd(ctypes.byref(P.mix), st), "mms_missing_mix_fwd")
+            for q in bl[n_pre:]:
                 _lib.check(lib.mms_linear_big_fwd(ctypes.byref(q), st), "mms_linear_big_fwd")
             return
         lf = P.lin_fwd[train]
@@ -622,12 +639,21 @@ class SurvivalEngine:
         B, (D, H, W) = P.B, (P.dims if P.has_enc else (1, 1, 1))
         n_pre = prog["n_pre"]
         if P.big:
-            for L, q in zip(reversed(prog["lins"]), reversed(P.big_lin[True])):
+            def big_bwd(i):
+                L, q = prog["lins"][i], P.big_lin[True][i]
                 _lib.check(lib.mms_linear_big_bwd_w(ctypes.byref(q), st), "mms_linear_big_bwd_w")
                 if L.need_dx:
                     _lib.check(lib.mms_linear_big_bwd_x(ctypes.byref(q), st), "mms_linear_big_bwd_x")
                     if L.pro_bn is not None:
                         _lib.check(lib.mms_bn1d_bwd_apply(ctypes.byref(q), st), "mms_bn1d_bwd_apply")
+            for i in range(len(prog["lins"]) - 1, n_pre - 1, -1):
+                big_bwd(i)
+            if P.gate is not None:         # (mms_gate_bwd: the row-tiled form above 32 rows)
+                _lib.check(lib.mms_gate_bwd(ctypes.byref(P.gate), st), "mms_gate_bwd")
+            if P.mix is not None:
+                _lib.check(lib.mms_missing_mix_bwd(ctypes.byref(P.mix), st), "mms_missing_mix_bwd")
+            for i in range(n_pre - 1, -1, -1):
+                big_bwd(i)
             return
         if P.moe is not None:
             _lib.check(lib.mms_moe_bwd(ctypes.byref(P.moe_bwd[1]), st), "mms_moe_bwd")
@@ -806,6 +832,10 @@ class SurvivalEngine:
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None, bn_world=ddp_world if (sync_bn and ddp_world > 1) else 1)
         self.load_batch(P, ct, rna, clinical, mask, time, event, valid)
         self.sync_packs()
+        if ddp_world > 1 and P.big and self.prog["encoder"] is not None:
+            raise RuntimeError("the data-parallel steps of the imaging models are limited to 32 rows per rank (their staged graphs are "
+                               "built and tested on the small-batch head kernels); got %d -- lower the per-rank batch (the global batch is "
+                               "ddp_world times it) or train large batches on one GPU" % B)
         if ddp_world > 1 and P.moe is not None:
             raise RuntimeError("SimMLM_SurvivalNet: the data-parallel step (ddp_world > 1) is not implemented for this model; "
                                "train its folds as a fold group or one per process instead")

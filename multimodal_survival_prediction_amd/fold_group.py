@@ -82,8 +82,8 @@ class FoldGroupEngine:
         if key in self.plans:
             return self.plans[key]
         if B > 32:
-            raise RuntimeError("fold groups batch the small-batch head kernels (<= 32 rows per model); train large-batch "
-                               "RNA-seq-only folds one engine at a time (SurvivalEngine.train_step)")
+            raise RuntimeError("fold groups batch the small-batch head kernels, limited to 32 rows per model; got %d -- train "
+                               "larger batches with one engine per fold (SurvivalEngine.train_step, fold after fold)" % B)
         eng = [self.engines[i] for i in members]
         Ps = [e.plan(B, dims) for e in eng]
         GP = _GroupPlan()

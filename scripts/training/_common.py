@@ -57,8 +57,11 @@ def data_mod():
     return data
 
 
-def lockstep_enabled(n_local_folds):
-    """Folds of this rank train in lock-step as one fold group (MMS_LOCKSTEP=0 restores fold-after-fold order)."""
+def lockstep_enabled(n_local_folds, batch_size=None):
+    """Folds of this rank train in lock-step as one fold group (MMS_LOCKSTEP=0 restores fold-after-fold order).  batch_size: fold
+    groups are limited to 32 rows per model (FoldGroupEngine.plan); above that the folds run one after the other, one engine each."""
+    if batch_size is not None and batch_size > 32:
+        return False
     return env_int("MMS_LOCKSTEP", 1) != 0 and 2 <= n_local_folds <= 10
 
 

@@ -44,7 +44,7 @@ def main():
     os.makedirs("models/final", exist_ok=True)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
-    if lockstep_enabled(len(my_folds)):      # all local folds advance together, one launch sequence per batch position
+    if lockstep_enabled(len(my_folds), BATCH_SIZE):      # all local folds advance together, one launch sequence per batch position
         loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=SEED + f),
                     data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False)) for f in my_folds]
         models = [MultiModalSurvivalNet().to(device) for _ in my_folds]

@@ -43,7 +43,7 @@ def main():
     opt_kw = dict(lr=LEARNING_RATE, weight_decay=WEIGHT_DECAY, adamw=True)
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
     local = []
-    if lockstep_enabled(len(my_folds)):
+    if lockstep_enabled(len(my_folds), BATCH_SIZE):
         loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=f + 1, style="simple"),
                     data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False, style="simple")) for f in my_folds]
         models = [FlexibleMultimodalModel(rna_dim=cohort["rnaseq"].shape[1]).to(device) for _ in my_folds]

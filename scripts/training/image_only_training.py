@@ -48,7 +48,7 @@ def main():
     kw = dict(lr=LEARNING_RATE, weight_decay=1e-4, adamw=False)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
-    if lockstep_enabled(len(my_folds)):
+    if lockstep_enabled(len(my_folds), BATCH_SIZE):
         splits = [(usable[folds[f][0]], usable[folds[f][1]]) for f in my_folds]
         loaders = [(data.BatchLoader(cohort, tr, BATCH_SIZE, shuffle=True, seed=SEED + f),
                     data.BatchLoader(cohort, va, BATCH_SIZE, shuffle=False)) for f, (tr, va) in zip(my_folds, splits)]

@@ -46,7 +46,7 @@ def main():
     os.makedirs("models/partial_modality", exist_ok=True)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
-    if lockstep_enabled(len(my_folds)):
+    if lockstep_enabled(len(my_folds), BATCH_SIZE):
         splits = [(np.concatenate([survival[folds[f][0]], non_survival]), survival[folds[f][1]]) for f in my_folds]
         loaders = [(data.BatchLoader(cohort, tr_all, BATCH_SIZE, shuffle=True, seed=SEED + f),
                     data.BatchLoader(cohort, va_s, BATCH_SIZE, shuffle=False)) for f, (tr_all, va_s) in zip(my_folds, splits)]

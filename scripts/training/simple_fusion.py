@@ -39,7 +39,7 @@ def main():
     folds = data.kfold_indices(cohort["n"], N_FOLDS, seed=42)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
-    if lockstep_enabled(len(my_folds)):
+    if lockstep_enabled(len(my_folds), BATCH_SIZE):
         loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=f + 1, style="simple"),
                     data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False, style="simple")) for f in my_folds]
         models = [SimpleFusionModel(rna_dim=cohort["rnaseq"].shape[1]).to(device) for _ in my_folds]
