@@ -554,6 +554,36 @@ typedef struct GatherP {
     const float* present[8]; int present_ld[8];   // optional availability flag of row r: present[i][r * present_ld[i]]
 } GatherP;
 
+/* Batch assembly WITH augmentation (mms_gather_aug_group): the gather above with one parameter record per batch row applied inside
+ * the copy -- no extra launch, no extra pass over the volumes.  Contract:
+ *   CT volume  out[z,y,x] = scale * v + offset,  v = src[sz,sy,sx] inside the volume, 0 (air) outside,
+ *              sz = (flip bit 0 ? D-1-z : z) - dz, likewise H (bit 1, dy) and W (bit 2, dx): the flip acts on the destination index
+ *              first, then the shift.  No clamping.  scale == 1 && offset == 0 copies bits unchanged.
+ *   drop bit j hides modality j (0 image, 1 rnaseq, 2 clinical: the column order of the cohort's mask): every source whose
+ *              drop_bit is j is zero-filled without being read, column j of every MMS_AUG_MASK source is written as 0.
+ *   Rows that are absent by GatherP.present stay all-zero (neither read nor transformed; offset is NOT added).
+ * A record with flip = 0, shift = 0, scale = 1, offset = 0, drop = 0 yields exactly what mms_gather_rows_group yields. */
+typedef struct AugRec {
+    int flip;                       // bit 0 / 1 / 2: reverse axis D / H / W
+    int dz; int dy; int dx;         // integer voxel translation, |dz| < D, |dy| < H, |dx| < W
+    float scale; float offset;      // intensity map
+    int drop;                       // bit 0 / 1 / 2: hide image / rnaseq / clinical
+    int reserved;                   // 0 (keeps a record at 32 bytes)
+} AugRec;
+#define MMS_AUG_PLAIN 0             /* copied as by mms_gather_rows_group (plus the drop zero-fill) */
+#define MMS_AUG_VOLUME 1            /* [D][H][W] CT volume, width == D*H*W; at most one per GatherP */
+#define MMS_AUG_MASK 2              /* modality mask: GatherP.width <= 3 columns, column j belongs to modality j */
+typedef struct AugP {
+    const AugRec* rec;              // [B] records of this member's batch rows (device)
+    int role[8];                    // MMS_AUG_* of GatherP source i
+    int drop_bit[8];                // modality (0..2) whose drop bit zero-fills source i; -1: none
+    int D; int H; int W;            // the volume source's shape
+    int max_shift[3];               // bound on |dz|, |dy|, |dx| that the CALLER declares for its records: each must be < D / H / W, else MMS_ERR_ARG.
+                                    // The records live on the device, so the launch cannot read them: the real check is the caller's, on the host
+                                    // (augment.check_records).  The kernel is memory-safe for any record: it bounds-checks every source coordinate
+                                    // and treats a shift of magnitude >= the extent as exactly the extent (everything is air)
+} AugP;
+
 /* ---- ABI self-description ---- */
 int mms_abi_sizeof(const char* name);      /* sizeof(struct <name>) as compiled, -1 if unknown */
 int mms_abi_version(void);
@@ -715,6 +745,7 @@ int mms_bn_running_update_group(const void* const* tables_dev, int ng, int n, fl
 int mms_missing_mix_fwd_group(const MixP* p, int ng, hipStream_t s);
 int mms_missing_mix_bwd_group(const MixP* p, int ng, hipStream_t s);
 int mms_gather_rows_group(const GatherP* p, int ng, hipStream_t s);
+int mms_gather_aug_group(const GatherP* p, const AugP* a, int ng, hipStream_t s);   /* gather + per-row augmentation records */
 int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s);  /* scratch[g]: model g's [nlayers][27][32][128] tap-major scratch; dw[g][i]: canonical gradient of layer i; nlayers <= 58 */
 int mms_zero_regions_group(void* const* regions_dev, int ng, size_t bytes, hipStream_t s);   /* 16-B aligned regions of equal size, zero-filled by one launch */
 int mms_linear_fwd_group(const LinearFwdP* p, int ng, hipStream_t s);

@@ -1,0 +1,227 @@
+"""GPU batch augmentation applied INSIDE the batch-assembly launch (mms_gather_aug_group, include/mmsurv.h: AugRec / AugP).
+
+The reference's dataset takes a `transform` argument ("image augmentation", create_multimodal_dataset.py:197-211) that is stored and
+never applied, and lists "Data augmentation for imaging" under future work (final_comparison.py:331-335).  Here every batch row gets
+one parameter record
+
+    [flip, dz, dy, dx, scale, offset, drop, 0]       (8 x 32 bit: an int32 row whose columns 4 and 5 hold fp32 bit patterns)
+
+and the gather launch that copies the row applies it:  CT voxel  out[z,y,x] = scale * v + offset  with  v = src[sz,sy,sx]  inside the
+volume and 0 (air after min-max normalisation) outside,  sz = (flip & 1 ? D-1-z : z) - dz  and likewise H (bit 1, dy) / W (bit 2, dx);
+drop bit j hides modality j (image / rnaseq / clinical) exactly as if the patient lacked it: its row is zero-filled and column j of
+the mask the model sees becomes 0.  Rows of a modality the patient lacks stay all-zero.  Gaussian noise and elastic / rotation
+transforms are left out on purpose: they need a device RNG whose stream a CPU reference cannot reproduce bit for bit.
+
+AugmentSpec names the distribution, sample_records draws one epoch's records in ONE vectorised call from a generator of its own
+(turning augmentation on leaves the batch order of a seeded run unchanged), apply() runs the kernel over an already materialised batch.
+"""
+import ctypes
+import dataclasses
+
+import torch
+
+REC_WORDS = 8
+FLIP, DZ, DY, DX, SCALE, OFFSET, DROP = range(7)
+MASKLESS_STYLES = ("final", "simple", "image", "rnaseq")        # their models take no modality mask: nothing can tell them a row is hidden
+ROLE_PLAIN, ROLE_VOLUME, ROLE_MASK = 0, 1, 2                     # include/mmsurv.h: MMS_AUG_*
+
+
+def make_records(n, flip=0, shift=(0, 0, 0), scale=1.0, offset=0.0, drop=0):
+    """-> [n, 8] int32 records; every argument is a scalar or an [n] (shift: [n, 3]) array-like."""
+    r = torch.zeros(n, REC_WORDS, dtype=torch.int32)
+    r[:, FLIP] = torch.as_tensor(flip, dtype=torch.int32)
+    r[:, DZ:DX + 1] = torch.as_tensor(shift, dtype=torch.int32)
+    f = r.view(torch.float32)
+    f[:, SCALE] = torch.as_tensor(scale, dtype=torch.float32)
+    f[:, OFFSET] = torch.as_tensor(offset, dtype=torch.float32)
+    r[:, DROP] = torch.as_tensor(drop, dtype=torch.int32)
+    return r
+
+
+def identity_records(n):
+    return make_records(n)
+
+
+def _triple(v, cast):
+    v = tuple(v) if isinstance(v, (tuple, list)) else (v,)
+    if len(v) == 1:
+        v = v * 3
+    if len(v) != 3:
+        raise ValueError("expected one value or one per axis D:H:W, got %r" % (v,))
+    return tuple(cast(x) for x in v)
+
+
+@dataclasses.dataclass(frozen=True)
+class AugmentSpec:
+    """Distribution of the per-row records.  flip_p: probability of reversing axis D / H / W; max_shift: the shift of an axis is
+    uniform on the integers [-max_shift, max_shift]; scale_range / offset_range: uniform fp32 intensity map; modality_drop_p: each
+    modality the patient HAS is hidden with this probability (never the last one left); seed: of the sampler's own generator."""
+    flip_p: tuple = (0.0, 0.0, 0.0)
+    max_shift: tuple = (0, 0, 0)
+    scale_range: tuple = (1.0, 1.0)
+    offset_range: tuple = (0.0, 0.0)
+    modality_drop_p: float = 0.0
+    seed: int = 0
+
+    def __post_init__(self):
+        object.__setattr__(self, "flip_p", _triple(self.flip_p, float))
+        object.__setattr__(self, "max_shift", _triple(self.max_shift, int))
+        object.__setattr__(self, "scale_range", tuple(float(x) for x in self.scale_range))
+        object.__setattr__(self, "offset_range", tuple(float(x) for x in self.offset_range))
+        if any(not 0.0 <= p <= 1.0 for p in self.flip_p) or not 0.0 <= self.modality_drop_p <= 1.0:
+            raise ValueError("augment: probabilities must lie in [0, 1]")
+        if any(s < 0 for s in self.max_shift):
+            raise ValueError("augment: max_shift must be >= 0")
+        for name in ("scale_range", "offset_range"):
+            r = getattr(self, name)
+            if len(r) != 2 or r[0] > r[1]:
+                raise ValueError("augment: %s must be lo:hi with lo <= hi" % name)
+
+    @classmethod
+    def parse(cls, text):
+        """"flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=7" -- every key optional; flip and shift take one
+        value for all axes or D:H:W."""
+        kw, seen = {}, set()
+        for item in str(text).split(","):
+            item = item.strip()
+            if not item:
+                continue
+            if "=" not in item:
+                raise ValueError("augment: expected key=value, got %r" % item)
+            key, val = (x.strip() for x in item.split("=", 1))
+            if key in seen:
+                raise ValueError("augment: %r given twice" % key)
+            seen.add(key)
+            try:
+                if key == "flip":
+                    kw["flip_p"] = _triple(val.split(":"), float)
+                elif key == "shift":
+                    kw["max_shift"] = _triple(val.split(":"), int)
+                elif key in ("scale", "offset"):
+                    lo, hi = val.split(":")
+                    kw[key + "_range"] = (float(lo), float(hi))
+                elif key == "moddrop":
+                    kw["modality_drop_p"] = float(val)
+                elif key == "seed":
+                    kw["seed"] = int(val)
+                else:
+                    raise KeyError(key)
+            except KeyError:
+                raise ValueError("augment: unknown key %r (flip, shift, scale, offset, moddrop, seed)" % key) from None
+            except ValueError:
+                raise ValueError("augment: cannot read %r" % item) from None
+        return cls(**kw)
+
+    def __str__(self):
+        c = lambda v: ":".join(repr(x) for x in v)
+        return "flip=%s,shift=%s,scale=%s,offset=%s,moddrop=%r,seed=%d" % (c(self.flip_p), c(self.max_shift), c(self.scale_range),
+                                                                           c(self.offset_range), self.modality_drop_p, self.seed)
+
+    def validate(self, style=None, dims=None):
+        """Refuse what cannot work: hiding modalities from a model that takes no mask, shifts that move the whole volume out."""
+        if style is not None and self.modality_drop_p > 0 and style in MASKLESS_STYLES:
+            raise ValueError("augment: moddrop=%g cannot be used with style %r: its model takes no modality mask, a hidden modality "
+                             "would look like real zeros (styles with a mask: partial, simmlm, flexible)" % (self.modality_drop_p, style))
+        if dims is not None:
+            for a, (s, d) in enumerate(zip(self.max_shift, dims)):
+                if s >= d:
+                    raise ValueError("augment: max_shift[%d] = %d must be smaller than the volume's extent %d" % (a, s, d))
+        return self
+
+
+def as_spec(x):
+    return x if x is None or isinstance(x, AugmentSpec) else AugmentSpec.parse(x)
+
+
+def sample_records(spec, gen, mask, dims, style=None):
+    """One epoch's records in one call: mask [n, 3] (host) = the modality mask of the n rows in epoch order -> [n, 8] int32.
+    A modality the patient lacks is never "dropped"; a patient never loses the last modality they have.  style "flexible": its model
+    sees image and rnaseq only, so only those two are dropped and counted."""
+    spec.validate(style, dims)
+    has = torch.as_tensor(mask).cpu()[:, :3] != 0
+    n = has.shape[0]
+    u = torch.rand(n, 12, generator=gen)             # one draw per row, always the same width: a field's stream never depends on the others
+    flip = ((u[:, 0:3] < torch.tensor(spec.flip_p)).to(torch.int32) * torch.tensor([1, 2, 4], dtype=torch.int32)).sum(1)
+    ms = torch.tensor(spec.max_shift, dtype=torch.float32)
+    shift = (torch.floor(u[:, 3:6] * (2 * ms + 1)) - ms).clamp(-ms, ms).to(torch.int32)
+    scale = spec.scale_range[0] + (spec.scale_range[1] - spec.scale_range[0]) * u[:, 6]
+    offset = spec.offset_range[0] + (spec.offset_range[1] - spec.offset_range[0]) * u[:, 7]
+    usable = has.clone()
+    if style == "flexible":
+        usable[:, 2] = False
+    drop = (u[:, 8:11] < spec.modality_drop_p) & usable
+    lost = (drop == usable).all(1) & usable.any(1)              # every modality the patient has would be hidden: keep one of them
+    keep = torch.where(usable, u[:, 8:11], torch.full_like(u[:, 8:11], -1.0)).argmax(1)
+    drop[lost, keep[lost]] = False
+    bits = (drop.to(torch.int32) * torch.tensor([1, 2, 4], dtype=torch.int32)).sum(1)
+    return make_records(n, flip, shift, scale, offset, bits)
+
+
+def check_records(rec, dims=None, has_mask=True):
+    """Host-side validation of a record array before it reaches the kernel -> per-axis max |shift|."""
+    rec = torch.as_tensor(rec)
+    if rec.dtype != torch.int32 or rec.shape[-1] != REC_WORDS or rec.is_cuda:
+        raise ValueError("augment records must be a host int32 array of %d words per row (augment.make_records)" % REC_WORDS)
+    mx = rec.reshape(-1, REC_WORDS)[:, DZ:DX + 1].abs().amax(0).tolist() if rec.numel() else [0, 0, 0]
+    if dims is not None:
+        for a, (s, d) in enumerate(zip(mx, dims)):
+            if s >= d:
+                raise ValueError("augment: a record shifts axis %d by %d voxels, the volume's extent is %d" % (a, s, d))
+    if not has_mask and bool((rec.reshape(-1, REC_WORDS)[:, DROP] != 0).any()):
+        raise ValueError("augment: records drop modalities but the model takes no modality mask")
+    if bool(((rec.reshape(-1, REC_WORDS)[:, FLIP] & ~7) != 0).any()) or bool(((rec.reshape(-1, REC_WORDS)[:, DROP] & ~7) != 0).any()):
+        raise ValueError("augment: flip and drop hold 3 bits each")
+    return [int(x) for x in mx]
+
+
+def aug_block(rec_dev, roles, dims, max_shift):
+    """AugP (include/mmsurv.h) -- roles: per gather source (role, drop_bit)."""
+    from . import _lib
+    A = _lib.structs()["AugP"]()
+    A.rec = rec_dev.data_ptr()
+    for i, (role, bit) in enumerate(roles):
+        A.role[i], A.drop_bit[i] = role, bit
+    if dims is not None:
+        A.D, A.H, A.W = (int(d) for d in dims)
+    for a in range(3):
+        A.max_shift[a] = int(max_shift[a])
+    return A
+
+
+def apply(batch, records, present_ok=(True, True)):
+    """The augmenting gather over an already materialised batch (device tensors image / rnaseq / clinical / mask as
+    data.BatchLoader yields them), out of place, identity indices: -> the batch dict with those four replaced.  present_ok: per
+    (image, rnaseq) whether rows whose mask column is 0 are known to be all-zero in the cohort (then they are not read, as in
+    SurvivalEngine.gather_block)."""
+    from . import _lib, ops
+    img, rna, clin, mask = batch["image"], batch["rnaseq"], batch["clinical"], batch["mask"]
+    B, dims = img.shape[0], tuple(img.shape[-3:])
+    rec = torch.as_tensor(records)
+    if rec.shape != (B, REC_WORDS):
+        raise ValueError("augment.apply: one record per batch row, got %r for %d rows" % (tuple(rec.shape), B))
+    mx = check_records(rec, dims)
+    S = _lib.structs()
+    dev = img.device
+    mask = mask.contiguous()
+    srcs = [(img.reshape(B, -1), ROLE_VOLUME, 0, mask if present_ok[0] else None),
+            (rna.contiguous(), ROLE_PLAIN, 1, mask[:, 1:] if present_ok[1] else None),
+            (clin.reshape(B, -1), ROLE_PLAIN, 2, None), (mask, ROLE_MASK, -1, None)]
+    outs = [torch.empty_like(a) for a, _, _, _ in srcs]
+    idx = torch.arange(B, dtype=torch.int64, device=dev)
+    rec_dev = rec.to(dev)
+    G = S["GatherP"]()
+    G.idx, G.B, G.nsrc = idx.data_ptr(), B, len(srcs)
+    roles = []
+    for i, ((a, role, bit, flag), o) in enumerate(zip(srcs, outs)):
+        if a.dtype != torch.float32 or not a.is_cuda:
+            raise TypeError("augment.apply works on fp32 device tensors: keep the cohort in HBM (data.cohort_to) or let a lazy loader name "
+                            "the batches of a pinned-host cohort (the gather launch then augments them)")
+        G.src[i], G.dst[i], G.src_ld[i], G.dst_ld[i], G.width[i] = a.data_ptr(), o.data_ptr(), a.stride(0), o.stride(0), a.shape[1]
+        if flag is not None:
+            G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
+        roles.append((role, bit))
+    A = aug_block(rec_dev, roles, dims, mx)
+    _lib.check(_lib.load_library().mms_gather_aug_group(ctypes.byref(G), ctypes.byref(A), 1, ops.stream()), "mms_gather_aug_group")
+    out = dict(batch)
+    out["image"], out["rnaseq"], out["clinical"], out["mask"] = (outs[0].view(img.shape), outs[1], outs[2].view(clin.shape), outs[3])
+    return out

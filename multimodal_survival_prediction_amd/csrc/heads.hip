@@ -918,6 +918,145 @@ extern "C" int mms_gather_rows_group(const GatherP* pp, int ng, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// batch assembly with augmentation (include/mmsurv.h: AugRec, AugP): the gather above with one record per batch row applied
+// inside the copy.  CT volume rows: D / H flips and shifts only choose WHICH source line (W contiguous floats) a destination line
+// comes from, so whole source lines are staged through LDS with 16-byte loads (pinned-host cohorts: no 4-byte PCIe reads), the W
+// flip / shift and the intensity map are applied on the LDS read, destination lines leave as 16-byte stores.
+// ------------------------------------------------------------------------------------------------------
+#define AUG_TILE4 1024                       // float4 slots of the LDS staging tile (16 KB): 4 loads in flight per thread
+struct AugK { const AugRec* rec; unsigned meta; unsigned pad; };        // meta: 4 bits per source = role | (drop_bit + 1) << 2
+struct AugGrp { AugK k[MMS_MAX_GROUP]; int D, H, W; };
+
+// the copy of gather_rows_kernel for one row (zero: the row is absent or dropped -- zero-filled without being read)
+__device__ __forceinline__ void gather_copy_row(const float* __restrict__ src, float* __restrict__ dst, int w, bool zero, int t0, int stride) {
+    if ((w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+        if (zero) { for (int i = t0; i < (w >> 2); i += stride) ((float4*)dst)[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        else {
+            int i = t0;
+            for (; i + 3 * stride < (w >> 2); i += 4 * stride) {        // four 16-B loads in flight per thread (host-resident rows: PCIe latency)
+                const float4 a = ((const float4*)src)[i], b = ((const float4*)src)[i + stride], c = ((const float4*)src)[i + 2 * stride],
+                             d = ((const float4*)src)[i + 3 * stride];
+                ((float4*)dst)[i] = a; ((float4*)dst)[i + stride] = b; ((float4*)dst)[i + 2 * stride] = c; ((float4*)dst)[i + 3 * stride] = d;
+            }
+            for (; i < (w >> 2); i += stride) ((float4*)dst)[i] = ((const float4*)src)[i];
+        }
+    } else {
+        for (int i = t0; i < w; i += stride) dst[i] = zero ? 0.f : src[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_aug_kernel(const Grp<GatherP> grp, const AugGrp ag) {
+    __shared__ float4 tile[AUG_TILE4];
+    const GatherP& p = grp.p[blockIdx.z];
+    const AugK& k = ag.k[blockIdx.z];
+    const int b = blockIdx.y;
+    if (b >= p.B) return;                                   // (uniform per workgroup, as every branch around a barrier below)
+    const long long row = p.idx[b];
+    const AugRec r = k.rec[b];
+    const int t0 = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    const bool ident_i = r.scale == 1.f && r.offset == 0.f;
+    const bool ident = ident_i && (r.flip & 7) == 0 && r.dz == 0 && r.dy == 0 && r.dx == 0;
+    for (int s = 0; s < p.nsrc; ++s) {
+        const float* src = p.src[s] + (size_t)row * p.src_ld[s];
+        float* dst = p.dst[s] + (size_t)b * p.dst_ld[s];
+        const int w = p.width[s];
+        const unsigned m = (k.meta >> (4 * s)) & 15u;
+        const int role = (int)(m & 3u), dbit = (int)(m >> 2) - 1;
+        if (role == MMS_AUG_MASK) {                         // column j of a mask destination: 0 when modality j is dropped
+            for (int i = t0; i < w; i += stride) dst[i] = ((r.drop >> i) & 1) ? 0.f : src[i];
+            continue;
+        }
+        const bool absent = p.present[s] && p.present[s][(size_t)row * p.present_ld[s]] == 0.f;     // all-zero row by contract: not read
+        const bool zero = absent || (dbit >= 0 && ((r.drop >> dbit) & 1));
+        if (role != MMS_AUG_VOLUME || zero || ident) { gather_copy_row(src, dst, w, zero, t0, stride); continue; }
+        const int D = ag.D, H = ag.H, W = ag.W;
+        // a shift of magnitude >= the extent moves everything out, whatever its value: clamped, so that no record can overflow the index arithmetic
+        const int dz = max(-D, min(D, r.dz)), dy = max(-H, min(H, r.dy)), dx = max(-W, min(W, r.dx));
+        const bool fD = r.flip & 1, fH = r.flip & 2, fW = r.flip & 4;
+        if ((W & 3) == 0 && W <= 4 * AUG_TILE4 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+            const int W4 = W >> 2, LT = AUG_TILE4 / W4, nlines = D * H, ntiles = (nlines + LT - 1) / LT;
+            for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+                const int l0 = t * LT, n4 = min(LT, nlines - l0) * W4;          // whole lines per tile
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {                                   // stage: up to four 16-B loads in flight per thread
+                    const int j = threadIdx.x + u * 256;
+                    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (j < n4) {
+                        const int l = l0 + j / W4, xq = j - (j / W4) * W4;
+                        const int z = l / H, y = l - z * H;
+                        const int sz = (fD ? D - 1 - z : z) - dz, sy = (fH ? H - 1 - y : y) - dy;
+                        if (sz >= 0 && sz < D && sy >= 0 && sy < H)             // a source line outside the volume is air: not read
+                            v[u] = ((const float4*)src)[(size_t)(sz * H + sy) * W4 + xq];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { const int j = threadIdx.x + u * 256; if (j < n4) tile[j] = v[u]; }
+                __syncthreads();
+                const float* tf = (const float*)tile;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = threadIdx.x + u * 256;
+                    if (j < n4) {
+                        const int ll = j / W4, x0 = (j - ll * W4) * 4;
+                        float o[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int x = x0 + e, sx = (fW ? W - 1 - x : x) - dx;
+                            const float q = (sx >= 0 && sx < W) ? tf[ll * W + sx] : 0.f;
+                            o[e] = ident_i ? q : fmaf(r.scale, q, r.offset);
+                        }
+                        ((float4*)dst)[(size_t)l0 * W4 + j] = make_float4(o[0], o[1], o[2], o[3]);
+                    }
+                }
+                __syncthreads();
+            }
+        } else {                                            // any other W or alignment: scalar, merely correct
+            for (int i = t0; i < w; i += stride) {
+                const int x = i % W, l = i / W, y = l % H, z = l / H;
+                const int sz = (fD ? D - 1 - z : z) - dz, sy = (fH ? H - 1 - y : y) - dy, sx = (fW ? W - 1 - x : x) - dx;
+                const float q = (sz >= 0 && sz < D && sy >= 0 && sy < H && sx >= 0 && sx < W) ? src[((size_t)sz * H + sy) * W + sx] : 0.f;
+                dst[i] = ident_i ? q : fmaf(r.scale, q, r.offset);
+            }
+        }
+    }
+}
+extern "C" int mms_gather_aug_group(const GatherP* pp, const AugP* aa, int ng, hipStream_t s) {
+    Grp<GatherP> a;
+    if (!grp_fill(a, pp, ng, 1) || !aa) return MMS_ERR_ARG;
+    AugGrp ag = {};
+    int wmax = 0;
+    for (int g = 0; g < ng; ++g) {
+        const GatherP& q = pp[g];
+        const AugP& u = aa[g];
+        if (q.B != pp->B || q.B <= 0 || !q.idx || q.nsrc < 1 || q.nsrc > 8 || !u.rec) return MMS_ERR_ARG;
+        int nvol = 0;
+        unsigned meta = 0;
+        for (int i = 0; i < q.nsrc; ++i) {
+            if (!q.src[i] || !q.dst[i] || q.width[i] <= 0) return MMS_ERR_ARG;
+            if (u.role[i] < MMS_AUG_PLAIN || u.role[i] > MMS_AUG_MASK || u.drop_bit[i] < -1 || u.drop_bit[i] > 2) return MMS_ERR_ARG;
+            if (u.role[i] == MMS_AUG_MASK && q.width[i] > 3) return MMS_ERR_ARG;
+            if (u.role[i] == MMS_AUG_VOLUME) {
+                if (++nvol > 1 || u.D <= 0 || u.H <= 0 || u.W <= 0 || (long long)u.D * u.H * u.W != (long long)q.width[i]) return MMS_ERR_ARG;
+                if (u.max_shift[0] < 0 || u.max_shift[0] >= u.D || u.max_shift[1] < 0 || u.max_shift[1] >= u.H || u.max_shift[2] < 0 ||
+                    u.max_shift[2] >= u.W)
+                    return MMS_ERR_ARG;
+                if (ag.D && (ag.D != u.D || ag.H != u.H || ag.W != u.W)) return MMS_ERR_ARG;      // one volume shape per group
+                ag.D = u.D; ag.H = u.H; ag.W = u.W;
+            }
+            meta |= ((unsigned)u.role[i] | (unsigned)(u.drop_bit[i] + 1) << 2) << (4 * i);
+            if (q.width[i] > wmax) wmax = q.width[i];
+        }
+        ag.k[g].rec = u.rec; ag.k[g].meta = meta; ag.k[g].pad = 0;
+    }
+    int blocks = (wmax / 4 + 1023) / 1024;       // ~4 float4 per thread on the widest source (one LDS tile of a volume per workgroup)
+    if (blocks < 1) blocks = 1;
+    if (blocks > 64) blocks = 64;
+    MMS_LAUNCH(gather_aug_kernel, dim3(blocks, pp->B, ng), dim3(256), 0, s, a, ag);
+    return mms_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // learnable missing-modality bias (flexible_multimodal.py:243-250): one thread per feature column
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void missing_mix_kernel(const Grp<MixP> grp, int bwd) {

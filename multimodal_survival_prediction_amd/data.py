@@ -9,9 +9,13 @@ bench.py build a seeded synthetic cohort with the same tensors, shapes, dtypes a
   label    (2,) = [survival_time, survival_status]; mask (3,) = [has_image, has_rnaseq, has_clinical]
 Survival times are distinct (no ties), so every Cox formulation of the reference coincides.
 """
+import copy
+
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import augment as _augment
 
 COHORT_608 = dict(n=608, imaging=142, rnaseq=427, clinical=587, survival=348, complete=109)   # R/README.md:21-25
 
@@ -90,12 +94,28 @@ class BatchLoader:
     shuffle uses its own seeded generator; drop_last=False like the reference's DataLoader calls.
     lazy=True (device-resident cohorts, lock-step training): a batch is only NAMED -- dict(index=[B] patient indices,
     has_survival=[...], gather=<gather_view>) -- and assembled on the GPU by the consumer's single gather launch instead of
-    ~8 indexing kernels + copies per fold and batch here."""
+    ~8 indexing kernels + copies per fold and batch here.
+    augment (an augment.AugmentSpec or its string; the reference dataset's unused `transform=` hook): every epoch draws one record
+    per row from a generator of the loader's own -- the shuffle generator, hence the batch order, is the same with and without it.
+    A lazy loader adds augment=<records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them inside its
+    gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both yield the
+    same augmented batches.  augment_style: the model style ("partial", "final", ...) the spec is checked against."""
 
-    def __init__(self, cohort, indices, batch_size, shuffle=False, seed=0, style="final", lazy=False, with_valid=True):
+    def __init__(self, cohort, indices, batch_size, shuffle=False, seed=0, style="final", lazy=False, with_valid=True, augment=None,
+                 augment_style=None):
         self.c, self.idx, self.bs, self.shuffle, self.style = cohort, torch.as_tensor(indices), batch_size, shuffle, style
         self.gen = torch.Generator().manual_seed(seed)
         self.lazy = lazy
+        self.augment = _augment.as_spec(augment)
+        if self.augment is not None:
+            self.augment_style = augment_style
+            self.augment.validate(augment_style, tuple(cohort["image"].shape[-3:]))
+            if not lazy and not cohort["image"].is_cuda:
+                raise ValueError("augment: a loader that materialises its batches augments them on the GPU and needs the cohort in HBM "
+                                 "(data.cohort_to); over a pinned-host cohort pass lazy=True -- the consumer's gather launch then reads "
+                                 "and augments the rows")
+            self.aug_gen = torch.Generator().manual_seed((self.augment.seed * 1000003 + seed) % (1 << 62))
+            self.mask_cpu = cohort["mask"].cpu()         # the sampler never hides a modality the patient lacks
         if lazy:
             self.view = gather_view(cohort, with_valid)
             self.hs_cpu = cohort["has_survival"].cpu().tolist()
@@ -103,13 +123,37 @@ class BatchLoader:
     def __len__(self):
         return (len(self.idx) + self.bs - 1) // self.bs
 
+    def without_augment(self):
+        """This loader minus its augmentation (validation is never augmented); shares the shuffle generator."""
+        if self.augment is None:
+            return self
+        ld = copy.copy(self)
+        ld.augment = None
+        return ld
+
+    def _present_ok(self):
+        """Per (image, rnaseq): rows whose mask column is 0 are all-zero in the cohort (checked once; SurvivalEngine.gather_block)."""
+        chk = self.c.setdefault("_absent_rows_zero", {})
+        for j, key in enumerate(("image", "rnaseq")):
+            if key not in chk:
+                gone = self.c["mask"][:, j] == 0
+                chk[key] = bool((self.c[key][gone] == 0).all()) if bool(gone.any()) else True
+        return chk["image"], chk["rnaseq"]
+
     def __iter__(self):
         idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
         dev = self.c["image"].device
+        recs = None
+        if self.augment is not None:         # one vectorised draw per epoch
+            recs = _augment.sample_records(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
+                                           self.augment_style)
         for i in range(0, len(idx), self.bs):
             if self.lazy:
                 jj = idx[i:i + self.bs]
-                yield dict(index=jj, has_survival=[self.hs_cpu[int(k)] for k in jj], gather=self.view)
+                b = dict(index=jj, has_survival=[self.hs_cpu[int(k)] for k in jj], gather=self.view)
+                if recs is not None:
+                    b["augment"] = recs[i:i + self.bs]
+                yield b
                 continue
             j = idx[i:i + self.bs].to(dev)
             b = dict(image=self.c["image"][j], rnaseq=self.c["rnaseq"][j], clinical=self.c["clinical"][j],
@@ -117,6 +161,8 @@ class BatchLoader:
             if self.style == "simple":   # simple_fusion.py:152-153
                 b["time"] = self.c["label"][j, 0:1]
                 b["event"] = self.c["label"][j, 1:2].long()
+            if recs is not None:
+                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok())
             yield b
 
 

@@ -783,6 +783,22 @@ class SurvivalEngine:
         that the caller refills before each launch.  With a modality mask in the cohort, image / rnaseq rows of patients without that
         modality are zero-filled instead of read -- after checking once that they are all-zero in the cohort, as the reference's
         dataset makes them (partial_modality_training.py:96-141)."""
+        G, _ = self._gather_sources(P, cohort, idx_dev)
+        return G
+
+    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev):
+        """(GatherP, AugP) of mms_gather_aug_group: gather_block's sources plus what each of them is to the augmentation records
+        rec_dev ([B, 8] int32 device tensor, augment.make_records) -- the CT volume, a row that modality j's drop bit zero-fills,
+        a mask whose column j that bit clears.  time / event / valid are plain copies."""
+        from . import augment
+        G, roles = self._gather_sources(P, cohort, idx_dev)
+        dims = tuple(P.ct.shape[-3:]) if P.has_enc else None
+        return G, augment.aug_block(rec_dev, roles, dims, (0, 0, 0))
+
+    def _gather_sources(self, P, cohort, idx_dev):
+        """-> (GatherP, per source (augment role, drop bit)).  A source is (cohort tensor, destination, width or None = all columns,
+        availability flags or None, role, modality whose drop bit zero-fills it or -1)."""
+        from .augment import ROLE_MASK, ROLE_PLAIN, ROLE_VOLUME
         G = _S()["GatherP"]()
         G.idx, G.B = idx_dev.data_ptr(), P.B
         flags = {}
@@ -794,23 +810,22 @@ class SurvivalEngine:
                     chk[key] = bool((cohort[key][gone] == 0).all()) if bool(gone.any()) else True
                 if chk[key]:
                     flags[key] = cohort["mask"][:, j:]
-        srcs = [(cohort["rnaseq"], P.buf["rna"], None, flags.get("rnaseq"))] if "rna" in P.buf else []
+        srcs = [(cohort["rnaseq"], P.buf["rna"], None, flags.get("rnaseq"), ROLE_PLAIN, 1)] if "rna" in P.buf else []
         if P.has_enc:
-            srcs.append((cohort["image"].view(cohort["image"].shape[0], -1), P.ct.view(P.B, -1), None, flags.get("image")))
+            srcs.append((cohort["image"].view(cohort["image"].shape[0], -1), P.ct.view(P.B, -1), None, flags.get("image"), ROLE_VOLUME, 0))
         if "clin" in P.buf:
-            srcs.append((cohort["clinical"], P.buf["clin"], None))
+            srcs.append((cohort["clinical"], P.buf["clin"], None, None, ROLE_PLAIN, 2))
         if P.gate is not None or P.moe is not None:
-            srcs.append((cohort["mask"], P.mask, None))
+            srcs.append((cohort["mask"], P.mask, None, None, ROLE_MASK, -1))
         if P.mix is not None:            # [has_image, has_rnaseq] = the first columns of the cohort's modality mask
-            srcs.append((cohort["mask"], P.mask2, P.mask2.shape[1]))
+            srcs.append((cohort["mask"], P.mask2, P.mask2.shape[1], None, ROLE_MASK, -1))
         lab = cohort["label"]
-        srcs.append((lab, P.time.view(P.B, 1), 1))
-        srcs.append((lab[:, 1:], P.event.view(P.B, 1), 1))
+        srcs.append((lab, P.time.view(P.B, 1), 1, None, ROLE_PLAIN, -1))
+        srcs.append((lab[:, 1:], P.event.view(P.B, 1), 1, None, ROLE_PLAIN, -1))
         if "valid" in cohort:
-            srcs.append((cohort["valid"].view(-1, 1), P.valid.view(P.B, 1), 1))
+            srcs.append((cohort["valid"].view(-1, 1), P.valid.view(P.B, 1), 1, None, ROLE_PLAIN, -1))
         G.nsrc = len(srcs)
-        for i, src in enumerate(srcs):
-            a, b, w, flag = src if len(src) == 4 else src + (None,)
+        for i, (a, b, w, flag, _, _) in enumerate(srcs):
             if a.dtype != torch.float32 or not (a.is_cuda or a.is_pinned()):
                 raise TypeError("gather sources must be fp32 tensors in device or pinned host memory")
             G.src[i], G.dst[i] = a.data_ptr(), b.data_ptr()
@@ -818,7 +833,7 @@ class SurvivalEngine:
             G.width[i] = w if w is not None else a.shape[1]
             if flag is not None:
                 G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
-        return G
+        return G, [(role, bit) for *_, role, bit in srcs]
 
     def train_step(self, ct=None, rna=None, clinical=None, mask=None, time=None, event=None, valid=None, skip_if_unusable=True,
                    use_graph=True, ddp_world=1, global_cox=False, sync_bn=False):

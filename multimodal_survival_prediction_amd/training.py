@@ -433,6 +433,11 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
         group.engines[g].model.train()
         group.engines[g].reset_epoch_stats()
 
+    for ld in loaders:                       # augmentation specs (data.BatchLoader(augment=)) are checked against THIS style
+        if getattr(ld, "augment", None) is not None:
+            ld.augment.validate(style)
+            ld.augment_style = style
+
     def advance(pos):
         lazy = [(g, b) for g, b in pos.items() if "gather" in b]
         if lazy:        # batches named by index (data.BatchLoader(lazy=True)): one gather launch per (sub-)group step
@@ -440,10 +445,11 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
             for g, b in lazy:
                 if style in ("simple", "flexible") and sum(bool(x) for x in b["has_survival"]) < 2:
                     continue                          # skipped before the forward (simple_fusion.py:257-258)
-                by.setdefault((len(b["index"]), id(b["gather"])), []).append((g, b))
-            for items in by.values():
+                by.setdefault((len(b["index"]), id(b["gather"]), "augment" in b), []).append((g, b))
+            for items in by.values():                 # (named batches that carry augmentation records: applied inside the gather launch)
+                aug = torch.stack([b["augment"] for _, b in items]) if "augment" in items[0][1] else None
                 group.train_step_indexed(items[0][1]["gather"], torch.stack([torch.as_tensor(b["index"]) for _, b in items]),
-                                         members=tuple(g for g, _ in items), skip_if_unusable=_skip_unusable(style))
+                                         members=tuple(g for g, _ in items), skip_if_unusable=_skip_unusable(style), augment=aug)
             pos = {g: b for g, b in pos.items() if "gather" not in b}
         by_size = {}
         for g, batch in pos.items():
@@ -585,6 +591,7 @@ def validate_lockstep(group, loaders, style, device, members=None, concurrent=1)
     -> per member (val_loss, c_index).  Loaders that NAME their batches (final / partial / simple styles) take _validate_lockstep_named;
     concurrent = n: as train_epoch_lockstep, n sub-groups on n HIP streams (that path only)."""
     members = tuple(range(len(group))) if members is None else tuple(members)
+    loaders = [ld.without_augment() if hasattr(ld, "without_augment") else ld for ld in loaders]       # validation is never augmented
     if style in ("final", "partial", "simple") and all(getattr(ld, "lazy", False) for ld in loaders):
         return _validate_lockstep_named(group, loaders, style, members, concurrent)
     acc = {g: dict(total=0.0, nb=0, hs=[], ts=[], es=[]) for g in members}

@@ -25,6 +25,22 @@ def env_dims(default=(64, 64, 32)):
     return tuple(int(x) for x in v.split(",")) if v else tuple(default)
 
 
+def augment_spec(style):
+    """MMS_AUGMENT="flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=0" (unset by default): GPU batch
+    augmentation of the TRAINING loaders (multimodal_survival_prediction_amd.augment) -> AugmentSpec checked against the model
+    style (moddrop needs a model that takes a modality mask), or None."""
+    v = os.environ.get("MMS_AUGMENT")
+    if not v:
+        return None
+    from multimodal_survival_prediction_amd.augment import AugmentSpec
+    return AugmentSpec.parse(v).validate(style, env_dims())
+
+
+def augment_hparams(spec):
+    """-> {"augment": "<spec>"} for cv_results.json's hyperparameters; nothing when augmentation is off (today's JSON unchanged)."""
+    return {} if spec is None else {"augment": str(spec)}
+
+
 def setup_device():
     from multimodal_survival_prediction_amd import distributed as D
     world, rank, local = D.init()

@@ -14,7 +14,7 @@ import time
 import numpy as np
 import torch
 
-from _common import cv_lockstep, env_dims, env_float, env_int, lockstep_enabled, save_json, setup_device
+from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, lockstep_enabled, save_json, setup_device
 
 from multimodal_survival_prediction_amd import data, distributed as D
 from multimodal_survival_prediction_amd.losses import ConcordanceIndex, neg_partial_log_likelihood  # noqa: F401
@@ -30,6 +30,7 @@ BATCH_SIZE = env_int("MMS_BATCH_SIZE", 8)
 LEARNING_RATE = env_float("MMS_LR", 1e-4)
 WEIGHT_DECAY = env_float("MMS_WEIGHT_DECAY", 1e-3)
 N_PATIENTS = env_int("MMS_PATIENTS", 88)
+AUGMENT = augment_spec("simple")        # MMS_AUGMENT: GPU batch augmentation of the training loaders (unset: off)
 
 
 def main():
@@ -40,7 +41,8 @@ def main():
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
     if lockstep_enabled(len(my_folds), BATCH_SIZE):
-        loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=f + 1, style="simple"),
+        loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=f + 1, style="simple",
+                                     augment=AUGMENT, augment_style="simple"),
                     data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False, style="simple")) for f in my_folds]
         models = [SimpleFusionModel(rna_dim=cohort["rnaseq"].shape[1]).to(device) for _ in my_folds]
         res = cv_lockstep("simple", models, loaders, dict(lr=LEARNING_RATE, weight_decay=WEIGHT_DECAY, adamw=True), NUM_EPOCHS, None,
@@ -53,7 +55,8 @@ def main():
     for fold0 in my_folds:
         fold = fold0 + 1
         train_ids, val_ids = folds[fold0]
-        train_loader = data.BatchLoader(cohort, train_ids, BATCH_SIZE, shuffle=True, seed=fold, style="simple")
+        train_loader = data.BatchLoader(cohort, train_ids, BATCH_SIZE, shuffle=True, seed=fold, style="simple",
+                                        augment=AUGMENT, augment_style="simple")
         val_loader = data.BatchLoader(cohort, val_ids, BATCH_SIZE, shuffle=False, style="simple")
         model = SimpleFusionModel(rna_dim=cohort["rnaseq"].shape[1]).to(device)
         optimizer = FusedOptimizer(model, lr=LEARNING_RATE, weight_decay=WEIGHT_DECAY, adamw=True)
@@ -78,7 +81,8 @@ def main():
         c = [r["best_c_index"] for r in fold_results]
         save_json(os.path.join(RESULTS_DIR, "cv_results.json"), {
             "model": "Simple-Fusion (RNA+Image)", "n_folds": N_FOLDS, "num_epochs": NUM_EPOCHS,
-            "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)), "fold_results": fold_results})
+            "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)), "fold_results": fold_results,
+            **({"hyperparameters": augment_hparams(AUGMENT)} if AUGMENT is not None else {})})
         print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f}; saved {RESULTS_DIR}/cv_results.json")
 
 
