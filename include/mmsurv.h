@@ -334,6 +334,19 @@ typedef struct Conv0BwdWP {                 // dW0[64][343] += sum_m bn0bwd(dbn0
                                     // NULL / 0: atomics straight into dw
 } Conv0BwdWP;
 
+/* conv0 backward-data with norm0 frozen (input-gradient attribution; csrc/attrib.hip):
+ *   dx[b,d,h,w] = sum_c sum_taps a_c * dbn[b,(d+3-kd)/2,(h+3-kh)/2,(w+3-kw)/2,c] * w[c][kd,kh,kw],  a_c = gamma_c / sqrt(rvar_c + eps)
+ * over the taps whose three quotients are integral and inside the output grid.  dx is WRITTEN (every element, no atomics: two calls give
+ * the same bits); the caller need not zero it.  bn.train must be 0 (running statistics); out = ceil(in / 2) per axis. */
+typedef struct Conv0BwdDataP {
+    const float* dbn;               // [B*out][64] gradient at norm0's output, already masked by relu0 (what mms_pool_bwd leaves)
+    BnSrc bn;                       // norm0, train = 0: gamma and rvar are read
+    const float* w;                 // [64][343]
+    Dims3 in; Dims3 out;            // out = ceil(in/2)
+    int M;                          // B*out voxels
+    float* dx;                      // [B][D][H][W]
+} Conv0BwdDataP;
+
 /* =========================== fallback CT encoder (R/scripts/training/final_multimodal.py:75-86) ==================
  * 3 x [Conv3d(k3, s2, p1, bias) + BatchNorm3d + ReLU] (1->32->64->128) + AdaptiveAvgPool3d(1): what the reference
  * runs when MONAI is absent.  Channels-last activations; each conv stores its raw output (+bias) and batch
@@ -635,6 +648,25 @@ int mms_fb3_forward(void* ws, size_t ws_bytes, const int* widths, int B, int D, 
                     const void* const* buffers, float* out, int ldo, int train, hipStream_t s);
 int mms_fb3_backward(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params,
                      const float* dout, int lddout, void* const* grads, hipStream_t s);
+
+/* ---- input-gradient attribution (csrc/attrib.hip): the data path of a backward with FROZEN statistics -- every BatchNorm is the
+ *      per-channel affine map of its running statistics, its backward dx = gamma / sqrt(rvar + eps) * dy.  No weight gradient, no parameter
+ *      or buffer is written, no float atomics (two calls give the same bits), no workgroup waits for another. ---- */
+int mms_conv0_bwd_data(const Conv0BwdDataP* p, hipStream_t s);   /* norm0 (frozen) backward + conv0 wrt the volume */
+int mms_conv0_bwd_data_group(const Conv0BwdDataP* p, int ng, hipStream_t s);     /* grid z = member; members of identical shape */
+/* DenseNet121-3D: after an EVAL-mode mms_dn121_forward of the same x on the same workspace, run in its per-layer forms (MmsDnOpts
+ * persist_b3 = persist_b4 = fuse_layers = -1: they leave y0, argmax, the slabs and every layer's y1): dx [B][D][H][W] = gradient of
+ * sum_b dout[b] . features[b] with respect to the volume, written.  params / buffers / opts as mms_dn121_forward (buffers required: the
+ * running statistics; opts must select the same conv2 pack layout as the forward: w2_packed, conv3_small).  Runs the training
+ * backward's data kernels with BnSrc.train = 0, then mms_pool_bwd and mms_conv0_bwd_data; the per-step statistic scratch of the
+ * workspace is overwritten (the next training forward zeroes it), nothing else. */
+int mms_dn121_input_grad(void* ws, int B, int D, int H, int W, const float* x, const void* const* params, const void* const* buffers,
+                         const float* dout, int lddout, float* dx, const MmsDnOpts* opts, hipStream_t s);
+/* After an EVAL-mode mms_fb3_forward of the same x on the same workspace (it leaves the three raw convolution outputs): dx [B][D][H][W] =
+ * gradient of sum_b dout[b] . features[b] with respect to the volume, written.  Arguments as mms_fb3_backward, buffers as mms_fb3_forward
+ * (running statistics, required); overwrites only the workspace's gradient scratch, which every training backward rewrites before use. */
+int mms_fb3_input_grad(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params,
+                       const void* const* buffers, const float* dout, int lddout, float* dx, hipStream_t s);
 
 /* ---- heads ---- */
 int mms_linear_fwd(const LinearFwdP* p, hipStream_t s);        /* nn.Linear (+ preceding BN1d/ReLU/Dropout, + following ReLU) */

@@ -6,15 +6,19 @@ There is no CPU fallback: ops raise if the library is missing.
 
 Modules: models (the reference's nn.Modules), losses, training (train_epoch_* / validate_* of each script, lock-step
 K-fold variants), engine (fused HIP-graph step of one model), fold_group (K fold models advanced by one launch sequence),
-data / cohort_io (synthetic cohorts, on-disk contract, GPU preprocessing), distributed (fold sharding, DDP helpers).
+data / cohort_io (synthetic cohorts, on-disk contract, GPU preprocessing), distributed (fold sharding, DDP helpers),
+attribution (input-gradient saliency maps, gene scores and modality shares of an eval-mode model).
 """
 from ._lib import lib_path, load_library  # noqa: F401
 
-__all__ = ["load_library", "lib_path", "ImageOnlyModel"]
+__all__ = ["load_library", "lib_path", "ImageOnlyModel", "attribution"]
 
 
 def __getattr__(name):      # (models pulls in torch and the engine: imported on first use)
     if name == "ImageOnlyModel":
         from .models import ImageOnlyModel
         return ImageOnlyModel
+    if name == "attribution":
+        import importlib
+        return importlib.import_module(".attribution", __name__)
     raise AttributeError(name)

@@ -147,7 +147,14 @@ __device__ __forceinline__ void bn_consts1(const BnSrc& b, int c, float& mean, f
 
 // Everything a BatchNorm-backward consumer needs for channel c of a training-mode BatchNorm -- (mean, rstd, gamma) and the two backward
 // sums (s1 = sum dy, s2 = sum dy * xhat) -- with all five base loads issued together (one round trip instead of five).
+// Frozen statistics (b.train == 0, the input-gradient path of mms_dn121_input_grad): the BatchNorm is a per-channel affine map, its
+// backward has no mean terms -- t1 = t2 = 0 and bb is not read.
 __device__ __forceinline__ void bn_bwd_consts(const BnSrc& b, const BnBwd& bb, int c, float& mean, float& rstd, float& gamma, double& t1, double& t2) {
+    if (!b.train) {
+        gamma = b.gamma[c]; mean = b.rmean[c]; rstd = 1.0f / sqrtf(b.rvar[c] + b.eps);
+        t1 = 0.0; t2 = 0.0;
+        return;
+    }
     double sq[2] = {b.sum[c], b.sumsq[c]}, tt[2] = {bb.s1[c], bb.s2[c]};
     gamma = b.gamma[c];
     { const double* const p[2] = {b.sum + c, b.sumsq + c}; rep_add(p, b.nrep, (size_t)b.rep_stride, sq); }

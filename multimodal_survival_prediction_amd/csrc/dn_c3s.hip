@@ -287,12 +287,14 @@ __global__ __launch_bounds__(256) void conv3s_bwd_data_kernel(const Grp<Conv3Bwd
             const int m = m0 + 4 * h + r;
             yv[j][r] = y1[(size_t)(m < M ? m : M - 1) * 128 + c];
         }
-        bs[j] = bn.sum[c]; bq[j] = bn.sumsq[c];
+        if (bn.train) { bs[j] = bn.sum[c]; bq[j] = bn.sumsq[c]; }
+        else { mu[j] = bn.rmean[c]; rstd[j] = bn.rvar[c]; bs[j] = 0; bq[j] = 0; }      // frozen statistics (mms_dn121_input_grad)
         ga[j] = bn.gamma[c]; be[j] = bn.beta[c];
     }
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
         const int c = cin0 + 16 * j + li;
+        if (!bn.train) { rstd[j] = 1.0f / sqrtf(rstd[j] + bn.eps); continue; }
         for (int r = 1; r < bn.nrep; ++r) { bs[j] += bn.sum[c + (size_t)r * bn.rep_stride]; bq[j] += bn.sumsq[c + (size_t)r * bn.rep_stride]; }
         const double m = bs[j] * (double)bn.inv_count;
         double v = bq[j] * (double)bn.inv_count - m * m;

@@ -69,6 +69,9 @@ int mms_c3s_bwd_data(const Conv3BwdDataP* pp, int ng, const MmsDnOpts& o, hipStr
 #define MMS_FUSE_MAXG 4
 int mms_c3s_c1s_fwd(const Conv3FwdP* p3, const Conv1FwdP* p1, unsigned* const* flags, unsigned* const* errs, int ng, hipStream_t s);
 
+// head of the input-gradient path (attrib.hip): class_layers + norm5 backward with frozen statistics, data only
+int mms_head_input_grad(const HeadBwdP* pp, hipStream_t s);
+
 // ---- dense blocks 3 / 4 as one launch per pass (dn_cl.hip, dn_b4.hip); internal to the network drivers ---------------------------
 struct B4Layer {               // device table entry, one per dense layer (built by mms_dn121_init)
     const float *g1, *b1, *w1;                 // norm1 gamma / beta [C], conv1 weight [128][C]

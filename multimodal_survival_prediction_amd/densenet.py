@@ -171,6 +171,28 @@ class DenseNet121(nn.Module):
         _lib.check(e["lib"].mms_dn121_backward(e["ws"].data_ptr(), B, D, H, W, x.data_ptr(), e["ptab"],
                                                dout.data_ptr(), dout.stride(0), gtab, ctypes.byref(self._opts()), st), "mms_dn121_backward")
 
+    def input_grad(self, x, dout):
+        """Eval mode only: -> (features [B, out], dx like x), dx = gradient of (features * dout).sum() with respect to the volume,
+        BatchNorm statistics frozen (mms_dn121_input_grad after an eval forward in the per-layer forms).  Touches no parameter, buffer
+        or .grad."""
+        if self.training:
+            raise RuntimeError("DenseNet121 (HIP): input_grad needs eval mode (frozen BatchNorm statistics); call .eval() first")
+        from . import ops
+        x = self._check_input(x)
+        e = self._tables(x)
+        B, D, H, W = e["dims"]
+        nout = self.class_layers.out.out_features
+        opts = ops.dn_opts(self.dn_opts, out_features=nout, persist_b3=-1, persist_b4=-1, fuse_layers=-1)
+        out = torch.empty(B, nout, device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        dout = dout.contiguous().float()
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(e["lib"].mms_dn121_forward(e["ws"].data_ptr(), B, D, H, W, x.data_ptr(), e["ptab"], e["btab"], out.data_ptr(),
+                                              out.stride(0), 0, ctypes.byref(opts), st), "mms_dn121_forward")
+        _lib.check(e["lib"].mms_dn121_input_grad(e["ws"].data_ptr(), B, D, H, W, x.data_ptr(), e["ptab"], e["btab"], dout.data_ptr(),
+                                                 dout.stride(0), dx.data_ptr(), ctypes.byref(opts), st), "mms_dn121_input_grad")
+        return out, dx
+
     def workspace_region(self, name, index=0, dtype=torch.float32):
         """Diagnostic view of a named workspace region (tests)."""
         e = self._eng

@@ -577,7 +577,8 @@ class SurvivalEngine:
         self._opts_live = o          # (keeps the block alive for the duration of the call)
         return ctypes.byref(o)
 
-    def _forward(self, P, train):
+    def _forward(self, P, train, enc_opts=None):
+        """enc_opts: `const MmsDnOpts*` of the DenseNet121 driver call instead of _opts_arg's (attribute: the per-layer forms)."""
         self.sync_packs()
         st = ops.stream()
         lib, prog = self.lib, self.prog
@@ -591,7 +592,8 @@ class SurvivalEngine:
                                                feats.stride(0), 1 if train else 0, st), "mms_fb3_forward")
             else:
                 _lib.check(lib.mms_dn121_forward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
-                                                 feats.stride(0), 1 if train else 0, self._opts_arg(P), st), "mms_dn121_forward")
+                                                 feats.stride(0), 1 if train else 0, enc_opts if enc_opts is not None else self._opts_arg(P), st),
+                           "mms_dn121_forward")
         if P.big:
             if train:
                 P.big_stats.zero_()
@@ -1081,6 +1083,109 @@ class SurvivalEngine:
         else:
             self._forward(P, False)
         return P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)
+
+    # ---- input-gradient attribution ----------------------------------------------------------------------
+    def _attr_blocks(self, P):
+        """Parameter blocks of the attribution backward on plan P (B <= 32): every Linear with its prologue in EVAL mode, no weight
+        gradient and dx requested down to the raw inputs; the gate without its entropy term, its weight gradients into a private
+        scratch; the missing-modality mix without its bias gradient.  Nothing here points into gflat."""
+        A = getattr(P, "attr", None)
+        if A is not None:
+            return A
+        S, dev, prog = _S(), self.device, self.prog
+        A = dict(dct=torch.zeros_like(P.ct) if P.has_enc else None, lin=[], gate=None, mix=None)
+        for k in ("rna", "clin"):
+            if k in P.buf:
+                A["d" + k] = torch.zeros(P.B, prog["bufs"][k], device=dev)
+        for i, L in enumerate(prog["lins"]):
+            (xs, xo), (ys, yo) = L.src, L.dst
+            x, y, dy = P.buf[xs][:, xo:], P.buf[ys][:, yo:], P.dbuf[ys][:, yo:]
+            dx = A["d" + xs] if xs in ("rna", "clin") else P.dbuf[xs][:, xo:]
+            A["lin"].append(S["LinearBwdP"](dy.data_ptr(), dy.stride(0), y.data_ptr(), y.stride(0), 1 if L.out_relu else 0,
+                                            x.data_ptr(), x.stride(0), P.B, L.lin.in_features, self._prolog(L, i, False),
+                                            L.lin.weight.data_ptr(), L.lin.out_features, None, None, dx.data_ptr(), dx.stride(0), None, None))
+        if P.gate is not None:
+            G = S["GateP"]()
+            ctypes.memmove(ctypes.byref(G), ctypes.byref(P.gate), ctypes.sizeof(G))
+            A["gate_scratch"] = torch.zeros(64 * 291 + 64 + 3 * 64 + 3, device=dev)
+            b = A["gate_scratch"].data_ptr()
+            G.ent_weight, G.dgate_ext, G.entropy = 0.0, None, None
+            G.dw1, G.db1, G.dw2, G.db2 = b, b + 4 * 64 * 291, b + 4 * (64 * 291 + 64), b + 4 * (64 * 291 + 64 + 192)
+            A["gate"] = G
+        if P.mix is not None:
+            M = S["MixP"]()
+            ctypes.memmove(ctypes.byref(M), ctypes.byref(P.mix), ctypes.sizeof(M))
+            for i in range(4):
+                M.dbias[i] = None
+            A["mix"] = M
+        if P.has_enc and not P.fallback:     # the encoder's per-layer forms: nothing on this path waits inside a launch
+            A["opts"] = ops.dn_opts(self.dn_opts, persist_b3=-1, persist_b4=-1, fuse_layers=-1)
+        P.attr = A
+        return A
+
+    def _attribute_chunk(self, P, ct, rna, clinical, mask):
+        st, lib, prog = ops.stream(), self.lib, self.prog
+        A = self._attr_blocks(P)
+        self.load_batch(P, ct, rna, clinical, mask)
+        self._forward(P, False, enc_opts=ctypes.byref(A["opts"]) if "opts" in A else None)
+        P.dbuf["hz"].fill_(1.0)           # d hazard[b] / d hazard[b] = 1: rows do not interact in eval mode
+        n_pre = prog["n_pre"]
+        for i in range(len(A["lin"]) - 1, n_pre - 1, -1):
+            _lib.check(lib.mms_linear_bwd(ctypes.byref(A["lin"][i]), st), "mms_linear_bwd")
+        if A["gate"] is not None:
+            _lib.check(lib.mms_gate_bwd(ctypes.byref(A["gate"]), st), "mms_gate_bwd")
+        if A["mix"] is not None:
+            _lib.check(lib.mms_missing_mix_bwd(ctypes.byref(A["mix"]), st), "mms_missing_mix_bwd")
+        for i in range(n_pre - 1, -1, -1):
+            _lib.check(lib.mms_linear_bwd(ctypes.byref(A["lin"][i]), st), "mms_linear_bwd")
+        if P.has_enc:
+            B, (D, H, W) = P.B, P.dims
+            dfe = P.dbuf["feats"]
+            dct = dfe[:, prog["ct_cols"]:]
+            if P.fallback:
+                _lib.check(lib.mms_fb3_input_grad(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab,
+                                                  dct.data_ptr(), dfe.stride(0), A["dct"].data_ptr(), st), "mms_fb3_input_grad")
+            else:
+                _lib.check(lib.mms_dn121_input_grad(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, dct.data_ptr(),
+                                                    dfe.stride(0), A["dct"].data_ptr(), ctypes.byref(A["opts"]), st), "mms_dn121_input_grad")
+        out = dict(hazard=P.buf["hz"][:, 0].clone(), gate=P.gatew.clone() if P.gate is not None else None)
+        out["ct"] = A["dct"].clone() if P.has_enc else None
+        out["rna"] = A["drna"].clone() if "drna" in A else None
+        out["clinical"] = A["dclin"].clone() if "dclin" in A else None
+        return out
+
+    def attribute(self, ct=None, rna=None, clinical=None, mask=None, wrt=("ct", "rna", "clinical")):
+        """Input-gradient attribution of an EVAL-mode model: -> dict(hazard [B], gate [B, 3] | None, ct [B, 1, D, H, W], rna [B, rna_dim],
+        clinical [B, clinical_dim]); entry m of `wrt` is the gradient of row b's hazard with respect to row b's raw input m (None for an
+        input the model does not have or that is not in `wrt`).  BatchNorm statistics are frozen, so rows do not interact and one
+        backward with dhazard = 1 per row gives every row's gradient; more than 32 rows run in chunks of 32 (exact).  Eval forward ->
+        heads' backward with eval-mode prologues and no weight gradients -> the encoder's input-gradient driver (mms_dn121_input_grad /
+        mms_fb3_input_grad).  Touches no .grad, no optimiser state, no running statistic, no conv2 pack and no training graph."""
+        kind = self.prog["kind"]
+        if kind == "SimMLM_SurvivalNet":
+            raise RuntimeError("attribute: SimMLM_SurvivalNet is not supported -- its mixture-of-experts kernels (csrc/moe.hip) have no "
+                               "input-gradient form; supported: the five imaging classes and RNASeqSurvivalModel")
+        if self.model.training:
+            raise RuntimeError("attribute needs the model in eval mode (call model.eval()): input gradients are taken with frozen "
+                               "BatchNorm statistics; train-mode (batch-statistic) input gradients are not computed")
+        bad = [w for w in wrt if w not in ("ct", "rna", "clinical")]
+        if bad:
+            raise ValueError("attribute: wrt takes 'ct', 'rna', 'clinical'; got %r" % (bad,))
+        ref = rna if rna is not None else ct
+        B = ref.shape[0]
+        dims = tuple(ct.shape[-3:]) if (ct is not None and self.prog["encoder"] is not None) else None
+        parts = []
+        for b0 in range(0, B, 32):
+            b1 = min(B, b0 + 32)
+            cut = lambda t: None if t is None else t[b0:b1]
+            P = self.plan(b1 - b0, dims)
+            parts.append(self._attribute_chunk(P, cut(ct), cut(rna), cut(clinical), cut(mask)))
+        out = {}
+        for k in ("hazard", "gate", "ct", "rna", "clinical"):
+            vals = [p[k] for p in parts]
+            keep = k in ("hazard", "gate") or k in wrt
+            out[k] = None if (vals[0] is None or not keep) else (vals[0] if len(vals) == 1 else torch.cat(vals, 0))
+        return out
 
     def reset_epoch_stats(self):
         self.acc.zero_()

@@ -404,6 +404,11 @@ class FoldGroupEngine:
         self._graph(GP, "evalloss", lambda: self._eval_loss_body(GP)).replay()
         return [(P.buf["hz"][:, 0], P.cox_eval_out) for P in GP.Ps]
 
+    def attribute(self, *args, **kw):
+        """Input-gradient attribution is a single-model path (SurvivalEngine.attribute)."""
+        raise RuntimeError("FoldGroupEngine.attribute: input-gradient attribution is not implemented for fold groups (no lock-step "
+                           "form of mms_dn121_input_grad / mms_fb3_input_grad); call SurvivalEngine.attribute on each fold's model")
+
     def forward_eval(self, batches, members=None, use_graph=True):
         """Eval-mode forward of every member -> list of (hazard [B] view, gate [B,3] or None) per member."""
         members = tuple(range(len(self.engines))) if members is None else tuple(members)

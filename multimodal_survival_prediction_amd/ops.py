@@ -197,6 +197,18 @@ def conv0_bwd_weight(dbn, y0, bn, bb, x, in_dims, out_dims, coords, dw, msplit, 
     call("mms_conv0_bwd_weight", p)
 
 
+def conv0_bwd_data(dbn, bn, w, in_dims, out_dims, dx, group=None):
+    """norm0 (frozen: bn.train = 0) backward + conv0 with respect to the volume (mms_conv0_bwd_data): dbn [B*out, 64] -> dx [B, D, H, W],
+    written.  group: a list of (dbn, bn, w, dx) members of identical shape for ONE mms_conv0_bwd_data_group launch (grid z = member)."""
+    S = _S()["Conv0BwdDataP"]
+    mk = lambda d, b, w_, x_: S(ptr(d), b, ptr(w_), dims3(in_dims), dims3(out_dims), d.shape[0], ptr(x_))
+    if group is None:
+        call("mms_conv0_bwd_data", mk(dbn, bn, w, dx))
+        return
+    arr = (S * len(group))(*[mk(*m) for m in group])
+    _lib.check(_lib.load_library().mms_conv0_bwd_data_group(arr, len(group), stream()), "mms_conv0_bwd_data_group")
+
+
 # ---- heads ------------------------------------------------------------------------------------------------
 def inprolog(bn=None, train=False, drop_p=0.0, drop_mask=None, rng=None, stream_id=0):
     """bn: None or a torch.nn.BatchNorm1d-like holder with weight/bias/running_mean/running_var/num_batches_tracked."""

@@ -11,6 +11,7 @@ and the Kaplan-Meier tables as CSV.
 
     python scripts/analysis/evaluate_model.py                            # evaluates an existing results/test_predictions.csv
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1
+    python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute
 
 --predict runs the checkpoint's eval-mode forward on the MI355X (the HIP path; no CPU fallback) over the validation split
 of that fold of the cohort the training entry points use (data/processed/* under MMS_DATA_ROOT when present, else the seeded
@@ -44,7 +45,7 @@ MODELS = {
 }
 
 
-def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
+def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
     labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth."""
@@ -75,6 +76,12 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
     model.to(device).eval()
     eng = engine_of(model)
     risks = []
+    ids = cohort.get("patient_id")
+    pid = lambda i: ids[i] if ids is not None else f"SYN-{i:04d}"
+    gene_sum, gene_rows = None, 0
+    if attribute_dir:
+        from multimodal_survival_prediction_amd import attribution
+        os.makedirs(attribute_dir, exist_ok=True)
     for s in range(0, len(idx), batch_size):
         j = torch.as_tensor(idx[s:s + batch_size], device=device)
         ct, rna, clin, mask = cohort["image"][j], cohort["rnaseq"][j], cohort["clinical"][j], cohort["mask"][j]
@@ -91,10 +98,28 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv):
         else:
             hz, _ = eng.forward_eval(None, rna)
         risks.append(hz.clone().cpu())
+        if attribute_dir:
+            has = (mask != 0).cpu().numpy() if mask is not None else np.ones((len(j), 3), bool)
+            res = attribution.attribute(model, dict(ct=ct, rna=rna, clinical=clin, mask=mask if kind in ("partial", "flexible") else None))
+            if res["ct"] is not None:
+                vols = res["ct"][:, 0].cpu().numpy()
+                for r, i in enumerate(idx[s:s + batch_size]):
+                    if has[r, 0]:
+                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct.npy"), vols[r])
+            if res["rna"] is not None and has[:, 1].any():
+                g = res["rna"].abs().double().cpu().numpy()[has[:, 1]]
+                gene_sum = g.sum(0) if gene_sum is None else gene_sum + g.sum(0)
+                gene_rows += len(g)
+    if attribute_dir and gene_sum is not None:
+        names = cohort.get("gene_names") or [f"g{i}" for i in range(len(gene_sum))]
+        score = gene_sum / gene_rows
+        order = np.argsort(-score, kind="stable")[:top]
+        pd.DataFrame({"gene": [names[i] for i in order], "mean_abs_grad": score[order]}).to_csv(
+            os.path.join(attribute_dir, "gene_scores.csv"), index=False)
+        print(f"wrote {attribute_dir}: saliency volumes and gene_scores.csv ({len(order)} genes over {gene_rows} patients)")
     eng.check_b4()                                     # a timed-out block-4 hand-off must not end up in the predictions file
     lab = cohort["label"].cpu().numpy()[idx]
-    ids = cohort.get("patient_id")
-    df = pd.DataFrame({"patient_id": [ids[i] for i in idx] if ids is not None else [f"SYN-{i:04d}" for i in idx],
+    df = pd.DataFrame({"patient_id": [pid(i) for i in idx],
                        "survival_time": lab[:, 0], "event": lab[:, 1].astype(int), "risk_score": torch.cat(risks).numpy()})
     os.makedirs(os.path.dirname(out_csv) or ".", exist_ok=True)
     df.to_csv(out_csv, index=False)
@@ -177,8 +202,13 @@ def main(argv=None):
     ap.add_argument("--n-folds", type=int, default=0, help="default: the training script's N_FOLDS (MMS_FOLDS)")
     ap.add_argument("--batch-size", type=int, default=0, help="default: the training script's BATCH_SIZE (MMS_BATCH_SIZE)")
     ap.add_argument("--no-plots", action="store_true")
+    ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv")
+    ap.add_argument("--top", type=int, default=50, help="rows of gene_scores.csv")
     a = ap.parse_args(argv)
-    df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions) if a.predict else pd.read_csv(a.predictions)
+    if a.attribute and not a.predict:
+        ap.error("--attribute needs --predict CHECKPOINT (the gradients are taken on the checkpoint's model)")
+    adir = os.path.join(a.outdir, "attribution") if a.attribute else None
+    df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top) if a.predict else pd.read_csv(a.predictions)
     s = evaluate(df, a.outdir, plots=not a.no_plots)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
