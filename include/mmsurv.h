@@ -93,6 +93,15 @@ typedef struct MmsDnOpts {
                               conv2 and ONE conv1 launch at the block's end, the members described by compact records over the layer tables
                               mms_dn121_init wrote (mms_wgrad_tab_group; the parameter pointers of the call must be those given to
                               mms_dn121_init); -1 = launches of at most MMS_MAX_GROUP by-value members (rounds 2-5) */
+    int skip_dead_bwd;     /* encoder backward of a model whose feature gradient is all zero (a batch without a CT under a modality mask):
+                              0 = the head launch of mms_dn121_backward / _mt / _group records in the workspace word "bwd_live" whether any
+                              element of dout compares unequal to 0.0f (NaN counts; -0.0f is zero), and every later launch of the call
+                              returns at once for a model whose word is 0 -- every quantity they compute is linear in dout, so they would
+                              add exact zeros to the gradients.  The word is data, not a launch parameter: one captured graph serves live
+                              and dead batches.  -1 = every launch does its work whatever dout holds.  Never on under SyncBN or a
+                              statistics hook (the BatchNorm-backward sums couple the ranks), in mms_dn121_backward_stage and in
+                              mms_dn121_input_grad (they do not run this call's head launch).  The one difference in results: with a
+                              zero dout and a non-finite saved activation the full backward yields NaN gradients, the skipped one none */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.
@@ -220,6 +229,8 @@ typedef struct Conv3BwdDataP {
     int nsplit;
     int srep; int sstride;          // statistic-accumulator replicas written by this op: workgroup x adds to replica x % srep (stride in doubles)
     int wfrag;                      // 1: wpb is in MFMA-fragment order [tap][cin/16][cout/16][lane = ((cout/4)%4)*16 + cin%16][cout%4] (mms_pack_conv3_frag); as Conv3FwdP.wfrag
+    const unsigned* live;           // optional (MmsDnOpts.skip_dead_bwd): device word; 0 = every workgroup of this member returns at once.  NULL = always run.
+                                    // (PoolBwdP, HeadBwdP and MmsWgradModel keep their layouts: the drivers pass their words beside them, csrc/dn_ops.h)
 } Conv3BwdDataP;
 
 // conv3 backward-weight: dW[cout][cin][tap] += sum_m relu(bn(y1))[nbr(m,tap)][cin] * dz[m][cout]
@@ -234,6 +245,7 @@ typedef struct Conv3BwdWP {
                                     //    rate; mms_unpack_conv3_grads adds it into the canonical gradient;
                                     // 2: [32][27][128] (cout, tap, cin) -- the PACKED PRIMARY layout of MmsDnOpts.w2_packed: the same
                                     //    512-byte runs, and the buffer IS the parameter's gradient (no scratch, no unpack)
+    const unsigned* live;           // optional, as Conv3BwdDataP.live
 } Conv3BwdWP;
 
 /* Weight gradients of many (model, layer) members of ONE dense block as one launch per op (csrc/dn_bwd.hip): the members' parameter
@@ -292,6 +304,7 @@ typedef struct Conv1BwdP {
        fuse_dgamma += s2, fuse_dbeta += s1; dbn / s1 / s2 are not written and no mms_bn_bwd_apply launch follows. */
     float* fuse_dx; int fuse_lddx; int fuse_accumulate;
     float* fuse_dgamma; float* fuse_dbeta;
+    const unsigned* live;           // optional, as Conv3BwdDataP.live (data and weight kernels)
 } Conv1BwdP;
 
 // dslab[:, 0:C] (+)= g*rstd*(dbn - s1/M - xhat*s2/M)
@@ -301,6 +314,7 @@ typedef struct BnBwdApplyP {
     float* dx; int lddx;
     int M; int C; BnSrc bn; BnBwd bb; int accumulate;
     float* dgamma; float* dbeta;    // [C] written by block 0 (dgamma = s2, dbeta = s1)
+    const unsigned* live;           // optional, as Conv3BwdDataP.live
 } BnBwdApplyP;
 
 typedef struct HeadBwdP {
@@ -332,6 +346,7 @@ typedef struct Conv0BwdWP {                 // dW0[64][343] += sum_m bn0bwd(dbn0
     float* dw_rep; int nrep;        // optional: nrep zeroed replicas [nrep][64*343] -- workgroup x adds to replica x % nrep and a second launch adds the
                                     // replicas into dw (256 workgroups x 22 k atomics on the 686 lines of ONE gradient serialise at the memory side);
                                     // NULL / 0: atomics straight into dw
+    const unsigned* live;           // optional, as Conv3BwdDataP.live (both launches)
 } Conv0BwdWP;
 
 /* conv0 backward-data with norm0 frozen (input-gradient attribution; csrc/attrib.hip):
@@ -696,6 +711,11 @@ int mms_w2_pack(const AdamP* p, hipStream_t s);                /* the derived co
 int mms_ablation_build(void);      /* 1: the library was built with a timing-ablation flag (MMS_CXXFLAGS=-DMMS_ABLATE_..., tools/ablate*.sh): launches
                                       may be left out of the step -- diagnostics only; bench.py refuses to report a value from such a build */
 int mms_dn121_workspace_bytes(int B, int D, int H, int W, size_t* bytes);
+/* Named workspace regions (tests, diagnostics): byte offset and size.  "y0", "slab" / "dslab" [block], "y1" [layer], "tpool" [transition],
+ * "stats" (the per-step zeroed region), "b4_err", "hx", and "bwd_live": ONE 32-bit word per workspace, written by the head launch of
+ * every mms_dn121_backward / _mt / _group call with MmsDnOpts.skip_dead_bwd on -- 1 = this model's dout had an element unequal to 0.0f
+ * (or was too large to scan), 0 = the later launches of that call returned at once.  Outside the per-step zeroed region; undefined
+ * before the first such call, not touched by the staged / SyncBN / input-gradient drivers. */
 int mms_dn121_region(int B, int D, int H, int W, const char* name, int index, size_t* off, size_t* bytes);
 int mms_dn121_init(void* ws, int B, int D, int H, int W, const void* const* params, const void* const* buffers, const MmsDnOpts* opts, hipStream_t s);
 /* which dense layers (bit l, l < 58) get their conv2 packs in MFMA-fragment order for this problem and these options (the layers whose

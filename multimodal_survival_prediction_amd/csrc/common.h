@@ -14,7 +14,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Fold groups: one launch advances up to MMS_MAX_GROUP independent models of identical shape (the K-fold models of the
 // reference's cross-validation loop, final_multimodal.py:316-402).  The kernel argument is the array of the models'
-// parameter blocks BY VALUE (<= 10 x 352 B, kernarg segment); the model index is an extra grid dimension: blockIdx.z for
+// parameter blocks BY VALUE (<= 10 x 368 B, kernarg segment); the model index is an extra grid dimension: blockIdx.z for
 // plain kernels, blockIdx.z / zdim for the tile-GEMM core (whose own z = blockIdx.z % zdim).  Per-model work is exactly
 // the single-model kernel's: grouping changes placement only, never results.
 template <class P> struct Grp { P p[MMS_MAX_GROUP]; int zdim; };
@@ -46,6 +46,30 @@ __device__ __forceinline__ void xcd_place(int& gi, int& bx) {
     } else {
         bx = k * per + (blockIdx.x >> 3);
     }
+}
+
+// Dead-backward skip (include/mmsurv.h MmsDnOpts.skip_dead_bwd): the backward kernels of a model return at once when the model's
+// "bwd_live" word -- written by the head launch, an earlier launch on the same stream, and by nothing else during the backward -- is 0.
+// The test is uniform over every workgroup of the model, so kernels whose workgroups wait for each other leave together.
+// live_issue requests the word (first thing in the kernel); live_dead tests it AFTER the kernel's own first loads have been issued, so a
+// live model pays no extra memory round trip.  A relaxed agent-scope atomic load: a vector load the compiler neither sinks to the test
+// nor repeats, retired in order ahead of the loads issued behind it.  NULL = no word, always live.
+__device__ __forceinline__ unsigned live_issue(const unsigned* w) {
+    return w ? __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
+}
+__device__ __forceinline__ bool live_dead(unsigned v) { return __builtin_amdgcn_readfirstlane(v) == 0u; }
+// Words of the launches whose parameter blocks have no `live` member (PoolBwdP, HeadBwdP: layouts kept), by value beside the Grp<>
+struct LiveTab { const unsigned* w[MMS_MAX_GROUP]; };
+static inline LiveTab live_tab(const unsigned* const* live, int ng) {
+    LiveTab t{};
+    for (int g = 0; live && g < ng && g < MMS_MAX_GROUP; ++g) t.w[g] = live[g];
+    return t;
+}
+// Parameter blocks with a `live` member (the backward ones); others (the forward's) never skip: resolved at compile time.
+template <class P, class = void> struct has_live_word { static constexpr bool value = false; };
+template <class P> struct has_live_word<P, decltype((void)std::declval<const P&>().live)> { static constexpr bool value = true; };
+template <class P> __device__ __forceinline__ const unsigned* live_word_of(const P& p) {
+    if constexpr (has_live_word<P>::value) return p.live; else return nullptr;
 }
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(<N - 1>) in order.  (A `#pragma unroll` loop whose body holds rarely taken

@@ -121,11 +121,13 @@ struct Conv3BwdDataOp {
 // tap-split variant: sum the 27 partials, apply the relu2 mask, write dbn2 and the BN2-backward sums
 __global__ __launch_bounds__(256) void conv3_bwd_data_reduce_kernel(const Grp<Conv3BwdDataP> grp) {
     const Conv3BwdDataP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);
     __shared__ double red[2][2][128];
     const int c = threadIdx.x & 127, rg = threadIdx.x >> 7;
     float mu, rstd;
     bn_mean_rstd(p.bn, c, mu, rstd);
     const float ga = p.bn.gamma[c], be = p.bn.beta[c];
+    if (live_dead(alive)) return;
     double s1 = 0, s2 = 0;
     const int mend = blockIdx.x * 4 + 4 < p.M ? blockIdx.x * 4 + 4 : p.M;
     for (int m = blockIdx.x * 4 + rg; m < mend; m += 2) {
@@ -154,11 +156,13 @@ __global__ __launch_bounds__(256) void conv3_bwd_data_reduce_kernel(const Grp<Co
 template <int RT>      // rows per thread; 2 RT rows per workgroup
 __global__ __launch_bounds__(256) void conv3_bwd_data_reduce16_kernel(const Grp<Conv3BwdDataP> grp) {
     const Conv3BwdDataP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);
     __shared__ double red[2][2][128];
     const int c = threadIdx.x & 127, rg = threadIdx.x >> 7;
     float mu, rstd;
     bn_mean_rstd(p.bn, c, mu, rstd);
     const float ga = p.bn.gamma[c], be = p.bn.beta[c];
+    if (live_dead(alive)) return;
     const int m0 = blockIdx.x * (2 * RT) + rg;
     float v[RT][4], y[RT];
 #pragma unroll
@@ -209,6 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     int gi, bx;
     xcd_place(gi, bx);
     const Conv3BwdDataP& p = grp.p[gi];
+    const unsigned alive = live_issue(p.live);
     const float* __restrict__ dz = p.dz;
     const float* __restrict__ wpb = p.wpb;
     const float* __restrict__ y1 = p.y1;
@@ -243,6 +248,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     };
     bload(b[0], 0);
     bload(b[1], 1);
+    if (live_dead(alive)) return;                                      // (dead model: every load of the prologue is in flight, nothing stored yet)
 #pragma unroll
     for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
@@ -469,10 +475,11 @@ __global__ __launch_bounds__(256) void unpack_conv3_grads_kernel(const UnpackTab
 // fold-group form: the scratch of layer i of model g is scratch[g] + i * 27*32*128 (how the driver lays it out), so a table
 // entry is just the destination pointer: 8 models x 58 layers x 8 B = 3.7 KB of kernarg, one launch for the group
 #define UNPACK_MAXG 7        // 7 x 58 x 8 B + 56 B = 3.3 KB of kernarg; larger groups take two launches
-struct UnpackGroup { const float* scratch[UNPACK_MAXG]; float* dw[UNPACK_MAXG][58]; };
+struct UnpackGroup { const float* scratch[UNPACK_MAXG]; float* dw[UNPACK_MAXG][58]; const unsigned* live[UNPACK_MAXG]; };
 __global__ __launch_bounds__(256) void unpack_conv3_grads_group_kernel(const UnpackGroup tab) {
     __shared__ float t[27 * 129];
     const int co = blockIdx.x, layer = blockIdx.y, g = blockIdx.z;
+    if (live_dead(live_issue(tab.live[g]))) return;      // (dead model: its scratch holds the forward's zeros)
     const float* scratch = tab.scratch[g] + (size_t)layer * 27 * 32 * 128;
     for (int idx = threadIdx.x; idx < 27 * 128; idx += 256) {
         const int tap = idx >> 7, cin = idx & 127;
@@ -485,7 +492,7 @@ __global__ __launch_bounds__(256) void unpack_conv3_grads_group_kernel(const Unp
         dst[idx] += t[tap * 129 + cin];
     }
 }
-extern "C" int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s) {
+extern "C" int mms_unpack_conv3_grads_group_live(const float* const* scratch, float* const* const* dw, const unsigned* const* live, int ng, int nlayers, hipStream_t s) {
     if (nlayers <= 0) return MMS_OK;
     if (!scratch || !dw || ng < 1 || ng > MMS_MAX_GROUP || nlayers > 58) return MMS_ERR_ARG;
     for (int g0 = 0; g0 < ng; g0 += UNPACK_MAXG) {
@@ -493,6 +500,7 @@ extern "C" int mms_unpack_conv3_grads_group(const float* const* scratch, float* 
         UnpackGroup t;
         for (int g = 0; g < n; ++g) {
             t.scratch[g] = scratch[g0 + g];
+            t.live[g] = live ? live[g0 + g] : nullptr;
             for (int i = 0; i < nlayers; ++i) t.dw[g][i] = dw[g0 + g][i];
         }
         MMS_LAUNCH(unpack_conv3_grads_group_kernel, dim3(32, nlayers, n), dim3(256), 0, s, t);
@@ -500,6 +508,9 @@ extern "C" int mms_unpack_conv3_grads_group(const float* const* scratch, float* 
         if (rc != MMS_OK) return rc;
     }
     return MMS_OK;
+}
+extern "C" int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s) {
+    return mms_unpack_conv3_grads_group_live(scratch, dw, nullptr, ng, nlayers, s);
 }
 extern "C" int mms_unpack_conv3_grads(const void* table_host, int nlayers, hipStream_t s) {
     if (nlayers <= 0) return MMS_OK;
@@ -534,6 +545,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
         } else { gi = flat / zdim; z = flat - gi * zdim; }
     }
     const Conv3BwdWP& p = grp.p[gi];
+    const unsigned alive = live_issue(p.live);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* vf = (float2*)(smem + 2 * C3W_STAGE);                      // per chunk row: 1/0 for "kw = 0 valid", "kw = 2 valid"
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
@@ -546,6 +558,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     const int c0 = (tid & 31) * 4;
     float mean[4], sc[4], beta[4];
     bn_consts4(p.bn, c0, mean, sc, beta);
+    if (live_dead(alive)) return;
     // zero padding: the (kd, kh) part of a row's tap validity is common to the three taps and is folded into the staged dz
     // row; the kw part (kw = 1 is always valid) is a per-row factor pair read next to the dz fragment
     for (int j = tid; j < mc; j += 256) {
@@ -999,7 +1012,7 @@ extern "C" int mms_conv1_bwd_weight_group(const Conv1BwdP* pp, int ng, hipStream
 MMS_SINGLE(mms_conv1_bwd_weight, Conv1BwdP)
 
 // ---- table-fed weight-gradient launches (include/mmsurv.h MmsWgradModel): every (model, layer) member of a dense block in one launch per op.
-// The by-value form above carries MMS_MAX_GROUP parameter blocks of 136 / 352 bytes; here a member is 40 bytes in the kernel argument, and a
+// The by-value form above carries MMS_MAX_GROUP parameter blocks of 144 / 368 bytes; here a member is 40 bytes in the kernel argument, and a
 // workgroup rebuilds its member's Conv3BwdWP / Conv1BwdP -- field for field what the network driver builds on the host -- from the model's
 // header and layer table, then runs the same tile_gemm_body<Op>: same arithmetic, same bits.
 struct WgradTab {
@@ -1007,6 +1020,7 @@ struct WgradTab {
     MmsWgradMember mem[MMS_WGRAD_MAX_MEMBERS];
     MmsWgradShape sh;
     float inv_count;
+    const unsigned* live[MMS_WGRAD_MAX_MODELS];      // dead-backward skip: the models' words (NULL = always run)
 };
 static_assert(sizeof(WgradTab) <= 4096, "kernel-argument segment");
 
@@ -1027,7 +1041,7 @@ __global__ __launch_bounds__(256) MMS_TGK_ATTR void wgrad_tab_conv3_kernel(const
     p.y1 = L.y1; p.coords = md.coords; p.g = md.g; p.M = md.M;
     p.bn = wgrad_bn(L.st_y1, 128, L.g2, L.b2, t.inv_count, md.srep);
     p.dz = md.dslab + t.sh.C0 + 32 * m.layer; p.lddz = t.sh.ld;
-    p.dw = m.dw2; p.msplit = t.sh.ms3; p.dw_layout = t.sh.dw_layout;
+    p.dw = m.dw2; p.msplit = t.sh.ms3; p.dw_layout = t.sh.dw_layout; p.live = t.live[m.model];
     tile_gemm_body<Conv3BwdWOp>(p, z, 0);
 }
 
@@ -1047,12 +1061,16 @@ __global__ __launch_bounds__(256) MMS_TGK_ATTR void wgrad_tab_conv1_kernel(const
     p.x = md.slab; p.ldx = t.sh.ld; p.K = K;
     p.bn_in = wgrad_bn(md.st_slab, t.sh.ld, L.g1, L.b1, t.inv_count, md.srep);
     p.w = L.w1; p.dw = m.dw1;
-    p.msplit = t.sh.ms1; p.dgamma_out = m.dgamma2; p.dbeta_out = m.dbeta2;
+    p.msplit = t.sh.ms1; p.dgamma_out = m.dgamma2; p.dbeta_out = m.dbeta2; p.live = t.live[m.model];
     tile_gemm_body<Conv1BwdWOp<false>>(p, z, blockIdx.x);
 }
 
 extern "C" int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, const MmsWgradMember* members, int nmembers,
                                    const MmsWgradShape* shape, int which, hipStream_t s) {
+    return mms_wgrad_tab_group_live(models, nullptr, nmodels, members, nmembers, shape, which, s);
+}
+extern "C" int mms_wgrad_tab_group_live(const MmsWgradModel* models, const unsigned* const* live, int nmodels, const MmsWgradMember* members, int nmembers,
+                                        const MmsWgradShape* shape, int which, hipStream_t s) {
     if (!models || !members || !shape || nmodels < 1 || nmodels > MMS_WGRAD_MAX_MODELS || nmembers < 1 || nmembers > MMS_WGRAD_MAX_MEMBERS ||
         which < 1 || which > 3) return MMS_ERR_ARG;
     const MmsWgradShape& sh = *shape;
@@ -1076,7 +1094,7 @@ extern "C" int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, con
     }
     WgradTab t;
     memset(&t, 0, sizeof(t));
-    for (int g = 0; g < nmodels; ++g) t.mod[g] = models[g];
+    for (int g = 0; g < nmodels; ++g) { t.mod[g] = models[g]; t.live[g] = live ? live[g] : nullptr; }
     for (int i = 0; i < nmembers; ++i) t.mem[i] = members[i];
     t.sh = sh; t.inv_count = 1.0f / (float)sh.count;
     if (which & 1) {
@@ -1101,6 +1119,7 @@ extern "C" int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, con
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const Grp<BnBwdApplyP> grp, const int rows) {
     const BnBwdApplyP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);
     // workgroup = `rows` rows x one chunk of <= 256 channels.  The per-channel constants (fp64 replica sums of four
     // accumulators) are computed ONCE per workgroup, one channel per thread, and shared through LDS; the threads then map
     // densely onto (channel quad, row): a 64-channel layer keeps all 256 lanes busy (16 quads x 16 rows).
@@ -1120,6 +1139,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const Grp<BnBwdApplyP
             p.dbeta[c] += (float)t1;
         }
     }
+    if (live_dead(alive)) return;           // (dead model: the sums above are the forward's zeros)
     __syncthreads();
     const int nq = nc >> 2, rpar = 256 / nq;                  // row lanes per pass
     const int q = tid % nq, rl = tid / nq;
@@ -1217,8 +1237,21 @@ __global__ __launch_bounds__(256) void head_bwd_feat_kernel(const Grp<HeadBwdP> 
         p.dbeta[c] += (float)t1;
     }
 }
-__global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp) {
+#define HEAD_LIVE_SCAN 16384
+__global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp, const LiveTab lt) {
     const HeadBwdP& p = grp.p[blockIdx.z];
+    // the model's "bwd_live" word (mms_head_bwd_group_live; read by every later launch of the backward): 1 if any of the B x N elements of
+    // dout compares unequal to 0.0f.  Workgroup 0 scans dout -- a few loads per thread up to HEAD_LIVE_SCAN elements; a larger dout is
+    // not scanned and counts as live.  The head launches themselves always do their work: with dout == 0 they write the zeros that the
+    // later launches would read.
+    unsigned* const live_out = (unsigned*)lt.w[blockIdx.z];
+    if (blockIdx.x == 0 && live_out) {
+        const int n_el = p.B * p.N;
+        int any = n_el > HEAD_LIVE_SCAN;
+        if (!any) for (int i = threadIdx.x; i < n_el; i += 256) any |= p.dout[(i / p.N) * p.lddout + i % p.N] != 0.0f;      // NaN: unequal; -0.0f: equal
+        any = __syncthreads_or(any);
+        if (threadIdx.x == 0) __hip_atomic_store(live_out, any ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.N * p.C) return;
     const int n = idx / p.C, c = idx % p.C;
@@ -1231,7 +1264,8 @@ __global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp
         p.dbias[n] += d;
     }
 }
-extern "C" int mms_head_bwd_group(const HeadBwdP* pp, int ng, hipStream_t s) {
+extern "C" int mms_head_bwd_group(const HeadBwdP* pp, int ng, hipStream_t s) { return mms_head_bwd_group_live(pp, nullptr, ng, s); }
+extern "C" int mms_head_bwd_group_live(const HeadBwdP* pp, unsigned* const* live_out, int ng, hipStream_t s) {
     Grp<HeadBwdP> a;
     if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
     const HeadBwdP& p = *pp;
@@ -1241,7 +1275,7 @@ extern "C" int mms_head_bwd_group(const HeadBwdP* pp, int ng, hipStream_t s) {
         if (q.B != p.B || q.C != p.C || q.N != p.N || q.V != p.V) return MMS_ERR_ARG;
     }
     MMS_LAUNCH(head_bwd_feat_kernel, dim3((p.C + 63) / 64, 1, ng), dim3(256), 0, s, a);
-    MMS_LAUNCH(head_bwd_w_kernel, dim3((p.N * p.C + 255) / 256, 1, ng), dim3(256), 0, s, a);
+    MMS_LAUNCH(head_bwd_w_kernel, dim3((p.N * p.C + 255) / 256, 1, ng), dim3(256), 0, s, a, live_tab((const unsigned* const*)live_out, ng));
     return mms_check_launch();
 }
 MMS_SINGLE(mms_head_bwd, HeadBwdP)
@@ -1297,7 +1331,7 @@ extern "C" int mms_head_bwd_apply(const HeadBwdP* pp, hipStream_t s) {
     Grp<HeadBwdP> a;
     if (!grp_fill(a, pp, 1, 1)) return MMS_ERR_ARG;
     MMS_LAUNCH(head_bwd_apply_kernel, dim3((pp->C + 255) / 256), dim3(256), 0, s, *pp);
-    MMS_LAUNCH(head_bwd_w_kernel, dim3((pp->N * pp->C + 255) / 256, 1, 1), dim3(256), 0, s, a);
+    MMS_LAUNCH(head_bwd_w_kernel, dim3((pp->N * pp->C + 255) / 256, 1, 1), dim3(256), 0, s, a, LiveTab{});      // (SyncBN: no word)
     return mms_check_launch();
 }
 
@@ -1305,8 +1339,9 @@ extern "C" int mms_head_bwd_apply(const HeadBwdP* pp, hipStream_t s) {
 // maxpool(3,2,1) backward (gather form, no atomics on the gradient) + relu0 mask -> dbn0, BN0 sums
 // one workgroup = 256 conv0-grid voxels x 64 channels
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pool_bwd_kernel(const Grp<PoolBwdP> grp) {
+__global__ __launch_bounds__(256) void pool_bwd_kernel(const Grp<PoolBwdP> grp, const LiveTab lt) {
     const PoolBwdP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(lt.w[blockIdx.z]);
     // workgroup = 64 conv0-grid voxels x 64 channels.  Each input voxel is covered by 1 or 2 windows per axis
     // (od in {id>>1, (id+1)>>1}; they coincide for even id): all 8 candidates are loaded unconditionally from clamped
     // addresses and selected afterwards (the duplicate candidate of an even coordinate is masked out).
@@ -1314,6 +1349,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const Grp<PoolBwdP> grp) 
     const int c = threadIdx.x & 63, vr = threadIdx.x >> 6;
     float mu, rs, ga, be;
     bn_consts1(p.bn, c, mu, rs, ga, be);
+    if (live_dead(alive)) return;
     const int vox_in = p.in.D * p.in.H * p.in.W, Min = p.B * vox_in, vox_out = p.out.D * p.out.H * p.out.W;
     double s1 = 0, s2 = 0;
     for (int it = 0; it < 16; ++it) {
@@ -1365,8 +1401,9 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const Grp<PoolBwdP> grp) 
 // voxels; the <= 2 x 3 x (WT/2+1) pooled voxels whose windows can reach it are staged in LDS once (argmax byte + gradient,
 // coalesced 64-channel rows), so a voxel's 8 candidates cost 16 LDS reads instead of 16 global loads (8 of them 1-byte).
 template <int WT>
-__global__ __launch_bounds__(256) void pool_bwd_brick_kernel(const Grp<PoolBwdP> grp) {
+__global__ __launch_bounds__(256) void pool_bwd_brick_kernel(const Grp<PoolBwdP> grp, const LiveTab lt) {
     const PoolBwdP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(lt.w[blockIdx.z]);
     constexpr int WO = WT / 2 + 1, NC = 2 * 3 * WO;
     __shared__ float cg[NC][64];
     __shared__ uint8_t ca[NC][64];
@@ -1389,6 +1426,7 @@ __global__ __launch_bounds__(256) void pool_bwd_brick_kernel(const Grp<PoolBwdP>
     }
     float mu, rs, ga, be;
     bn_consts1(p.bn, c, mu, rs, ga, be);
+    if (live_dead(alive)) return;
     __syncthreads();
     double s1 = 0, s2 = 0;
     for (int v = vr; v < 8 * WT; v += 4) {
@@ -1420,7 +1458,9 @@ __global__ __launch_bounds__(256) void pool_bwd_brick_kernel(const Grp<PoolBwdP>
     }
 }
 
-extern "C" int mms_pool_bwd_group(const PoolBwdP* pp, int ng, hipStream_t s) {
+extern "C" int mms_pool_bwd_group(const PoolBwdP* pp, int ng, hipStream_t s) { return mms_pool_bwd_group_live(pp, nullptr, ng, s); }
+extern "C" int mms_pool_bwd_group_live(const PoolBwdP* pp, const unsigned* const* live, int ng, hipStream_t s) {
+    const LiveTab lt = live_tab(live, ng);
     Grp<PoolBwdP> a;
     if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
     const PoolBwdP& p = *pp;
@@ -1433,13 +1473,13 @@ extern "C" int mms_pool_bwd_group(const PoolBwdP* pp, int ng, hipStream_t s) {
     }
     if (p.in.D % 2 == 0 && p.in.H % 4 == 0 && p.in.W % 16 == 0) {
         if (p.in.W % 32 == 0) {
-            MMS_LAUNCH(pool_bwd_brick_kernel<32>, dim3(p.B * (p.in.D / 2) * (p.in.H / 4) * (p.in.W / 32), 1, ng), dim3(256), 0, s, a);
+            MMS_LAUNCH(pool_bwd_brick_kernel<32>, dim3(p.B * (p.in.D / 2) * (p.in.H / 4) * (p.in.W / 32), 1, ng), dim3(256), 0, s, a, lt);
         } else {
-            MMS_LAUNCH(pool_bwd_brick_kernel<16>, dim3(p.B * (p.in.D / 2) * (p.in.H / 4) * (p.in.W / 16), 1, ng), dim3(256), 0, s, a);
+            MMS_LAUNCH(pool_bwd_brick_kernel<16>, dim3(p.B * (p.in.D / 2) * (p.in.H / 4) * (p.in.W / 16), 1, ng), dim3(256), 0, s, a, lt);
         }
         return mms_check_launch();
     }
-    MMS_LAUNCH(pool_bwd_kernel, dim3((Min + 63) / 64, 1, ng), dim3(256), 0, s, a);
+    MMS_LAUNCH(pool_bwd_kernel, dim3((Min + 63) / 64, 1, ng), dim3(256), 0, s, a, lt);
     return mms_check_launch();
 }
 MMS_SINGLE(mms_pool_bwd, PoolBwdP)
@@ -1565,6 +1605,7 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
     const int b0 = gs - model * nbox, b1 = seg_end - model * nbox;
     gs = seg_end;
     const Conv0BwdWP& p = grp.p[model];
+    const unsigned alive = live_issue(p.live);
     __syncthreads();                          // the previous segment is done with cst / xs / dys
     if (tid < 64) {
         float mu, rs, ga_;
@@ -1579,6 +1620,7 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
             p.dbeta[tid] += (float)t1;
         }
     }
+    if (live_dead(alive)) continue;           // dead model: on to the workgroup's next segment (the whole workgroup takes this branch)
     __syncthreads();
     // staging roles: 6 region elements per thread; dy: voxel tid >> 3, channels (tid & 7) * 8 .. + 7
     const int sv = tid >> 3, sc0 = (tid & 7) * 8;
@@ -1685,11 +1727,13 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
 }
 __global__ __launch_bounds__(256) void conv0_dw_reduce_kernel(const Grp<Conv0BwdWP> grp) {
     const Conv0BwdWP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 64 * 343) return;
     float v[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = p.dw_rep[(size_t)(r < p.nrep ? r : 0) * (64 * 343) + i];
+    if (live_dead(alive)) return;             // (dead model: the replicas hold the forward's zeros)
     float a = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) if (r < p.nrep) { a += v[r]; p.dw_rep[(size_t)r * (64 * 343) + i] = 0.f; }      // (left zeroed for the next call)

@@ -34,6 +34,7 @@ constexpr int C1SB_P = 132;         // LDS pitch of the [rows][128] gradient pan
 
 __global__ __launch_bounds__(256) void conv1s_bwd_kernel(const Grp<Conv1BwdP> grp) {
     const Conv1BwdP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);         // dead-backward skip (common.h): requested first, tested behind the batch of loads
     const float* __restrict__ dyraw = p.dyraw;         // kernel arguments read once (see conv1s_fwd_kernel)
     const float* __restrict__ yf = p.y;
     const float* __restrict__ x = p.x;
@@ -87,6 +88,7 @@ __global__ __launch_bounds__(256) void conv1s_bwd_kernel(const Grp<Conv1BwdP> gr
         bn_consts1(p.bn_in, k0 + c, mu, rs, ga, be);
         ein[c] = mu; ein[16 + c] = rs; ein[32 + c] = ga; ein[48 + c] = be;
     }
+    if (live_dead(alive)) return;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 16; ++i) {

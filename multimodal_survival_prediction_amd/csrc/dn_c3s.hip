@@ -233,6 +233,7 @@ __global__ __launch_bounds__(256) void conv3s_bwd_data_kernel(const Grp<Conv3Bwd
     int tile_, half_, model_;
     c3s_place(tile_, half_, model_);
     const Conv3BwdDataP& p = grp.p[model_];
+    const unsigned alive = live_issue(p.live);         // dead-backward skip (common.h): requested first, tested behind the prologue's loads
     const float* __restrict__ dz = p.dz;               // kernel arguments read once (see conv3s_fwd_kernel)
     const float* __restrict__ wpb = p.wpb;
     const float* __restrict__ y1 = p.y1;
@@ -302,6 +303,7 @@ __global__ __launch_bounds__(256) void conv3s_bwd_data_kernel(const Grp<Conv3Bwd
         mu[j] = (float)m; rstd[j] = 1.0f / sqrtf((float)v + bn.eps);
     }
     const unsigned m9 = myrow < M ? c3s_mask9(mycoord, g, true) : 0u;
+    if (live_dead(alive)) return;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const int s = (tid >> 3) + 32 * i;

@@ -453,6 +453,7 @@ constexpr int CLDZP = 36, CLDYP = 132;
 
 __global__ __launch_bounds__(256) void cl_bwd_kernel(const Grp<ClBwdP> grp) {
     const ClBwdP& p = grp.p[blockIdx.z];
+    const unsigned alive = live_issue(p.live);        // dead-backward skip (common.h): one word per model, so all eight workgroups of the cluster leave together
     const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, k4 = lane >> 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     B4Layer* tabs = (B4Layer*)smem;            // [<= 24] the block's layer table
@@ -508,6 +509,7 @@ __global__ __launch_bounds__(256) void cl_bwd_kernel(const Grp<ClBwdP> grp) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) { const int e = tid + 256 * j, m = e >> 5; dzs[m * CLDZP + (e & 31)] = m < M ? p.dslab[(size_t)m * ld + Cl + (e & 31)] : 0.f; }
     }
+    if (live_dead(alive)) return;                     // before the first barrier and the first hand-off: no workgroup of a dead model publishes or waits
     __syncthreads();
     if (tid == 0) {
         int n = 0;

@@ -45,6 +45,7 @@ struct Plan {
     int cl_rt[NB], cl_rpc[NB], cl_ncl[NB];
     size_t cl_xa[NB], cl_xb[NB], cl_gst[NB], cl_tab[NB], cl_zero_begin, cl_ga, cl_gz;
     size_t b4_err;
+    size_t bwd_live;                // one word: the head launch of the backward found a non-zero element in dout (MmsDnOpts.skip_dead_bwd)
     size_t hx;                      // arrival words of the fused block-3 forward launches, one per dense layer (inside the per-step zeroed region)
     size_t bb_y0, bb_y1[NLAYER], bb_in[NLAYER], bb_tr[3], bb_head;   // backward (s1 | s2)
     size_t total;
@@ -142,6 +143,7 @@ bool make_plan(Plan& P, int B, int D, int H, int W) {
     for (int t = 0; t < 3; ++t) P.tpool[t] = take((size_t)P.M[t + 1] * CTOT[t] * 4);
     P.counters = take(4096 * 4);
     P.b4_err = take(1024);
+    P.bwd_live = take(4);           // outside the per-step zeroed region: written by every backward that reads it
     for (int b = 0; b < NB; ++b) P.cl_tab[b] = take(sizeof(B4Layer) * LAYERS[b]);
     P.total = o;
     return true;
@@ -185,7 +187,6 @@ inline BnSrc mk_bn(void* ws, size_t st_off, int Ctot_, const float* const* prm, 
 extern "C" int mms_init_coords(int*, int, int, int, int, hipStream_t);
 extern "C" int mms_pack_conv3_table_group_ex(const void* const*, int, int, uint64_t, hipStream_t);
 extern "C" int mms_unpack_conv3_grads(const void*, int, hipStream_t);
-extern "C" int mms_unpack_conv3_grads_group(const float* const*, float* const* const*, int, int, hipStream_t);
 extern "C" int mms_bn_running_update_group(const void* const*, int, int, float, hipStream_t);
 extern "C" int mms_zero_regions_group(void* const*, int, size_t, hipStream_t);
 extern "C" int mms_conv0_fwd_group(const Conv0FwdP*, int, const MmsDnOpts*, hipStream_t);
@@ -254,6 +255,7 @@ extern "C" int mms_dn121_region(int B, int D, int H, int W, const char* name, in
     if (!strcmp(name, "stats")) return set(P.stats_begin, P.stats_end - P.stats_begin);
     if (!strcmp(name, "b4_err")) return set(P.b4_err, 1024);
     if (!strcmp(name, "hx")) return set(P.hx, 256);
+    if (!strcmp(name, "bwd_live")) return set(P.bwd_live, 4);
     return MMS_ERR_ARG;
 }
 
@@ -579,13 +581,24 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
     const bool sync = dp.hook != nullptr || bnw > 1;
     const bool packed = o.w2_packed != 0;
     auto bbsrc = [&](void* ws, size_t off, int stride, int nrep) { return BnBwd{at<double>(ws, off), at<double>(ws, off) + stride, nrep, 2 * stride}; };
+    // Dead-backward skip (MmsDnOpts.skip_dead_bwd): the head launch below records per model whether dout has a non-zero element; every
+    // later launch of this call carries the word's address and returns at once for a model whose word is 0.  Never under SyncBN or a
+    // statistics hook -- the BatchNorm-backward sums are all-reduced over the ranks, so a zero dout on THIS rank does not make its
+    // backward zero -- and never in a backward stage, whose head launch (if any) belongs to another call: the word is not written and
+    // no launch is given its address.
+    const bool skip_dead = o.skip_dead_bwd >= 0 && !sync && !dp.staged && dp.b_hi == NB - 1;
+    auto lv = [&](const Ctx& c) -> unsigned* { return skip_dead ? at<unsigned>(c.ws, P.bwd_live) : nullptr; };
+    const unsigned* lvs[MMS_MAX_GROUP];     // the same words as an array, for the launches that take them beside their parameter blocks
+    FOR_G lvs[g] = lv(cx[g]);
     if (dp.b_hi == NB - 1) {
         HeadBwdP hb[MMS_MAX_GROUP];
+        unsigned* hlive[MMS_MAX_GROUP];
         FOR_G {
             const Ctx& c = cx[g];
             hb[g] = HeadBwdP{c.dout, lddout, at<float>(c.ws, P.pooled), at<float>(c.ws, P.slab[3]), CTOT[3], 1024, B, P.M[3] / B,
                              mk_bn(c.ws, P.st_slab[3], CTOT[3], c.prm, IDX.n5w, nullptr, 0, P.M[3] * bnw, 1, P.R[3]), c.prm[IDX.outw], nout,
                              c.grd[IDX.outw], c.grd[IDX.outb], c.grd[IDX.n5w], c.grd[IDX.n5b], at<float>(c.ws, P.dslab[3]), CTOT[3]};
+            hlive[g] = lv(c);
         }
         if (sync) {     // norm5's backward sums must span all ranks: sums kernel | all-reduce | apply kernel
             hb[0].ext_sums = at<double>(cx[0].ws, P.bb_head);
@@ -593,7 +606,7 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
             SYNC(at<double>(cx[0].ws, P.bb_head), 1, 2 * 1024, 1024, 1024);
             TRY(mms_head_bwd_apply(hb, s));
         } else {
-            TRY(mms_head_bwd_group(hb, ng, s));
+            TRY(mms_head_bwd_group_live(hb, hlive, ng, s));
         }
     }
     // Weight gradients are off the backward's critical chain (nothing reads them before the optimiser).  In blocks 2-4 a
@@ -621,8 +634,8 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
     int nwq = 0;
     auto flush_w = [&](int b) -> int {
         if (nwq > 0) {
-            TRYS(12 + b, mms_wgrad_tab_group(wmod, ng, wmem, nwq, &wsh, 1, s));
-            TRYS(16 + b, mms_wgrad_tab_group(wmod, ng, wmem, nwq, &wsh, 2, s));
+            TRYS(12 + b, mms_wgrad_tab_group_live(wmod, lvs, ng, wmem, nwq, &wsh, 1, s));
+            TRYS(16 + b, mms_wgrad_tab_group_live(wmod, lvs, ng, wmem, nwq, &wsh, 2, s));
             nwq = 0;
         }
         if (nq == 0) return MMS_OK;
@@ -666,6 +679,7 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                     const int ip = IDX.layer[NLAYER - LAYERS[3] + i];
                     q[g].dg1[i] = (float*)c.grd[ip]; q[g].db1[i] = (float*)c.grd[ip + 1];
                 }
+                q[g].live = lv(c);
             }
             TRYS(33, mms_cl_bwd_group(q, ng, s));
         }
@@ -692,9 +706,9 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                                       at<float>(c.ws, P.y1[l]), bn2, dmid,
                                       at<double>(c.ws, P.bb_y1[l]), at<double>(c.ws, P.bb_y1[l]) + 128,
                                       ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
-                bd[g].srep = P.R[b]; bd[g].sstride = 2 * 128; bd[g].wfrag = conv3_frag_block(P, b, ng, o) ? 1 : 0;
+                bd[g].srep = P.R[b]; bd[g].sstride = 2 * 128; bd[g].wfrag = conv3_frag_block(P, b, ng, o) ? 1 : 0; bd[g].live = lv(c);
                 bw[g] = Conv3BwdWP{at<float>(c.ws, P.y1[l]), at<int>(c.ws, P.coords[b]), P.g[b], M, bn2, dslab + C, CTOT[b],
-                                   packed ? c.grd[ip + 5] : at<float>(c.ws, P.dwp[l]), ms3, packed ? 2 : 1};
+                                   packed ? c.grd[ip + 5] : at<float>(c.ws, P.dwp[l]), ms3, packed ? 2 : 1, lv(c)};
                 Conv1BwdP& q = c1[g];
                 q = Conv1BwdP{};
                 q.dyraw = dmid; q.lddy = 128;
@@ -708,9 +722,10 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 q.s1 = at<double>(c.ws, P.bb_in[l]); q.s2 = at<double>(c.ws, P.bb_in[l]) + 1024;
                 q.srep = P.R[b]; q.sstride = 2 * 1024;
                 q.msplit = ms1; q.dgamma_out = c.grd[ip + 3]; q.dbeta_out = c.grd[ip + 4];
+                q.live = lv(c);
                 if (fuse_apply) { q.fuse_dx = dslab; q.fuse_lddx = CTOT[b]; q.fuse_accumulate = 1; q.fuse_dgamma = c.grd[ip]; q.fuse_dbeta = c.grd[ip + 1]; }
                 ap[g] = BnBwdApplyP{at<float>(c.ws, P.dbn_in), CTOT[b], slab, CTOT[b], dslab, CTOT[b], M, C, bn1,
-                                    bbsrc(c.ws, P.bb_in[l], 1024, P.R[b]), 1, c.grd[ip], c.grd[ip + 1]};
+                                    bbsrc(c.ws, P.bb_in[l], 1024, P.R[b]), 1, c.grd[ip], c.grd[ip + 1], lv(c)};
             }
             if (side && side_pending) {       // the previous layer's weight kernels read dbn_mid: join before overwriting it
                 if (hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return MMS_ERR_LAUNCH;
@@ -774,9 +789,9 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 q.dbn = at<float>(c.ws, P.dbn_in); q.lddbn = CTOT[t];
                 q.s1 = at<double>(c.ws, P.bb_tr[t]); q.s2 = at<double>(c.ws, P.bb_tr[t]) + 1024;
                 q.srep = P.R[t]; q.sstride = 2 * 1024;
-                q.msplit = ms1; q.dgamma_out = nullptr; q.dbeta_out = nullptr;
+                q.msplit = ms1; q.dgamma_out = nullptr; q.dbeta_out = nullptr; q.live = lv(c);
                 ap[g] = BnBwdApplyP{at<float>(c.ws, P.dbn_in), CTOT[t], at<float>(c.ws, P.slab[t]), CTOT[t], at<float>(c.ws, P.dslab[t]), CTOT[t],
-                                    Mp, Kp, bnt, bbsrc(c.ws, P.bb_tr[t], 1024, P.R[t]), 0, c.grd[ip], c.grd[ip + 1]};
+                                    Mp, Kp, bnt, bbsrc(c.ws, P.bb_tr[t], 1024, P.R[t]), 0, c.grd[ip], c.grd[ip + 1], lv(c)};
             }
             if (o.trans_prepass >= 0) {       // the weight gradient reads the pooled operand the forward left in the workspace
                 Conv1BwdP cw[MMS_MAX_GROUP];
@@ -798,9 +813,9 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 pb[g].srep = P.R0; pb[g].sstride = 2 * 64;
                 cw[g] = Conv0BwdWP{at<float>(c.ws, P.dbn0), at<float>(c.ws, P.y0), bn0, bbsrc(c.ws, P.bb_y0, 64, P.R0), c.x, P.in, P.g0,
                                    at<int>(c.ws, P.coords0), P.M0, c.grd[IDX.conv0], ms0, c.grd[IDX.n0w], c.grd[IDX.n0b],
-                                   at<float>(c.ws, P.dw0_rep), 8};
+                                   at<float>(c.ws, P.dw0_rep), 8, lv(c)};
             }
-            TRYS(29, mms_pool_bwd_group(pb, ng, s));
+            TRYS(29, mms_pool_bwd_group_live(pb, lvs, ng, s));
             SYNC(at<double>(cx[0].ws, P.bb_y0), P.R0, 2 * 64, 64, 64);
             TRYS(29, mms_conv0_bwd_weight_group(cw, ng, &o, s));
         }
@@ -823,7 +838,7 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
             for (int i = 0; i < nl; ++i) dwt[g][i] = cx[g].grd[IDX.layer[l0 + i] + 5];
             dwp_[g] = dwt[g];
         }
-        TRY(mms_unpack_conv3_grads_group(scr, dwp_, ng, nl, s));
+        TRY(mms_unpack_conv3_grads_group_live(scr, dwp_, lvs, ng, nl, s));
     }
     return MMS_OK;
 }

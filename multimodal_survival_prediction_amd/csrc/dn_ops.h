@@ -72,6 +72,14 @@ int mms_c3s_c1s_fwd(const Conv3FwdP* p3, const Conv1FwdP* p1, unsigned* const* f
 // head of the input-gradient path (attrib.hip): class_layers + norm5 backward with frozen statistics, data only
 int mms_head_input_grad(const HeadBwdP* pp, hipStream_t s);
 
+// ---- dead-backward skip (MmsDnOpts.skip_dead_bwd; common.h live_issue): the launches whose public parameter blocks carry no `live`
+// word take the models' words as an array beside them (NULL, or per model NULL = always run); the public entry points pass NULL.
+extern "C" int mms_head_bwd_group_live(const HeadBwdP* pp, unsigned* const* live_out, int ng, hipStream_t s);      // live_out[g]: WRITTEN (dn_bwd.hip head_bwd_w_kernel)
+extern "C" int mms_pool_bwd_group_live(const PoolBwdP* pp, const unsigned* const* live, int ng, hipStream_t s);
+extern "C" int mms_wgrad_tab_group_live(const MmsWgradModel* models, const unsigned* const* live, int nmodels, const MmsWgradMember* members, int nmembers,
+                                        const MmsWgradShape* shape, int which, hipStream_t s);
+extern "C" int mms_unpack_conv3_grads_group_live(const float* const* scratch, float* const* const* dw, const unsigned* const* live, int ng, int nlayers, hipStream_t s);
+
 // ---- dense blocks 3 / 4 as one launch per pass (dn_cl.hip, dn_b4.hip); internal to the network drivers ---------------------------
 struct B4Layer {               // device table entry, one per dense layer (built by mms_dn121_init)
     const float *g1, *b1, *w1;                 // norm1 gamma / beta [C], conv1 weight [128][C]
@@ -103,5 +111,6 @@ struct ClBwdP {                // the data path of a single-cluster block's back
     unsigned long long* ga; unsigned long long* gz;      // {tag, value} granule buffers, ZERO on entry: [2][8][256] (hand-off A, by layer parity), [512] (dz broadcast)
     unsigned* err;                             // sticky time-out flag
     float* dg1[16]; float* db1[16];            // norm1 gamma / beta gradients of the layers (accumulated into)
+    const unsigned* live;                      // optional, as Conv3BwdDataP.live (include/mmsurv.h): 0 = the whole cluster returns at once
 };
 extern "C" int mms_cl_bwd_group(const ClBwdP* pp, int ng, hipStream_t s);

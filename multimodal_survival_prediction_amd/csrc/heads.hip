@@ -400,16 +400,25 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const Grp<GateP> grp) {
         p.dfeats[(size_t)m * GATE_F + i] = (p.dfused[(size_t)m * GATE_F + i] * g[sg] + dG) * p.mask[m * 3 + sg];
     }
 }
-// Row-tiled backward for M > 32: a workgroup owns GATE_TR consecutive rows, keeps its share of dw1 / db1 / dw2 / db2 in registers over
+// Row-tiled backward for M > 32 and for M <= GATE_TR (one accumulating workgroup per model: order-fixed sums): a workgroup owns GATE_TR consecutive rows, keeps its share of dw1 / db1 / dw2 / db2 in registers over
 // those rows and flushes once -- 1 / GATE_TR of the atomics of the kernel above (which issues 64 x 291 + 64 x 4 + 3 per row).  Thread t owns
 // column t of dw1 (all 64 hidden units) and, for t < GATE_IN - 256, column 256 + t; threads t < 64 own db1[t] and dw2[.][t]; thread 0 db2.
 // Per row the arithmetic (dgate, entropy term, dgate_ext, dfeats) is that of gate_bwd_kernel.
+// SPLIT (launches of ONE tile, M <= GATE_TR: the fold groups' batch of 4): grid.y = 1 + rows.  Workgroup y = 0 accumulates the tile's parameter
+// gradients over the rows in order and flushes them -- the only adds to those addresses, so the sums are the same bits in every run -- and
+// leaves dfeats to the workgroups y = 1 + r, one per row, which redo that row's few hundred FLOPs up to dhp and write its dfeats: the rows'
+// dfeats loops (64 weight loads per thread and row) then run side by side instead of one after the other (72 us -> the per-row kernel's 21 us
+// at 4 rows).  Same arithmetic per element as the unsplit form.
 #define GATE_TR 8
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void gate_bwd_tiled_kernel(const Grp<GateP> grp) {
     const GateP& p = grp.p[blockIdx.z];
     __shared__ float G[GATE_IN + 1], h[64], g[3], dl[3], dhp[64], red[4][3];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m_lo = blockIdx.x * GATE_TR, m_hi = m_lo + GATE_TR < p.M ? m_lo + GATE_TR : p.M;
+    const int role = SPLIT ? (int)blockIdx.y : 0;
+    const bool do_acc = !SPLIT || role == 0, do_feats = !SPLIT || role > 0;
+    int m_lo = blockIdx.x * GATE_TR, m_hi = m_lo + GATE_TR < p.M ? m_lo + GATE_TR : p.M;
+    if (SPLIT && role > 0) { m_lo += role - 1; if (m_lo >= m_hi) return; m_hi = m_lo + 1; }
     const bool two = t < GATE_IN - 256;
     float a0[64], a1[64];
 #pragma unroll
@@ -448,16 +457,20 @@ __global__ __launch_bounds__(256) void gate_bwd_tiled_kernel(const Grp<GateP> gr
             ab1 += dhp[t];
         }
         __syncthreads();
-        const float g0 = G[t], g1 = two ? G[256 + t] : 0.f;
+        if (do_acc) {
+            const float g0 = G[t], g1 = two ? G[256 + t] : 0.f;
 #pragma unroll
-        for (int j = 0; j < 64; ++j) { const float d = dhp[j]; a0[j] = fmaf(d, g0, a0[j]); a1[j] = fmaf(d, g1, a1[j]); }
-        for (int i = t; i < GATE_F; i += 256) {
-            float dG = 0.f;
-            for (int j = 0; j < 64; ++j) dG = fmaf(dhp[j], p.w1[j * GATE_IN + i], dG);
-            const int sg = gate_seg(i);
-            p.dfeats[(size_t)m * GATE_F + i] = (p.dfused[(size_t)m * GATE_F + i] * g[sg] + dG) * p.mask[m * 3 + sg];
+            for (int j = 0; j < 64; ++j) { const float d = dhp[j]; a0[j] = fmaf(d, g0, a0[j]); a1[j] = fmaf(d, g1, a1[j]); }
         }
+        if (do_feats)
+            for (int i = t; i < GATE_F; i += 256) {
+                float dG = 0.f;
+                for (int j = 0; j < 64; ++j) dG = fmaf(dhp[j], p.w1[j * GATE_IN + i], dG);
+                const int sg = gate_seg(i);
+                p.dfeats[(size_t)m * GATE_F + i] = (p.dfused[(size_t)m * GATE_F + i] * g[sg] + dG) * p.mask[m * 3 + sg];
+            }
     }
+    if (!do_acc) return;
 #pragma unroll
     for (int j = 0; j < 64; ++j) {
         atomicAdd(&p.dw1[j * GATE_IN + t], a0[j]);
@@ -508,7 +521,11 @@ extern "C" int mms_gate_fwd_group(const GateP* pp, int ng, hipStream_t s) {
 extern "C" int mms_gate_bwd_group(const GateP* pp, int ng, hipStream_t s) {
     Grp<GateP> a;
     if (!gate_group(a, pp, ng)) return MMS_ERR_ARG;
-    if (pp->M > 32) MMS_LAUNCH(gate_bwd_tiled_kernel, dim3((pp->M + GATE_TR - 1) / GATE_TR, 1, ng), dim3(256), 0, s, a);
+    // Up to GATE_TR rows (the fold groups' batch of 4) ONE workgroup per model walks the rows in order and adds each gradient element to
+    // the caller's buffer exactly once, so the gate's gradients are the same bits in every run -- with a workgroup per row the rows' fp32
+    // atomics met in an order that changed from run to run (1-2 units in the last place).  9 .. 32 rows keep the row-parallel kernel.
+    if (pp->M <= GATE_TR) MMS_LAUNCH(gate_bwd_tiled_kernel<true>, dim3(1, 1 + pp->M, ng), dim3(256), 0, s, a);
+    else if (pp->M > 32) MMS_LAUNCH(gate_bwd_tiled_kernel<false>, dim3((pp->M + GATE_TR - 1) / GATE_TR, 1, ng), dim3(256), 0, s, a);
     else MMS_LAUNCH(gate_bwd_kernel, dim3(pp->M, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }

@@ -95,8 +95,12 @@ __device__ __forceinline__ void tile_gemm_body(const typename Op::Params& p, con
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
     const int m0 = bx * TM, n0 = blockIdx.y * TN;
 
+    // dead-backward skip (common.h live_issue): the word is requested before the op's setup loads and tested behind them; every
+    // workgroup of a dead model leaves here, before the first barrier (forward parameter blocks have no such word: compiled out)
+    const unsigned alive = live_issue(live_word_of(p));
     Op op;
     op.setup(p, m0, n0, z, extra, tid);
+    if (live_dead(alive)) return;
     __syncthreads();
     int kb, ke;
     op.krange(p, z, kb, ke);
