@@ -102,6 +102,16 @@ typedef struct MmsDnOpts {
                               statistics hook (the BatchNorm-backward sums couple the ranks), in mms_dn121_backward_stage and in
                               mms_dn121_input_grad (they do not run this call's head launch).  The one difference in results: with a
                               zero dout and a non-finite saved activation the full backward yields NaN gradients, the skipped one none */
+    int c0_zero_skip;      /* all-zero input boxes of features.conv0 (the zero-filled volume of a patient without a CT), boxed kernels only:
+                              0 = a 4x4x4-voxel output box of the forward whose 13x13x13 input region (halo included) compares equal to 0.0f
+                              everywhere gets +0.0f stored to its outputs and adds nothing to the statistics instead of running its MFMAs;
+                              a 2x4x4 box of the weight gradient whose 9x13x13 region is all zero skips its MFMAs, and a workgroup whose
+                              boxes of a model were all zero skips its atomic flush.  Decided inside the kernels from the data they stage
+                              (-0.0f is zero, NaN is not): no flag from the caller, nothing to go stale.  -1 = every box does its work
+                              (A/B runs, tests).  Either way the boxes of a model are walked sample-minor (box j / B of sample j % B), so
+                              the statistics and the weight gradient are summed in that grouping.  The one difference in results: with a
+                              non-finite conv0 weight the full forward gives NaN in a zero box, the skip gives 0; with a non-finite dy0 the
+                              full weight gradient gives NaN, the skip gives none */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.

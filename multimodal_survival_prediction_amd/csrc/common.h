@@ -72,6 +72,22 @@ template <class P> __device__ __forceinline__ const unsigned* live_word_of(const
     if constexpr (has_live_word<P>::value) return p.live; else return nullptr;
 }
 
+// __syncthreads() that also returns the workgroup-wide OR of `flag` (workgroups of 256 threads = 4 waves), for a vote that rides on a
+// barrier the caller needs anyway.  Each wave ballots, its first lane leaves one word in `vote` before the barrier and every thread reads
+// the four words behind it: ONE barrier, where __syncthreads_or compiles to three (clear, barrier, LDS atomic, barrier, read, barrier) --
+// with one wave per SIMD every barrier is a stall nothing covers.  vote: __shared__, 16-byte aligned, [2][4]; par: the caller's slot
+// counter, 0 at the start.  Slots alternate, so a wave that is still reading vote k never meets the write of vote k + 1, and the write of
+// vote k + 2 comes behind barrier k + 1, which no wave passes before every wave has read vote k.  The result is the same in every thread
+// and is returned through readfirstlane, so branches on it are scalar.
+__device__ __forceinline__ bool syncthreads_any(bool flag, int (*vote)[4], int& par) {
+    const int w = __ballot(flag) != 0ull;
+    if ((threadIdx.x & 63) == 0) vote[par][threadIdx.x >> 6] = w;
+    __syncthreads();
+    const int4 v = *(const int4*)vote[par];
+    par ^= 1;
+    return __builtin_amdgcn_readfirstlane(v.x | v.y | v.z | v.w) != 0;
+}
+
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(<N - 1>) in order.  (A `#pragma unroll` loop whose body holds rarely taken
 // branches is costed at full size per iteration and left rolled; arrays it indexes by the loop counter then live in scratch.)
 template <class F, int... T>

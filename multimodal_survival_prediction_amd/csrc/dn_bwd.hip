@@ -1570,16 +1570,25 @@ struct Conv0BwdWOp {
 // Work distribution: the boxes of all models of the group form one pool that is dealt evenly over gridDim.x workgroups
 // (a multiple of the CU count: the kernel is MFMA-bound, so an uneven deal costs its full imbalance); a workgroup whose
 // range crosses a model boundary flushes its accumulators there (grp.zdim = number of models).
-__global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0BwdWP> grp) {
+// Zero boxes (zskip; MmsDnOpts.c0_zero_skip): a box whose staged 9 x 13 x 13 region of x compares equal to 0.0f everywhere -- the volume of
+// a patient without a CT -- contributes x^T dy0 = exact zeros, so its MFMAs are skipped; a segment without a non-zero box skips its flush
+// as well.  As in conv0_fwd_box_kernel the decision comes from the data: every thread ORs the magnitude bits of the 6 region elements it
+// stages and the barrier that publishes the region carries the vote (common.h syncthreads_any).  (dbn0 / y0 of a zero box are still loaded
+// and staged: they are requested together with x, one box ahead; skipping them would need x two boxes ahead.)
+// Box order: position j of a model's range is box j / B of sample j % B (sample-minor), so zero and non-zero boxes spread evenly over the
+// workgroups that serve the model.
+__global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0BwdWP> grp, const int zskip) {
     __shared__ float xs[2][C0_REG + 7];
     __shared__ float dys[2][32 * C0_DYP];
     __shared__ float cst[5 * 64];
     __shared__ float Cs[4][32 * 65];
+    __shared__ __attribute__((aligned(16))) int zvote[2][4];
+    int zpar = 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kq = lane >> 5;
     float *cA = cst, *cB = cst + 64, *cC = cst + 128, *cM = cst + 192, *cR = cst + 256;
     const int D0 = grp.p[0].out.D, H0 = grp.p[0].out.H, W0 = grp.p[0].out.W, Di = grp.p[0].in.D, Hi = grp.p[0].in.H, Wi = grp.p[0].in.W;
     const int bh = H0 >> 2, bw = W0 >> 2, bps = (D0 >> 1) * bh * bw;          // boxes per sample
-    const int nbox = (grp.p[0].M / (D0 * H0 * W0)) * bps;                      // boxes per model
+    const int NB = grp.p[0].M / (D0 * H0 * W0), nbox = NB * bps;               // samples, boxes per model
     const int total = nbox * grp.zdim;
     const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
     const int g0 = blockIdx.x * per, g1 = g0 + per < total ? g0 + per : total;
@@ -1627,7 +1636,7 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
     float xr[6];
     float4 rg0, rg1, ry0, ry1;
     auto gload = [&](int bx) {
-        const int b = bx / bps, r = bx - b * bps, bz = r / (bh * bw), r2 = r - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
+        const int r = bx / NB, b = bx - r * NB, bz = r / (bh * bw), r2 = r - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
         const int od0 = 2 * bz, oh0 = 4 * by, ow0 = 4 * bxw, id0 = 2 * od0 - 3, ih0 = 2 * oh0 - 3, iw0 = 2 * ow0 - 3;
         const float* xb = p.x + (size_t)b * Di * Hi * Wi;
 #pragma unroll
@@ -1652,6 +1661,14 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
         *(float4*)(d + 4) = make_float4(dyv(rg1.x, ry1.x, sc0 + 4), dyv(rg1.y, ry1.y, sc0 + 5), dyv(rg1.z, ry1.z, sc0 + 6), dyv(rg1.w, ry1.w, sc0 + 7));
     };
 
+    // the barrier after a box is staged, and the vote on its region: true = every element of x is +-0.0f (NaN is not zero)
+    auto staged_zero = [&](bool fresh) {
+        unsigned m = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) m |= __float_as_uint(xr[i]) & 0x7fffffffu;           // (elements outside the region were loaded as 0)
+        return !syncthreads_any(fresh && m != 0, zvote, zpar) && zskip != 0;
+    };
+
     f32x16 acc[3][2];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
@@ -1660,10 +1677,11 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][c][r] = 0.f;
 
+    bool seg_nz = false;                      // a box of this segment ran its MFMAs: the accumulators may hold something
     if (b0 < b1) {
         gload(b0);
         sstore(0);
-        __syncthreads();
+        bool zero = staged_zero(true);
         int buf = 0;
         for (int bx = b0; bx < b1; ++bx) {
 #ifdef C0_NO_STAGE
@@ -1674,36 +1692,40 @@ __global__ __launch_bounds__(256) void conv0_bwd_weight_kernel(const Grp<Conv0Bw
             if (more) gload(bx + 1);
             const float* xb = xs[buf];
             const float* db = dys[buf];
+            seg_nz |= !zero;
 #ifndef C0_NO_MMA
-            // operands of voxel pair q + 1 are requested before the MFMAs of pair q, order pinned (one wave per SIMD: nothing else covers
-            // the LDS latency; left alone the compiler exposes it twice per pair)
-            float bv0[2], bv1[2], a0[2], a1[2], a2[2];
-            auto oread = [&](int q, int j) __attribute__((always_inline)) {
-                bv0[j] = db[(2 * q + kq) * C0_DYP + li]; bv1[j] = db[(2 * q + kq) * C0_DYP + 32 + li];
-                a0[j] = xb[koff[0] + moff[q]]; a1[j] = xb[koff[1] + moff[q]]; a2[j] = xb[koff[2] + moff[q]];
-            };
-            oread(0, 0);
-            static_for<16>([&](auto Q) __attribute__((always_inline)) {
-                constexpr int q = decltype(Q)::value, j = q & 1;
-                if constexpr (q + 1 < 16) oread(q + 1, j ^ 1);
-                asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], bv0[j], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], bv1[j], acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], bv0[j], acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], bv1[j], acc[1][1], 0, 0, 0);
-                if (t2ok) {
-                    acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], bv0[j], acc[2][0], 0, 0, 0);
-                    acc[2][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], bv1[j], acc[2][1], 0, 0, 0);
-                }
-                asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-            });
+            if (!zero) {
+                // operands of voxel pair q + 1 are requested before the MFMAs of pair q, order pinned (one wave per SIMD: nothing else covers
+                // the LDS latency; left alone the compiler exposes it twice per pair)
+                float bv0[2], bv1[2], a0[2], a1[2], a2[2];
+                auto oread = [&](int q, int j) __attribute__((always_inline)) {
+                    bv0[j] = db[(2 * q + kq) * C0_DYP + li]; bv1[j] = db[(2 * q + kq) * C0_DYP + 32 + li];
+                    a0[j] = xb[koff[0] + moff[q]]; a1[j] = xb[koff[1] + moff[q]]; a2[j] = xb[koff[2] + moff[q]];
+                };
+                oread(0, 0);
+                static_for<16>([&](auto Q) __attribute__((always_inline)) {
+                    constexpr int q = decltype(Q)::value, j = q & 1;
+                    if constexpr (q + 1 < 16) oread(q + 1, j ^ 1);
+                    asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
+                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], bv0[j], acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], bv1[j], acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], bv0[j], acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], bv1[j], acc[1][1], 0, 0, 0);
+                    if (t2ok) {
+                        acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], bv0[j], acc[2][0], 0, 0, 0);
+                        acc[2][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], bv1[j], acc[2][1], 0, 0, 0);
+                    }
+                    asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
+                });
+            }
 #endif
             if (more) sstore(buf ^ 1);
-            __syncthreads();
+            zero = staged_zero(more);
             buf ^= 1;
         }
     }
     // epilogue: per wave, tile by tile through LDS so that the atomics run along k (dW0[n][k] is contiguous in k)
+    if (!seg_nz) continue;                    // only zero boxes: the accumulators are exact zeros (the whole workgroup takes this branch)
     float* cs = Cs[wave];
     float* dwdst = p.dw_rep ? p.dw_rep + (size_t)(blockIdx.x % (unsigned)p.nrep) * (64 * 343) : p.dw;
 #pragma unroll
@@ -1760,7 +1782,8 @@ extern "C" int mms_conv0_bwd_weight_group(const Conv0BwdWP* pp, int ng, const Mm
     int nwg = (opts && opts->c0_nwg > 0) ? opts->c0_nwg : (boxes >= 256L * 8 ? 256 : (int)((boxes + 7) / 8));
     if (nwg < 1) nwg = 1;
     for (int g = 0; g < ng; ++g) if ((pp[g].dw_rep != nullptr) != (p.dw_rep != nullptr) || pp[g].nrep != p.nrep || (p.dw_rep && (p.nrep < 1 || p.nrep > 8))) return MMS_ERR_ARG;
-    MMS_LAUNCH(conv0_bwd_weight_kernel, dim3(nwg, 1, 1), dim3(256), 0, s, a);
+    const int zskip = (opts && opts->c0_zero_skip < 0) ? 0 : 1;
+    MMS_LAUNCH(conv0_bwd_weight_kernel, dim3(nwg, 1, 1), dim3(256), 0, s, a, zskip);
     if (p.dw_rep) {
         const int rc = mms_check_launch();
         if (rc != MMS_OK) return rc;

@@ -641,17 +641,26 @@ struct Conv0FwdOp {
 // model), so the steady state is: 9 global loads per thread and box, then 172 MFMAs per wave fed by LDS only.
 // 4 waves = 2 voxel tiles (d-slices {0,1} / {2,3} of the box) x 2 channel tiles.  Boxes of all models are pooled over
 // gridDim.x workgroups (grp.zdim = number of models) as in conv0_bwd_weight_kernel.
+// Zero boxes (zskip; MmsDnOpts.c0_zero_skip): a box whose whole staged region compares equal to 0.0f -- the volume of a patient without a
+// CT -- gets +0.0f stored to its 64 x 64 outputs, which is what the MFMA sequence would produce from finite weights, and adds nothing to
+// the statistics.  The decision is taken from the data each thread already stages: every thread ORs the magnitude bits of its 9 region
+// elements and the barrier that publishes the staged region carries the vote (common.h syncthreads_any), so the flag is workgroup-uniform
+// and costs no flag from the caller, no word in memory, no further barrier and no register that lives across the MFMA sequence.
+// Box order: position j of a model's range is box j / B of sample j % B (sample-minor), so the consecutive positions of a workgroup cycle
+// through the samples and the zero boxes of absent samples spread evenly over the workgroups that serve the model.
 // ------------------------------------------------------------------------------------------------------
 #define C0F_REG (13 * 13 * 13)      // 2197
 __host__ __device__ constexpr int c0f_koff(int tap) { return (tap / 49) * 169 + ((tap / 7) % 7) * 13 + tap % 7; }
-__global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP> grp) {
+__global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP> grp, const int zskip) {
     __shared__ float xs[2][C0F_REG + 3];
     __shared__ float Cs[4][32 * 33];
+    __shared__ __attribute__((aligned(16))) int zvote[2][4];
+    int zpar = 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kq = lane >> 5;
     const int vt = wave >> 1, ct = wave & 1;                       // voxel tile, channel tile
     const int D0 = grp.p[0].out.D, H0 = grp.p[0].out.H, W0 = grp.p[0].out.W, Di = grp.p[0].in.D, Hi = grp.p[0].in.H, Wi = grp.p[0].in.W;
     const int bh = H0 >> 2, bw = W0 >> 2, bps = (D0 >> 2) * bh * bw;
-    const int nbox = (grp.p[0].M / (D0 * H0 * W0)) * bps;
+    const int NB = grp.p[0].M / (D0 * H0 * W0), nbox = NB * bps;
     const int total = nbox * grp.zdim;
     const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
     const int g0 = blockIdx.x * per, g1 = g0 + per < total ? g0 + per : total;
@@ -686,7 +695,7 @@ __global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP>
         double ssum = 0, ssq = 0;
         float xr[9];
         auto gload = [&](int bx) {
-            const int b = bx / bps, r = bx - b * bps, bz = r / (bh * bw), r2 = r - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
+            const int r = bx / NB, b = bx - r * NB, bz = r / (bh * bw), r2 = r - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
             const int id0 = 8 * bz - 3, ih0 = 8 * by - 3, iw0 = 8 * bxw - 3;
             const float* xb = p.x + (size_t)b * Di * Hi * Wi;
 #pragma unroll
@@ -701,63 +710,81 @@ __global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP>
 #pragma unroll
             for (int i = 0; i < 9; ++i) { const int e = tid + 256 * i; if (e < C0F_REG) xs[buf][e] = xr[i]; }
         };
+        // the barrier after a region is staged, and the vote on it: true = every element of the region is +-0.0f (NaN is not zero)
+        auto staged_zero = [&](bool fresh) {
+            unsigned m = 0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) m |= __float_as_uint(xr[i]) & 0x7fffffffu;       // (elements outside the region were loaded as 0)
+            return !syncthreads_any(fresh && m != 0, zvote, zpar) && zskip != 0;
+        };
         __syncthreads();                                       // previous segment done with xs
         gload(b0);
         sstore(0);
-        __syncthreads();
+        bool zero = staged_zero(true);
         int buf = 0;
         for (int bx = b0; bx < b1; ++bx) {
             const bool more = bx + 1 < b1;
             if (more) gload(bx + 1);
-            // tap offsets are compile-time constants of the unrolled step: the two lane halves differ by koff(2s+1) - koff(2s)
-            // (1, 7 or 85), so the address is one of three per-lane bases plus an immediate -- no index arithmetic per MFMA.
-            // Two accumulators alternate so that consecutive MFMAs do not wait on each other's result.
-            const float* xb = xs[buf] + moff;
-            f32x16 acc, acc2;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
-            // The A operand of MFMA s is requested C0F_PF MFMAs ahead and the order is pinned: left alone the compiler puts each ds_read right
-            // before its two MFMAs and the wave -- the only one on its SIMD: 343 VGPRs -- idles for the LDS latency once per pair.
-            constexpr int C0F_PF = 8;
-            float ring[C0F_PF];
-            auto aread = [&](int s_) __attribute__((always_inline)) {
-                const int k0 = c0f_koff(2 * s_), k1 = c0f_koff(2 * s_ + 1 < 343 ? 2 * s_ + 1 : 342);
-                return xb[k0 + kq * (k1 - k0)];
-            };
-#pragma unroll
-            for (int s_ = 0; s_ < C0F_PF; ++s_) ring[s_] = aread(s_);
-            static_for<172>([&](auto S) __attribute__((always_inline)) {
-                constexpr int s_ = decltype(S)::value;
-                const float a = ring[s_ % C0F_PF];
-                if constexpr (s_ + C0F_PF < 172) ring[s_ % C0F_PF] = aread(s_ + C0F_PF);
-                asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-                if constexpr ((s_ & 1) == 0) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, breg[s_], acc, 0, 0, 0);
-                else acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, breg[s_], acc2, 0, 0, 0);
-                asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
-            });
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-            // statistics (channel 32*ct + li, this lane's 16 voxel rows) and the store through a per-wave LDS transpose
-            float fs = 0.f, fq = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { fs += acc[r]; fq = fmaf(acc[r], acc[r], fq); }
-            ssum += fs; ssq += fq;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) cs[((r & 3) + 8 * (r >> 2) + 4 * kq) * 33 + li] = acc[r];
-            __builtin_amdgcn_wave_barrier();
-            {
-                const int b = bx / bps, r = bx - b * bps, bz = r / (bh * bw), r2 = r - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
+            const int rb = bx / NB, b = bx - rb * NB, bz = rb / (bh * bw), r2 = rb - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
+            if (zero) {
+                // same addresses as the store below: voxel 2i + kq of this wave's tile, channel 32 ct + li
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int v = 2 * i + kq;                  // voxel of this wave's tile
+                    const int v = 2 * i + kq;
                     const int od = 4 * bz + 2 * vt + (v >> 4), oh = 4 * by + ((v >> 2) & 3), ow = 4 * bxw + (v & 3);
                     const size_t m = ((size_t)(b * D0 + od) * H0 + oh) * W0 + ow;
-                    p.y[m * 64 + 32 * ct + li] = cs[v * 33 + li];
+                    p.y[m * 64 + 32 * ct + li] = 0.f;
                 }
+            } else {
+                // tap offsets are compile-time constants of the unrolled step: the two lane halves differ by koff(2s+1) - koff(2s)
+                // (1, 7 or 85), so the address is one of three per-lane bases plus an immediate -- no index arithmetic per MFMA.
+                // Two accumulators alternate so that consecutive MFMAs do not wait on each other's result.
+                const float* xb = xs[buf] + moff;
+                f32x16 acc, acc2;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
+                // The A operand of MFMA s is requested C0F_PF MFMAs ahead and the order is pinned: left alone the compiler puts each ds_read right
+                // before its two MFMAs and the wave -- the only one on its SIMD: 343 VGPRs -- idles for the LDS latency once per pair.
+                constexpr int C0F_PF = 8;
+                float ring[C0F_PF];
+                auto aread = [&](int s_) __attribute__((always_inline)) {
+                    const int k0 = c0f_koff(2 * s_), k1 = c0f_koff(2 * s_ + 1 < 343 ? 2 * s_ + 1 : 342);
+                    return xb[k0 + kq * (k1 - k0)];
+                };
+#pragma unroll
+                for (int s_ = 0; s_ < C0F_PF; ++s_) ring[s_] = aread(s_);
+                static_for<172>([&](auto S) __attribute__((always_inline)) {
+                    constexpr int s_ = decltype(S)::value;
+                    const float a = ring[s_ % C0F_PF];
+                    if constexpr (s_ + C0F_PF < 172) ring[s_ % C0F_PF] = aread(s_ + C0F_PF);
+                    asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
+                    if constexpr ((s_ & 1) == 0) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, breg[s_], acc, 0, 0, 0);
+                    else acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, breg[s_], acc2, 0, 0, 0);
+                    asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
+                });
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
+                // statistics (channel 32*ct + li, this lane's 16 voxel rows) and the store through a per-wave LDS transpose
+                float fs = 0.f, fq = 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { fs += acc[r]; fq = fmaf(acc[r], acc[r], fq); }
+                ssum += fs; ssq += fq;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) cs[((r & 3) + 8 * (r >> 2) + 4 * kq) * 33 + li] = acc[r];
+                __builtin_amdgcn_wave_barrier();
+                {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int v = 2 * i + kq;                  // voxel of this wave's tile
+                        const int od = 4 * bz + 2 * vt + (v >> 4), oh = 4 * by + ((v >> 2) & 3), ow = 4 * bxw + (v & 3);
+                        const size_t m = ((size_t)(b * D0 + od) * H0 + oh) * W0 + ow;
+                        p.y[m * 64 + 32 * ct + li] = cs[v * 33 + li];
+                    }
             }
             __builtin_amdgcn_wave_barrier();
+            }
             if (more) sstore(buf ^ 1);
-            __syncthreads();
+            zero = staged_zero(more);
             buf ^= 1;
         }
         if (p.osum) {
@@ -793,7 +820,8 @@ extern "C" int mms_conv0_fwd_group(const Conv0FwdP* pp, int ng, const MmsDnOpts*
     constexpr int smem = 64 * 343 * (int)sizeof(float);            // 87.8 KB of dynamic LDS (the weight block) + 34.5 KB static
     static std::once_flag attr_once;
     std::call_once(attr_once, [&] { hipFuncSetAttribute((const void*)conv0_fwd_box_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem); });
-    MMS_LAUNCH(conv0_fwd_box_kernel, dim3(nwg, 1, 1), dim3(256), smem, s, a);
+    const int zskip = (opts && opts->c0_zero_skip < 0) ? 0 : 1;
+    MMS_LAUNCH(conv0_fwd_box_kernel, dim3(nwg, 1, 1), dim3(256), smem, s, a, zskip);
     return mms_check_launch();
 }
 MMS_SINGLE_O(mms_conv0_fwd, Conv0FwdP)
