@@ -242,8 +242,8 @@ def gate_params(feats, mask, w1, b1, w2, b2, hidden, gate, fused, dfused=None, e
 TIE_MODES = {"breslow": 0, "efron": 1}
 
 
-def cox_fwd_bwd(h, time, event, valid=None, scale=1.0, want_grad=True, ties="breslow"):
-    """h: [n] or [n,1] fp32 on device -> (out[2] = {loss, usable}, dh or None).  ties: CoxP.tie_mode (include/mmsurv.h)."""
+def _cox_p(h, time, event, valid, scale, want_grad, ties):
+    """-> (CoxP, out, dh, scratch tensors the launch writes)"""
     n = h.shape[0]
     lse = torch.empty(n, device=h.device)
     out = torch.empty(2, device=h.device)
@@ -251,8 +251,23 @@ def cox_fwd_bwd(h, time, event, valid=None, scale=1.0, want_grad=True, ties="bre
     frac = torch.empty(n, device=h.device) if TIE_MODES[ties] == 1 else None
     p = _S()["CoxP"](ptr(h), h.stride(0), ptr(time), ptr(event), ptr(valid), n, float(scale), ptr(lse), ptr(dh), 1, ptr(out),
                      TIE_MODES[ties], ptr(frac))
+    return p, out, dh, (lse, frac)
+
+
+def cox_fwd_bwd(h, time, event, valid=None, scale=1.0, want_grad=True, ties="breslow"):
+    """h: [n] or [n,1] fp32 on device -> (out[2] = {loss, usable}, dh or None).  ties: CoxP.tie_mode (include/mmsurv.h)."""
+    p, out, dh, _scratch = _cox_p(h, time, event, valid, scale, want_grad, ties)
     call("mms_cox_fwd_bwd", p)
     return out, dh
+
+
+def cox_fwd_bwd_group(members):
+    """The fold-group form: ONE mms_cox_fwd_bwd_group launch pair over `members`, dicts of cox_fwd_bwd's arguments (h, time, event
+    [, valid, scale, ties]) with the same n -> [(out, dh)] per member."""
+    built = [_cox_p(m["h"], m["time"], m["event"], m.get("valid"), m.get("scale", 1.0), True, m.get("ties", "breslow")) for m in members]
+    arr = (_S()["CoxP"] * len(built))(*[b[0] for b in built])
+    _lib.check(_lib.load_library().mms_cox_fwd_bwd_group(arr, len(built), stream()), "mms_cox_fwd_bwd_group")
+    return [(b[1], b[2]) for b in built]
 
 
 def cindex_counts(h, time, event):

@@ -1,4 +1,7 @@
-"""CPU restatement of the three train_epoch / validate pairs (the measured unit)."""
+"""CPU restatement of the reference's train_epoch / validate pairs (the measured unit).
+
+(on_cindex: test hook of the validate functions, called with the hazards / events / times that enter the C-index.)"""
+import numpy as np
 import torch
 
 from .losses import concordance_index_np, cox_loss, gate_entropy_loss, neg_partial_log_likelihood
@@ -126,7 +129,7 @@ def validate_rnaseq(model, loader, device="cpu"):
     return total / len(loader), concordance_index_np(hs, es, ts)
 
 
-def validate_partial(model, loader, device, tie_credit=0.5):
+def validate_partial(model, loader, device, tie_credit=0.5, on_cindex=None):
     """partial_modality_training.py:438-485: eval forward of every batch; only batches with >= 2 labelled patients and >= 1
     event contribute a loss term AND their labelled hazards to the C-index.  C-index rule: calculate_cindex = torchsurv /
     lifelines (0.5 credit for tied scores; tie_credit=0 = the simple_fusion fallback counting)."""
@@ -145,11 +148,13 @@ def validate_partial(model, loader, device, tie_credit=0.5):
                     total += cox_loss(h, e, t).item()
                     nb += 1
                     hs.extend(h.cpu().numpy()); ts.extend(t.cpu().numpy()); es.extend(e.cpu().numpy())
+    if hs and on_cindex is not None:
+        on_cindex(np.asarray(hs), np.asarray(es), np.asarray(ts))
     c = concordance_index_np(hs, es, ts, tie_credit=tie_credit) if hs else 0.5
     return (total / nb if nb > 0 else 0), c
 
 
-def validate_simple(model, loader, device, tie_credit=0.0):
+def validate_simple(model, loader, device, tie_credit=0.0, on_cindex=None):
     """simple_fusion.py:281-333: batches with < 2 labelled patients are skipped BEFORE the forward, batches without events after it."""
     model.eval()
     total, nb = 0.0, 0
@@ -168,7 +173,67 @@ def validate_simple(model, loader, device, tie_credit=0.0):
             total += neg_partial_log_likelihood(lh_s, e_s, t_s).item()
             nb += 1
             hs.append(lh_s.cpu()); ts.append(t_s.cpu()); es.append(e_s.cpu())
+    return _simple_result(total, nb, hs, es, ts, tie_credit, on_cindex)
+
+
+def _simple_result(total, nb, hs, es, ts, tie_credit, on_cindex):
+    """simple_fusion.py:320-333 = flexible_multimodal.py:341-351: (0.0, 0.5) when no batch contributed."""
     if not hs:
         return 0.0, 0.5
-    c = concordance_index_np(torch.cat(hs).numpy(), torch.cat(es).numpy(), torch.cat(ts).numpy(), tie_credit=tie_credit)
-    return (total / nb if nb > 0 else 0.0), c
+    h, e, t = torch.cat(hs).numpy(), torch.cat(es).numpy(), torch.cat(ts).numpy()
+    if on_cindex is not None:
+        on_cindex(h, e, t)
+    return (total / nb if nb > 0 else 0.0), concordance_index_np(h, e, t, tie_credit=tie_credit)
+
+
+def train_epoch_flexible(model, loader, optimizer, device, on_batch=None):
+    """flexible_multimodal.py:262-299: simple_fusion's loop with the (B, 2) modality mask as the model's third input.  Batches with < 2
+    labelled patients `continue` BEFORE the forward (:277-278); batches without an event among the labelled `continue` AFTER the
+    training-mode forward (:287-288: BatchNorm running statistics have moved, no step).  The loss is the in-file fallback with 1e-8
+    inside the logarithm (:43-52).  (on_batch: test hook, each stepped batch's loss.)"""
+    model.train()
+    total, nb = 0.0, 0
+    for batch in loader:
+        image, rnaseq, mask = batch['image'].to(device), batch['rnaseq'].to(device), batch['mask'].to(device)
+        time, event = batch['time'].squeeze().to(device), batch['event'].squeeze().to(device)
+        smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
+        if smask.sum() < 2:
+            continue
+        optimizer.zero_grad()
+        lh = model(image, rnaseq, mask)
+        lh_s, t_s, e_s = lh[smask], time[smask], event[smask].bool()
+        if e_s.sum() == 0:
+            continue
+        loss = neg_partial_log_likelihood(lh_s, e_s, t_s, eps=1e-8)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+        optimizer.step()
+        total += loss.item()
+        nb += 1
+        if on_batch is not None:
+            on_batch(loss.item())
+    return total / nb if nb > 0 else 0.0
+
+
+def validate_flexible(model, loader, device, tie_credit=0.0, on_cindex=None):
+    """flexible_multimodal.py:301-351: the two skips of the training loop (:321-322 before the forward, :329-330 after it); only the
+    labelled rows of the remaining batches contribute a loss term and enter the C-index (in-file fallback :54-67: tied scores earn
+    nothing)."""
+    model.eval()
+    total, nb = 0.0, 0
+    hs, ts, es = [], [], []
+    with torch.no_grad():
+        for batch in loader:
+            image, rnaseq, mask = batch['image'].to(device), batch['rnaseq'].to(device), batch['mask'].to(device)
+            time, event = batch['time'].squeeze().to(device), batch['event'].squeeze().to(device)
+            smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
+            if smask.sum() < 2:
+                continue
+            lh = model(image, rnaseq, mask)
+            lh_s, t_s, e_s = lh[smask], time[smask], event[smask].bool()
+            if e_s.sum() == 0:
+                continue
+            total += neg_partial_log_likelihood(lh_s, e_s, t_s, eps=1e-8).item()
+            nb += 1
+            hs.append(lh_s.cpu()); ts.append(t_s.cpu()); es.append(e_s.cpu())
+    return _simple_result(total, nb, hs, es, ts, tie_credit, on_cindex)

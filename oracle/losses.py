@@ -103,12 +103,14 @@ def cox_loss(hazard, event, time):
     return -torch.sum((hazard - log_cumsum) * event) / (event.sum() + 1e-8)
 
 
-def neg_partial_log_likelihood(log_hazard, event, time):
-    """simple_fusion.py:47-57 (log(cumsum(exp)) form, event may be bool)."""
+def neg_partial_log_likelihood(log_hazard, event, time, eps=0.0):
+    """simple_fusion.py:47-57 (log(cumsum(exp)) form, event may be bool).  eps=1e-8: the copy at flexible_multimodal.py:43-52, which
+    adds 1e-8 to the cumulative sum before the logarithm (:48)."""
     idx = torch.argsort(time, descending=True)
     log_hazard = log_hazard[idx]
     event = event[idx]
-    log_risk = torch.log(torch.cumsum(torch.exp(log_hazard), dim=0))
+    risk = torch.cumsum(torch.exp(log_hazard), dim=0)
+    log_risk = torch.log(risk + eps if eps else risk)
     return -torch.sum((log_hazard - log_risk) * event) / (torch.sum(event) + 1e-8)
 
 

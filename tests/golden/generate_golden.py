@@ -22,7 +22,12 @@ How each reference file is harvested:
     with USE_MONAI = USE_TORCHSURV = False, exactly the branch an install without
     MONAI/torchsurv would take.
 
-Usage:  python tests/golden/generate_golden.py   (from the repo root)
+  * the epoch loops of partial_modality_training.py (:382-485), simple_fusion.py (:242-333) and flexible_multimodal.py
+    (:262-351, with its fallback loss / metric :42-67) sit after the data access or the SimpleITK import: exec'd by line range
+    into the namespaces above, with GATE_ENTROPY_WEIGHT = 0.01 (partial :369) and tqdm = an identity function of this harness.
+
+Usage:  python tests/golden/generate_golden.py          (from the repo root) writes g9_loops.npz and g10_cindex_ties.npz
+        python tests/golden/generate_golden.py --all    also rewrites g1 ... g6 (same arrays; the zip members carry new time stamps)
 """
 import contextlib
 import io
@@ -71,10 +76,24 @@ def harvest():
     _exec_lines(f"{REF}/final_multimodal.py", [(238, 305)], fm)
     rn = _exec_until_data(f"{REF}/train_rnaseq_only.py")
     # train_rnaseq_only.py defines its model and train_epoch/validate before the data access: rn holds RNASeqSurvivalModel too
-    base = {"torch": torch, "nn": nn, "np": np, "USE_MONAI": False, "USE_TORCHSURV": False}
+    base = {"torch": torch, "nn": nn, "np": np, "USE_MONAI": False, "USE_TORCHSURV": False, "tqdm": _tqdm}
     pm = _exec_lines(f"{REF}/partial_modality_training.py", [(165, 331)], dict(base))
     sf = _exec_lines(f"{REF}/simple_fusion.py", [(46, 73), (160, 236)], dict(base))
+    # the epoch loops: partial :382-485 (reads GATE_ENTROPY_WEIGHT, :369), simple :242-333
+    pm["GATE_ENTROPY_WEIGHT"] = 0.01
+    _exec_lines(f"{REF}/partial_modality_training.py", [(382, 485)], pm)
+    _exec_lines(f"{REF}/simple_fusion.py", [(242, 333)], sf)
     return fm, rn, pm, sf
+
+
+def _tqdm(it, **kw):
+    return it
+
+
+def harvest_flexible():
+    """flexible_multimodal.py: fallback loss / metric (:42-67), FlexibleMultimodalModel (:157-256), train_epoch / validate (:262-351)."""
+    base = {"torch": torch, "nn": nn, "np": np, "USE_MONAI": False, "USE_TORCHSURV": False, "tqdm": _tqdm}
+    return _exec_lines(f"{REF}/flexible_multimodal.py", [(42, 67), (157, 256), (262, 351)], base)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -276,7 +295,7 @@ def gen_extra_models(rn):
     before any class exists).  Dropout forced to 0; weights from torch.manual_seed construction; small variants store the
     full state_dict and gradients, default-width variants only outputs and gradient norms."""
     out = {}
-    fx = _exec_lines(f"{REF}/flexible_multimodal.py", [(157, 256)], {"torch": torch, "nn": nn, "np": np, "USE_MONAI": False})
+    fx = harvest_flexible()
     for tag, seed, B, rna_dim, vol in (("small", 21, 6, 40, (16, 16, 8)), ("full", 22, 16, 5005, (32, 32, 16))):
         rng = np.random.default_rng(300 + seed)
         ct = rng.random((B, 1) + vol, dtype=np.float32)
@@ -380,17 +399,210 @@ def gen_epoch(fm):
     print("g5_epoch:", losses, val_loss)
 
 
+# ----------------------------------------------------------------------------------------------
+# g9: the partial / simple / flexible epoch loops on ONE special-batch cohort
+# ----------------------------------------------------------------------------------------------
+
+LOOP_VOL, LOOP_RNA, LOOP_B, LOOP_NTRAIN = (16, 16, 8), 96, 4, 22
+LOOP_SGD = (1e-2, 0.9)          # lr, momentum of the optimizer handed to the loops
+
+
+def special_cohort(seed=2024, vol=LOOP_VOL, rna_dim=LOOP_RNA):
+    """36 patients (numpy only; tests/test_oracle_golden.py and tests/test_gpu_flexible_epoch.py restate this function and are
+    pinned to it by the arrays stored in g9_loops.npz).  Training split = patients 0..21 in batches of 4:
+      batch 0  all labelled, events present            batch 3  2 labelled (1 event) + 2 unlabelled
+      batch 1  all labelled, NO event                  batch 4  all labelled
+      batch 2  ONE labelled patient + 3 unlabelled     batch 5  ragged tail of 2
+    validation split = patients 22..35: batch A ordinary, batch B without events, batch C three labelled + one unlabelled patient,
+    batch D (tail of 2) one unlabelled + one labelled patient.
+    Rows of absent modalities (mask column 0) are zero, unlabelled patients carry time = event = 0."""
+    rng = np.random.default_rng(seed)
+    n, v = 36, LOOP_NTRAIN
+    ct = rng.random((n, 1) + tuple(vol), dtype=np.float32)
+    rna = rng.normal(0, 1, (n, rna_dim)).astype(np.float32)
+    age = (np.clip(rng.normal(60, 11, n), 30, 90) / 100.0).astype(np.float32)
+    time = (rng.exponential(1000.0, n) + 1.0 + np.arange(n) * 1e-2).astype(np.float32)
+    event = (rng.random(n) < 0.6).astype(np.float32)
+    has = np.ones(n, bool)
+    event[0], event[3] = 1, 0
+    event[4:8] = 0
+    has[9:12] = False; event[8] = 1
+    has[14:16] = False; event[12], event[13] = 1, 0
+    event[16] = 1
+    event[20], event[21] = 1, 0
+    event[v] = 1
+    event[v + 4:v + 8] = 0
+    event[v + 8] = 1; has[v + 9] = False
+    has[v + 12] = False; event[v + 13] = 1
+    mask = np.ones((n, 3), np.float32)          # [has_image, has_rnaseq, has_clinical]
+    mask[1, 0] = 0; mask[5, 1] = 0; mask[10, 0] = 0; mask[13, 2] = 0; mask[17, 0] = 0; mask[18, 1] = 0; mask[19, :2] = 0
+    mask[v + 1, 0] = 0; mask[v + 2, 1] = 0
+    ct[mask[:, 0] == 0] = 0.0
+    rna[mask[:, 1] == 0] = 0.0
+    clin = (age * mask[:, 2]).astype(np.float32).reshape(n, 1)
+    time = np.where(has, time, 0.0).astype(np.float32)
+    event = np.where(has, event, 0.0).astype(np.float32)
+    assert len(np.unique(time[has])) == int(has.sum())
+    return dict(image=ct, rnaseq=rna, clinical=clin, time=time, event=event, has_survival=has, mask=mask, n=n)
+
+
+def loop_batches(c, idx, style, B=LOOP_B):
+    """Plain dicts in the key layout each reference loop reads (partial: label / mask (B, 3) / clinical; simple and flexible: time (B, 1)
+    float, event (B, 1) long; flexible: mask (B, 2)); has_survival is a list of bools."""
+    out = []
+    for i in range(0, len(idx), B):
+        j = np.asarray(idx[i:i + B])
+        b = dict(image=torch.tensor(c["image"][j]), rnaseq=torch.tensor(c["rnaseq"][j]), has_survival=[bool(x) for x in c["has_survival"][j]])
+        if style == "partial":
+            b["clinical"] = torch.tensor(c["clinical"][j])
+            b["label"] = torch.tensor(np.stack([c["time"][j], c["event"][j]], 1))
+            b["mask"] = torch.tensor(c["mask"][j])
+        else:
+            b["time"] = torch.tensor(c["time"][j]).view(-1, 1)
+            b["event"] = torch.tensor(c["event"][j]).long().view(-1, 1)
+            if style == "flexible":
+                b["mask"] = torch.tensor(c["mask"][j][:, :2])
+        out.append(b)
+    return out
+
+
+class _Recorder:
+    """Harness code: records what a loop hands to its C-index (hazards, events, times), then calls the original."""
+
+    def __init__(self):
+        self.calls = []
+
+    def function(self, fn):
+        def wrapped(hazard, event, time):
+            self.calls.append(tuple(np.asarray(torch.as_tensor(a).numpy()).copy() for a in (hazard, event, time)))
+            return fn(hazard, event, time)
+        return wrapped
+
+    def metric_class(self, cls):
+        rec = self
+
+        class Recording:
+            def __call__(self, log_hazard, event, time):
+                return rec.function(cls())(log_hazard, event, time)
+        return Recording
+
+
+def gen_loops(pm, sf, fx):
+    try:
+        import lifelines  # noqa: F401
+        have_lifelines = True
+    except ImportError:
+        have_lifelines = False
+    c = special_cohort()
+    out = dict(cohort_seed=np.int64(2024), time=c["time"], event=c["event"], has_survival=c["has_survival"], mask=c["mask"],
+               image_sum=np.float64(c["image"].astype(np.float64).sum()), rnaseq_sum=np.float64(c["rnaseq"].astype(np.float64).sum()),
+               lifelines=np.bool_(have_lifelines))
+    tr, va = np.arange(LOOP_NTRAIN), np.arange(LOOP_NTRAIN, c["n"])
+    cpu = torch.device("cpu")
+    # The optimizer is the caller's argument, not part of the loop text: plain SGD.  Under the scripts' Adam the parameters whose true
+    # gradient is exactly zero (every bias that feeds a training-mode BatchNorm) move by +-lr per step along the SIGN of rounding
+    # noise, which depends on the host's thread count -- measured between 1 and 8 threads: running means apart by 4.5e-3 of their
+    # maximum after two epochs.  SGD moves them by the noise itself, and a step taken or left out is as visible as under Adam.
+    mkopt = lambda p: torch.optim.SGD(p, lr=LOOP_SGD[0], momentum=LOOP_SGD[1])
+    # (tag, namespace, model, model seed, C-index entry point that is recorded)
+    specs = (("partial", pm, "PartialModalityNet", 31, "calculate_cindex"),
+             ("simple", sf, "SimpleFusionModel", 32, "ConcordanceIndex"),
+             ("flexible", fx, "FlexibleMultimodalModel", 33, "ConcordanceIndex"))
+    out["sgd_lr_momentum"] = np.array(LOOP_SGD, np.float64)
+    for tag, ns, cls, seed, metric in specs:
+        trb, vab = loop_batches(c, tr, tag), loop_batches(c, va, tag)
+        torch.manual_seed(seed)                       # construction, then dropout ACTIVE: the loops draw from the same generator
+        m = ns[cls](rna_dim=LOOP_RNA)
+        opt = mkopt(m.parameters())
+        rets = [ns["train_epoch"](m, trb, opt, cpu) for _ in range(2)]
+        rec, orig = _Recorder(), ns[metric]
+        ns[metric] = rec.function(orig) if metric == "calculate_cindex" else rec.metric_class(orig)
+        try:
+            val = ns["validate"](m, vab, cpu)
+        finally:
+            ns[metric] = orig
+        assert len(rec.calls) == 1, (tag, len(rec.calls))
+        m.eval()
+        with torch.no_grad():
+            b0 = trb[0]
+            hz = (m(b0["image"], b0["rnaseq"], b0["clinical"], b0["mask"])[0] if tag == "partial" else
+                  m(b0["image"], b0["rnaseq"]) if tag == "simple" else m(b0["image"], b0["rnaseq"], b0["mask"]))
+        out[f"{tag}_model_seed"] = np.int64(seed)
+        out[f"{tag}_train"] = np.array(rets, np.float64)                 # partial: (avg_cox, avg_entropy) per epoch
+        out[f"{tag}_val"] = np.array(val, np.float64)                    # (avg_loss, c_index)
+        out[f"{tag}_hazard_b0"] = hz.numpy()
+        out[f"{tag}_cindex_h"], out[f"{tag}_cindex_e"], out[f"{tag}_cindex_t"] = (a.astype(np.float32) for a in rec.calls[0])
+        for k, b in m.named_buffers():
+            out[f"{tag}_buf/{k}"] = b.numpy().copy()
+        assert np.all(np.array(rets, np.float64).reshape(2, -1)[:, 0] > 0), (tag, rets)
+        if tag == "partial" and not have_lifelines:
+            assert val[1] == 0.5                      # the bare `except` of calculate_cindex (:318-319)
+        print("g9", tag, rets, val, len(rec.calls[0][0]), "samples in the C-index")
+    np.savez_compressed(f"{OUT}/g9_loops.npz", **out)
+    print("g9_loops done:", len(out), "arrays")
+
+
+# ----------------------------------------------------------------------------------------------
+# g10: C-index on tied risk scores and tied times
+# ----------------------------------------------------------------------------------------------
+
+def tied_case(rng, n, pattern):
+    """hazards from 3 to 7 distinct float32 values, times from ceil(n / 3) distinct values (every value used), events by `pattern`
+    ("mixed" | "all" | "none" | "maxtime").  A mixed case with n >= 4 is given one permissible pair of equal scores by construction."""
+    kh, kt = int(rng.integers(3, 8)), -(-n // 3)
+    hv = np.unique(rng.normal(0, 1, 16).astype(np.float32))[:kh]
+    tv = (np.sort(rng.exponential(1000.0, kt)) + 1.0 + np.arange(kt)).astype(np.float32)
+    h = hv[rng.integers(len(hv), size=n)]
+    t = tv[rng.permutation(np.concatenate([np.arange(kt), rng.integers(kt, size=n - kt)]))]
+    if pattern == "all":
+        e = np.ones(n, np.float32)
+    elif pattern == "none":
+        e = np.zeros(n, np.float32)
+    elif pattern == "maxtime":
+        e = np.zeros(n, np.float32)
+        e[np.argmax(t)] = 1
+    else:
+        e = (rng.random(n) < 0.57).astype(np.float32)
+        if n >= 4:
+            i, j = int(np.argmin(t)), int(np.argmax(t))
+            e[i] = 1
+            h[j] = h[i]
+    return h.astype(np.float32), e, t
+
+
+def gen_cindex_ties(rn, sf, fx):
+    out = {}
+    rng = np.random.default_rng(9876)
+    for n in (4, 23, 116):
+        h, e, t = tied_case(rng, n, "mixed")
+        args = (torch.tensor(h), torch.tensor(e), torch.tensor(t))
+        cs = [ns["ConcordanceIndex"]()(*args).item() for ns in (rn, sf, fx)]     # train_rnaseq_only.py:55, simple_fusion.py:59, flexible_multimodal.py:54
+        assert cs[0] == cs[1] == cs[2], (n, cs)
+        perm = (t[None, :] > t[:, None]) & (e[:, None] == 1)
+        assert (perm & (h[:, None] == h[None, :])).sum() > 0 and len(np.unique(t)) < n
+        out[f"n{n}_h"], out[f"n{n}_e"], out[f"n{n}_t"] = h, e, t
+        out[f"n{n}_cindex"] = np.float64(cs[0])
+    np.savez_compressed(f"{OUT}/g10_cindex_ties.npz", **out)
+    print("g10_cindex_ties done")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     fm, rn, pm, sf = harvest()
+    fx = harvest_flexible()
     for name, ns, keys in (("final_multimodal", fm, ["MultiModalSurvivalNet", "cox_loss", "calculate_cindex", "train_epoch", "validate"]),
                            ("train_rnaseq_only", rn, ["neg_partial_log_likelihood", "ConcordanceIndex", "RNASeqSurvivalModel", "train_epoch", "validate"]),
                            ("partial_modality_training", pm, ["PartialModalityNet", "cox_loss", "gate_entropy_loss"]),
                            ("simple_fusion", sf, ["SimpleFusionModel", "neg_partial_log_likelihood", "ConcordanceIndex"])):
         missing = [k for k in keys if k not in ns]
         assert not missing, (name, missing)
-    gen_cox(fm, rn, sf)
-    gen_cindex(rn, sf)
-    gen_models(fm, pm, sf)
-    gen_extra_models(rn)
-    gen_epoch(fm)
+    for name, ns in (("partial_modality_training", pm), ("simple_fusion", sf), ("flexible_multimodal", fx)):
+        assert "train_epoch" in ns and "validate" in ns, name
+    if "--all" in sys.argv[1:]:
+        gen_cox(fm, rn, sf)
+        gen_cindex(rn, sf)
+        gen_models(fm, pm, sf)
+        gen_extra_models(rn)
+        gen_epoch(fm)
+    gen_loops(pm, sf, fx)
+    gen_cindex_ties(rn, sf, fx)

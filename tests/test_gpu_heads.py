@@ -223,3 +223,147 @@ def test_clip_adam_matches_torch(ops, adamw):
     ops.call("mms_grad_sumsq", ap); ops.call("mms_clip_adam", ap)
     torch.cuda.synchronize()
     assert torch.equal(before, pd) and step.item() == 4.0
+
+
+# ---- ties and edges of the C-index and Cox kernels --------------------------------------------------------------------------------
+def _tied_case(rng, n, pattern, time_div=3):
+    """hazards from 3 to 7 distinct float32 values, times from ceil(n / time_div) distinct values (every value used), events by
+    `pattern`.  A mixed case with n >= 4 gets one permissible pair of equal scores by construction (generate_golden.tied_case)."""
+    kh, kt = int(rng.integers(3, 8)), -(-n // time_div)
+    hv = np.unique(rng.normal(0, 1, 16).astype(np.float32))[:kh]
+    tv = (np.sort(rng.exponential(1000.0, kt)) + 1.0 + np.arange(kt)).astype(np.float32)
+    h = hv[rng.integers(len(hv), size=n)]
+    t = tv[rng.permutation(np.concatenate([np.arange(kt), rng.integers(kt, size=n - kt)]))]
+    if pattern == "all":
+        e = np.ones(n, np.float32)
+    elif pattern == "none":
+        e = np.zeros(n, np.float32)
+    elif pattern == "maxtime":          # a single event, at the largest time: no permissible pair
+        e = np.zeros(n, np.float32)
+        e[np.argmax(t)] = 1
+    else:
+        e = (rng.random(n) < 0.57).astype(np.float32)
+        if n >= 4:
+            i, j = int(np.argmin(t)), int(np.argmax(t))
+            e[i] = 1
+            h[j] = h[i]
+    return h.astype(np.float32), e, t
+
+
+def _cindex_brute(h, e, t):
+    """(concordant, tied, permissible) as int64 from O(n^2) boolean outer comparisons: pair (i, j) is permissible iff i had its event
+    and t_j > t_i STRICTLY; concordant iff h_i > h_j, tied iff h_i == h_j."""
+    perm = (t[None, :] > t[:, None]) & (e[:, None] == 1)
+    conc = perm & (h[:, None] > h[None, :])
+    tied = perm & (h[:, None] == h[None, :])
+    return np.int64(conc.sum()), np.int64(tied.sum()), np.int64(perm.sum())
+
+
+def test_cindex_ties_and_edges(ops, monkeypatch):
+    """cindex_kernel on tied scores, tied times and degenerate event patterns: the three pair counts EQUAL an integer brute force; sizes
+    around the 4-rows-per-workgroup edge, the 64-lane stride and a partial last stride.  On top of the counts: calculate_cindex gives
+    tied scores the credit it is asked for, ConcordanceIndex() without torchsurv gives them none (it returns an fp32 tensor, as the
+    reference's class does: compared with the fp32 rounding of the exact value), both 0.5 without a permissible pair.  The n = 4 / 23 /
+    116 cases of tests/golden/g10_cindex_ties.npz carry the value of the reference's own fallback ConcordanceIndex."""
+    from multimodal_survival_prediction_amd import losses
+    monkeypatch.setattr(losses, "USE_TORCHSURV", False)
+    rng = np.random.default_rng(2468)
+    dev = lambda *a: (torch.tensor(x).to(DEV) for x in a)
+    for n in (1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1025):
+        for pattern in ("mixed", "all", "none", "maxtime"):
+            h, e, t = _tied_case(rng, n, pattern)
+            conc, tied, perm = _cindex_brute(h, e, t)
+            if pattern == "mixed" and n >= 4:
+                assert tied > 0 and len(np.unique(t)) < n, (n, conc, tied, perm)     # the case has its ties
+            if pattern in ("none", "maxtime") or n <= 3:
+                assert perm == 0, (n, pattern)
+            hd, ed, td = dev(h, e, t)
+            got = ops.cindex_counts(hd, td, ed).cpu().tolist()
+            assert got == [int(conc), int(tied), int(perm)], (n, pattern, got, (conc, tied, perm))
+            want = lambda credit: (float(conc) + credit * float(tied)) / float(perm) if perm > 0 else 0.5
+            assert abs(losses.calculate_cindex(hd, ed, td, tie_credit=0.5) - want(0.5)) <= 1e-12, (n, pattern)
+            assert abs(losses.calculate_cindex(hd, ed, td, tie_credit=0.0) - want(0.0)) <= 1e-12, (n, pattern)
+            c = losses.ConcordanceIndex()(hd, ed, td)
+            assert abs(c.item() - float(np.float32(want(0.0)))) <= 1e-12, (n, pattern, c.item(), want(0.0))
+    z = np.load(f"{G}/g10_cindex_ties.npz")
+    for n in ("n4", "n23", "n116"):
+        h, e, t = z[n + "_h"], z[n + "_e"], z[n + "_t"]
+        conc, tied, perm = _cindex_brute(h, e, t)
+        assert tied > 0 and perm > 0
+        got = ops.cindex_counts(*dev(h, t, e)).cpu().tolist()
+        assert got == [int(conc), int(tied), int(perm)], (n, got)
+        assert abs(got[0] / got[2] - float(z[n + "_cindex"])) <= 6e-8, n      # tied scores earn nothing (the reference returns fp32)
+
+
+def _cox_check(ops, h, e, t, valid=None, scale=1.0, what=""):
+    """ops.cox_fwd_bwd (Breslow) against the fp64 risk-set oracle on the valid rows; criteria of test_cox_large_risk_set_vs_fp64_oracle."""
+    from oracle.losses import cox_npll_grad_np, cox_npll_np
+    idx = np.ones(len(h), bool) if valid is None else valid > 0
+    ref = cox_npll_np(h[idx], e[idx], t[idx])
+    g = np.zeros(len(h))
+    g[idx] = scale * cox_npll_grad_np(h[idx], e[idx], t[idx])
+    assert np.isfinite(ref) and np.isfinite(g).all() and float(np.abs(g).max()) > 0, what
+    out, dh = ops.cox_fwd_bwd(*(torch.tensor(a).to(DEV) for a in (h, t, e)), valid=None if valid is None else torch.tensor(valid).to(DEV),
+                              scale=scale, ties="breslow")
+    torch.cuda.synchronize()
+    assert abs(out[0].item() - ref) <= 1e-4 * max(1.0, abs(ref)) and out[1].item() == 1.0, (what, out.tolist(), ref)
+    assert float(np.abs(dh.cpu().numpy().astype(np.float64) - g).max()) <= 1e-4 * float(np.abs(g).max()), what
+
+
+def _big_hazards(rng, n):
+    """distinct times, |h| up to ~90 with max - min >= 150: exp(h) overflows fp32, exp(h - max over the risk set) does not"""
+    h = rng.uniform(-90.0, 90.0, n).astype(np.float32)
+    h[rng.permutation(n)[:2]] = (-80.0, 89.5)
+    t = (rng.exponential(1000, n) + 1 + np.arange(n) * 1e-2).astype(np.float32)
+    e = (rng.random(n) < 0.6).astype(np.float32)
+    e[np.argmin(t)] = 1
+    with np.errstate(over="ignore"):
+        assert float(h.max() - h.min()) >= 150 and len(np.unique(t)) == n and not np.isfinite(np.exp(h)).all()
+    return h, e, t
+
+
+def test_cox_breslow_ties_extremes_and_group(ops):
+    """cox_lse_kernel / cox_grad_kernel in Breslow mode against oracle.losses.cox_npll_np / cox_npll_grad_np (fp64): tied survival
+    times (with and without a label mask, scale != 1), hazards whose plain exp overflows fp32, label masks that leave fewer than two
+    rows or no event, and the group launch (ng = 3, different data per member) bit-identical to the single launches.
+    The reference's custom cox_loss sorts by time and takes a cumulative log-sum-exp, so on tied times its value depends on the sort
+    order among the ties; the project chose the risk-set (Breslow) form for that case, and the reference is not pinned on ties."""
+    rng = np.random.default_rng(1357)
+    keep = {}
+    for n in (4, 5, 64, 65, 257):
+        # tied times: ceil(n / 4) distinct values
+        h, e, t = _tied_case(rng, n, "mixed", time_div=4)
+        h = rng.normal(0, 1, n).astype(np.float32)
+        assert len(np.unique(t)) == -(-n // 4) < n
+        _cox_check(ops, h, e, t, scale=0.5, what="tied times n=%d" % n)
+        valid = np.ones(n, np.float32)
+        valid[rng.permutation(n)[:max(1, n // 4)]] = 0
+        valid[np.argmin(t)] = 1                                  # (that row carries an event: the masked batch stays usable)
+        _cox_check(ops, h, e, t, valid=valid, scale=3.0, what="tied times + mask n=%d" % n)
+        hb, eb, tb = _big_hazards(rng, n)
+        _cox_check(ops, hb, eb, tb, what="large hazards n=%d" % n)
+        _cox_check(ops, hb, eb, tb, valid=valid, scale=0.5, what="large hazards + mask n=%d" % n)
+        keep[n] = (h, e, t, valid, hb, eb, tb)
+        # label masks that leave nothing to train on: one valid row; two valid rows without an event (events on the masked rows)
+        ev = np.ones(n, np.float32)
+        one = np.zeros(n, np.float32); one[n // 2] = 1
+        two = np.zeros(n, np.float32); two[[0, n - 1]] = 1
+        ev2 = ev.copy(); ev2[[0, n - 1]] = 0
+        for v, e_ in ((one, ev), (two, ev2)):
+            out, dh = ops.cox_fwd_bwd(*(torch.tensor(a).to(DEV) for a in (hb, tb, e_)), valid=torch.tensor(v).to(DEV), scale=2.0)
+            torch.cuda.synchronize()
+            assert out.tolist() == [0.0, 0.0] and torch.equal(dh, torch.zeros_like(dh)), (n, out.tolist())
+    for n in (5, 65):
+        h, e, t, valid, hb, eb, tb = keep[n]
+        d = lambda a: torch.tensor(a).to(DEV)
+        members = [dict(h=d(h), time=d(t), event=d(e), valid=d(valid), scale=2.0),
+                   dict(h=d(hb), time=d(tb), event=d(eb)),
+                   dict(h=d(h), time=d(t), event=d(e), ties="efron", scale=0.5)]
+        grouped = ops.cox_fwd_bwd_group(members)
+        singles = [ops.cox_fwd_bwd(m["h"], m["time"], m["event"], valid=m.get("valid"), scale=m.get("scale", 1.0), ties=m.get("ties", "breslow"))
+                   for m in members]
+        torch.cuda.synchronize()
+        for g, ((o1, d1), (o2, d2)) in enumerate(zip(grouped, singles)):
+            assert torch.equal(o1, o2) and torch.equal(d1, d2), (n, g, o1.tolist(), o2.tolist())
+            assert o1[1].item() == 1.0 and float(d1.abs().max()) > 0
+        assert not torch.equal(grouped[0][1], grouped[2][1])         # the members differ (mask + Breslow vs Efron)

@@ -263,3 +263,94 @@ def test_rnaseq_epoch_matches_reference():
     np.testing.assert_allclose(losses, z["ep_losses"], rtol=2e-5)
     vl, vc = LO.validate_rnaseq(m, loader)
     np.testing.assert_allclose([vl, vc], z["ep_val"], rtol=2e-5)
+
+
+# ---- g9: the partial / simple / flexible epoch loops, executed from the reference's text on the special-batch cohort ----------------
+LOOP_CLASSES = {"partial": "PartialModalityNet", "simple": "SimpleFusionModel", "flexible": "FlexibleMultimodalModel"}
+
+
+def _check_loop_pair(tag):
+    """Two train_epoch calls + validate of oracle/loops.py against what the reference's own loop text returned on the same batches
+    (tests/golden/g9_loops.npz), dropout ACTIVE: model construction and both epochs draw from one torch.manual_seed stream, so the
+    RNG consumption order is pinned too.  The optimizer handed to the loops is plain SGD (why: generate_golden.gen_loops).  Same torch
+    on a CPU on both sides: tolerances of test_train_epoch_trajectory_matches_reference (returned means and validation loss 1e-4,
+    hazards rtol 1e-3 + 1e-5; the running statistics take the hazards' numbers relative to the tensor's max -- a forward more or less
+    moves them by ~10 % of a batch statistic); measured between the fixture (8 threads) and runs on 1 / 3 / 16 threads: means
+    <= 1.2e-7, running statistics <= 1.7e-5, hazards <= 6.5e-6 of their maximum.  num_batches_tracked and WHICH samples enter the
+    C-index (their times and events; times are distinct) exactly."""
+    from test_gpu_flexible_epoch import LOOP_NTRAIN, LOOP_RNA, loop_batches, special_cohort
+    z = np.load(f"{G}/g9_loops.npz")
+    c = special_cohort(int(z["cohort_seed"]))
+    for k in ("time", "event", "has_survival", "mask"):            # the restated cohort is the generator's
+        np.testing.assert_array_equal(c[k], z[k], err_msg=k)
+    assert float(c["image"].astype(np.float64).sum()) == float(z["image_sum"])
+    assert float(c["rnaseq"].astype(np.float64).sum()) == float(z["rnaseq_sum"])
+    cls = LOOP_CLASSES[tag]
+    lr, momentum = (float(v) for v in z["sgd_lr_momentum"])      # the optimizer is the caller's: the generator hands the loops plain SGD
+    mkopt = lambda p: torch.optim.SGD(p, lr=lr, momentum=momentum)
+    trb = loop_batches(c, np.arange(LOOP_NTRAIN), tag)
+    vab = loop_batches(c, np.arange(LOOP_NTRAIN, c["n"]), tag)
+    cpu = torch.device("cpu")
+    torch.manual_seed(int(z[f"{tag}_model_seed"]))
+    m = getattr(OM, cls)(rna_dim=LOOP_RNA, use_monai=False)
+    opt = mkopt(m.parameters())
+    rets = [getattr(OLP, "train_epoch_" + tag)(m, trb, opt, cpu) for _ in range(2)]
+    np.testing.assert_allclose(np.array(rets, np.float64), z[f"{tag}_train"], rtol=1e-4)
+    seen = []
+    val = getattr(OLP, "validate_" + tag)(m, vab, cpu, on_cindex=lambda h, e, t: seen.append((h, e, t)))
+    assert val[0] == pytest.approx(float(z[f"{tag}_val"][0]), rel=1e-4)
+    assert len(seen) == 1
+    h, e, t = seen[0]
+    np.testing.assert_array_equal(np.asarray(t, np.float32), z[f"{tag}_cindex_t"])
+    np.testing.assert_array_equal(np.asarray(e, np.float32), z[f"{tag}_cindex_e"])
+    np.testing.assert_allclose(np.asarray(h, np.float32), z[f"{tag}_cindex_h"], rtol=1e-3, atol=1e-5)
+    if tag == "partial" and not bool(z["lifelines"]):
+        # generated without lifelines: the reference's calculate_cindex took its bare `except` (partial_modality_training.py:318-319)
+        # and returned 0.5 whatever the hazards; the samples that entered it are pinned above, its value is not comparable
+        assert float(z["partial_val"][1]) == 0.5
+    else:
+        assert val[1] == pytest.approx(float(z[f"{tag}_val"][1]), abs=6e-8)
+    m.eval()
+    with torch.no_grad():
+        b0 = trb[0]
+        hz = (m(b0["image"], b0["rnaseq"], b0["clinical"], b0["mask"])[0] if tag == "partial" else
+              m(b0["image"], b0["rnaseq"]) if tag == "simple" else m(b0["image"], b0["rnaseq"], b0["mask"]))
+    np.testing.assert_allclose(hz.numpy(), z[f"{tag}_hazard_b0"], rtol=1e-3, atol=1e-5)
+    bufs = dict(m.named_buffers())
+    keys = [k.split("/", 1)[1] for k in z.files if k.startswith(f"{tag}_buf/")]
+    assert sorted(keys) == sorted(bufs) and len(keys) >= 12
+    for k in keys:
+        ref = z[f"{tag}_buf/{k}"]
+        if "num_batches" in k:
+            assert int(bufs[k]) == int(ref), k         # forwards in training mode: tells "skipped before the forward" from "after it"
+        else:
+            np.testing.assert_allclose(bufs[k].numpy(), ref, rtol=1e-3, atol=1e-5 * float(np.abs(ref).max()), err_msg=k)
+
+
+def test_partial_epoch_loops_match_reference():
+    """partial_modality_training.py:382-485: entropy-only steps, num_survival_batches next to num_batches."""
+    _check_loop_pair("partial")
+
+
+def test_simple_epoch_loops_match_reference():
+    """simple_fusion.py:242-333: one `continue` before the forward, one after it (BatchNorm running statistics still move)."""
+    _check_loop_pair("simple")
+
+
+def test_flexible_epoch_loops_match_reference():
+    """flexible_multimodal.py:262-351."""
+    _check_loop_pair("flexible")
+
+
+def test_cindex_tied_scores_match_reference():
+    """Tied risk scores AND tied times (tests/golden/g10_cindex_ties.npz, the fallback ConcordanceIndex of train_rnaseq_only.py:55,
+    simple_fusion.py:59 and flexible_multimodal.py:54 -- asserted identical at generation time): a pair of equal scores earns nothing,
+    a pair of equal times is not permissible."""
+    z = np.load(f"{G}/g10_cindex_ties.npz")
+    for n in ("n4", "n23", "n116"):
+        h, e, t = z[n + "_h"], z[n + "_e"], z[n + "_t"]
+        perm = (t[None, :] > t[:, None]) & (e[:, None] == 1)
+        assert int((perm & (h[:, None] == h[None, :])).sum()) > 0 and len(np.unique(t)) < len(t), n       # the fixture has its ties
+        c = OL.concordance_index_np(h, e, t, tie_credit=0.0)
+        assert c == pytest.approx(float(z[n + "_cindex"]), abs=6e-8), n      # reference returns an fp32 tensor
+        assert OL.concordance_index_np(h, e, t, tie_credit=0.5) > c + 1e-4, n
