@@ -20,9 +20,11 @@ import dataclasses
 
 import torch
 
+from .training import styles_without_mask
+
 REC_WORDS = 8
 FLIP, DZ, DY, DX, SCALE, OFFSET, DROP = range(7)
-MASKLESS_STYLES = ("final", "simple", "image", "rnaseq")        # their models take no modality mask: nothing can tell them a row is hidden
+MASKLESS_STYLES = styles_without_mask()      # (training's style table) their models take no modality mask: nothing can tell them a row is hidden
 ROLE_PLAIN, ROLE_VOLUME, ROLE_MASK = 0, 1, 2                     # include/mmsurv.h: MMS_AUG_*
 
 

@@ -7,7 +7,8 @@ One `SurvivalEngine` per model instance.  It
     and the prebuilt C-ABI parameter blocks (ctypes structs holding raw device pointers) for every launch;
   * runs a plan either eagerly (autograd-compatible path used by the nn.Module's forward/backward) or as a
     captured HIP graph of the WHOLE training step (zero-grad -> forward -> Cox -> backward -> clip -> Adam),
-    which is what `training.train_epoch_*` and bench.py replay once per batch.
+    which is what `training.train_epoch_*` (one loop, `training._train_epoch`, over the per-style table there) and bench.py
+    replay once per batch.
 
 PyTorch supplies device memory, streams and graph capture only; every numeric op is a kernel behind
 include/mmsurv.h.  Nothing here falls back to torch math.

@@ -4,7 +4,8 @@ Constructor signatures, forward signatures, sub-module names (state_dict keys) a
 the reference's (final_multimodal.py:59-150, partial_modality_training.py:165-277, simple_fusion.py:160-236,
 flexible_multimodal.py:157-256, train_rnaseq_only.py:126-151; MONAI branch).  The nn.Sequential containers only own parameters; they are never called.  Parameters stay ordinary
 autograd leaves: `torch.optim.Adam(model.parameters())`, `clip_grad_norm_`, `state_dict()/load_state_dict()` keep
-working (the autograd-compatible path), while `training.train_epoch_*` drive the fused HIP-graph step.
+working (the autograd-compatible path), while `training.train_epoch_*` drive the fused HIP-graph step (what each model's loop feeds
+it is that style's row of `training._STYLES`).
 """
 import torch
 import torch.nn as nn

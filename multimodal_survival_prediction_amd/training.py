@@ -1,12 +1,18 @@
-"""train_epoch / validate of the three reference scripts, driving the fused HIP-graph step.
+"""train_epoch / validate of the reference's scripts, driving the fused HIP-graph step.
 
 Signatures are the reference's: train_epoch(model, loader, optimizer, device) / validate(model, loader, device)
-(final_multimodal.py:238-305, partial_modality_training.py:382-485, simple_fusion.py:242-333).  `optimizer` may be
+(final_multimodal.py:238-305, partial_modality_training.py:382-485, simple_fusion.py:242-333, flexible_multimodal.py:262-357,
+train_rnaseq_only.py:157-209; "simmlm" and "image" are project-defined).  `optimizer` may be
   * a `FusedOptimizer` (below): the whole step -- zero-grad, forward, Cox loss, backward, clip_grad_norm_(1.0),
     Adam/AdamW -- is ONE replayed HIP graph per batch, losses accumulate on the device, one host sync per epoch;
-  * any torch.optim optimizer: the reference's own loop body runs unchanged on the autograd-compatible path.
-Batch-skipping rules, loss averaging and return values follow each script exactly.
+  * any torch.optim optimizer ("final" and "image" only): the reference's own loop body runs unchanged on the autograd-compatible path.
+Batch-skipping rules, loss averaging and return values follow each script exactly.  What differs between the seven loop styles -- model
+inputs, targets, skips, the skip flag, the returned mean, validation's rows, batch rule, loss and C-index -- is stated ONCE, as that
+style's row of the table `_STYLES`; the eager loops (_train_epoch / _validate behind the public train_epoch_<style> / validate_<style>)
+and the lock-step K-fold drivers (train_epoch_lockstep / validate_lockstep) all read it.
 """
+import dataclasses
+
 import torch
 
 from . import losses, ops
@@ -71,21 +77,7 @@ def _t(x, dev):
     return x.to(dev, non_blocking=True) if isinstance(x, torch.Tensor) else torch.as_tensor(x).to(dev)
 
 
-# ---- final_multimodal.py --------------------------------------------------------------------------------
-def train_epoch_final(model, loader, optimizer, device):
-    if not isinstance(optimizer, FusedOptimizer):
-        return _train_epoch_final_autograd(model, loader, optimizer, device)
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        label = batch['label']
-        eng.train_step(batch['image'], batch['rnaseq'], batch['clinical'], time=label[:, 0], event=label[:, 1],
-                       skip_if_unusable=True)      # degenerate batch: loss 0 without graph -> no update (:173-176)
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0
-
-
+# ---- the two autograd fallbacks (any torch.optim optimizer: the reference's own loop body) ------------------------------------------
 def _train_epoch_final_autograd(model, loader, optimizer, device):
     model.train()
     total, nb = 0.0, 0
@@ -101,123 +93,6 @@ def _train_epoch_final_autograd(model, loader, optimizer, device):
         total += loss.item()
         nb += 1
     return total / nb if nb > 0 else 0
-
-
-def validate_final(model, loader, device):
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        label = _t(batch['label'], device)
-        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'], batch['clinical'])
-        hz = hz.clone()
-        total += losses.cox_loss(hz, label[:, 1], label[:, 0]).item()
-        nb += 1
-        hs.append(hz); ts.append(label[:, 0]); es.append(label[:, 1])
-    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
-    eng.check_b4()
-    return (total / nb if nb > 0 else 0), c
-
-
-# ---- partial_modality_training.py -----------------------------------------------------------------------------
-def train_epoch_partial(model, loader, optimizer, device):
-    if not isinstance(optimizer, FusedOptimizer):
-        raise TypeError("train_epoch_partial drives the fused step; pass a FusedOptimizer")
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        label = batch['label']
-        valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
-        eng.train_step(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'], time=label[:, 0],
-                       event=label[:, 1], valid=valid, skip_if_unusable=False)   # entropy term: every batch steps (:418-428)
-    st = eng.epoch_stats()
-    avg_cox = st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0
-    avg_ent = st["sum_entropy"] / st["n_batches"] if st["n_batches"] > 0 else 0
-    return avg_cox, avg_ent
-
-
-def validate_partial(model, loader, device):
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        label = _t(batch['label'], device)
-        smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
-        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'])
-        if int(smask.sum()) > 0:
-            h, t, e = hz[smask].clone(), label[smask, 0], label[smask, 1]
-            if h.shape[0] >= 2 and float(e.sum()) > 0:
-                total += losses.cox_loss(h, e, t).item()
-                nb += 1
-                hs.append(h); ts.append(t); es.append(e)
-    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
-    eng.check_b4()
-    return (total / nb if nb > 0 else 0), c
-
-
-# ---- SimMLM_SurvivalNet (generate_km_curves.py:158-281; the reference ships no training loop for it) ------------------------
-def train_epoch_simmlm(model, loader, optimizer, device):
-    """One epoch of the project-defined objective L = cox(ensemble; has_survival) + lambda sum_m cox(h_m; has_survival and mask_m)
-    (lambda = the engine's expert_weight), fused step per batch; a batch whose ensemble term is unusable takes no step.
-    -> mean of L over the usable batches."""
-    if not isinstance(optimizer, FusedOptimizer):
-        raise TypeError("train_epoch_simmlm drives the fused step; pass a FusedOptimizer")
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        label = batch['label']
-        valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
-        eng.train_step(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'], time=label[:, 0],
-                       event=label[:, 1], valid=valid, skip_if_unusable=True)
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0
-
-
-def validate_simmlm(model, loader, device):
-    """-> (mean ensemble Cox loss over the usable batches, C-index of the ensemble hazard over their labelled patients); the batch
-    rule of validate_partial over the labelled patients WITH at least one modality (a row whose mask is all zero has a NaN ensemble
-    hazard: it is left out, as it is left out of the training objective)."""
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        label = _t(batch['label'], device)
-        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'], batch['clinical'], mask=batch['mask'])
-        smask = _simmlm_rows(batch, device)
-        if int(smask.sum()) > 0:
-            h, t, e = hz[smask].clone(), label[smask, 0], label[smask, 1]
-            if h.shape[0] >= 2 and float(e.sum()) > 0:
-                total += losses.cox_loss(h, e, t).item()
-                nb += 1
-                hs.append(h); ts.append(t); es.append(e)
-    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
-    eng.check_b4()
-    return (total / nb if nb > 0 else 0), c
-
-
-def _simmlm_rows(batch, device):
-    """labelled patients with at least one modality (the ensemble term's set)"""
-    smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
-    return smask & (_t(batch['mask'], device) != 0).any(1)
-
-
-# ---- ImageOnlyModel (generate_km_curves.py:28-54; the reference ships no training loop for it) ---------------------------------
-def train_epoch_image(model, loader, optimizer, device):
-    """The loop of final_multimodal.py:238-266 on the image alone (project-defined): a forward on every batch (BatchNorm
-    running statistics move even on a degenerate one), Cox loss over the whole batch, clip at 1.0; a batch with fewer than 2 patients or
-    without an event has loss 0 and takes no optimiser step.  -> mean loss over all batches."""
-    if not isinstance(optimizer, FusedOptimizer):
-        return _train_epoch_image_autograd(model, loader, optimizer, device)
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        label = batch['label']
-        eng.train_step(batch['image'], time=label[:, 0], event=label[:, 1], skip_if_unusable=True)
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0
 
 
 def _train_epoch_image_autograd(model, loader, optimizer, device):
@@ -237,176 +112,261 @@ def _train_epoch_image_autograd(model, loader, optimizer, device):
     return total / nb if nb > 0 else 0
 
 
-def validate_image(model, loader, device):
-    """Eval-mode forward of every batch -> (mean of the batches' Cox losses, C-index by pair counts over all patients)."""
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        label = _t(batch['label'], device)
-        hz, _ = eng.forward_eval(batch['image'])
-        hz = hz.clone()
-        total += losses.cox_loss(hz, label[:, 1], label[:, 0]).item()
-        nb += 1
-        hs.append(hz); ts.append(label[:, 0]); es.append(label[:, 1])
-    c = losses.calculate_cindex(torch.cat(hs), torch.cat(es), torch.cat(ts)) if hs else 0.5
-    return (total / nb if nb > 0 else 0), c
+# ---- the style table: ONE row per loop style holds everything that differs between the seven ------------------------------------------
+def _labelled(batch, device):
+    return torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
 
 
-# ---- simple_fusion.py -------------------------------------------------------------------------------------------
-def train_epoch_simple(model, loader, optimizer, device):
+def _simmlm_rows(batch, device):
+    """labelled patients with at least one modality (the ensemble term's set; a row whose mask is all zero has a NaN ensemble hazard)"""
+    return _labelled(batch, device) & (_t(batch['mask'], device) != 0).any(1)
+
+
+@dataclasses.dataclass(frozen=True)
+class _Style:
+    inputs: tuple                      # model inputs: keywords of the fused step / eval forward, read from the batch keys of _BATCH_KEY
+    label: bool                        # targets: batch['label'][:, 0] / [:, 1] (True) or batch['time'] / batch['event'] reshaped to [B] (False)
+    loss: str                          # validation loss and C-index: names in `losses`
+    cindex: str
+    zero: object                       # the mean of nothing: 0 or 0.0, as the style's script returns it
+    mask_cols: int = None              # the model sees only the first columns of batch['mask']
+    valid: bool = False                # has_survival is passed as `valid`: unlabelled patients stay out of the loss
+    pre_skip: bool = False             # fewer than 2 labelled patients: the batch is skipped BEFORE the forward, training and validation
+    skip_if_unusable: bool = True      # a batch whose loss is unusable (< 2 patients in it, or no event) takes no optimiser step
+    mean_over: str = "n_batches"       # training result: sum_loss / this count of epoch_stats() ...
+    entropy: bool = False              # ... paired with sum_entropy / n_batches
+    rows: object = None                # validation: (batch, device) -> the rows that count; None = all
+    counts: str = "every"              # validation: a batch counts always ("every"), with >= 2 selected rows and an event ("two_and_event"), or with an event ("event")
+    named: bool = False                # validate_lockstep has the named-batch path (_validate_lockstep_named) for it
+    autograd: object = None            # train_epoch_<style> with a torch.optim optimizer
+    needs: str = "a FusedOptimizer"    # ... or the TypeError's advice
+
+
+_BATCH_KEY = dict(ct='image', rna='rnaseq', clinical='clinical', mask='mask')
+_COX = dict(label=True, loss="cox_loss", cindex="calculate_cindex", zero=0)                      # final_multimodal.py's family
+_NPLL = dict(label=False, loss="neg_partial_log_likelihood", cindex="ConcordanceIndex", zero=0.0)   # simple_fusion.py's family
+_STYLES = {
+    # degenerate batch: loss 0 without graph -> no update (final_multimodal.py:173-176)
+    "final": _Style(("ct", "rna", "clinical"), **_COX, named=True, autograd=_train_epoch_final_autograd),
+    # entropy term: every batch steps (partial_modality_training.py:418-428)
+    "partial": _Style(("ct", "rna", "clinical", "mask"), **_COX, valid=True, skip_if_unusable=False, mean_over="n_usable", entropy=True,
+                      rows=_labelled, counts="two_and_event", named=True),
+    # project-defined: a batch whose ensemble term is unusable takes no step
+    "simmlm": _Style(("ct", "rna", "clinical", "mask"), **_COX, valid=True, mean_over="n_usable", rows=_simmlm_rows,
+                     counts="two_and_event"),
+    # project-defined: final_multimodal.py's rules on the image alone
+    "image": _Style(("ct",), **_COX, autograd=_train_epoch_image_autograd),
+    # `continue` before the forward (simple_fusion.py:257-258); no events: forward ran (BN stats moved), no update (:267-268)
+    "simple": _Style(("ct", "rna"), **_NPLL, valid=True, pre_skip=True, mean_over="n_usable", rows=_labelled, counts="event", named=True),
+    # flexible_multimodal.py:276-277 / :287-288
+    "flexible": _Style(("ct", "rna", "mask"), **_NPLL, mask_cols=2, valid=True, pre_skip=True, mean_over="n_usable", rows=_labelled,
+                       counts="event"),
+    # a batch without events yields loss 0 / zero gradients, and still steps (train_rnaseq_only.py:168-172)
+    "rnaseq": _Style(("rna",), **_NPLL, skip_if_unusable=False, needs="a FusedOptimizer(model, adamw=True, max_norm=0)"),
+}
+
+
+def has_named_validation(style):
+    """validate_lockstep evaluates lazily NAMED batches of this style with one gather + one graph per lock-step position."""
+    return _STYLES[style].named
+
+
+def styles_without_mask():
+    """The styles whose models take no modality mask (augment.MASKLESS_STYLES)."""
+    return tuple(s for s, row in _STYLES.items() if "mask" not in row.inputs)
+
+
+def _n_labelled(batch):
+    return sum(bool(x) for x in batch['has_survival'])
+
+
+def _model_inputs(row, batch):
+    """-> keyword inputs of the model, or None when the script skips the batch before the forward."""
+    if row.pre_skip and _n_labelled(batch) < 2:
+        return None
+    kw = {k: batch[_BATCH_KEY[k]] for k in row.inputs}
+    if row.mask_cols:
+        kw["mask"] = kw["mask"][:, :row.mask_cols]
+    return kw
+
+
+def _batch_size(kw):
+    return int((kw["rna"] if "rna" in kw else kw["ct"]).shape[0])
+
+
+def _targets(row, batch, device=None):
+    """-> (time, event) of the batch: as the batch holds them (training), or on `device` (validation)."""
+    if row.label:
+        label = batch['label'] if device is None else _t(batch['label'], device)
+        return label[:, 0], label[:, 1]
+    time, event = batch['time'].reshape(-1), batch['event'].reshape(-1)
+    return (time, event) if device is None else (_t(time, device), _t(event, device).float())
+
+
+def _train_kwargs(style, batch):
+    """-> keyword arguments of the fused step, or None when the script skips the batch before the forward.  The only place that turns a
+    batch into step arguments: the eager loop and train_epoch_lockstep both call it."""
+    row = _STYLES[style]
+    kw = _model_inputs(row, batch)
+    if kw is None:
+        return None
+    kw["time"], kw["event"] = _targets(row, batch)
+    if row.valid:
+        kw["valid"] = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
+    return kw
+
+
+def _train_result(row, st):
+    """What train_epoch_<style> returns for the epoch statistics st."""
+    avg = st["sum_loss"] / st[row.mean_over] if st[row.mean_over] > 0 else row.zero
+    return (avg, st["sum_entropy"] / st["n_batches"] if st["n_batches"] > 0 else row.zero) if row.entropy else avg
+
+
+def _train_epoch(style, model, loader, optimizer, device):
+    row = _STYLES[style]
     if not isinstance(optimizer, FusedOptimizer):
-        raise TypeError("train_epoch_simple drives the fused step; pass a FusedOptimizer")
+        if row.autograd is None:
+            raise TypeError(f"train_epoch_{style} drives the fused step; pass {row.needs}")
+        return row.autograd(model, loader, optimizer, device)
     model.train()
     eng = optimizer.engine
     eng.reset_epoch_stats()
     for batch in loader:
-        hs = batch['has_survival']
-        valid = torch.as_tensor(hs, dtype=torch.float32)
-        if float(valid.sum()) < 2:
-            continue                                   # :257-258, before the forward
-        eng.train_step(batch['image'], batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1),
-                       valid=valid, skip_if_unusable=True)   # no events: forward ran (BN stats moved), no update (:267-268)
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0.0
+        kw = _train_kwargs(style, batch)
+        if kw is not None:
+            eng.train_step(**kw, skip_if_unusable=row.skip_if_unusable)
+    return _train_result(row, eng.epoch_stats())
+
+
+def _score_batch(row, batch, hz, device):
+    """One validation batch after its forward -> (loss, hazards, times, events) of the rows that count, or None when the batch does not."""
+    t, e = _targets(row, batch, device)
+    if row.rows is not None:
+        keep = row.rows(batch, device)
+        hz, t, e = hz[keep], t[keep], e[keep]
+    if row.counts == "two_and_event" and not (hz.shape[0] >= 2 and float(e.sum()) > 0):
+        return None
+    if row.counts == "event" and float(e.sum()) == 0:
+        return None
+    h = hz.clone()                                  # hz is a view of a static buffer
+    return getattr(losses, row.loss)(h, e, t).item(), h, t, e
+
+
+def _cindex(row, H, E, T):
+    f = getattr(losses, row.cindex)
+    return f()(H, E, T).item() if row.cindex == "ConcordanceIndex" else f(H, E, T)
+
+
+def _val_result(row, scored):
+    """(mean loss, C-index) of one model's validation pass: scored = what _score_batch returned for its batches."""
+    scored = [s for s in scored if s is not None]
+    if not scored:
+        return row.zero, 0.5
+    loss, hs, ts, es = zip(*scored)
+    return sum(loss) / len(loss), _cindex(row, torch.cat(hs), torch.cat(es), torch.cat(ts))
+
+
+def _validate(style, model, loader, device):
+    row = _STYLES[style]
+    model.eval()
+    eng = engine_of(model)
+    scored = []
+    for batch in loader:
+        kw = _model_inputs(row, batch)
+        if kw is not None:
+            scored.append(_score_batch(row, batch, eng.forward_eval(**kw)[0], device))
+    eng.check_b4()                  # a timed-out block-4 hand-off must not yield a C-index (no-op without the DenseNet encoder)
+    return _val_result(row, scored)
+
+
+# ---- the reference's names: train_epoch(model, loader, optimizer, device) / validate(model, loader, device) of each script ------------
+def train_epoch_final(model, loader, optimizer, device):
+    """final_multimodal.py:238-266: Cox loss on the whole batch, clip at 1.0.  -> mean loss over all batches."""
+    return _train_epoch("final", model, loader, optimizer, device)
+
+
+def validate_final(model, loader, device):
+    """final_multimodal.py:268-305: every batch counts.  -> (mean of the batches' Cox losses, C-index over all patients)."""
+    return _validate("final", model, loader, device)
+
+
+def train_epoch_partial(model, loader, optimizer, device):
+    """partial_modality_training.py:382-435: Cox loss over the labelled patients + the gate-entropy term, every batch steps.
+    -> (mean Cox loss over the usable batches, mean gate entropy over all batches)."""
+    return _train_epoch("partial", model, loader, optimizer, device)
+
+
+def validate_partial(model, loader, device):
+    """partial_modality_training.py:438-485: a batch counts, and its labelled patients enter the C-index, only when >= 2 of them are
+    labelled and one has an event."""
+    return _validate("partial", model, loader, device)
+
+
+def train_epoch_simmlm(model, loader, optimizer, device):
+    """SimMLM_SurvivalNet (generate_km_curves.py:158-281; the reference ships no training loop for it).  One epoch of the project-defined
+    objective L = cox(ensemble; has_survival) + lambda sum_m cox(h_m; has_survival and mask_m) (lambda = the engine's expert_weight),
+    fused step per batch; a batch whose ensemble term is unusable takes no step.  -> mean of L over the usable batches."""
+    return _train_epoch("simmlm", model, loader, optimizer, device)
+
+
+def validate_simmlm(model, loader, device):
+    """-> (mean ensemble Cox loss over the usable batches, C-index of the ensemble hazard over their labelled patients); the batch
+    rule of validate_partial over the labelled patients WITH at least one modality (a row whose mask is all zero has a NaN ensemble
+    hazard: it is left out, as it is left out of the training objective)."""
+    return _validate("simmlm", model, loader, device)
+
+
+def train_epoch_image(model, loader, optimizer, device):
+    """ImageOnlyModel (generate_km_curves.py:28-54; the reference ships no training loop for it).  The loop of final_multimodal.py:238-266
+    on the image alone (project-defined): a forward on every batch (BatchNorm running statistics move even on a
+    degenerate one), Cox loss over the whole batch, clip at 1.0; a batch with fewer than 2 patients or without an event has loss 0 and
+    takes no optimiser step.  -> mean loss over all batches."""
+    return _train_epoch("image", model, loader, optimizer, device)
+
+
+def validate_image(model, loader, device):
+    """Eval-mode forward of every batch -> (mean of the batches' Cox losses, C-index by pair counts over all patients)."""
+    return _validate("image", model, loader, device)
+
+
+def train_epoch_simple(model, loader, optimizer, device):
+    """simple_fusion.py:242-279: batches with < 2 labelled patients are skipped before the forward (:257-258), batches without an event
+    after it (:267-268).  -> mean loss over the stepped batches."""
+    return _train_epoch("simple", model, loader, optimizer, device)
 
 
 def validate_simple(model, loader, device):
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
-        if int(smask.sum()) < 2:
-            continue
-        time, event = _t(batch['time'].reshape(-1), device), _t(batch['event'].reshape(-1), device)
-        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'])
-        h, t, e = hz[smask].clone(), time[smask], event[smask].float()
-        if float(e.sum()) == 0:
-            continue
-        total += losses.neg_partial_log_likelihood(h, e, t).item()
-        nb += 1
-        hs.append(h); ts.append(t); es.append(e)
-    if not hs:
-        return 0.0, 0.5
-    c = losses.ConcordanceIndex()(torch.cat(hs), torch.cat(es), torch.cat(ts)).item()
-    eng.check_b4()
-    return (total / nb if nb > 0 else 0.0), c
+    """simple_fusion.py:281-333: the two skips of the training loop; (0.0, 0.5) when no batch counts."""
+    return _validate("simple", model, loader, device)
 
 
-# ---- flexible_multimodal.py (rows of SURVEY section 8f: same kernels, learnable missing-modality bias) ---------------------
 def train_epoch_flexible(model, loader, optimizer, device):
-    """flexible_multimodal.py:262-303: the simple_fusion loop with the (B,2) modality mask as a third model input."""
-    if not isinstance(optimizer, FusedOptimizer):
-        raise TypeError("train_epoch_flexible drives the fused step; pass a FusedOptimizer")
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
-        if float(valid.sum()) < 2:
-            continue                                   # :276-277
-        eng.train_step(batch['image'], batch['rnaseq'], mask=batch['mask'][:, :2], time=batch['time'].reshape(-1),
-                       event=batch['event'].reshape(-1), valid=valid, skip_if_unusable=True)     # :287-288
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0.0
+    """flexible_multimodal.py:262-303 (rows of SURVEY section 8f: same kernels, learnable missing-modality bias): the simple_fusion loop
+    with the (B,2) modality mask as a third model input."""
+    return _train_epoch("flexible", model, loader, optimizer, device)
 
 
 def validate_flexible(model, loader, device):
     """flexible_multimodal.py:305-357."""
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
-        if int(smask.sum()) < 2:
-            continue
-        time, event = _t(batch['time'].reshape(-1), device), _t(batch['event'].reshape(-1), device)
-        hz, _ = eng.forward_eval(batch['image'], batch['rnaseq'], mask=batch['mask'][:, :2])
-        h, t, e = hz[smask].clone(), time[smask], event[smask].float()
-        if float(e.sum()) == 0:
-            continue
-        total += losses.neg_partial_log_likelihood(h, e, t).item()
-        nb += 1
-        hs.append(h); ts.append(t); es.append(e)
-    if not hs:
-        return 0.0, 0.5
-    c = losses.ConcordanceIndex()(torch.cat(hs), torch.cat(es), torch.cat(ts)).item()
-    eng.check_b4()
-    return (total / nb if nb > 0 else 0.0), c
+    return _validate("flexible", model, loader, device)
 
 
-# ---- train_rnaseq_only.py ------------------------------------------------------------------------------------------------
 def train_epoch_rnaseq(model, loader, optimizer, device):
     """train_rnaseq_only.py:157-176: NPLL on the whole batch, every batch steps, NO gradient clipping (build the
     FusedOptimizer with max_norm=0), mean over len(loader)."""
-    if not isinstance(optimizer, FusedOptimizer):
-        raise TypeError("train_epoch_rnaseq drives the fused step; pass a FusedOptimizer(model, adamw=True, max_norm=0)")
-    model.train()
-    eng = optimizer.engine
-    eng.reset_epoch_stats()
-    for batch in loader:
-        eng.train_step(None, batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1),
-                       skip_if_unusable=False)       # a batch without events yields loss 0 / zero gradients, and still steps (:168-172)
-    st = eng.epoch_stats()
-    return st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0.0
+    return _train_epoch("rnaseq", model, loader, optimizer, device)
 
 
 def validate_rnaseq(model, loader, device):
-    """train_rnaseq_only.py:178-209."""
-    model.eval()
-    eng = engine_of(model)
-    total, nb, hs, ts, es = 0.0, 0, [], [], []
-    for batch in loader:
-        time, event = _t(batch['time'].reshape(-1), device), _t(batch['event'].reshape(-1), device).float()
-        hz, _ = eng.forward_eval(None, batch['rnaseq'])
-        h = hz.clone()
-        total += losses.neg_partial_log_likelihood(h, event, time).item()
-        nb += 1
-        hs.append(h); ts.append(time); es.append(event)
-    c = losses.ConcordanceIndex()(torch.cat(hs), torch.cat(es), torch.cat(ts)).item()
-    return total / nb, c
+    """train_rnaseq_only.py:178-209; (0.0, 0.5) on an empty loader."""
+    return _validate("rnaseq", model, loader, device)
 
 
 # ---- K folds in lock-step (fold groups) ------------------------------------------------------------------------------
 # The reference trains its folds one after the other; they are independent, so a FoldGroupEngine advances all of them by
 # one batch with ONE launch sequence (fold_group.py).  Per fold, batch order, skipping rules, loss averaging and return
-# values are exactly those of train_epoch_<style> / validate_<style> above; only the interleaving of the folds differs.
-def _train_kwargs(style, batch):
-    """-> (keyword arguments of the fused step, skip_if_unusable) or None when the script skips the batch before the forward."""
-    if style == "final":
-        label = batch['label']
-        return dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], time=label[:, 0], event=label[:, 1])
-    if style == "rnaseq":
-        return dict(rna=batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1))
-    if style == "image":
-        label = batch['label']
-        return dict(ct=batch['image'], time=label[:, 0], event=label[:, 1])
-    valid = torch.as_tensor(batch['has_survival'], dtype=torch.float32)
-    if style in ("partial", "simmlm"):
-        label = batch['label']
-        return dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], mask=batch['mask'], time=label[:, 0],
-                    event=label[:, 1], valid=valid)
-    if style in ("simple", "flexible"):
-        if float(valid.sum()) < 2:
-            return None                                      # simple_fusion.py:257-258, flexible_multimodal.py:276-277
-        kw = dict(ct=batch['image'], rna=batch['rnaseq'], time=batch['time'].reshape(-1), event=batch['event'].reshape(-1),
-                  valid=valid)
-        if style == "flexible":
-            kw["mask"] = batch['mask'][:, :2]
-        return kw
-    raise ValueError(style)
-
-
-_SKIP_UNUSABLE = {"final": True, "partial": False, "simple": True, "flexible": True, "rnaseq": False}
-
-
-def _skip_unusable(style):
-    """the reference scripts' rule (_SKIP_UNUSABLE); "simmlm" (train_epoch_simmlm): a batch whose ensemble term is unusable takes no step;
-    "image" (train_epoch_image): final_multimodal.py's rule"""
-    return True if style in ("simmlm", "image") else _SKIP_UNUSABLE[style]
-
-
+# values are those of train_epoch_<style> / validate_<style> above, read from the same table rows; only the interleaving
+# of the folds differs.
 def _lockstep(loaders, members):
     """Yield, batch position by batch position, {member: batch} of the folds that still have a batch."""
     its = {g: iter(l) for g, l in zip(members, loaders)}
@@ -428,6 +388,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
     (one sub-group's latency-bound kernels overlap the others').  Every member's loader is iterated under its sub-group's
     stream, so batch tensors are allocated and consumed on the same stream.
     -> per member, what train_epoch_<style> returns for that fold."""
+    row = _STYLES[style]
     members = tuple(range(len(group))) if members is None else tuple(members)
     for g in members:
         group.engines[g].model.train()
@@ -443,38 +404,26 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
         if lazy:        # batches named by index (data.BatchLoader(lazy=True)): one gather launch per (sub-)group step
             by = {}
             for g, b in lazy:
-                if style in ("simple", "flexible") and sum(bool(x) for x in b["has_survival"]) < 2:
-                    continue                          # skipped before the forward (simple_fusion.py:257-258)
+                if row.pre_skip and _n_labelled(b) < 2:
+                    continue                          # skipped before the forward
                 by.setdefault((len(b["index"]), id(b["gather"]), "augment" in b), []).append((g, b))
             for items in by.values():                 # (named batches that carry augmentation records: applied inside the gather launch)
                 aug = torch.stack([b["augment"] for _, b in items]) if "augment" in items[0][1] else None
                 group.train_step_indexed(items[0][1]["gather"], torch.stack([torch.as_tensor(b["index"]) for _, b in items]),
-                                         members=tuple(g for g, _ in items), skip_if_unusable=_skip_unusable(style), augment=aug)
+                                         members=tuple(g for g, _ in items), skip_if_unusable=row.skip_if_unusable, augment=aug)
             pos = {g: b for g, b in pos.items() if "gather" not in b}
         by_size = {}
         for g, batch in pos.items():
             kw = _train_kwargs(style, batch)
             if kw is not None:
-                n = int((kw["rna"] if "rna" in kw else kw["ct"]).shape[0])
-                by_size.setdefault(n, []).append((g, kw))
+                by_size.setdefault(_batch_size(kw), []).append((g, kw))
         for items in by_size.values():           # a ragged last batch forms its own (sub-)group step
-            group.train_step([kw for _, kw in items], members=tuple(g for g, _ in items),
-                             skip_if_unusable=_skip_unusable(style))
+            group.train_step([kw for _, kw in items], members=tuple(g for g, _ in items), skip_if_unusable=row.skip_if_unusable)
 
     _run_subgroups(group, loaders, members, concurrent, advance)
     if concurrent > 1:
         torch.cuda.synchronize()
-    out = []
-    for g in members:
-        st = group.engines[g].epoch_stats()
-        if style in ("final", "rnaseq", "image"):
-            out.append(st["sum_loss"] / st["n_batches"] if st["n_batches"] > 0 else 0)
-        elif style == "partial":
-            out.append((st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0,
-                        st["sum_entropy"] / st["n_batches"] if st["n_batches"] > 0 else 0))
-        else:
-            out.append(st["sum_loss"] / st["n_usable"] if st["n_usable"] > 0 else 0.0)
-    return out
+    return [_train_result(row, group.engines[g].epoch_stats()) for g in members]
 
 
 def subgroup_sizes(n_members, concurrent):
@@ -562,100 +511,52 @@ def _validate_lockstep_named(group, loaders, style, members, concurrent=1):
     torch.cuda.synchronize()
     for g in members:
         group.engines[g].check_b4()          # the pass's single sync point: a timed-out block-4 hand-off must not yield a C-index
-    out = []
+    row, out = _STYLES[style], []
     for g, ld in zip(members, loaders):
         a = group.engines[g].acc_eval.tolist()
         if not order[g]:
-            out.append((0.0 if style == "simple" else 0, 0.5))
+            out.append((row.zero, 0.5))
             continue
         lab = ld.c["label"]
         idx = torch.cat([i for i, _ in order[g]])
-        if style == "final":
+        if row.counts == "every":
             keep = torch.ones(len(idx), dtype=torch.bool)
-            avg = a[0] / a[3] if a[3] > 0 else 0
+            avg = a[0] / a[3] if a[3] > 0 else row.zero
         else:
             usable = flags[g][:len(order[g]), 1].cpu() > 0
             keep = torch.cat([m & bool(u) for (_, m), u in zip(order[g], usable)])
-            avg = a[0] / a[1] if a[1] > 0 else 0
+            avg = a[0] / a[1] if a[1] > 0 else row.zero
         if not bool(keep.any()):
-            out.append((0.0 if style == "simple" else 0, 0.5))
+            out.append((row.zero, 0.5))
             continue
         sel = idx[keep].to(lab.device)
         H, T, E = hz[g][keep.to(dev)], lab[sel, 0].to(dev), lab[sel, 1].to(dev)
-        out.append((avg, losses.ConcordanceIndex()(H, E.float(), T).item() if style == "simple" else losses.calculate_cindex(H, E, T)))
+        out.append((avg, _cindex(row, H, E.float(), T)))
     return out
 
 
 def validate_lockstep(group, loaders, style, device, members=None, concurrent=1):
     """validate_<style> of the folds `members`, their eval forwards issued as fold-group launches.
-    -> per member (val_loss, c_index).  Loaders that NAME their batches (final / partial / simple styles) take _validate_lockstep_named;
+    -> per member (val_loss, c_index).  Loaders that NAME their batches (styles with has_named_validation) take _validate_lockstep_named;
     concurrent = n: as train_epoch_lockstep, n sub-groups on n HIP streams (that path only)."""
+    row = _STYLES[style]
     members = tuple(range(len(group))) if members is None else tuple(members)
     loaders = [ld.without_augment() if hasattr(ld, "without_augment") else ld for ld in loaders]       # validation is never augmented
-    if style in ("final", "partial", "simple") and all(getattr(ld, "lazy", False) for ld in loaders):
+    if row.named and all(getattr(ld, "lazy", False) for ld in loaders):
         return _validate_lockstep_named(group, loaders, style, members, concurrent)
-    acc = {g: dict(total=0.0, nb=0, hs=[], ts=[], es=[]) for g in members}
+    scored = {g: [] for g in members}
     for g in members:
         group.engines[g].model.eval()
     for pos in _lockstep(loaders, members):
-        by_size, meta = {}, {}
+        by_size = {}
         for g, batch in pos.items():
-            if style == "final":
-                kw = dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'])
-            elif style in ("partial", "simmlm"):
-                kw = dict(ct=batch['image'], rna=batch['rnaseq'], clinical=batch['clinical'], mask=batch['mask'])
-            elif style == "rnaseq":
-                kw = dict(rna=batch['rnaseq'])
-            elif style == "image":
-                kw = dict(ct=batch['image'])
-            else:
-                if int(torch.as_tensor(batch['has_survival']).sum()) < 2:
-                    continue
-                kw = dict(ct=batch['image'], rna=batch['rnaseq'])
-                if style == "flexible":
-                    kw["mask"] = batch['mask'][:, :2]
-            meta[g] = batch
-            by_size.setdefault(int((kw["rna"] if "rna" in kw else kw["ct"]).shape[0]), []).append((g, kw))
+            kw = _model_inputs(row, batch)
+            if kw is not None:
+                by_size.setdefault(_batch_size(kw), []).append((g, kw, batch))
         for items in by_size.values():
-            outs = group.forward_eval([kw for _, kw in items], members=tuple(g for g, _ in items))
-            for (g, _), (hz, _gate) in zip(items, outs):
-                batch, a = meta[g], acc[g]
-                if style in ("final", "image"):
-                    label = _t(batch['label'], device)
-                    h, t, e = hz.clone(), label[:, 0], label[:, 1]
-                    a["total"] += losses.cox_loss(h, e, t).item(); a["nb"] += 1
-                elif style in ("partial", "simmlm"):
-                    label = _t(batch['label'], device)
-                    smask = (torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device) if style == "partial"
-                             else _simmlm_rows(batch, device))
-                    if int(smask.sum()) == 0:
-                        continue
-                    h, t, e = hz[smask].clone(), label[smask, 0], label[smask, 1]
-                    if not (h.shape[0] >= 2 and float(e.sum()) > 0):
-                        continue
-                    a["total"] += losses.cox_loss(h, e, t).item(); a["nb"] += 1
-                elif style == "rnaseq":
-                    t, e = _t(batch['time'].reshape(-1), device), _t(batch['event'].reshape(-1), device).float()
-                    h = hz.clone()
-                    a["total"] += losses.neg_partial_log_likelihood(h, e, t).item(); a["nb"] += 1
-                else:
-                    smask = torch.as_tensor(batch['has_survival'], dtype=torch.bool, device=device)
-                    time, event = _t(batch['time'].reshape(-1), device), _t(batch['event'].reshape(-1), device)
-                    h, t, e = hz[smask].clone(), time[smask], event[smask].float()
-                    if float(e.sum()) == 0:
-                        continue
-                    a["total"] += losses.neg_partial_log_likelihood(h, e, t).item(); a["nb"] += 1
-                a["hs"].append(h); a["ts"].append(t); a["es"].append(e)
-    out = []
+            outs = group.forward_eval([kw for _, kw, _ in items], members=tuple(g for g, _, _ in items))
+            for (g, _, batch), (hz, _gate) in zip(items, outs):
+                scored[g].append(_score_batch(row, batch, hz, device))
     for g in members:
         group.engines[g].check_b4()
-    for g in members:
-        a = acc[g]
-        if not a["hs"]:
-            out.append((0.0 if style in ("simple", "flexible", "rnaseq") else 0, 0.5))
-            continue
-        H, E, T = torch.cat(a["hs"]), torch.cat(a["es"]), torch.cat(a["ts"])
-        c = (losses.ConcordanceIndex()(H, E, T).item() if style in ("simple", "flexible", "rnaseq")
-             else losses.calculate_cindex(H, E, T))
-        out.append((a["total"] / a["nb"] if a["nb"] > 0 else 0, c))
-    return out
+    return [_val_result(row, scored[g]) for g in members]

@@ -90,10 +90,10 @@ def cv_lockstep(style, models, loaders, group_kw, num_epochs, patience, make_sch
     import inspect
     import time
     from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
-    from multimodal_survival_prediction_amd.training import FusedOptimizer, train_epoch_lockstep, validate_lockstep
+    from multimodal_survival_prediction_amd.training import FusedOptimizer, has_named_validation, train_epoch_lockstep, validate_lockstep
     group = FoldGroupEngine(models, **group_kw)
     for tl, vl in loaders:                     # cohort in HBM (or pinned host memory): name the batches, let the group gather them
-        for ld in ((tl, vl) if style in ("final", "partial", "simple") else (tl,)):      # (validate_lockstep's named-batch path: final / partial / simple)
+        for ld in ((tl, vl) if has_named_validation(style) else (tl,)):      # (validate_lockstep's named-batch path)
             if env_int("MMS_LAZY_BATCHES", 1) and (ld.c["image"].is_cuda or ld.c["image"].is_pinned()):
                 ld.lazy = True
                 ld.view = data_mod().gather_view(ld.c, with_valid=(style != "final"))

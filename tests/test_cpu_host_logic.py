@@ -224,7 +224,9 @@ def test_lockstep_iteration_and_batch_rules():
     assert set(T._train_kwargs("rnaseq", b)) == {"rna", "time", "event"}
     b["has_survival"] = [True, False, False]
     assert T._train_kwargs("simple", b) is None and T._train_kwargs("flexible", b) is None     # < 2 labelled: skipped before the forward
-    assert T._SKIP_UNUSABLE == {"final": True, "partial": False, "simple": True, "flexible": True, "rnaseq": False}
+    assert {s: row.skip_if_unusable for s, row in T._STYLES.items()} == {
+        "final": True, "partial": False, "simmlm": True, "image": True, "simple": True, "flexible": True, "rnaseq": False}
+    assert {s for s in T._STYLES if T.has_named_validation(s)} == {"final", "partial", "simple"}
 
 
 def test_subgroup_sizes_rule(monkeypatch):
