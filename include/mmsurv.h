@@ -622,6 +622,39 @@ typedef struct AugP {
                                     // and treats a shift of magnitude >= the extent as exactly the extent (everything is air)
 } AugP;
 
+/* Batch assembly with RESAMPLING augmentation (mms_gather_affine_group): the gather above with, per batch row, the AugRec AND a
+ * second record that carries an affine source-coordinate map and additive noise.  Contract, for the
+ * MMS_AUG_VOLUME source of a row that is neither absent nor dropped, destination voxel (z, y, x), i = (z*H + y)*W + x:
+ *   source coordinate (voxel-index units, fp32, this fmaf chain and no other):
+ *              cz = fmaf(m[0], z, fmaf(m[1], y, fmaf(m[2], x, m[3]))), cy likewise from m[4..7], cx from m[8..11]
+ *   v        = trilinear sample of src at (cz, cy, cx): cell = floorf(c), weight of the upper corner = c - floorf(c) per axis; any of the
+ *              eight corners outside [0,D) x [0,H) x [0,W) contributes 0 (air) -- the zero padding of
+ *              grid_sample(padding_mode="zeros", align_corners=True), continuous in the coordinate.  A NaN coordinate is air.
+ *   out      = fmaf(sigma, g(seed, i), fmaf(scale, v, offset)),  scale / offset from the row's AugRec; sigma == 0: no noise term
+ *   g(seed,i): h0 = mix(seed, 2i), h1 = mix(seed, 2i + 1) with mix(s, k) = hash(k * 0x9E3779B9 + hash(s)) in uint32 arithmetic and
+ *              hash(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  (the mixer of the dropout masks);
+ *              S = the sum of the eight bytes of h0 and h1 (0..2040); g = (float)(S - 1020) * 0x1.39897ep-8f  (= fp32 of 1/sqrt(43690)).
+ *              The sum of eight uniform bytes has mean 1020 and variance 8 (256^2 - 1) / 12 = 43690: g has zero mean and unit variance,
+ *              is bell-shaped and bounded by 4.88 -- an Irwin-Hall approximation of a Gaussian, reproducible bit for bit on a CPU and
+ *              independent of the launch geometry.
+ * AugRec.flip / dz / dy / dx are NOT read here: the host folds them into m (augment.affine_records).  drop, absent rows and every
+ * source that is not the volume behave exactly as in mms_gather_aug_group (zero-filled rows get neither offset nor noise).  A record
+ * with m = identity, sigma == 0, scale == 1, offset == 0 takes the copy path: the bits of mms_gather_rows_group.
+ * The kernel is memory-safe for ANY m (NaN, Inf, huge: air): coordinates are clamped to [-2, extent + 1] before they become indices,
+ * which changes no sample, and every corner index is bounds-checked. */
+typedef struct AffRec {
+    float m[12];                    // row-major 3x4: (cz, cy, cx) = m * (z, y, x, 1)
+    float sigma;                    // noise amplitude, >= 0
+    unsigned seed;                  // of this row's noise
+    int reserved[2];                // 0 (keeps a record at 64 bytes)
+} AffRec;
+typedef struct AffP {
+    const AffRec* rec;              // [B] records of this member's batch rows (device)
+    int stage_floats;               // LDS staging budget of a destination tile's source box, in floats; 0: the library default (8192 = 32 KB
+                                    // of the CU's 160 KB); larger values are capped there; a box that does not fit is sampled with bounds-checked
+                                    // global loads instead (direct form: a small value forces it everywhere -- tests, A/B timing)
+} AffP;
+
 /* ---- ABI self-description ---- */
 int mms_abi_sizeof(const char* name);      /* sizeof(struct <name>) as compiled, -1 if unknown */
 int mms_abi_version(void);
@@ -808,6 +841,7 @@ int mms_missing_mix_fwd_group(const MixP* p, int ng, hipStream_t s);
 int mms_missing_mix_bwd_group(const MixP* p, int ng, hipStream_t s);
 int mms_gather_rows_group(const GatherP* p, int ng, hipStream_t s);
 int mms_gather_aug_group(const GatherP* p, const AugP* a, int ng, hipStream_t s);   /* gather + per-row augmentation records */
+int mms_gather_affine_group(const GatherP* p, const AugP* a, const AffP* f, int ng, hipStream_t s);   /* ... + affine resampling and noise records */
 int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s);  /* scratch[g]: model g's [nlayers][27][32][128] tap-major scratch; dw[g][i]: canonical gradient of layer i; nlayers <= 58 */
 int mms_zero_regions_group(void* const* regions_dev, int ng, size_t bytes, hipStream_t s);   /* 16-B aligned regions of equal size, zero-filled by one launch */
 int mms_linear_fwd_group(const LinearFwdP* p, int ng, hipStream_t s);

@@ -9,21 +9,41 @@ one parameter record
 and the gather launch that copies the row applies it:  CT voxel  out[z,y,x] = scale * v + offset  with  v = src[sz,sy,sx]  inside the
 volume and 0 (air after min-max normalisation) outside,  sz = (flip & 1 ? D-1-z : z) - dz  and likewise H (bit 1, dy) / W (bit 2, dx);
 drop bit j hides modality j (image / rnaseq / clinical) exactly as if the patient lacked it: its row is zero-filled and column j of
-the mask the model sees becomes 0.  Rows of a modality the patient lacks stay all-zero.  Gaussian noise and elastic / rotation
-transforms are left out on purpose: they need a device RNG whose stream a CPU reference cannot reproduce bit for bit.
+the mask the model sees becomes 0.  Rows of a modality the patient lacks stay all-zero.
+
+Rotation / zoom and additive noise (spec keys rot, zoom, noise; mms_gather_affine_group, include/mmsurv.h: AffRec / AffP) ride a SECOND
+record of 16 words per row
+
+    [m (3 x 4 fp32, row-major), sigma, seed, 0, 0]
+
+and the same single launch resamples the volume: source coordinate (cz, cy, cx) = m (z, y, x, 1) in voxel-index units, trilinear
+sample with zero padding (air), then  out = sigma * g(seed, voxel) + scale * v + offset.  The host composes m in float64 and rounds it
+to fp32 (affine_records): the flip / shift of the 8-word record FIRST (q = flip(p) - shift, today's integer map), then
+p_src = c + A (q - c) about the volume's centre c = ((D-1)/2, (H-1)/2, (W-1)/2) with A = (1/zoom) R^-1 and
+R = R_D(a0) R_H(a1) R_W(a2) (R_D turns the (H, W) plane about the D axis, R_H the (W, D) plane, R_W the (D, H) plane, each
+counter-clockwise for a positive angle); the 8-word records handed on have flip and shift zeroed.  The rotation acts in VOXEL-INDEX
+space: the cohort tensors do not carry the voxel spacing, so on anisotropic grids an angle is not a physical angle.  The noise g is a
+counter hash of (seed, voxel index) summed over eight bytes (an Irwin-Hall approximation of a unit Gaussian, |g| <= 4.88) that a CPU
+reproduces bit for bit; the interpolation has a derived tolerance instead of bit equality (tests/test_gpu_augment_affine.py).  Elastic
+deformation is left out: it needs a displacement field per row, not a record.
 
 AugmentSpec names the distribution, sample_records draws one epoch's records in ONE vectorised call from a generator of its own
-(turning augmentation on leaves the batch order of a seeded run unchanged), apply() runs the kernel over an already materialised batch.
+(turning augmentation on leaves the batch order of a seeded run unchanged; a spec with rot / zoom / noise makes a second call, after
+the first, so the first call's fields are the same with and without them), apply() runs the kernel over an already materialised batch.
 """
 import ctypes
 import dataclasses
+import math
 
+import numpy as np
 import torch
 
 from .training import styles_without_mask
 
 REC_WORDS = 8
 FLIP, DZ, DY, DX, SCALE, OFFSET, DROP = range(7)
+AFF_WORDS = 16                               # include/mmsurv.h: AffRec
+AFF_SIGMA, AFF_SEED = 12, 13                 # words 0..11: the 3 x 4 matrix
 MASKLESS_STYLES = styles_without_mask()      # (training's style table) their models take no modality mask: nothing can tell them a row is hidden
 ROLE_PLAIN, ROLE_VOLUME, ROLE_MASK = 0, 1, 2                     # include/mmsurv.h: MMS_AUG_*
 
@@ -57,13 +77,18 @@ def _triple(v, cast):
 class AugmentSpec:
     """Distribution of the per-row records.  flip_p: probability of reversing axis D / H / W; max_shift: the shift of an axis is
     uniform on the integers [-max_shift, max_shift]; scale_range / offset_range: uniform fp32 intensity map; modality_drop_p: each
-    modality the patient HAS is hidden with this probability (never the last one left); seed: of the sampler's own generator."""
+    modality the patient HAS is hidden with this probability (never the last one left); seed: of the sampler's own generator.
+    rot_max: the angle about axis D / H / W is uniform in +-rot_max degrees; zoom_range: isotropic zoom, uniform (above 1 enlarges the
+    anatomy); noise_range: sigma of the additive noise, uniform per row."""
     flip_p: tuple = (0.0, 0.0, 0.0)
     max_shift: tuple = (0, 0, 0)
     scale_range: tuple = (1.0, 1.0)
     offset_range: tuple = (0.0, 0.0)
     modality_drop_p: float = 0.0
     seed: int = 0
+    rot_max: tuple = (0.0, 0.0, 0.0)
+    zoom_range: tuple = (1.0, 1.0)
+    noise_range: tuple = (0.0, 0.0)
 
     def __post_init__(self):
         object.__setattr__(self, "flip_p", _triple(self.flip_p, float))
@@ -74,15 +99,29 @@ class AugmentSpec:
             raise ValueError("augment: probabilities must lie in [0, 1]")
         if any(s < 0 for s in self.max_shift):
             raise ValueError("augment: max_shift must be >= 0")
-        for name in ("scale_range", "offset_range"):
+        object.__setattr__(self, "rot_max", _triple(self.rot_max, float))
+        object.__setattr__(self, "zoom_range", tuple(float(x) for x in self.zoom_range))
+        object.__setattr__(self, "noise_range", tuple(float(x) for x in self.noise_range))
+        for name in ("scale_range", "offset_range", "zoom_range", "noise_range"):
             r = getattr(self, name)
-            if len(r) != 2 or r[0] > r[1]:
+            if len(r) != 2 or not r[0] <= r[1] or not all(math.isfinite(x) for x in r):
                 raise ValueError("augment: %s must be lo:hi with lo <= hi" % name)
+        if any(not (0.0 <= a and math.isfinite(a)) for a in self.rot_max):
+            raise ValueError("augment: rot takes maximum angles >= 0 (degrees)")
+        if self.zoom_range[0] <= 0:
+            raise ValueError("augment: zoom must be > 0")
+        if self.noise_range[0] < 0:
+            raise ValueError("augment: noise sigma must be >= 0")
+
+    @property
+    def has_affine(self):
+        """The spec asks for resampling or noise: its rows carry a second record and the launch is mms_gather_affine_group."""
+        return any(a > 0 for a in self.rot_max) or self.zoom_range != (1.0, 1.0) or self.noise_range != (0.0, 0.0)
 
     @classmethod
     def parse(cls, text):
-        """"flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=7" -- every key optional; flip and shift take one
-        value for all axes or D:H:W."""
+        """"flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=7,rot=10,zoom=0.9:1.1,noise=0:0.03" -- every key
+        optional; flip, shift and rot take one value for all axes or D:H:W."""
         kw, seen = {}, set()
         for item in str(text).split(","):
             item = item.strip()
@@ -99,7 +138,9 @@ class AugmentSpec:
                     kw["flip_p"] = _triple(val.split(":"), float)
                 elif key == "shift":
                     kw["max_shift"] = _triple(val.split(":"), int)
-                elif key in ("scale", "offset"):
+                elif key == "rot":
+                    kw["rot_max"] = _triple(val.split(":"), float)
+                elif key in ("scale", "offset", "zoom", "noise"):
                     lo, hi = val.split(":")
                     kw[key + "_range"] = (float(lo), float(hi))
                 elif key == "moddrop":
@@ -109,15 +150,18 @@ class AugmentSpec:
                 else:
                     raise KeyError(key)
             except KeyError:
-                raise ValueError("augment: unknown key %r (flip, shift, scale, offset, moddrop, seed)" % key) from None
+                raise ValueError("augment: unknown key %r (flip, shift, scale, offset, moddrop, seed, rot, zoom, noise)" % key) from None
             except ValueError:
                 raise ValueError("augment: cannot read %r" % item) from None
         return cls(**kw)
 
     def __str__(self):
         c = lambda v: ":".join(repr(x) for x in v)
-        return "flip=%s,shift=%s,scale=%s,offset=%s,moddrop=%r,seed=%d" % (c(self.flip_p), c(self.max_shift), c(self.scale_range),
-                                                                           c(self.offset_range), self.modality_drop_p, self.seed)
+        s = "flip=%s,shift=%s,scale=%s,offset=%s,moddrop=%r,seed=%d" % (c(self.flip_p), c(self.max_shift), c(self.scale_range),
+                                                                        c(self.offset_range), self.modality_drop_p, self.seed)
+        if self.has_affine:                  # (a spec without the new keys prints as it always did)
+            s += ",rot=%s,zoom=%s,noise=%s" % (c(self.rot_max), c(self.zoom_range), c(self.noise_range))
+        return s
 
     def validate(self, style=None, dims=None):
         """Refuse what cannot work: hiding modalities from a model that takes no mask, shifts that move the whole volume out."""
@@ -159,6 +203,85 @@ def sample_records(spec, gen, mask, dims, style=None):
     return make_records(n, flip, shift, scale, offset, bits)
 
 
+def sample_affine(spec, gen, recs, dims):
+    """The second draw of a spec that `has_affine`, made right after sample_records' on the same generator: recs [n, 8] (as drawn) ->
+    (the records to hand on, flip and shift zeroed: they now live in the matrix; [n, 16] int32 affine records).  One
+    torch.rand(n, 8) call: columns 0..2 angles, 3 zoom, 4 sigma, 5 and 6 the two 16-bit halves of the noise seed, 7 spare."""
+    n = recs.shape[0]
+    u = torch.rand(n, 8, generator=gen).double()
+    angles = (2.0 * u[:, 0:3] - 1.0) * torch.tensor(spec.rot_max, dtype=torch.float64)
+    zoom = spec.zoom_range[0] + (spec.zoom_range[1] - spec.zoom_range[0]) * u[:, 3]
+    sigma = spec.noise_range[0] + (spec.noise_range[1] - spec.noise_range[0]) * u[:, 4]
+    seed = (torch.floor(u[:, 5] * 65536.0).long() << 16) | torch.floor(u[:, 6] * 65536.0).long()
+    aff = affine_records(recs, angles, zoom, sigma, seed, dims)
+    out = recs.clone()
+    out[:, FLIP:DX + 1] = 0
+    return out, aff
+
+
+def sample(spec, gen, mask, dims, style=None):
+    """sample_records, then sample_affine when the spec asks for it -> (records [n, 8], affine records [n, 16] or None)."""
+    recs = sample_records(spec, gen, mask, dims, style)
+    return sample_affine(spec, gen, recs, dims) if spec.has_affine else (recs, None)
+
+
+def rotation(angles_deg):
+    """angles [n, 3] in degrees about D / H / W -> R [n, 3, 3] float64 = R_D(a0) R_H(a1) R_W(a2) in (z, y, x) coordinates.  R_D maps
+    (y, x) -> (y cos - x sin, y sin + x cos), R_H (x, z) likewise, R_W (z, y) likewise.  Entries below 1e-12 in magnitude are the
+    rounding residue of cos(90 degrees) and are set to 0: quarter turns are exact integer maps."""
+    a = np.deg2rad(np.asarray(angles_deg, dtype=np.float64).reshape(-1, 3))
+    c, s = np.cos(a), np.sin(a)
+    n = a.shape[0]
+    R = np.zeros((3, n, 3, 3))
+    for k, (i, j) in enumerate(((1, 2), (2, 0), (0, 1))):       # the plane (i, j) that axis k's rotation turns
+        R[k, :, k, k] = 1.0
+        R[k, :, i, i], R[k, :, i, j], R[k, :, j, i], R[k, :, j, j] = c[:, k], -s[:, k], s[:, k], c[:, k]
+    out = R[0] @ R[1] @ R[2]
+    out[np.abs(out) < 1e-12] = 0.0
+    return out
+
+
+def affine_records(recs, angles=0.0, zoom=1.0, sigma=0.0, seed=0, dims=None):
+    """Compose the source-coordinate map of every row -> [n, 16] int32 records (words 0..12 hold fp32 bit patterns; AffRec).
+    recs [n, 8]: their flip / shift are folded in (q = flip(p_dst) - shift, then p_src = c + A (q - c), A = (1/zoom) R(angles)^-1);
+    angles [n, 3] degrees, zoom / sigma / seed [n] or scalars; dims = (D, H, W).  float64 on the host, rounded once to fp32."""
+    recs = torch.as_tensor(recs).reshape(-1, REC_WORDS)
+    n = recs.shape[0]
+    dims = np.asarray(dims, dtype=np.float64)
+    vec = lambda v, w: np.broadcast_to(np.asarray(torch.as_tensor(v).double().numpy() if torch.is_tensor(v) else v, dtype=np.float64),
+                                       (n,) + w).copy()
+    angles, zoom, sigma = vec(angles, (3,)), vec(zoom, ()), vec(sigma, ())
+    seed = np.broadcast_to(np.asarray(torch.as_tensor(seed).numpy() if torch.is_tensor(seed) else seed, dtype=np.int64), (n,))
+    r = recs.numpy()
+    fl = np.stack([(r[:, FLIP] >> a) & 1 for a in range(3)], 1).astype(np.float64)
+    S = 1.0 - 2.0 * fl                                                       # q = S p + t
+    t = fl * (dims - 1.0) - r[:, DZ:DX + 1].astype(np.float64)
+    A = np.transpose(rotation(angles), (0, 2, 1)) / zoom[:, None, None]      # R^-1 = R^T
+    c = (dims - 1.0) / 2.0
+    M = A * S[:, None, :]
+    tr = c + np.einsum("nij,nj->ni", A, t - c)
+    out = np.zeros((n, AFF_WORDS), dtype=np.int32)
+    f = out.view(np.float32)
+    f[:, :12] = np.concatenate([M, tr[:, :, None]], 2).reshape(n, 12).astype(np.float32)
+    f[:, AFF_SIGMA] = sigma.astype(np.float32)
+    out[:, AFF_SEED] = (seed & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    return torch.from_numpy(out)
+
+
+def check_affine_records(aff, n=None):
+    """Host-side validation of affine records before they reach the kernel: shape, dtype, finite matrices, sigma >= 0."""
+    aff = torch.as_tensor(aff)
+    if aff.dtype != torch.int32 or aff.shape[-1] != AFF_WORDS or aff.is_cuda:
+        raise ValueError("affine records must be a host int32 array of %d words per row (augment.affine_records)" % AFF_WORDS)
+    if n is not None and aff.reshape(-1, AFF_WORDS).shape[0] != n:
+        raise ValueError("augment: one affine record per row, got %d for %d rows" % (aff.reshape(-1, AFF_WORDS).shape[0], n))
+    f = aff.reshape(-1, AFF_WORDS).view(torch.float32)
+    if not bool(torch.isfinite(f[:, :12]).all()):
+        raise ValueError("augment: an affine record's matrix is not finite")
+    if not bool((f[:, AFF_SIGMA] >= 0).all()) or not bool(torch.isfinite(f[:, AFF_SIGMA]).all()):
+        raise ValueError("augment: noise sigma must be finite and >= 0")
+
+
 def check_records(rec, dims=None, has_mask=True):
     """Host-side validation of a record array before it reaches the kernel -> per-axis max |shift|."""
     rec = torch.as_tensor(rec)
@@ -190,11 +313,20 @@ def aug_block(rec_dev, roles, dims, max_shift):
     return A
 
 
-def apply(batch, records, present_ok=(True, True)):
+def aff_block(aff_dev, stage_floats=0):
+    """AffP (include/mmsurv.h).  stage_floats: 0 = the library's LDS staging budget; a small value forces the direct form."""
+    from . import _lib
+    F = _lib.structs()["AffP"]()
+    F.rec, F.stage_floats = aff_dev.data_ptr(), int(stage_floats)
+    return F
+
+
+def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0):
     """The augmenting gather over an already materialised batch (device tensors image / rnaseq / clinical / mask as
     data.BatchLoader yields them), out of place, identity indices: -> the batch dict with those four replaced.  present_ok: per
     (image, rnaseq) whether rows whose mask column is 0 are known to be all-zero in the cohort (then they are not read, as in
-    SurvivalEngine.gather_block)."""
+    SurvivalEngine.gather_block).  affine: [B, 16] affine records (affine_records): the launch is then mms_gather_affine_group, which
+    ignores the records' flip / shift."""
     from . import _lib, ops
     img, rna, clin, mask = batch["image"], batch["rnaseq"], batch["clinical"], batch["mask"]
     B, dims = img.shape[0], tuple(img.shape[-3:])
@@ -202,6 +334,9 @@ def apply(batch, records, present_ok=(True, True)):
     if rec.shape != (B, REC_WORDS):
         raise ValueError("augment.apply: one record per batch row, got %r for %d rows" % (tuple(rec.shape), B))
     mx = check_records(rec, dims)
+    if affine is not None:
+        affine = torch.as_tensor(affine)
+        check_affine_records(affine, B)
     S = _lib.structs()
     dev = img.device
     mask = mask.contiguous()
@@ -223,7 +358,13 @@ def apply(batch, records, present_ok=(True, True)):
             G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
         roles.append((role, bit))
     A = aug_block(rec_dev, roles, dims, mx)
-    _lib.check(_lib.load_library().mms_gather_aug_group(ctypes.byref(G), ctypes.byref(A), 1, ops.stream()), "mms_gather_aug_group")
+    if affine is not None:
+        aff_dev = affine.reshape(B, AFF_WORDS).to(dev)
+        F = aff_block(aff_dev, stage_floats)
+        _lib.check(_lib.load_library().mms_gather_affine_group(ctypes.byref(G), ctypes.byref(A), ctypes.byref(F), 1, ops.stream()),
+                   "mms_gather_affine_group")
+    else:
+        _lib.check(_lib.load_library().mms_gather_aug_group(ctypes.byref(G), ctypes.byref(A), 1, ops.stream()), "mms_gather_aug_group")
     out = dict(batch)
     out["image"], out["rnaseq"], out["clinical"], out["mask"] = (outs[0].view(img.shape), outs[1], outs[2].view(clin.shape), outs[3])
     return out

@@ -7,6 +7,7 @@
 // statistics, their backward and the per-row dropout are lane-local (no atomics, no extra launches); weights
 // are streamed once with coalesced loads (these layers are HBM/L2-bound: 2.7 M parameters, 4 rows).
 #include "common.h"
+#include "gather_rows.h"
 
 // ------------------------------------------------------------------------------------------------------
 // input prologue  x' = dropout(relu(bn1d(x)))  on the M values of one column, lane-local
@@ -941,26 +942,6 @@ extern "C" int mms_gather_rows_group(const GatherP* pp, int ng, hipStream_t s) {
 // flip / shift and the intensity map are applied on the LDS read, destination lines leave as 16-byte stores.
 // ------------------------------------------------------------------------------------------------------
 #define AUG_TILE4 1024                       // float4 slots of the LDS staging tile (16 KB): 4 loads in flight per thread
-struct AugK { const AugRec* rec; unsigned meta; unsigned pad; };        // meta: 4 bits per source = role | (drop_bit + 1) << 2
-struct AugGrp { AugK k[MMS_MAX_GROUP]; int D, H, W; };
-
-// the copy of gather_rows_kernel for one row (zero: the row is absent or dropped -- zero-filled without being read)
-__device__ __forceinline__ void gather_copy_row(const float* __restrict__ src, float* __restrict__ dst, int w, bool zero, int t0, int stride) {
-    if ((w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-        if (zero) { for (int i = t0; i < (w >> 2); i += stride) ((float4*)dst)[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
-        else {
-            int i = t0;
-            for (; i + 3 * stride < (w >> 2); i += 4 * stride) {        // four 16-B loads in flight per thread (host-resident rows: PCIe latency)
-                const float4 a = ((const float4*)src)[i], b = ((const float4*)src)[i + stride], c = ((const float4*)src)[i + 2 * stride],
-                             d = ((const float4*)src)[i + 3 * stride];
-                ((float4*)dst)[i] = a; ((float4*)dst)[i + stride] = b; ((float4*)dst)[i + 2 * stride] = c; ((float4*)dst)[i + 3 * stride] = d;
-            }
-            for (; i < (w >> 2); i += stride) ((float4*)dst)[i] = ((const float4*)src)[i];
-        }
-    } else {
-        for (int i = t0; i < w; i += stride) dst[i] = zero ? 0.f : src[i];
-    }
-}
 
 __global__ __launch_bounds__(256) void gather_aug_kernel(const Grp<GatherP> grp, const AugGrp ag) {
     __shared__ float4 tile[AUG_TILE4];
@@ -974,18 +955,10 @@ __global__ __launch_bounds__(256) void gather_aug_kernel(const Grp<GatherP> grp,
     const bool ident_i = r.scale == 1.f && r.offset == 0.f;
     const bool ident = ident_i && (r.flip & 7) == 0 && r.dz == 0 && r.dy == 0 && r.dx == 0;
     for (int s = 0; s < p.nsrc; ++s) {
-        const float* src = p.src[s] + (size_t)row * p.src_ld[s];
-        float* dst = p.dst[s] + (size_t)b * p.dst_ld[s];
+        const float* src;
+        float* dst;
+        if (gather_plain_source(p, k.meta, r.drop, s, row, b, ident, t0, stride, src, dst)) continue;
         const int w = p.width[s];
-        const unsigned m = (k.meta >> (4 * s)) & 15u;
-        const int role = (int)(m & 3u), dbit = (int)(m >> 2) - 1;
-        if (role == MMS_AUG_MASK) {                         // column j of a mask destination: 0 when modality j is dropped
-            for (int i = t0; i < w; i += stride) dst[i] = ((r.drop >> i) & 1) ? 0.f : src[i];
-            continue;
-        }
-        const bool absent = p.present[s] && p.present[s][(size_t)row * p.present_ld[s]] == 0.f;     // all-zero row by contract: not read
-        const bool zero = absent || (dbit >= 0 && ((r.drop >> dbit) & 1));
-        if (role != MMS_AUG_VOLUME || zero || ident) { gather_copy_row(src, dst, w, zero, t0, stride); continue; }
         const int D = ag.D, H = ag.H, W = ag.W;
         // a shift of magnitude >= the extent moves everything out, whatever its value: clamped, so that no record can overflow the index arithmetic
         const int dz = max(-D, min(D, r.dz)), dy = max(-H, min(H, r.dy)), dx = max(-W, min(W, r.dx));
@@ -1042,33 +1015,8 @@ extern "C" int mms_gather_aug_group(const GatherP* pp, const AugP* aa, int ng, h
     Grp<GatherP> a;
     if (!grp_fill(a, pp, ng, 1) || !aa) return MMS_ERR_ARG;
     AugGrp ag = {};
-    int wmax = 0;
-    for (int g = 0; g < ng; ++g) {
-        const GatherP& q = pp[g];
-        const AugP& u = aa[g];
-        if (q.B != pp->B || q.B <= 0 || !q.idx || q.nsrc < 1 || q.nsrc > 8 || !u.rec) return MMS_ERR_ARG;
-        int nvol = 0;
-        unsigned meta = 0;
-        for (int i = 0; i < q.nsrc; ++i) {
-            if (!q.src[i] || !q.dst[i] || q.width[i] <= 0) return MMS_ERR_ARG;
-            if (u.role[i] < MMS_AUG_PLAIN || u.role[i] > MMS_AUG_MASK || u.drop_bit[i] < -1 || u.drop_bit[i] > 2) return MMS_ERR_ARG;
-            if (u.role[i] == MMS_AUG_MASK && q.width[i] > 3) return MMS_ERR_ARG;
-            if (u.role[i] == MMS_AUG_VOLUME) {
-                if (++nvol > 1 || u.D <= 0 || u.H <= 0 || u.W <= 0 || (long long)u.D * u.H * u.W != (long long)q.width[i]) return MMS_ERR_ARG;
-                if (u.max_shift[0] < 0 || u.max_shift[0] >= u.D || u.max_shift[1] < 0 || u.max_shift[1] >= u.H || u.max_shift[2] < 0 ||
-                    u.max_shift[2] >= u.W)
-                    return MMS_ERR_ARG;
-                if (ag.D && (ag.D != u.D || ag.H != u.H || ag.W != u.W)) return MMS_ERR_ARG;      // one volume shape per group
-                ag.D = u.D; ag.H = u.H; ag.W = u.W;
-            }
-            meta |= ((unsigned)u.role[i] | (unsigned)(u.drop_bit[i] + 1) << 2) << (4 * i);
-            if (q.width[i] > wmax) wmax = q.width[i];
-        }
-        ag.k[g].rec = u.rec; ag.k[g].meta = meta; ag.k[g].pad = 0;
-    }
-    int blocks = (wmax / 4 + 1023) / 1024;       // ~4 float4 per thread on the widest source (one LDS tile of a volume per workgroup)
-    if (blocks < 1) blocks = 1;
-    if (blocks > 64) blocks = 64;
+    int blocks = 0;
+    if (!gather_aug_args(pp, aa, ng, ag, blocks)) return MMS_ERR_ARG;
     MMS_LAUNCH(gather_aug_kernel, dim3(blocks, pp->B, ng), dim3(256), 0, s, a, ag);
     return mms_check_launch();
 }

@@ -99,7 +99,8 @@ class BatchLoader:
     per row from a generator of the loader's own -- the shuffle generator, hence the batch order, is the same with and without it.
     A lazy loader adds augment=<records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them inside its
     gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both yield the
-    same augmented batches.  augment_style: the model style ("partial", "final", ...) the spec is checked against."""
+    same augmented batches.  A spec with rot / zoom / noise (AugmentSpec.has_affine) draws a second, 16-word record per row: a lazy loader
+    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  augment_style: the model style ("partial", "final", ...) the spec is checked against."""
 
     def __init__(self, cohort, indices, batch_size, shuffle=False, seed=0, style="final", lazy=False, with_valid=True, augment=None,
                  augment_style=None):
@@ -143,16 +144,18 @@ class BatchLoader:
     def __iter__(self):
         idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
         dev = self.c["image"].device
-        recs = None
-        if self.augment is not None:         # one vectorised draw per epoch
-            recs = _augment.sample_records(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
-                                           self.augment_style)
+        recs = aff = None
+        if self.augment is not None:         # one vectorised draw per epoch (a second one for rot / zoom / noise)
+            recs, aff = _augment.sample(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
+                                        self.augment_style)
         for i in range(0, len(idx), self.bs):
             if self.lazy:
                 jj = idx[i:i + self.bs]
                 b = dict(index=jj, has_survival=[self.hs_cpu[int(k)] for k in jj], gather=self.view)
                 if recs is not None:
                     b["augment"] = recs[i:i + self.bs]
+                if aff is not None:
+                    b["augment_affine"] = aff[i:i + self.bs]
                 yield b
                 continue
             j = idx[i:i + self.bs].to(dev)
@@ -162,7 +165,7 @@ class BatchLoader:
                 b["time"] = self.c["label"][j, 0:1]
                 b["event"] = self.c["label"][j, 1:2].long()
             if recs is not None:
-                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok())
+                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok(), affine=None if aff is None else aff[i:i + self.bs])
             yield b
 
 

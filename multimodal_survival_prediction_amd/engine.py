@@ -789,14 +789,16 @@ class SurvivalEngine:
         G, _ = self._gather_sources(P, cohort, idx_dev)
         return G
 
-    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev):
+    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev, aff_dev=None):
         """(GatherP, AugP) of mms_gather_aug_group: gather_block's sources plus what each of them is to the augmentation records
         rec_dev ([B, 8] int32 device tensor, augment.make_records) -- the CT volume, a row that modality j's drop bit zero-fills,
-        a mask whose column j that bit clears.  time / event / valid are plain copies."""
+        a mask whose column j that bit clears.  time / event / valid are plain copies.  aff_dev ([B, 16] int32 device tensor,
+        augment.affine_records): -> (GatherP, AugP, AffP), the blocks of mms_gather_affine_group."""
         from . import augment
         G, roles = self._gather_sources(P, cohort, idx_dev)
         dims = tuple(P.ct.shape[-3:]) if P.has_enc else None
-        return G, augment.aug_block(rec_dev, roles, dims, (0, 0, 0))
+        A = augment.aug_block(rec_dev, roles, dims, (0, 0, 0))
+        return (G, A) if aff_dev is None else (G, A, augment.aff_block(aff_dev))
 
     def _gather_sources(self, P, cohort, idx_dev):
         """-> (GatherP, per source (augment role, drop bit)).  A source is (cohort tensor, destination, width or None = all columns,

@@ -299,10 +299,11 @@ class FoldGroupEngine:
             return
         self._graph(GP, ("train", bool(skip_if_unusable)), lambda: self._train_body(GP, skip_if_unusable)).replay()
 
-    def _gather_indexed(self, GP, cohort, idx, augment=None):
+    def _gather_indexed(self, GP, cohort, idx, augment=None, affine=None):
         """Index copy (pinned ring -> device) + the ONE gather launch that assembles the group's batches in the plans' input buffers.
         augment: [len(members)][B] records (augment.make_records) -- they ride the same pinned ring as the indices and the launch
-        is mms_gather_aug_group; None: today's path."""
+        is mms_gather_aug_group; affine: [len(members)][B] affine records (augment.affine_records) beside them -- the launch is
+        mms_gather_affine_group; None: today's path."""
         members, B = GP.members, GP.B
         key = id(cohort)
         cache = GP.__dict__.setdefault("gather", {})
@@ -318,8 +319,10 @@ class FoldGroupEngine:
                     P.valid.fill_(1.0)
             cache[key] = (dev_idx, pin, blocks, cohort)       # the cohort reference keeps the source pointers alive
         dev_idx, pin, blocks, _ = cache[key]
+        if affine is not None and augment is None:
+            raise ValueError("affine records come with the 8-word records of the same rows (augment=)")
         if augment is not None:          # (validated before the ring is touched: a refused step leaves no copy without its event)
-            aug = self._aug_blocks(GP, cohort, dev_idx, pin, augment)
+            aug = self._aug_blocks(GP, cohort, dev_idx, pin, augment, affine)
         k = pin["k"]
         pin["k"] = (k + 1) % len(pin["bufs"])
         if pin["evs"][k] is not None:
@@ -329,23 +332,36 @@ class FoldGroupEngine:
         if augment is not None:
             aug["pin"][k].copy_(augment)               # (slot k's event above covers this buffer too)
             aug["dev"].copy_(aug["pin"][k], non_blocking=True)
+        if affine is not None:
+            aug["aff_pin"][k].copy_(affine)
+            aug["aff_dev"].copy_(aug["aff_pin"][k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         pin["evs"][k] = ev
+        if affine is not None:
+            _lib.check(self.lib.mms_gather_affine_group(aug["gather"], aug["aug"], aug["aff"], GP.ng, ops.stream()), "mms_gather_affine_group")
+            return
         if augment is not None:
             _lib.check(self.lib.mms_gather_aug_group(aug["gather"], aug["aug"], GP.ng, ops.stream()), "mms_gather_aug_group")
             return
         _lib.check(self.lib.mms_gather_rows_group(blocks, GP.ng, ops.stream()), "mms_gather_rows_group")
 
-    def _aug_blocks(self, GP, cohort, dev_idx, pin, augment):
-        """Per (plan, cohort): device + pinned record buffers and the (GatherP, AugP) arrays of mms_gather_aug_group; validates the
-        step's records on the host (they are host data) so that the launch cannot be refused with a bare code."""
+    def _aug_blocks(self, GP, cohort, dev_idx, pin, augment, affine=None):
+        """Per (plan, cohort): device + pinned record buffers and the (GatherP, AugP) arrays of mms_gather_aug_group -- with affine
+        records also theirs and the AffP array of mms_gather_affine_group; validates the step's records on the host (they are host
+        data) so that the launch cannot be refused with a bare code."""
         from . import augment as A
         has_mask = all(P.gate is not None or P.moe is not None or P.mix is not None for P in GP.Ps)
         if tuple(augment.shape) != (len(GP.members), GP.B, A.REC_WORDS):
             raise ValueError("augment must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
                              % (A.REC_WORDS, tuple(augment.shape), len(GP.members), GP.B))
         mx = A.check_records(augment, GP.dims if GP.has_enc else None, has_mask)
+        if affine is not None:
+            if tuple(affine.shape) != (len(GP.members), GP.B, A.AFF_WORDS):
+                raise ValueError("augment_affine must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
+                                 % (A.AFF_WORDS, tuple(affine.shape), len(GP.members), GP.B))
+            A.check_affine_records(affine)
+            mx = [0, 0, 0]               # (mms_gather_affine_group does not read the records' shifts)
         cache = GP.__dict__.setdefault("gather_aug", {})
         key = id(cohort)
         if key not in cache:
@@ -354,18 +370,24 @@ class FoldGroupEngine:
             cache[key] = dict(dev=dev, pin=[torch.zeros(dev.shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]],
                               gather=_arr([g for g, _ in pairs]), aug=_arr([a for _, a in pairs]))
         aug = cache[key]
+        if affine is not None and "aff" not in aug:
+            aug["aff_dev"] = torch.zeros(len(GP.members), GP.B, A.AFF_WORDS, dtype=torch.int32, device=self.device)
+            aug["aff_pin"] = [torch.zeros(aug["aff_dev"].shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]]
+            aug["aff"] = _arr([A.aff_block(aug["aff_dev"][g]) for g in range(GP.ng)])
         for g in range(GP.ng):
             for a in range(3):
                 aug["aug"][g].max_shift[a] = mx[a]
         return aug
 
-    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None):
+    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None, augment_affine=None):
         """Same step with the batches named by patient indices into a cohort that lives in HBM (data.cohort_to) or in pinned host
         memory (data.cohort_pin: the gather launch reads the rows over PCIe): indices: [len(members)][B] integer array-like (host).  The batch assembly of the whole group is one small
         host-to-device copy of the indices plus ONE gather launch (mms_gather_rows_group) instead of ~10 torch
         indexing/copy kernels per member.  augment: [len(members)][B] augmentation records (augment.make_records /
         augment.sample_records, host int32): the gather launch applies them while it copies (mms_gather_aug_group: CT flips, shifts
-        and intensity map, modality dropout); None: no augmentation, the plain gather."""
+        and intensity map, modality dropout); None: no augmentation, the plain gather.  augment_affine: [len(members)][B] affine records
+        (augment.affine_records / augment.sample) of the same rows: the launch is mms_gather_affine_group (rotation / zoom resampling,
+        additive noise; the flip / shift fields of `augment` are not read, they are folded into the matrices)."""
         members = tuple(range(len(self.engines))) if members is None else tuple(members)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if idx.dim() != 2 or idx.shape[0] != len(members):
@@ -374,7 +396,8 @@ class FoldGroupEngine:
         dims = tuple(cohort["image"].shape[-3:]) if self.engines[0].prog["encoder"] is not None else None
         self.engines[0].check_train_batch(B, dims)
         GP = self.plan(B, dims, members)
-        self._gather_indexed(GP, cohort, idx, None if augment is None else torch.as_tensor(augment))
+        self._gather_indexed(GP, cohort, idx, None if augment is None else torch.as_tensor(augment),
+                             None if augment_affine is None else torch.as_tensor(augment_affine))
         self._sync_packs(GP)
         if not use_graph:
             self._train_body(GP, skip_if_unusable)

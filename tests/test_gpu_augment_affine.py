@@ -1,0 +1,475 @@
+"""GPU: mms_gather_affine_group (rotation / zoom resampling and additive noise inside the batch gather) against
+tests/augment_affine_ref.py, the float64 restatement of the contract:
+  1. the kernel through the C ABI: identity records == mms_gather_rows_group; integer matrices (flips, shifts, quarter turns: weights
+     exactly 0 or 1) == tests/augment_ref.aug_volume bit for bit; generic records within a bound derived per record; the noise bit
+     for bit; NaN / Inf / huge matrices give air; bad arguments are refused.  Shapes (6, 12, 12) (16-byte path) and (5, 7, 9)
+     (scalar path), B = 4, ng = 2 with different records per member, device and pinned-host cohorts, rows without a CT and dropped
+     rows, and every geometric case in the staged form (stage_floats = 0) and the direct form (stage_floats = 16);
+  2. the step, the loaders, validation and one entry point.
+
+The bound of the generic records (not tuned; if the GPU exceeds it that is a finding).  E = 2^-24 (half an fp32 ulp of 1).
+  Coordinates: the kernel evaluates c = fmaf(m0, z, fmaf(m1, y, fmaf(m2, x, m3))) in fp32, the reference the same fp32 matrix in
+  float64.  Each of the three fmaf rounds once, by at most E times its result's magnitude (E is fp32's unit roundoff); every partial
+  result is at most  S = |m0| D + |m1| H + |m2| W + |m3|  in magnitude (plus earlier roundings), so the three roundings stay below
+  3 E S (1 + E)^2 < 4 E S; the clamp to [-2, extent + 1] moves no coordinate that has a corner in the volume:
+      delta_axis <= 4 E (|m0| D + |m1| H + |m2| W + |m3|).
+  Value: the zero-padded trilinear interpolant is continuous and piecewise linear along every axis with slope at most L, the largest
+  absolute difference of axis-neighbouring voxels of the zero-padded volume, so coordinate errors move v by at most
+  L (delta_z + delta_y + delta_x).  In the kernel's own arithmetic a weight c - floor(c) is exact or rounded once (E); each of the
+  three lerp levels fmaf(w, b - a, a) rounds twice on values of at most max|v| (the volumes are non-negative) and sees that weight
+  error: at most 3 E max|v| per level, 9 E max|v| together, times |scale|; the intensity fmaf rounds once on at most
+  |scale| max|v| + |offset|, the noise fmaf once more on that plus |sigma g| <= 4.88 sigma: together below
+      16 E (|scale| max|v| + |offset| + 5 sigma).
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import augment_affine_ref as R
+from augment_ref import aug_batch, aug_volume
+from gpu_util import DEV, GROUP_INDEPENDENT_OPTS as GI, rel_err
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E = 2.0 ** -24
+VEC, SCALAR = (6, 12, 12), (5, 7, 9)
+B, NG = 4, 2
+
+
+# ---- 1. the kernel through the C ABI ------------------------------------------------------------------------------------------------
+def _cohort(dims):
+    from multimodal_survival_prediction_amd import data
+    cpu = data.make_cohort(n=24, dims=dims, rna_dim=8 if dims[2] % 4 == 0 else 5, seed=3, complete=False)
+    cpu["valid"] = cpu["has_survival"].float()
+    return cpu
+
+
+@pytest.fixture(scope="module")
+def cohorts():
+    return {VEC: _cohort(VEC), SCALAR: _cohort(SCALAR)}
+
+
+def _placed(cpu, where):
+    from multimodal_survival_prediction_amd import data
+    return data.cohort_to(cpu, DEV) if where == "device" else data.cohort_pin(cpu)
+
+
+def _launch(cohort, idx, recs=None, aff=None, stage=0, edit=None):
+    """mms_gather_affine_group (recs, aff given) or mms_gather_rows_group over idx [ng][B] -> (rc, per member dict of destination
+    tensors; NaN where nothing was written).  stage: stage_floats of every member, or one value per member."""
+    from multimodal_survival_prediction_amd import _lib, augment as A, ops
+    lib, S = _lib.load_library(), _lib.structs()
+    ng, nb = idx.shape
+    dims = tuple(cohort["image"].shape[-3:])
+    vol = int(np.prod(dims))
+    idx_dev = torch.as_tensor(idx, dtype=torch.int64).to(DEV)
+    lab, mask = cohort["label"], cohort["mask"]
+    srcs = [("image", cohort["image"].view(-1, vol), vol, mask, (A.ROLE_VOLUME, 0)),
+            ("rnaseq", cohort["rnaseq"], cohort["rnaseq"].shape[1], mask[:, 1:], (A.ROLE_PLAIN, 1)),
+            ("clinical", cohort["clinical"], 1, None, (A.ROLE_PLAIN, 2)),
+            ("mask", mask, 3, None, (A.ROLE_MASK, -1)), ("time", lab, 1, None, (A.ROLE_PLAIN, -1)),
+            ("valid", cohort["valid"].view(-1, 1), 1, None, (A.ROLE_PLAIN, -1))]
+    outs, Gs = [], []
+    for g in range(ng):
+        o = {k: torch.full((nb, w), float("nan"), device=DEV) for k, _, w, _, _ in srcs}
+        G = S["GatherP"]()
+        G.idx, G.B, G.nsrc = idx_dev[g].data_ptr(), nb, len(srcs)
+        for i, (k, a, w, flag, _) in enumerate(srcs):
+            G.src[i], G.dst[i], G.src_ld[i], G.dst_ld[i], G.width[i] = a.data_ptr(), o[k].data_ptr(), a.stride(0), w, w
+            if flag is not None:
+                G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
+        outs.append(o); Gs.append(G)
+    Ga = (S["GatherP"] * ng)(*Gs)
+    if recs is None:
+        rc = lib.mms_gather_rows_group(Ga, ng, ops.stream())
+    else:
+        rec_dev, aff_dev = recs.to(DEV), aff.to(DEV)
+        stages = [stage] * ng if isinstance(stage, int) else list(stage)
+        Aa = (S["AugP"] * ng)(*[A.aug_block(rec_dev[g], [r for *_, r in srcs], dims, (0, 0, 0)) for g in range(ng)])
+        Fa = (S["AffP"] * ng)(*[A.aff_block(aff_dev[g], stages[g]) for g in range(ng)])
+        if edit is not None:
+            edit(Ga, Aa, Fa)
+        rc = lib.mms_gather_affine_group(Ga, Aa, Fa, ng, ops.stream())
+    torch.cuda.synchronize()
+    return rc, [{k: v.cpu() for k, v in o.items()} for o in outs]
+
+
+def _patients(cpu):
+    mask = cpu["mask"]
+    with_img = [int(i) for i in torch.nonzero(mask[:, 0] != 0).view(-1)]
+    full = [int(i) for i in torch.nonzero((mask != 0).all(1)).view(-1)]
+    no_img = [int(i) for i in torch.nonzero((mask[:, 0] == 0) & (mask[:, 1] != 0)).view(-1)]
+    assert len(with_img) >= 2 and full and no_img
+    return with_img, full, no_img
+
+
+def _pad_rows(rows, filler):
+    return rows + [filler] * (-len(rows) % (B * NG))
+
+
+def _members(rows):
+    """rows -> launches of NG members x B rows; the second member takes the table from its other end: different records per member."""
+    chunks = [rows[i:i + B] for i in range(0, len(rows), B)]
+    return [[chunks[i], chunks[-1 - i]] for i in range(len(chunks) // 2)]
+
+
+def _check_plain_sources(cpu, got, idx_row, drops):
+    j = torch.as_tensor(idx_row)
+    _, rna, clin, mask = aug_batch(cpu["image"][j], cpu["rnaseq"][j], cpu["clinical"][j], cpu["mask"][j],
+                                   [(0, (0, 0, 0), 1.0, 0.0, d) for d in drops])
+    assert torch.equal(got["rnaseq"], rna) and torch.equal(got["clinical"], clin) and torch.equal(got["mask"], mask)
+    assert torch.equal(got["time"], cpu["label"][j, 0:1]) and torch.equal(got["valid"], cpu["valid"][j].view(-1, 1))
+
+
+@pytest.mark.parametrize("where", ["device", "pinned"])
+def test_identity_records_equal_the_plain_gather(cohorts, where):
+    from multimodal_survival_prediction_amd import augment as A
+    for dims in (VEC, SCALAR):
+        cohort = _placed(cohorts[dims], where)
+        idx = np.array([[0, 5, 5, 23], [7, 1, 12, 3]])
+        recs = torch.stack([A.identity_records(B)] * NG)
+        aff = torch.stack([A.affine_records(recs[g], dims=dims) for g in range(NG)])
+        rc, got = _launch(cohort, idx, recs, aff)
+        assert rc == 0
+        _, plain = _launch(cohort, idx)
+        for g in range(NG):
+            for k in plain[g]:
+                assert torch.equal(got[g][k], plain[g][k]), k
+                assert not bool(torch.isnan(got[g][k]).any())
+
+
+def _integer_rows(dims, cpu):
+    """[(patient, flip, shift, quarter turns about D, drop)] -- every flip, shifts up to the extent on every axis, flips and shifts
+    combined, quarter turns where H == W, a row without a CT and a dropped row."""
+    with_img, full, no_img = _patients(cpu)
+    geo = [(f, (0, 0, 0), 0) for f in range(8)]
+    for a, n in enumerate(dims):
+        for d in (1, -1, n - 1, -(n - 1), n, -n):
+            s = [0, 0, 0]; s[a] = d
+            geo.append((0, tuple(s), 0))
+        s = [0, 0, 0]; s[a] = 1
+        geo.append((1 << a, tuple(s), 0))
+    geo += [(7, (1, -2, 3), 0), (5, (-1, 2, -3), 0)]
+    if dims[1] == dims[2]:
+        geo += [(0, (0, 0, 0), 1), (0, (0, 0, 0), -1)]
+    rows = [(with_img[k % len(with_img)], f, s, q, 0) for k, (f, s, q) in enumerate(geo)]
+    rows += [(no_img[0], 3, (1, -1, 2), 0, 0), (full[0], 6, (1, 1, 1), 0, 1), (full[0], 1, (0, 1, 0), 0, 2)]
+    return _pad_rows(rows, (with_img[0], 0, (0, 0, 0), 0, 0))
+
+
+@pytest.mark.parametrize("stage", [0, 16])
+@pytest.mark.parametrize("dims,where", [(VEC, "device"), (VEC, "pinned"), (SCALAR, "device")])
+def test_integer_matrices_are_bit_exact(cohorts, dims, where, stage):
+    """The 8-word records keep flip = 7 and a shift: mms_gather_affine_group must not read them (the matrix carries the geometry)."""
+    from multimodal_survival_prediction_amd import augment as A
+    cpu = cohorts[dims]
+    cohort = _placed(cpu, where)
+    n = 0
+    for members in _members(_integer_rows(dims, cpu)):
+        idx = np.array([[r[0] for r in c] for c in members])
+        folded = [A.make_records(B, [r[1] for r in c], [r[2] for r in c], drop=[r[4] for r in c]) for c in members]
+        aff = torch.stack([A.affine_records(f, angles=[[90.0 * r[3], 0, 0] for r in c], dims=dims) for f, c in zip(folded, members)])
+        recs = torch.stack([A.make_records(B, 7, (1, 1, 1), drop=[r[4] for r in c]) for c in members])       # geometry fields: decoys
+        rc, got = _launch(cohort, idx, recs, aff, stage)
+        assert rc == 0
+        for g, c in enumerate(members):
+            _check_plain_sources(cpu, got[g], idx[g], [r[4] for r in c])
+            for b, (p, flip, shift, quarter, drop) in enumerate(c):
+                v = cpu["image"][p].reshape(dims)
+                want = aug_volume(torch.rot90(v, quarter, (1, 2)) if quarter else v, flip, shift, 1.0, 0.0)
+                if cpu["mask"][p, 0] == 0 or drop & 1:
+                    want = torch.zeros(dims)
+                assert torch.equal(got[g]["image"][b].view(dims), want), (p, flip, shift, quarter, drop)
+                n += 1
+    assert n >= 30
+
+
+def _generic_rows(dims, cpu, rng):
+    """[(patient, m (3 x 4 float64), scale, offset, sigma, seed, drop)]: rotations up to 30 degrees about every axis, zoom 0.6 .. 1.5,
+    translations that move part of the volume out, intensity maps, some rows with noise."""
+    from multimodal_survival_prediction_amd import augment as A
+    with_img, full, no_img = _patients(cpu)
+    c = (np.asarray(dims) - 1) / 2
+    rows = []
+    for k in range(13):
+        ang = rng.uniform(-30, 30, 3) * ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1))[k % 4]
+        zoom = (0.6, 1.5)[k] if k < 2 else rng.uniform(0.6, 1.5)
+        A3 = A.rotation(ang[None])[0].T / zoom
+        t = rng.uniform(-0.7, 0.7, 3) * np.asarray(dims) * (k % 3 != 0)
+        m = np.concatenate([A3, (c - A3 @ c + t)[:, None]], 1)
+        sigma = 0.05 if k % 3 == 1 else 0.0
+        rows.append((with_img[k % len(with_img)], m, rng.uniform(0.5, 1.5), rng.uniform(-0.1, 0.1), sigma, int(rng.integers(0, 2 ** 32)), 0))
+    ident = np.eye(3, 4)
+    rows += [(no_img[0], rows[0][1], 1.5, 0.1, 0.05, 7, 0), (full[0], rows[1][1], 0.5, 0.1, 0.05, 8, 1), (full[0], rows[2][1], 1.0, 0.0, 0.0, 0, 6)]
+    return _pad_rows(rows, (with_img[0], ident, 1.0, 0.0, 0.0, 0, 0))
+
+
+def _records(A, c):
+    recs = A.make_records(len(c), scale=[r[2] for r in c], offset=[r[3] for r in c], drop=[r[6] for r in c])
+    aff = torch.zeros(len(c), A.AFF_WORDS, dtype=torch.int32)
+    f = aff.view(torch.float32)
+    f[:, :12] = torch.tensor(np.stack([r[1].reshape(12) for r in c]), dtype=torch.float32)
+    f[:, A.AFF_SIGMA] = torch.tensor([r[4] for r in c], dtype=torch.float32)
+    aff[:, A.AFF_SEED] = torch.tensor(np.array([r[5] for r in c], dtype=np.uint32).view(np.int32))
+    return recs, aff
+
+
+def _bound(vol, m32, scale, offset, sigma):
+    """The module docstring's bound for one record; vol float64 [D, H, W], m32 the fp32 matrix as float64."""
+    dims = np.asarray(vol.shape, dtype=np.float64)
+    delta = [4 * E * (abs(m32[a, 0]) * dims[0] + abs(m32[a, 1]) * dims[1] + abs(m32[a, 2]) * dims[2] + abs(m32[a, 3])) for a in range(3)]
+    pad = np.pad(vol, 1)
+    L = max(float(np.abs(np.diff(pad, axis=a)).max()) for a in range(3))
+    return L * sum(delta) + 16 * E * (abs(scale) * float(np.abs(vol).max()) + abs(offset) + 5 * sigma)
+
+
+@pytest.mark.parametrize("stage", [0, 16])
+@pytest.mark.parametrize("dims,where", [(VEC, "device"), (VEC, "pinned"), (SCALAR, "device")])
+def test_generic_records_within_the_derived_bound(cohorts, dims, where, stage):
+    from multimodal_survival_prediction_amd import augment as A
+    cpu = cohorts[dims]
+    cohort = _placed(cpu, where)
+    rows = _generic_rows(dims, cpu, np.random.default_rng(5))
+    n = partly_out = 0
+    worst = 0.0
+    for members in _members(rows):
+        idx = np.array([[r[0] for r in c] for c in members])
+        ra = [_records(A, c) for c in members]
+        rc, got = _launch(cohort, idx, torch.stack([r for r, _ in ra]), torch.stack([a for _, a in ra]), stage)
+        assert rc == 0
+        for g, c in enumerate(members):
+            _check_plain_sources(cpu, got[g], idx[g], [r[6] for r in c])
+            f = ra[g][1].view(torch.float32)
+            for b, (p, m, scale, offset, sigma, seed, drop) in enumerate(c):
+                gi = got[g]["image"][b].view(dims).double().numpy()
+                if cpu["mask"][p, 0] == 0 or drop & 1:
+                    assert not gi.any()                       # zero-filled: neither offset nor noise
+                    continue
+                vol = cpu["image"][p].reshape(dims).double().numpy()
+                m32 = f[b, :12].double().numpy().reshape(3, 4)
+                s32, o32, g32 = float(np.float32(scale)), float(np.float32(offset)), float(np.float32(sigma))
+                ref = R.affine_volume(vol, m32, s32, o32, g32, seed)
+                tol = _bound(vol, m32, s32, o32, g32)
+                err = float(np.abs(gi - ref).max())
+                worst = max(worst, err / tol)
+                print("dims %s stage %d patient %d: err %.3e bound %.3e" % (dims, stage, p, err, tol))
+                assert err <= tol, (p, m, err, tol)
+                air = R.trilinear_zero(np.ones(dims), *R.coords(m32, dims))
+                partly_out += int((air < 0.5).any() and (air > 0.5).any())
+                n += 1
+    print("largest err / bound = %.3f" % worst)
+    assert n >= 13 and partly_out >= 6
+
+
+@pytest.mark.parametrize("dims", [VEC, (8, 24, 32)])
+def test_noise_is_bit_exact(cohorts, dims):
+    """A zero volume, identity geometry: out = fmaf(sigma, g, 0) = float32(sigma) * g, the reference's bits -- in the staged and the
+    direct form, for both members (shared seeds), and at two launch widths: (6, 12, 12) is one block per row, (8, 24, 32) two."""
+    from multimodal_survival_prediction_amd import augment as A, data
+    cpu = _cohort(dims)
+    cpu["image"] = torch.zeros_like(cpu["image"])
+    cohort = data.cohort_to(cpu, DEV)
+    with_img, full, no_img = _patients(cpu)
+    idx = np.array([[with_img[0], with_img[1], no_img[0], full[0]]] * NG)
+    sig = [0.05, 1.0, 0.05, 0.05]
+    seeds = [1, 0xFFFFFFFF, 3, 4]
+    recs = torch.stack([A.make_records(B, drop=[0, 0, 0, 1])] * NG)
+    aff = torch.stack([A.affine_records(A.identity_records(B), sigma=sig, seed=seeds, dims=dims)] * NG)
+    outs = []
+    for stage in (0, 16):
+        rc, got = _launch(cohort, idx, recs, aff, stage)
+        assert rc == 0
+        outs += [got[g]["image"] for g in range(NG)]
+    nvox = int(np.prod(dims))
+    for o in outs:
+        for b in (0, 1):
+            want = np.float32(sig[b]) * R.noise(seeds[b], nvox)
+            assert np.array_equal(o[b].numpy(), want), b
+        assert not bool(o[2].any()) and not bool(o[3].any())  # a row without a CT and a dropped row stay exactly zero
+    assert float(outs[0][1].abs().max()) > 2.0                 # sigma = 1: the noise is there (864 values of a unit bell reach 2)
+
+
+def test_non_finite_and_huge_matrices_give_air(cohorts):
+    """A memory-safety property of the kernel's clamps, checked once: NaN, Inf and huge entries put every source coordinate outside the
+    volume, so every voxel is air: exactly `offset`, finite.  Member 0 takes the staged form, member 1 the direct one."""
+    from multimodal_survival_prediction_amd import augment as A, data
+    cpu = cohorts[VEC]
+    cohort = data.cohort_to(cpu, DEV)
+    with_img, _, _ = _patients(cpu)
+    nan, inf = float("nan"), float("inf")
+    eye = np.eye(3, 4)
+    ms = [np.full((3, 4), nan), eye + np.array([[0, 0, 0, inf], [0, 0, 0, -inf], [0, 0, 0, 3e38]]),
+          np.full((3, 4), 1e30), np.array([[inf, 0, 0, 0], [0, 1, 0, -1e30], [0, 0, nan, 0]])]
+    c = [(with_img[0], m, 1.5, 0.25, 0.0, 0, 0) for m in ms]
+    recs, aff = _records(A, c)
+    rc, got = _launch(cohort, np.array([[r[0] for r in c]] * NG), torch.stack([recs] * NG), torch.stack([aff] * NG), (0, 16))
+    assert rc == 0
+    for g in range(NG):
+        assert bool((got[g]["image"] == 0.25).all())
+
+
+def test_bad_arguments_are_refused(cohorts):
+    from multimodal_survival_prediction_amd import augment as A, data
+    cohort = data.cohort_to(cohorts[VEC], DEV)
+    idx, recs = np.array([[0, 1, 2, 3]]), A.identity_records(4)[None]
+    aff = A.affine_records(recs[0], dims=VEC)[None]
+    def no_affine_records(G, Au, F): F[0].rec = None
+    def negative_budget(G, Au, F): F[0].stage_floats = -1
+    def shift_bound_too_large(G, Au, F): Au[0].max_shift[0] = VEC[0]
+    def shift_bound_negative(G, Au, F): Au[0].max_shift[2] = -1
+    def wrong_width(G, Au, F): Au[0].W = 8
+    def two_volumes(G, Au, F): Au[0].role[1] = A.ROLE_VOLUME
+    def no_records(G, Au, F): Au[0].rec = None
+    def no_index(G, Au, F): G[0].idx = None
+    for edit in (no_affine_records, negative_budget, shift_bound_too_large, shift_bound_negative, wrong_width, two_volumes, no_records,
+                 no_index):
+        assert _launch(cohort, idx, recs, aff, edit=edit)[0] == -1, edit.__name__
+    assert _launch(cohort, idx, recs, aff)[0] == 0
+    assert _launch(cohort, idx, recs, aff, stage=10 ** 9)[0] == 0          # larger than the library's budget: capped, not refused
+
+
+# ---- 2. step, loaders, validation, entry point ----------------------------------------------------------------------------------------
+SPEC = "flip=0.5,shift=2:2:1,scale=0.9:1.1,offset=-0.05:0.05,rot=10,zoom=0.9:1.1,noise=0:0.02,seed=4"
+DIMS, RNA = (16, 16, 8), 64
+
+
+def _fallback_models(cls, G):
+    from test_gpu_augment import _fallback_models as f
+    return f(cls, G, RNA)
+
+
+@pytest.mark.parametrize("cls,style", [("PartialModalityNet", "partial"), ("MultiModalSurvivalNet", "final")])
+def test_indexed_augmented_step_equals_batch_step(cls, style):
+    """train_step_indexed(cohort, idx, augment=, augment_affine=) == train_step on the batches a materialising loader augmented
+    beforehand (augment.apply: the same kernel over the same records, so both engines get bit-identical inputs -- what is compared is
+    the plumbing of the two record arrays through the fold group; part 1 compares the kernel with the reference.  Tolerance of
+    tests/test_gpu_fold_group.py::test_indexed_step_equals_batch_step).  The materialised CT is also held against the float64
+    reference, loosely (1e-5 on values in [-0.1, 1.3]): the loaders hand the kernel the records they drew."""
+    import copy
+    from multimodal_survival_prediction_amd import augment as A, data, training as T
+    from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
+    cpu = data.make_cohort(n=24, dims=DIMS, rna_dim=RNA, seed=3, complete=False)
+    cohort = data.cohort_to(cpu, DEV)
+    base = _fallback_models(cls, NG)
+    Ae = FoldGroupEngine([copy.deepcopy(m).to(DEV).train() for m in base], dn_opts=GI)
+    Be = FoldGroupEngine([copy.deepcopy(m).to(DEV).train() for m in base], dn_opts=GI)
+    spec = SPEC + (",moddrop=0.3" if style == "partial" else "")
+    folds = [torch.arange(0, 12), torch.arange(12, 24)]
+    mk = lambda lazy: [data.BatchLoader(cohort, f, B, shuffle=True, seed=9 + g, style=style, lazy=lazy, with_valid=style == "partial",
+                                        augment=spec, augment_style=style) for g, f in enumerate(folds)]
+    skip = T._STYLES[style].skip_if_unusable
+    for it, (mts, lzs) in enumerate(zip(zip(*mk(False)), zip(*mk(True)))):
+        Ae.train_step([T._train_kwargs(style, mt) for mt in mts], skip_if_unusable=skip, use_graph=it > 0)
+        Be.train_step_indexed(lzs[0]["gather"], torch.stack([lz["index"] for lz in lzs]), skip_if_unusable=skip, use_graph=it > 0,
+                              augment=torch.stack([lz["augment"] for lz in lzs]),
+                              augment_affine=torch.stack([lz["augment_affine"] for lz in lzs]))
+        torch.cuda.synchronize()
+        if it == 0:
+            for g in range(NG):
+                e = rel_err(Be.engines[g].gflat, Ae.engines[g].gflat)
+                print(cls, "member", g, "rel_err(gflat) =", e, "max |gflat| =", float(Ae.engines[g].gflat.abs().max()))
+                assert float(Ae.engines[g].gflat.abs().max()) > 0 and e <= 2e-5
+            lz, mt = lzs[0], mts[0]
+            f8, f16 = lz["augment"].view(torch.float32), lz["augment_affine"].view(torch.float32)
+            seen = 0
+            for b, p in enumerate(lz["index"].tolist()):
+                if cpu["mask"][p, 0] == 0 or int(lz["augment"][b, A.DROP]) & 1:
+                    continue
+                ref = R.affine_volume(cpu["image"][p].reshape(DIMS).double().numpy(), f16[b, :12].double().numpy().reshape(3, 4),
+                                      float(f8[b, A.SCALE]), float(f8[b, A.OFFSET]), float(f16[b, A.AFF_SIGMA]),
+                                      int(lz["augment_affine"][b, A.AFF_SEED]) & 0xFFFFFFFF)
+                assert float(np.abs(mt["image"][b].reshape(DIMS).double().cpu().numpy() - ref).max()) <= 1e-5
+                seen += 1
+            assert seen > 0
+    assert it == 2
+    for a, b in zip(Ae.epoch_stats(), Be.epoch_stats()):
+        assert a["n_batches"] == b["n_batches"] == 3 and a["n_usable"] == b["n_usable"]
+
+
+@pytest.fixture(scope="module")
+def partial_group():
+    from multimodal_survival_prediction_amd import data
+    from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
+    cohort = data.cohort_to(data.make_cohort(n=24, dims=DIMS, rna_dim=RNA, seed=3, complete=False), DEV)
+    ge = FoldGroupEngine([m.to(DEV) for m in _fallback_models("PartialModalityNet", 2)], dn_opts=GI)
+    return cohort, ge
+
+
+def test_lazy_and_materialising_loaders_agree(partial_group):
+    from multimodal_survival_prediction_amd import data
+    cohort, ge = partial_group
+    mk = lambda lazy: data.BatchLoader(cohort, torch.arange(24), 4, shuffle=True, seed=9, lazy=lazy, augment=SPEC + ",moddrop=0.3",
+                                       augment_style="partial")
+    GP = ge.plan(4, DIMS, (0,))
+    P = GP.Ps[0]
+    n = changed = 0
+    for lz, mt in zip(mk(True), mk(False)):
+        ge._gather_indexed(GP, lz["gather"], lz["index"][None], lz["augment"][None], lz["augment_affine"][None])
+        torch.cuda.synchronize()
+        assert torch.equal(P.ct.view(mt["image"].shape), mt["image"]) and torch.equal(P.buf["rna"], mt["rnaseq"])
+        assert torch.equal(P.buf["clin"].view(mt["clinical"].shape), mt["clinical"]) and torch.equal(P.mask, mt["mask"])
+        assert torch.equal(cohort["label"][lz["index"].to(DEV)], mt["label"])
+        changed += int(not torch.equal(mt["image"], cohort["image"][lz["index"].to(DEV)]))
+        n += 1
+    assert n == 6 and changed > 0
+
+
+def test_validation_ignores_the_spec(partial_group):
+    from multimodal_survival_prediction_amd import data, training as T
+    cohort, ge = partial_group
+    lab = torch.nonzero(cohort["has_survival"]).view(-1).cpu()
+    for lazy in (True, False):
+        mk = lambda **kw: [data.BatchLoader(cohort, lab[f::2], 4, shuffle=False, lazy=lazy, **kw) for f in range(2)]
+        plain = T.validate_lockstep(ge, mk(), "partial", DEV)
+        withspec = T.validate_lockstep(ge, mk(augment=SPEC, augment_style="partial"), "partial", DEV)
+        assert plain == withspec, (lazy, plain, withspec)
+
+
+def test_an_affine_spec_takes_the_affine_gather(partial_group):
+    from multimodal_survival_prediction_amd import data, training as T
+    from test_gpu_augment import _Spy
+    cohort, ge = partial_group
+    mk = lambda spec: [data.BatchLoader(cohort, torch.arange(12 * f, 12 * f + 8), 4, shuffle=True, seed=f, lazy=True, augment=spec,
+                                        augment_style="partial") for f in range(2)]
+    real = ge.lib
+    try:
+        ge.lib = spy = _Spy(real)
+        T.train_epoch_lockstep(ge, mk(SPEC), "partial")
+        gathers = {c for c in spy.calls if c.startswith("mms_gather")}
+        assert gathers == {"mms_gather_affine_group"}, gathers
+        del spy.calls[:]
+        T.train_epoch_lockstep(ge, mk(SPEC.replace(",rot=10,zoom=0.9:1.1,noise=0:0.02", "")), "partial")
+        gathers = {c for c in spy.calls if c.startswith("mms_gather")}
+        assert gathers == {"mms_gather_aug_group"}, gathers                # a spec without the new keys launches what it launched
+    finally:
+        ge.lib = real
+        torch.cuda.synchronize()
+
+
+def test_entry_point_records_the_spec(tmp_path):
+    from test_gpu_augment import _CHILD
+    from multimodal_survival_prediction_amd.augment import AugmentSpec
+    scripts = os.path.join(ROOT, "scripts", "training")
+    code = _CHILD.format(root=ROOT, scripts=scripts, script=os.path.join(scripts, "partial_modality_training.py"))
+    aug = "rot=10,zoom=0.9:1.1,noise=0:0.02"
+    env = dict(os.environ, MMS_PATIENTS="24", MMS_EPOCHS="2", MMS_FOLDS="2", MMS_BATCH_SIZE="3", MMS_VOLUME="16,16,8", MMS_AUGMENT=aug)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, "-c", code], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    res = json.load(open(tmp_path / "results" / "partial_modality" / "cv_results.json"))
+    spec = AugmentSpec.parse(res["hyperparameters"]["augment"])
+    assert spec == AugmentSpec.parse(aug) and spec.has_affine
+
+    # the training log: "... epoch   1: train=(cox, entropy) val_loss=... C-index=..." per fold
+    lines = [ln.split("train=", 1)[1] for ln in r.stdout.splitlines() if "train=" in ln and "val_loss=" in ln]
+    assert len(lines) >= 2, r.stdout[-3000:]
+    for ln in lines:
+        vals = [float(x) for x in re.findall(r"[-+]?(?:\d+\.?\d*(?:[eE][-+]?\d+)?|nan|inf)", ln.split("C-index")[0])]
+        assert len(vals) >= 2 and all(np.isfinite(v) for v in vals), ln
