@@ -725,6 +725,31 @@ int mms_dn121_input_grad(void* ws, int B, int D, int H, int W, const float* x, c
  * (running statistics, required); overwrites only the workspace's gradient scratch, which every training backward rewrites before use. */
 int mms_fb3_input_grad(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params,
                        const void* const* buffers, const float* dout, int lddout, float* dx, hipStream_t s);
+/* Lock-step forms of the two drivers above: member g of the group is entry g of every array (one B, D, H, W and, for the 3-conv encoder,
+ * one width set).  The launch sequence is the single-model driver's, every launch issued once with ng parameter blocks (grid z = member);
+ * the single-model drivers ARE the ng = 1 calls.  x[g] may be the same pointer for every member (an ensemble reads one copy of the batch);
+ * ws[g], dout[g] and dx[g] are per member.  After the group's EVAL-mode forward in the per-layer forms (mms_dn121_forward_group with
+ * persist_b3 = persist_b4 = fuse_layers = -1 / mms_fb3_forward_group).  ng outside 1..MMS_MAX_GROUP, a NULL array or entry, a shape outside
+ * the workspace plan's domain or lddout below the feature width: MMS_ERR_ARG, nothing is launched. */
+int mms_dn121_input_grad_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
+                               const void* const* const* buffers, const float* const* dout, int lddout, float* const* dx,
+                               const MmsDnOpts* opts, hipStream_t s);
+int mms_fb3_input_grad_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                             const void* const* const* params, const void* const* const* buffers, const float* const* dout, int lddout,
+                             float* const* dx, hipStream_t s);
+
+/* ---- ensemble reduce (csrc/ensemble.hip): K members' values of one tensor -> their mean and population standard deviation ----
+ *   mean[i] = (1/K) sum_g x[g][i] (summed in member order),  spread[i] = sqrt((1/K) sum_g (x[g][i] - mean[i])^2)
+ * for i < n.  The K values of an element are held in registers and the deviations are taken from the finished mean (two passes, no
+ * cancellation); K = 1 gives the input bit for bit and a spread of exactly 0; a NaN in any member reaches both outputs.  spread may be
+ * NULL (the mean only).  Every pointer 16-byte aligned.  K outside 1..MMS_MAX_GROUP, a NULL x[g] for g < K, a NULL mean, n = 0 or a
+ * misaligned pointer: MMS_ERR_ARG.  No atomics: two calls give the same bits. */
+typedef struct EnsP {
+    const float* x[10];             // [MMS_MAX_GROUP] members, the first K read
+    int K; size_t n;
+    float* mean; float* spread;     // [n]; spread optional
+} EnsP;
+int mms_ensemble_reduce(const EnsP* p, hipStream_t s);
 
 /* ---- heads ---- */
 int mms_linear_fwd(const LinearFwdP* p, hipStream_t s);        /* nn.Linear (+ preceding BN1d/ReLU/Dropout, + following ReLU) */

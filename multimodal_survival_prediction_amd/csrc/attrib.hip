@@ -3,7 +3,9 @@
 // nothing but workspace scratch and the caller's dx is written.  No float atomics (two calls give the same bits) and no workgroup ever
 // waits for another: this is an inspection path.
 //   mms_conv0_bwd_data[_group]   DenseNet121 stem: norm0 (frozen) backward + conv0 with respect to the volume
-//   mms_fb3_input_grad           the 3-conv CT encoder, scalar kernels in the style of fallback.hip
+//   mms_fb3_input_grad[_group]   the 3-conv CT encoder, scalar kernels in the style of fallback.hip
+// Every kernel here takes its members by value (Grp<P>) with the member on the grid's z: the single-model entry points are the ng = 1
+// calls, a fold ensemble issues each launch once for its K members (mms_dn121_input_grad_group in dn_net.hip drives the DenseNet ones).
 #include "common.h"
 #include "dn_ops.h"
 #include "fb_plan.h"
@@ -135,7 +137,8 @@ MMS_SINGLE(mms_conv0_bwd_data, Conv0BwdDataP)
 // DenseNet121 head, data path with norm5 frozen: dslab[m][c] = a_c * [relu(bn(slab)) > 0] * (sum_n dout[b][n] * w[n][c]) / V.
 // One thread per channel (as head_bwd_sums_kernel, dn_bwd.hip); reads dout, slab, bn, w and writes dslab only.
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void head_input_grad_kernel(const HeadBwdP p) {
+__global__ __launch_bounds__(256) void head_input_grad_kernel(const Grp<HeadBwdP> grp) {
+    const HeadBwdP& p = grp.p[blockIdx.z];
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= p.C) return;
     float mu, rs, ga, be;
@@ -152,9 +155,14 @@ __global__ __launch_bounds__(256) void head_input_grad_kernel(const HeadBwdP p) 
         }
     }
 }
-int mms_head_input_grad(const HeadBwdP* pp, hipStream_t s) {          // driver-internal (dn_ops.h)
-    if (!pp || pp->B <= 0 || pp->bn.train != 0 || !pp->dout || !pp->slab || !pp->w || !pp->dslab) return MMS_ERR_ARG;
-    MMS_LAUNCH(head_input_grad_kernel, dim3((pp->C + 255) / 256), dim3(256), 0, s, *pp);
+int mms_head_input_grad_group(const HeadBwdP* pp, int ng, hipStream_t s) {          // driver-internal (dn_ops.h); grid z = member
+    Grp<HeadBwdP> a;
+    if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
+    for (int g = 0; g < ng; ++g) {
+        const HeadBwdP& q = pp[g];
+        if (q.B <= 0 || q.bn.train != 0 || !q.dout || !q.slab || !q.w || !q.dslab || q.C != pp->C) return MMS_ERR_ARG;
+    }
+    MMS_LAUNCH(head_input_grad_kernel, dim3((pp->C + 255) / 256, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
 
@@ -163,8 +171,9 @@ int mms_head_input_grad(const HeadBwdP* pp, hipStream_t s) {          // driver-
 // ------------------------------------------------------------------------------------------------------
 using namespace fbplan;
 
-// BN3 + ReLU + global average pool backward: dbn[b, v, c] = [relu(bn(y)) > 0] * dout[b, c] / V
-__global__ void fb_ig_pool_kernel(const FbPoolP p) {
+// BN3 + ReLU + global average pool backward: dbn[b, v, c] = [relu(bn(y)) > 0] * dout[b, c] / V.  Grid z = member.
+__global__ void fb_ig_pool_kernel(const Grp<FbPoolP> grp) {
+    const FbPoolP& p = grp.p[blockIdx.z];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.B * p.C) return;
     const int b = idx / p.C, c = idx % p.C;
@@ -179,9 +188,13 @@ __global__ void fb_ig_pool_kernel(const FbPoolP p) {
 
 // One convolution's backward-data.  p.dy: the masked gradient at the output BatchNorm's output [B*out][Cout]; bn_out: that BatchNorm
 // (frozen): dy_raw = a * p.dy.  Gather over the <= 8 (output voxel, tap) pairs that read this input voxel, then the input's own
-// BatchNorm + ReLU mask (p.has_bn; the first layer reads the raw volume, Cin = 1: no mask) -> p.dbn_in [B*in][Cin].
-__global__ __launch_bounds__(256) void fb_ig_conv_kernel(const FbConvP p, const BnSrc bn_out) {
+// BatchNorm + ReLU mask (p.has_bn; the first layer reads the raw volume, Cin = 1: no mask) -> p.dbn_in [B*in][Cin].  Grid z = member.
+struct FbIgConvArgs { Grp<FbConvP> c; BnSrc bn_out[MMS_MAX_GROUP]; };
+static_assert(sizeof(FbIgConvArgs) <= 4096, "ten members by value must fit the kernel-argument segment");
+__global__ __launch_bounds__(256) void fb_ig_conv_kernel(const FbIgConvArgs args) {
     __shared__ float a_out[128];
+    const FbConvP& p = args.c.p[blockIdx.z];
+    const BnSrc& bn_out = args.bn_out[blockIdx.z];
     if (threadIdx.x < p.Cout) {
         float mu, rs;
         bn_mean_rstd(bn_out, threadIdx.x, mu, rs);
@@ -219,31 +232,52 @@ __global__ __launch_bounds__(256) void fb_ig_conv_kernel(const FbConvP p, const 
 }
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != MMS_OK) return rc_; } while (0)
-extern "C" int mms_fb3_input_grad(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params_,
-                                  const void* const* buffers, const float* dout, int lddout, float* dx, hipStream_t s) {
+// The 3-conv encoder's input gradient for ng members in lock-step: four launches, each carrying every member's block.
+extern "C" int mms_fb3_input_grad_group(int ng, void* const* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* const* x,
+                                        const void* const* const* params, const void* const* const* buffers, const float* const* dout, int lddout,
+                                        float* const* dx, hipStream_t s) {
     FbPlan P;
-    if (!fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total || !ws || !x || !params_ || !buffers || !dout || !dx || lddout < P.C[3]) return MMS_ERR_ARG;
+    if (ng < 1 || ng > MMS_MAX_GROUP || !ws || !x || !params || !buffers || !dout || !dx) return MMS_ERR_ARG;
+    if (!fb_plan(P, widths, B, D, H, W) || ws_bytes != P.total || lddout < P.C[3]) return MMS_ERR_ARG;
     for (int l = 0; l < 3; ++l)
         if (256 % widths[l]) return MMS_ERR_ARG;                             // a thread per (voxel, channel) of a 256-thread workgroup
-    const float* const* prm = (const float* const*)params_;
-    for (int i = 0; i < 12; ++i)
-        if (!prm[i]) return MMS_ERR_ARG;
-    for (int i = 0; i < 9; ++i)
-        if (!buffers[i]) return MMS_ERR_ARG;
-    FbPoolP pl{};
-    pl.y = at<float>(ws, P.y[3]); pl.C = P.C[3]; pl.V = P.M[3] / B; pl.B = B; pl.bn = fb_bn(ws, P, 3, prm, buffers, 0);
-    pl.dout = dout; pl.lddout = lddout; pl.dbn = at<float>(ws, P.dbn[3]);
-    MMS_LAUNCH(fb_ig_pool_kernel, dim3((B * P.C[3] + 255) / 256), dim3(256), 0, s, pl);
+    for (int g = 0; g < ng; ++g) {
+        if (!ws[g] || !x[g] || !params[g] || !buffers[g] || !dout[g] || !dx[g]) return MMS_ERR_ARG;
+        for (int i = 0; i < 12; ++i)
+            if (!params[g][i]) return MMS_ERR_ARG;
+        for (int i = 0; i < 9; ++i)
+            if (!buffers[g][i]) return MMS_ERR_ARG;
+    }
+    if ((long)B * P.C[3] > 0x7fffffffL) return MMS_ERR_ARG;
+    Grp<FbPoolP> pl{};
+    pl.zdim = 1;
+    for (int g = 0; g < ng; ++g) {
+        const float* const* prm = (const float* const*)params[g];
+        FbPoolP& q = pl.p[g];
+        q.y = at<float>(ws[g], P.y[3]); q.C = P.C[3]; q.V = P.M[3] / B; q.B = B; q.bn = fb_bn(ws[g], P, 3, prm, buffers[g], 0);
+        q.dout = dout[g]; q.lddout = lddout; q.dbn = at<float>(ws[g], P.dbn[3]);
+    }
+    MMS_LAUNCH(fb_ig_pool_kernel, dim3((B * P.C[3] + 255) / 256, 1, ng), dim3(256), 0, s, pl);
     TRY(mms_check_launch());
     for (int l = 3; l >= 1; --l) {
-        FbConvP c{};
-        c.x = l == 1 ? x : at<float>(ws, P.y[l - 1]); c.Cin = P.C[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
-        c.has_bn = l > 1; if (l > 1) c.bn = fb_bn(ws, P, l - 1, prm, buffers, 0);
-        c.w = prm[4 * (l - 1)]; c.Cout = P.C[l]; c.dy = at<float>(ws, P.dbn[l]);
-        c.dbn_in = l == 1 ? dx : at<float>(ws, P.dbn[l - 1]);
-        const int VB = 256 / c.Cin;
-        MMS_LAUNCH(fb_ig_conv_kernel, dim3((P.M[l - 1] + VB - 1) / VB), dim3(256), 0, s, c, fb_bn(ws, P, l, prm, buffers, 0));
+        FbIgConvArgs a{};
+        a.c.zdim = 1;
+        for (int g = 0; g < ng; ++g) {
+            const float* const* prm = (const float* const*)params[g];
+            FbConvP& c = a.c.p[g];
+            c.x = l == 1 ? x[g] : at<float>(ws[g], P.y[l - 1]); c.Cin = P.C[l - 1]; c.in = P.g[l - 1]; c.out = P.g[l]; c.B = B;
+            c.has_bn = l > 1; if (l > 1) c.bn = fb_bn(ws[g], P, l - 1, prm, buffers[g], 0);
+            c.w = prm[4 * (l - 1)]; c.Cout = P.C[l]; c.dy = at<float>(ws[g], P.dbn[l]);
+            c.dbn_in = l == 1 ? dx[g] : at<float>(ws[g], P.dbn[l - 1]);
+            a.bn_out[g] = fb_bn(ws[g], P, l, prm, buffers[g], 0);
+        }
+        const int VB = 256 / P.C[l - 1];
+        MMS_LAUNCH(fb_ig_conv_kernel, dim3((P.M[l - 1] + VB - 1) / VB, 1, ng), dim3(256), 0, s, a);
         TRY(mms_check_launch());
     }
     return MMS_OK;
+}
+extern "C" int mms_fb3_input_grad(void* ws, size_t ws_bytes, const int* widths, int B, int D, int H, int W, const float* x, const void* const* params_,
+                                  const void* const* buffers, const float* dout, int lddout, float* dx, hipStream_t s) {
+    return mms_fb3_input_grad_group(1, &ws, ws_bytes, widths, B, D, H, W, &x, &params_, &buffers, &dout, lddout, &dx, s);
 }

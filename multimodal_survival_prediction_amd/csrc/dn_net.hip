@@ -868,82 +868,119 @@ extern "C" int mms_dn121_backward_mt(void* ws, int B, int D, int H, int W, const
 // statistics) -- so no workgroup waits for another.  The producers' BatchNorm-backward sums still land in the workspace's per-step
 // scratch (zeroed by the next training forward) and are never read.  No weight-gradient launch, no gradient table, no unpack.
 extern "C" int mms_conv0_bwd_data_group(const Conv0BwdDataP*, int, hipStream_t);
-extern "C" int mms_dn121_input_grad(void* ws, int B, int D, int H, int W, const float* x, const void* const* params, const void* const* buffers,
-                                    const float* dout, int lddout, float* dx, const MmsDnOpts* opts, hipStream_t s) {
+// One implementation over ng models in lock-step (as dn121_forward_impl / dn121_backward_impl): every launch carries the ng members'
+// blocks, grid z = member; Ctx.out is the member's dx.  The conv2 tap split and fragment form follow the group size, as in the
+// training backward, so a member's summation order may differ between group sizes.  x may be one pointer for every member.
+static int dn121_input_grad_impl(const Ctx* cx, int ng, int B, int D, int H, int W, int lddout, const MmsDnOpts* opts, hipStream_t s) {
     const MmsDnOpts o = mms_opts(opts);
     const int nout = out_features_of(o);
     Plan P;
-    if (!make_plan(P, B, D, H, W) || !ws || !x || !params || !buffers || !dout || !dx || nout > 4096 || lddout < nout) return MMS_ERR_ARG;
-    const float* const* prm = (const float* const*)params;
+    if (ng < 1 || ng > MMS_MAX_GROUP || !make_plan(P, B, D, H, W) || nout > 4096 || lddout < nout) return MMS_ERR_ARG;
+    FOR_G if (!cx[g].ws || !cx[g].x || !cx[g].prm || !cx[g].buf || !cx[g].dout || !cx[g].out) return MMS_ERR_ARG;
     const bool packed = o.w2_packed != 0;
-    auto bn = [&](size_t st, int Ctot_, int iw, int ord, int count, int nrep) { return mk_bn(ws, st, Ctot_, prm, iw, buffers, ord, count, 0, nrep); };
-    auto bbsrc = [&](size_t off, int stride, int nrep) { return BnBwd{at<double>(ws, off), at<double>(ws, off) + stride, nrep, 2 * stride}; };
+    auto bn = [&](const Ctx& c, size_t st, int Ctot_, int iw, int ord, int count, int nrep) { return mk_bn(c.ws, st, Ctot_, c.prm, iw, c.buf, ord, count, 0, nrep); };
+    auto bbsrc = [&](void* ws, size_t off, int stride, int nrep) { return BnBwd{at<double>(ws, off), at<double>(ws, off) + stride, nrep, 2 * stride}; };
     {
-        HeadBwdP hb{dout, lddout, at<float>(ws, P.pooled), at<float>(ws, P.slab[3]), CTOT[3], 1024, B, P.M[3] / B,
-                    bn(P.st_slab[3], CTOT[3], IDX.n5w, IDX.bn5, P.M[3], P.R[3]), prm[IDX.outw], nout,
-                    nullptr, nullptr, nullptr, nullptr, at<float>(ws, P.dslab[3]), CTOT[3]};
-        TRY(mms_head_input_grad(&hb, s));
+        HeadBwdP hb[MMS_MAX_GROUP];
+        FOR_G {
+            const Ctx& c = cx[g];
+            hb[g] = HeadBwdP{c.dout, lddout, at<float>(c.ws, P.pooled), at<float>(c.ws, P.slab[3]), CTOT[3], 1024, B, P.M[3] / B,
+                             bn(c, P.st_slab[3], CTOT[3], IDX.n5w, IDX.bn5, P.M[3], P.R[3]), c.prm[IDX.outw], nout,
+                             nullptr, nullptr, nullptr, nullptr, at<float>(c.ws, P.dslab[3]), CTOT[3]};
+        }
+        TRY(mms_head_input_grad_group(hb, ng, s));
     }
     int l = NLAYER;
     for (int b = NB - 1; b >= 0; --b) {
         int C = CTOT[b];
         const int M = P.M[b];
-        float* slab = at<float>(ws, P.slab[b]);
-        float* dslab = at<float>(ws, P.dslab[b]);
-        const int ns3 = conv3_nsplit(M, 1, P.partial_rows, P.g[b], o);
+        const int ns3 = conv3_nsplit(M, ng, P.partial_rows, P.g[b], o);
         for (int i = LAYERS[b] - 1; i >= 0; --i) {
             --l; C -= 32;
             const int ip = IDX.layer[l];
-            float* dmid = at<float>(ws, P.dbn_mid_l[l]);
-            const BnSrc bn1 = bn(P.st_slab[b], CTOT[b], ip, IDX.bn_layer1[l], M, P.R[b]);
-            const BnSrc bn2 = bn(P.st_y1[l], 128, ip + 3, IDX.bn_layer2[l], M, P.R[b]);
-            Conv3BwdDataP bd{dslab + C, CTOT[b], at<int>(ws, P.coords[b]), P.g[b], M, packed ? prm[NPARAM + 2 * l] : at<float>(ws, P.wpb[l]),
-                             at<float>(ws, P.y1[l]), bn2, dmid, at<double>(ws, P.bb_y1[l]), at<double>(ws, P.bb_y1[l]) + 128,
-                             ns3 > 1 ? at<float>(ws, P.partial) : nullptr, ns3};
-            bd.srep = P.R[b]; bd.sstride = 2 * 128; bd.wfrag = conv3_frag_block(P, b, 1, o) ? 1 : 0;
-            Conv1BwdP q{};
-            q.dyraw = dmid; q.lddy = 128;
-            q.y = at<float>(ws, P.y1[l]); q.ldy = 128;
-            q.bn_out = bn2; q.bb_out = bbsrc(P.bb_y1[l], 128, P.R[b]); q.has_bn_out = 1;
-            q.M = M; q.N = 128;
-            q.x = slab; q.ldx = CTOT[b]; q.K = C; q.bn_in = bn1;
-            q.w = prm[ip + 2]; q.pool = 0; q.in = Dims3{0, 0, 0};
-            q.dbn = at<float>(ws, P.dbn_in); q.lddbn = CTOT[b];
-            q.s1 = at<double>(ws, P.bb_in[l]); q.s2 = at<double>(ws, P.bb_in[l]) + 1024;
-            q.srep = P.R[b]; q.sstride = 2 * 1024; q.msplit = 1;
-            BnBwdApplyP ap{at<float>(ws, P.dbn_in), CTOT[b], slab, CTOT[b], dslab, CTOT[b], M, C, bn1,
-                           bbsrc(P.bb_in[l], 1024, P.R[b]), 1, nullptr, nullptr};
-            TRY(mms_conv3_bwd_data_group(&bd, 1, &o, s));
-            TRY(mms_conv1_bwd_data_group(&q, 1, &o, s));
-            TRY(mms_bn_bwd_apply_group(&ap, 1, s));
+            Conv3BwdDataP bd[MMS_MAX_GROUP];
+            Conv1BwdP c1[MMS_MAX_GROUP];
+            BnBwdApplyP ap[MMS_MAX_GROUP];
+            FOR_G {
+                const Ctx& c = cx[g];
+                float* slab = at<float>(c.ws, P.slab[b]);
+                float* dslab = at<float>(c.ws, P.dslab[b]);
+                float* dmid = at<float>(c.ws, P.dbn_mid_l[l]);
+                const BnSrc bn1 = bn(c, P.st_slab[b], CTOT[b], ip, IDX.bn_layer1[l], M, P.R[b]);
+                const BnSrc bn2 = bn(c, P.st_y1[l], 128, ip + 3, IDX.bn_layer2[l], M, P.R[b]);
+                bd[g] = Conv3BwdDataP{dslab + C, CTOT[b], at<int>(c.ws, P.coords[b]), P.g[b], M, packed ? c.prm[NPARAM + 2 * l] : at<float>(c.ws, P.wpb[l]),
+                                      at<float>(c.ws, P.y1[l]), bn2, dmid, at<double>(c.ws, P.bb_y1[l]), at<double>(c.ws, P.bb_y1[l]) + 128,
+                                      ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
+                bd[g].srep = P.R[b]; bd[g].sstride = 2 * 128; bd[g].wfrag = conv3_frag_block(P, b, ng, o) ? 1 : 0;
+                Conv1BwdP& q = c1[g];
+                q = Conv1BwdP{};
+                q.dyraw = dmid; q.lddy = 128;
+                q.y = at<float>(c.ws, P.y1[l]); q.ldy = 128;
+                q.bn_out = bn2; q.bb_out = bbsrc(c.ws, P.bb_y1[l], 128, P.R[b]); q.has_bn_out = 1;
+                q.M = M; q.N = 128;
+                q.x = slab; q.ldx = CTOT[b]; q.K = C; q.bn_in = bn1;
+                q.w = c.prm[ip + 2]; q.pool = 0; q.in = Dims3{0, 0, 0};
+                q.dbn = at<float>(c.ws, P.dbn_in); q.lddbn = CTOT[b];
+                q.s1 = at<double>(c.ws, P.bb_in[l]); q.s2 = at<double>(c.ws, P.bb_in[l]) + 1024;
+                q.srep = P.R[b]; q.sstride = 2 * 1024; q.msplit = 1;
+                ap[g] = BnBwdApplyP{at<float>(c.ws, P.dbn_in), CTOT[b], slab, CTOT[b], dslab, CTOT[b], M, C, bn1,
+                                    bbsrc(c.ws, P.bb_in[l], 1024, P.R[b]), 1, nullptr, nullptr};
+            }
+            TRY(mms_conv3_bwd_data_group(bd, ng, &o, s));
+            TRY(mms_conv1_bwd_data_group(c1, ng, &o, s));
+            TRY(mms_bn_bwd_apply_group(ap, ng, s));
         }
         if (b > 0) {   // transition b-1 -> b
             const int t = b - 1, ip = IDX.trans[t], Kp = CTOT[t], Mp = P.M[t];
-            const BnSrc bnt = bn(P.st_slab[t], CTOT[t], ip, IDX.bn_trans[t], Mp, P.R[t]);
-            Conv1BwdP q{};
-            q.dyraw = dslab; q.lddy = CTOT[b]; q.y = nullptr; q.ldy = 0; q.has_bn_out = 0;
-            q.bn_out = bnt; q.bb_out = BnBwd{nullptr, nullptr, 0, 0};
-            q.M = M; q.N = Kp / 2;
-            q.x = at<float>(ws, P.slab[t]); q.ldx = CTOT[t]; q.K = Kp; q.bn_in = bnt;
-            q.w = prm[ip + 2]; q.pool = 1; q.in = P.g[t];
-            q.dbn = at<float>(ws, P.dbn_in); q.lddbn = CTOT[t];
-            q.s1 = at<double>(ws, P.bb_tr[t]); q.s2 = at<double>(ws, P.bb_tr[t]) + 1024;
-            q.srep = P.R[t]; q.sstride = 2 * 1024; q.msplit = 1;
-            BnBwdApplyP ap{at<float>(ws, P.dbn_in), CTOT[t], at<float>(ws, P.slab[t]), CTOT[t], at<float>(ws, P.dslab[t]), CTOT[t],
-                           Mp, Kp, bnt, bbsrc(P.bb_tr[t], 1024, P.R[t]), 0, nullptr, nullptr};
-            TRY(mms_conv1_bwd_data_group(&q, 1, &o, s));
-            TRY(mms_bn_bwd_apply_group(&ap, 1, s));
+            Conv1BwdP c1[MMS_MAX_GROUP];
+            BnBwdApplyP ap[MMS_MAX_GROUP];
+            FOR_G {
+                const Ctx& c = cx[g];
+                const BnSrc bnt = bn(c, P.st_slab[t], CTOT[t], ip, IDX.bn_trans[t], Mp, P.R[t]);
+                Conv1BwdP& q = c1[g];
+                q = Conv1BwdP{};
+                q.dyraw = at<float>(c.ws, P.dslab[b]); q.lddy = CTOT[b]; q.y = nullptr; q.ldy = 0; q.has_bn_out = 0;
+                q.bn_out = bnt; q.bb_out = BnBwd{nullptr, nullptr, 0, 0};
+                q.M = M; q.N = Kp / 2;
+                q.x = at<float>(c.ws, P.slab[t]); q.ldx = CTOT[t]; q.K = Kp; q.bn_in = bnt;
+                q.w = c.prm[ip + 2]; q.pool = 1; q.in = P.g[t];
+                q.dbn = at<float>(c.ws, P.dbn_in); q.lddbn = CTOT[t];
+                q.s1 = at<double>(c.ws, P.bb_tr[t]); q.s2 = at<double>(c.ws, P.bb_tr[t]) + 1024;
+                q.srep = P.R[t]; q.sstride = 2 * 1024; q.msplit = 1;
+                ap[g] = BnBwdApplyP{at<float>(c.ws, P.dbn_in), CTOT[t], at<float>(c.ws, P.slab[t]), CTOT[t], at<float>(c.ws, P.dslab[t]), CTOT[t],
+                                    Mp, Kp, bnt, bbsrc(c.ws, P.bb_tr[t], 1024, P.R[t]), 0, nullptr, nullptr};
+            }
+            TRY(mms_conv1_bwd_data_group(c1, ng, &o, s));
+            TRY(mms_bn_bwd_apply_group(ap, ng, s));
         } else {       // stem: pool0 + relu0 backward, then norm0 (frozen) + conv0 with respect to the volume
-            const BnSrc bn0 = bn(P.st_y0, 64, IDX.n0w, IDX.bn0, P.M0, P.R0);
-            PoolBwdP pb{at<float>(ws, P.dslab[0]), CTOT[0], at<uint8_t>(ws, P.argmax), P.g[0], P.g0, B, at<float>(ws, P.y0), bn0,
-                        at<float>(ws, P.dbn0), at<double>(ws, P.bb_y0), at<double>(ws, P.bb_y0) + 64, at<int>(ws, P.coords0)};
-            pb.srep = P.R0; pb.sstride = 2 * 64;
-            Conv0BwdDataP cd{at<float>(ws, P.dbn0), bn0, prm[IDX.conv0], P.in, P.g0, P.M0, dx};
-            TRY(mms_pool_bwd_group(&pb, 1, s));
-            TRY(mms_conv0_bwd_data_group(&cd, 1, s));
+            PoolBwdP pb[MMS_MAX_GROUP];
+            Conv0BwdDataP cd[MMS_MAX_GROUP];
+            FOR_G {
+                const Ctx& c = cx[g];
+                const BnSrc bn0 = bn(c, P.st_y0, 64, IDX.n0w, IDX.bn0, P.M0, P.R0);
+                pb[g] = PoolBwdP{at<float>(c.ws, P.dslab[0]), CTOT[0], at<uint8_t>(c.ws, P.argmax), P.g[0], P.g0, B, at<float>(c.ws, P.y0), bn0,
+                                 at<float>(c.ws, P.dbn0), at<double>(c.ws, P.bb_y0), at<double>(c.ws, P.bb_y0) + 64, at<int>(c.ws, P.coords0)};
+                pb[g].srep = P.R0; pb[g].sstride = 2 * 64;
+                cd[g] = Conv0BwdDataP{at<float>(c.ws, P.dbn0), bn0, c.prm[IDX.conv0], P.in, P.g0, P.M0, c.out};
+            }
+            TRY(mms_pool_bwd_group(pb, ng, s));
+            TRY(mms_conv0_bwd_data_group(cd, ng, s));
         }
     }
     return MMS_OK;
+}
+extern "C" int mms_dn121_input_grad(void* ws, int B, int D, int H, int W, const float* x, const void* const* params, const void* const* buffers,
+                                    const float* dout, int lddout, float* dx, const MmsDnOpts* opts, hipStream_t s) {
+    Ctx c{ws, x, (const float* const*)params, buffers, dx, dout, nullptr};
+    return dn121_input_grad_impl(&c, 1, B, D, H, W, lddout, opts, s);
+}
+extern "C" int mms_dn121_input_grad_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x, const void* const* const* params,
+                                          const void* const* const* buffers, const float* const* dout, int lddout, float* const* dx,
+                                          const MmsDnOpts* opts, hipStream_t s) {
+    if (ng < 1 || ng > MMS_MAX_GROUP || !ws || !x || !params || !buffers || !dout || !dx) return MMS_ERR_ARG;
+    Ctx c[MMS_MAX_GROUP];
+    FOR_G c[g] = Ctx{ws[g], x[g], (const float* const*)params[g], buffers[g], dx[g], dout[g], nullptr};
+    return dn121_input_grad_impl(c, ng, B, D, H, W, lddout, opts, s);
 }
 
 // Data-parallel variants of the single-model drivers (one process per GPU; include/mmsurv.h).

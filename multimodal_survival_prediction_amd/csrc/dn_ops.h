@@ -70,7 +70,7 @@ int mms_c3s_bwd_data(const Conv3BwdDataP* pp, int ng, const MmsDnOpts& o, hipStr
 int mms_c3s_c1s_fwd(const Conv3FwdP* p3, const Conv1FwdP* p1, unsigned* const* flags, unsigned* const* errs, int ng, hipStream_t s);
 
 // head of the input-gradient path (attrib.hip): class_layers + norm5 backward with frozen statistics, data only
-int mms_head_input_grad(const HeadBwdP* pp, hipStream_t s);
+int mms_head_input_grad_group(const HeadBwdP* pp, int ng, hipStream_t s);
 
 // ---- dead-backward skip (MmsDnOpts.skip_dead_bwd; common.h live_issue): the launches whose public parameter blocks carry no `live`
 // word take the models' words as an array beside them (NULL, or per model NULL = always run); the public entry points pass NULL.

@@ -762,8 +762,9 @@ class SurvivalEngine:
         # (dropout counter and the epoch accumulators self.acc are advanced inside mms_grad_sumsq: AdamP.acc / .rng)
 
     # ---- public: fused training step ------------------------------------------------------------------
-    def load_batch(self, P, ct=None, rna=None, clinical=None, mask=None, time=None, event=None, valid=None):
-        if P.has_enc:
+    def load_batch(self, P, ct=None, rna=None, clinical=None, mask=None, time=None, event=None, valid=None, shared_ct=False):
+        """shared_ct: the volume is not copied -- the launches read another plan's copy (FoldGroupEngine.forward_eval_shared)."""
+        if P.has_enc and not shared_ct:
             P.ct.copy_(ct.reshape(P.ct.shape), non_blocking=True)
         if "rna" in P.buf:
             P.buf["rna"].copy_(rna, non_blocking=True)

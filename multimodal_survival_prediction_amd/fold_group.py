@@ -8,6 +8,9 @@ points of include/mmsurv.h: same kernels, same per-model arithmetic, G times the
 
 Per-model state stays per model (parameters, Adam moments, BatchNorm buffers, learning rate, dropout counters,
 epoch accumulators): a fold trained in a group follows exactly the trajectory it follows alone.
+
+After training, the same group serves as an ensemble (ensemble.py): `forward_eval_shared` / `attribute_lockstep` run every member on ONE
+batch -- one copy of the volumes, one launch sequence -- for a combined prediction and a combined saliency map.
 """
 import ctypes
 
@@ -131,23 +134,28 @@ class FoldGroupEngine:
         return GP
 
     # ---- launches ----------------------------------------------------------------------------------
-    def _forward(self, GP, train):
+    def _forward(self, GP, train, x=None, enc_opts=None, img_tail=None):
+        """x: the members' volume pointers instead of the plans' own (forward_eval_shared: one copy for all); enc_opts: `const MmsDnOpts*`
+        of the DenseNet121 driver call instead of _opts_arg's (attribute_lockstep: the per-layer forms); img_tail: False = ImageOnlyModel's
+        tail as its three launches whatever the group's setting."""
         st = ops.stream()
         lib, ng = self.lib, GP.ng
         prog = GP.eng[0].prog
         if GP.has_enc:
+            x = GP.x if x is None else x
             B, (D, H, W) = GP.B, GP.dims
-            if GP.img_tail:        # the encoder's pool launch carries the two Linear layers: no head launches
+            if GP.img_tail and img_tail is not False:        # the encoder's pool launch carries the two Linear layers: no head launches
                 lf = GP.lin_fwd[train]
-                _lib.check(lib.mms_img_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                _lib.check(lib.mms_img_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
                                                      1 if train else 0, lf[0], lf[1], st), "mms_img_forward_group")
                 return
             if GP.fallback:
-                _lib.check(lib.mms_fb3_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
+                _lib.check(lib.mms_fb3_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
                                                      1 if train else 0, st), "mms_fb3_forward_group")
             else:
-                _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.buffers, GP.out, GP.ld,
-                                                       1 if train else 0, self._opts_arg(GP), st), "mms_dn121_forward_group")
+                _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
+                                                       1 if train else 0, enc_opts if enc_opts is not None else self._opts_arg(GP), st),
+                           "mms_dn121_forward_group")
         self._forward_heads(GP, train)
 
     def _forward_heads(self, GP, train):
@@ -431,6 +439,126 @@ class FoldGroupEngine:
         """Input-gradient attribution is a single-model path (SurvivalEngine.attribute)."""
         raise RuntimeError("FoldGroupEngine.attribute: input-gradient attribution is not implemented for fold groups (no lock-step "
                            "form of mms_dn121_input_grad / mms_fb3_input_grad); call SurvivalEngine.attribute on each fold's model")
+
+    # ---- one batch seen by every member (ensembles) ----------------------------------------------------------
+    @staticmethod
+    def _rows(batch):
+        return (batch["rna"] if batch.get("rna") is not None else batch["ct"]).shape[0]
+
+    def _shared_plan(self, batch, members):
+        members = tuple(range(len(self.engines))) if members is None else tuple(members)
+        has_enc = self.engines[0].prog["encoder"] is not None
+        dims = tuple(batch["ct"].shape[-3:]) if has_enc else None
+        GP = self.plan(self._rows(batch), dims, members)
+        if GP.has_enc and getattr(GP, "x_shared", None) is None:
+            GP.x_shared = _ptrs([GP.Ps[0].ct.data_ptr()] * GP.ng)       # member 0's input buffer is the group's one copy of the volume
+        return GP
+
+    def _load_shared(self, GP, batch):
+        """The volume once (into member 0's input buffer); the small head inputs (rna, clinical, mask) per member."""
+        for g, (e, P) in enumerate(zip(GP.eng, GP.Ps)):
+            e.load_batch(P, shared_ct=g > 0, **batch)
+
+    def forward_eval_shared(self, batch, members=None, use_graph=True):
+        """Eval-mode forward of every member on ONE batch (a dict of SurvivalEngine.load_batch's keywords): the CT volume is stored once and
+        every member's launch block names that copy -> forward_eval's result."""
+        GP = self._shared_plan(batch, members)
+        self._load_shared(GP, batch)
+        self._sync_packs(GP)
+        x = GP.x_shared if GP.has_enc else None
+        if use_graph:
+            self._graph(GP, "eval_shared", lambda: self._forward(GP, False, x=x)).replay()
+        else:
+            self._forward(GP, False, x=x)
+        return [(P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)) for P in GP.Ps]
+
+    def _attr_group(self, GP):
+        """The members' attribution blocks (SurvivalEngine._attr_blocks) as the arrays of the *_group entry points."""
+        AG = getattr(GP, "attr", None)
+        if AG is not None:
+            return AG
+        As = [e._attr_blocks(P) for e, P in zip(GP.eng, GP.Ps)]
+        AG = dict(members=As, lin=[_arr([A["lin"][i] for A in As]) for i in range(len(As[0]["lin"]))],
+                  gate=_arr([A["gate"] for A in As]) if As[0]["gate"] is not None else None,
+                  mix=_arr([A["mix"] for A in As]) if As[0]["mix"] is not None else None,
+                  opts=As[0].get("opts"))                    # (the members share one options block: checked by the constructor)
+        if GP.has_enc:
+            cc = GP.eng[0].prog["ct_cols"]
+            AG["dout"] = _ptrs([P.dbuf["feats"][:, cc:].data_ptr() for P in GP.Ps])
+            AG["dx"] = _ptrs([A["dct"].data_ptr() for A in As])
+        GP.attr = AG
+        return AG
+
+    def _check_attribute(self, wrt):
+        kind = self.engines[0].prog["kind"]
+        if kind == "SimMLM_SurvivalNet":
+            raise RuntimeError("attribute: SimMLM_SurvivalNet is not supported -- its mixture-of-experts kernels (csrc/moe.hip) have no "
+                               "input-gradient form; supported: the five imaging classes and RNASeqSurvivalModel")
+        if any(e.model.training for e in self.engines):
+            raise RuntimeError("attribute needs the model in eval mode (call model.eval()): input gradients are taken with frozen "
+                               "BatchNorm statistics; train-mode (batch-statistic) input gradients are not computed")
+        bad = [w for w in wrt if w not in ("ct", "rna", "clinical")]
+        if bad:
+            raise ValueError("attribute: wrt takes 'ct', 'rna', 'clinical'; got %r" % (bad,))
+
+    def _attribute_lockstep_run(self, batch, members=None):
+        """attribute_lockstep's launches -> (GP, AG): the members' hazards are in their plans' buffers, their input gradients in
+        AG['members'][g]['dct' | 'drna' | 'dclin'], valid until the next call on this plan."""
+        st, lib = ops.stream(), self.lib
+        GP = self._shared_plan(batch, members)
+        ng, prog = GP.ng, GP.eng[0].prog
+        AG = self._attr_group(GP)
+        self._load_shared(GP, batch)
+        self._sync_packs(GP)
+        enc_opts = ctypes.byref(AG["opts"]) if AG["opts"] is not None else None
+        if ng == 1:
+            # a group of one IS the single model: its own launch sequence (on the 3-conv encoder the scalar forward of mms_fb3_forward,
+            # whose summation order the group's MFMA forward does not share)
+            GP.eng[0]._forward(GP.Ps[0], False, enc_opts=enc_opts)
+        else:
+            # ImageOnlyModel: the fused tail's forward does leave feats, the hidden layer and the hazard where the heads' backward reads
+            # them (img_tail_fwd_kernel writes all three); the three-launch tail is taken anyway, so that this path runs the sequence of
+            # SurvivalEngine._attribute_chunk for every class
+            self._forward(GP, False, x=GP.x_shared if GP.has_enc else None, enc_opts=enc_opts, img_tail=False)
+        for P in GP.Ps:
+            P.dbuf["hz"].fill_(1.0)           # d hazard[b] / d hazard[b] = 1: rows do not interact in eval mode
+        n_pre = prog["n_pre"]
+        for i in range(len(AG["lin"]) - 1, n_pre - 1, -1):
+            _lib.check(lib.mms_linear_bwd_group(AG["lin"][i], ng, st), "mms_linear_bwd_group")
+        if AG["gate"] is not None:
+            _lib.check(lib.mms_gate_bwd_group(AG["gate"], ng, st), "mms_gate_bwd_group")
+        if AG["mix"] is not None:
+            _lib.check(lib.mms_missing_mix_bwd_group(AG["mix"], ng, st), "mms_missing_mix_bwd_group")
+        for i in range(n_pre - 1, -1, -1):
+            _lib.check(lib.mms_linear_bwd_group(AG["lin"][i], ng, st), "mms_linear_bwd_group")
+        if GP.has_enc:
+            B, (D, H, W) = GP.B, GP.dims
+            if GP.fallback:
+                GP.eng[0]._check_scalar_path(GP.Ps[0])
+                _lib.check(lib.mms_fb3_input_grad_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x_shared, GP.params, GP.buffers,
+                                                        AG["dout"], GP.ld, AG["dx"], st), "mms_fb3_input_grad_group")
+            else:
+                _lib.check(lib.mms_dn121_input_grad_group(ng, GP.ws, B, D, H, W, GP.x_shared, GP.params, GP.buffers, AG["dout"], GP.ld,
+                                                          AG["dx"], enc_opts, st), "mms_dn121_input_grad_group")
+        return GP, AG
+
+    def attribute_lockstep(self, batch, members=None, wrt=("ct", "rna", "clinical")):
+        """Input-gradient attribution of every member on ONE batch (<= 32 rows; a dict of load_batch's keywords), in lock-step: the
+        group form of SurvivalEngine._attribute_chunk.  Shared-input eval forward in the per-layer forms -> dhazard = 1 -> the heads'
+        backward (eval prologues, no weight gradients, the gate's gradients into private scratch) -> the group input-gradient driver
+        (mms_dn121_input_grad_group / mms_fb3_input_grad_group), every launch once for the group.  -> per member what
+        SurvivalEngine.attribute returns.  Touches no .grad, no optimiser state, no running statistic, no conv2 pack and no training graph."""
+        self._check_attribute(wrt)
+        GP, AG = self._attribute_lockstep_run(batch, members)
+        res = []
+        for P, A in zip(GP.Ps, AG["members"]):
+            has_gate = P.gate is not None
+            out = dict(hazard=P.buf["hz"][:, 0].clone(), gate=P.gatew.clone() if has_gate else None)
+            out["ct"] = A["dct"].clone() if (P.has_enc and "ct" in wrt) else None
+            out["rna"] = A["drna"].clone() if ("drna" in A and "rna" in wrt) else None
+            out["clinical"] = A["dclin"].clone() if ("dclin" in A and "clinical" in wrt) else None
+            res.append(out)
+        return res
 
     def forward_eval(self, batches, members=None, use_graph=True):
         """Eval-mode forward of every member -> list of (hazard [B] view, gate [B,3] or None) per member."""

@@ -12,6 +12,7 @@ and the Kaplan-Meier tables as CSV.
     python scripts/analysis/evaluate_model.py                            # evaluates an existing results/test_predictions.csv
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute
+    python scripts/analysis/evaluate_model.py --ensemble models/final/fold_*_best.pth --model final [--combine rank] [--attribute]
 
 --predict runs the checkpoint's eval-mode forward on the MI355X (the HIP path; no CPU fallback) over the validation split
 of that fold of the cohort the training entry points use (data/processed/* under MMS_DATA_ROOT when present, else the seeded
@@ -45,6 +46,28 @@ MODELS = {
 }
 
 
+def _cohort_of(kind, device, external=False):
+    """-> (cohort, keep): the cohort --model's training entry point builds and the boolean mask of the patients it trains on.
+    external: every model class reads data/processed/* under MMS_DATA_ROOT when present (--ensemble: external validation)."""
+    import torch  # noqa: F401
+    from _common import env_dims, env_int, load_or_make_cohort
+    from multimodal_survival_prediction_amd import data
+    _, _, ckw, n_default, _, _ = MODELS[kind]
+    n = env_int("MMS_PATIENTS", n_default)
+    if kind == "image_only":          # image_only_training.py builds its cohort at MMS_VOLUME
+        cohort = load_or_make_cohort(device, n=n, dims=env_dims(), **ckw)
+    elif kind in ("partial", "simmim") or external:
+        cohort = load_or_make_cohort(device, n=n, **ckw)                 # data/processed/* under MMS_DATA_ROOT when present
+    else:
+        cohort = data.cohort_to(data.make_cohort(n=n, **ckw), device)
+    keep = cohort["has_survival"].cpu().bool()
+    if kind == "simmim":              # simmlm_training.py's cohort: labelled patients with at least one modality
+        keep &= (cohort["mask"].cpu() != 0).any(1)
+    if kind == "image_only":          # image_only_training.py's cohort: patients with an image and a label
+        keep &= cohort["mask"].cpu()[:, 0] != 0
+    return cohort, keep
+
+
 def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
@@ -56,18 +79,7 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     _, _, device = setup_device()
     cls, ctor, ckw, n_default, folds_default, batch_default = MODELS[kind]
     n_folds, batch_size = n_folds or env_int("MMS_FOLDS", folds_default), batch_size or env_int("MMS_BATCH_SIZE", batch_default)
-    n = env_int("MMS_PATIENTS", n_default)
-    if kind == "image_only":          # image_only_training.py builds its cohort at MMS_VOLUME
-        cohort = load_or_make_cohort(device, n=n, dims=env_dims(), **ckw)
-    elif kind in ("partial", "simmim"):
-        cohort = load_or_make_cohort(device, n=n, **ckw)                 # data/processed/* under MMS_DATA_ROOT when present
-    else:
-        cohort = data.cohort_to(data.make_cohort(n=n, **ckw), device)
-    keep = cohort["has_survival"].cpu().bool()
-    if kind == "simmim":              # simmlm_training.py's cohort: labelled patients with at least one modality
-        keep &= (cohort["mask"].cpu() != 0).any(1)
-    if kind == "image_only":          # image_only_training.py's cohort: patients with an image and a label
-        keep &= cohort["mask"].cpu()[:, 0] != 0
+    cohort, keep = _cohort_of(kind, device)
     labelled = torch.nonzero(keep).reshape(-1).numpy()
     _, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
     idx = labelled[val]
@@ -124,6 +136,62 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     os.makedirs(os.path.dirname(out_csv) or ".", exist_ok=True)
     df.to_csv(out_csv, index=False)
     print(f"wrote {out_csv}: {len(df)} patients of fold {fold}/{n_folds} ({cls})")
+    return df
+
+
+def predict_ensemble(checkpoints, kind, combine, batch_size, out_csv, attribute_dir=None, top=50):
+    """The K fold checkpoints as one predictor (multimodal_survival_prediction_amd.ensemble.FoldEnsemble) over EVERY labelled patient of
+    the loaded cohort -> results/test_predictions.csv with predict's columns (risk_score = the combined score) plus risk_std and
+    risk_fold_1..K.  On the cohort the folds were trained on the score is optimistic: each patient was seen by K - 1 members."""
+    import torch
+    from _common import env_int, setup_device
+    from multimodal_survival_prediction_amd import attribution, models
+    from multimodal_survival_prediction_amd.ensemble import FoldEnsemble
+    _, _, device = setup_device()
+    cls, ctor, _, _, _, batch_default = MODELS[kind]
+    batch_size = batch_size or env_int("MMS_BATCH_SIZE", batch_default)
+    cohort, keep = _cohort_of(kind, device, external=True)
+    idx = torch.nonzero(keep).reshape(-1).numpy()
+    ens = FoldEnsemble.from_checkpoints(checkpoints, lambda: getattr(models, cls)(**ctor(cohort)), device)
+    K = len(ens)
+    res = ens.predict_cohort(cohort, idx, batch_size=batch_size, combine=combine)
+    ids = cohort.get("patient_id")
+    pid = lambda i: ids[i] if ids is not None else f"SYN-{i:04d}"
+    if attribute_dir:
+        os.makedirs(attribute_dir, exist_ok=True)
+        gene_sum, gene_rows = None, 0
+        for s in range(0, len(idx), batch_size):
+            j = torch.as_tensor(idx[s:s + batch_size], device=device)
+            mask = cohort["mask"][j]
+            has = (mask != 0).cpu().numpy()
+            att = ens.attribute(dict(ct=cohort["image"][j], rna=cohort["rnaseq"][j], clinical=cohort["clinical"][j], mask=mask))
+            if att["ct"] is not None:
+                vols, stds = att["ct"][:, 0].cpu().numpy(), att["ct_std"][:, 0].cpu().numpy()
+                for r, i in enumerate(idx[s:s + batch_size]):
+                    if has[r, 0]:
+                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct.npy"), vols[r])
+                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct_std.npy"), stds[r])
+            if att["rna"] is not None and has[:, 1].any():
+                g = att["rna"].abs().double().cpu().numpy()[has[:, 1]]
+                gene_sum = g.sum(0) if gene_sum is None else gene_sum + g.sum(0)
+                gene_rows += len(g)
+        if gene_sum is not None:
+            names = cohort.get("gene_names") or [f"g{i}" for i in range(len(gene_sum))]
+            score = gene_sum / gene_rows
+            order = np.argsort(-score, kind="stable")[:top]
+            pd.DataFrame({"gene": [names[i] for i in order], "mean_abs_grad": score[order]}).to_csv(
+                os.path.join(attribute_dir, "gene_scores.csv"), index=False)
+        print(f"wrote {attribute_dir}: mean and spread saliency volumes of {K} members, gene_scores.csv")
+    lab = cohort["label"].cpu().numpy()[idx]
+    cols = {"patient_id": [pid(i) for i in idx], "survival_time": lab[:, 0], "event": lab[:, 1].astype(int),
+            "risk_score": res["hazard"].cpu().numpy(), "risk_std": res["hazard_std"].cpu().numpy()}
+    hz = res["hazards"].cpu().numpy()
+    for g in range(K):
+        cols[f"risk_fold_{g + 1}"] = hz[g]
+    df = pd.DataFrame(cols)
+    os.makedirs(os.path.dirname(out_csv) or ".", exist_ok=True)
+    df.to_csv(out_csv, index=False)
+    print(f"wrote {out_csv}: {len(df)} labelled patients scored by {K} fold models ({cls}, combine={combine})")
     return df
 
 
@@ -202,13 +270,26 @@ def main(argv=None):
     ap.add_argument("--n-folds", type=int, default=0, help="default: the training script's N_FOLDS (MMS_FOLDS)")
     ap.add_argument("--batch-size", type=int, default=0, help="default: the training script's BATCH_SIZE (MMS_BATCH_SIZE)")
     ap.add_argument("--no-plots", action="store_true")
-    ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv")
+    ap.add_argument("--ensemble", metavar="CKPT", nargs="+",
+                    help="the fold checkpoints of one model class as ONE predictor over every labelled patient of the loaded cohort (data/processed/* "
+                         "under MMS_DATA_ROOT when present: external validation; else the seeded synthetic cohort); adds the columns risk_std and "
+                         "risk_fold_1..K.  On the training cohort itself an ensemble's score is optimistic: each patient was seen in training by "
+                         "K-1 of the K members")
+    ap.add_argument("--combine", choices=("mean", "rank"), default="mean",
+                    help="with --ensemble: risk_score = the members' mean log-hazard, or their mean midrank over the predicted patients / N")
+    ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv; "
+                    "with --ensemble: the members' mean (<id>_ct.npy) and spread (<id>_ct_std.npy) and the mean gradient's gene_scores.csv")
     ap.add_argument("--top", type=int, default=50, help="rows of gene_scores.csv")
     a = ap.parse_args(argv)
-    if a.attribute and not a.predict:
+    if a.attribute and not (a.predict or a.ensemble):
         ap.error("--attribute needs --predict CHECKPOINT (the gradients are taken on the checkpoint's model)")
+    if a.predict and a.ensemble:
+        ap.error("--predict scores one fold's validation split, --ensemble every labelled patient: give one of them")
     adir = os.path.join(a.outdir, "attribution") if a.attribute else None
-    df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top) if a.predict else pd.read_csv(a.predictions)
+    if a.ensemble:
+        df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
+    else:
+        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top) if a.predict else pd.read_csv(a.predictions)
     s = evaluate(df, a.outdir, plots=not a.no_plots)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
