@@ -112,6 +112,20 @@ typedef struct MmsDnOpts {
                               the statistics and the weight gradient are summed in that grouping.  The one difference in results: with a
                               non-finite conv0 weight the full forward gives NaN in a zero box, the skip gives 0; with a non-finite dy0 the
                               full weight gradient gives NaN, the skip gives none */
+    int dup_zero;          /* identical all-zero volumes of a batch (patients without a CT) computed once by the multi-tap conv2 forward kernel
+                              (dense block 1 of the real volumes): 0 = the boxed conv0 forward counts the zero boxes of every sample into the
+                              workspace words "zero_words" (a sample is zero iff its word equals the boxes per sample); a multi-tap launch
+                              whose rows per sample are a multiple of its tile height then computes the tiles of the FIRST zero sample only,
+                              stores each of them to the same sample-relative rows of every other zero sample and multiplies its statistic
+                              partials by the number of zero samples (in fp64: exact) -- the workgroups of the other
+                              zero samples return, and the computed tiles are dealt evenly over the model's XCDs ("compacting form").  Every
+                              buffer is left complete, so nothing downstream changes.  1 = the same, but a duplicate's workgroup merely
+                              returns where it stands ("masking form"; A/B).  -1 = every sample does its work.  The words are data written
+                              by an earlier launch of the same forward from the volumes themselves: no flag from the caller, one captured
+                              graph serves every batch.  Off by itself when c0_zero_skip = -1 or conv0 takes the unboxed form (words stay 0),
+                              with more than 32 samples, and under SyncBN or a statistics hook.  Results: activations bit-identical; the
+                              statistics differ in summation order only.  The one difference: a non-finite value reaches all zero samples
+                              from the first one's computation -- which is what the full computation yields too */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.
@@ -171,6 +185,9 @@ typedef struct Conv3FwdP {
     int wfrag;                      // 1: wp is in MFMA-fragment order [tap][cin/32][(cin/16)%2][cout/16][lane = ((cin/4)%4)*16 + cout%16][cin%4]
                                     // (mms_pack_conv3_frag): every weight load of the small-grid kernel is one contiguous 1 KB per wave.
                                     // Only with partial == null on grids that kernel takes (H*W + W + 1 <= 52), else MMS_ERR_ARG
+    const unsigned* zwords; int zbps;   // optional (MmsDnOpts.dup_zero): the model's zero-box counts per sample as mms_conv0_fwd_group_zw left them, and the
+                                    // boxes per sample; sample b is a zero volume iff zwords[b] == zbps.  NULL / 0 = every sample is computed.
+                                    // Read by the multi-tap kernel only, and only when M / (D*H*W) <= 32 samples of a multiple of the tile height
 } Conv3FwdP;
 
 // ---- conv0: Conv3d(1,64,k7,s2,p3,no bias) -------------------------------------------------------------
@@ -838,6 +855,11 @@ int mms_rna_log_zscore(const float* counts, float* out, int n, int g, hipStream_
  * same kernel); a batch-4 step of one model cannot fill 256 CUs, a group of them can.
  * The convolution entry points that have several kernel forms take the launch-shape options (MmsDnOpts; NULL = defaults). */
 int mms_conv0_fwd_group(const Conv0FwdP* p, int ng, const MmsDnOpts* opts, hipStream_t s);
+/* The same, and the zero-sample words of MmsDnOpts.dup_zero (the parameter block's layout is kept, so they travel beside it): zwords[g] =
+ * model g's [B <= 32] words, ZERO on entry, or NULL; zwords NULL = none.  The boxed kernel adds to word b the number of 4x4x4 output boxes of
+ * sample b that it found all zero (c0_zero_skip), once per workgroup and model; afterwards sample b is an all-zero volume iff
+ * zwords[g][b] == (out.D/4)*(out.H/4)*(out.W/4).  Nothing is written by the unboxed form, with c0_zero_skip = -1 or with B > 32. */
+int mms_conv0_fwd_group_zw(const Conv0FwdP* p, unsigned* const* zwords, int ng, const MmsDnOpts* opts, hipStream_t s);
 int mms_pool_fwd_group(const PoolFwdP* p, int ng, hipStream_t s);
 int mms_pool_act_group(const PoolActP* p, int ng, hipStream_t s);       /* transition.norm / relu / pool (before transition.conv) */
 int mms_conv1_fwd_group(const Conv1FwdP* p, int ng, const MmsDnOpts* opts, hipStream_t s);

@@ -48,6 +48,61 @@ __device__ __forceinline__ void xcd_place(int& gi, int& bx) {
     }
 }
 
+// xcd_place with its parts: the model's XCD count X, this workgroup's XCD q among them and its slot sl there (slots are dispatched in
+// order, and all X workgroups of a slot before the next slot's); bx = q * (workgroups per XCD) + sl is xcd_place's tile.
+__device__ __forceinline__ void xcd_place_parts(int& gi, int& bx, int& X, int& q, int& sl) {
+    gi = blockIdx.z; bx = blockIdx.x; X = 1; q = 0; sl = blockIdx.x;
+    if ((gridDim.x & 7) != 0) return;
+    const int k = blockIdx.x & 7, per = gridDim.x >> 3, ng = gridDim.z;
+    if (ng > 1 && ng <= 8 && (8 % ng) == 0) {
+        X = 8 / ng; q = k % X; sl = (blockIdx.x >> 3) + per * blockIdx.z;
+        gi = k / X; bx = q * (per * ng) + sl;
+    } else {
+        X = 8; q = k; sl = blockIdx.x >> 3;
+        bx = k * per + sl;
+    }
+}
+
+// Duplicate zero samples (include/mmsurv.h MmsDnOpts.dup_zero).  The zero-box counts of a model's samples (mms_conv0_fwd_group_zw, written by an
+// earlier launch on the stream) say which samples are all-zero volumes; all of those are identical row for row through the forward, so an
+// M-tiled kernel whose samples are whole numbers of tiles computes the first of them (the representative) and stores its tiles to the others.
+// dup_issue requests the words (first thing in the kernel, one per lane: B <= 32), dup_resolve turns them into the plan of this workgroup
+// AFTER the kernel's sample-independent loads (constants, weights) have been issued, so the words ride on their round trip.
+//   mode: 0 = compacting, 1 = masking.  tps: tiles per sample.  j: the workgroup's dispatch-order index among its model's workgroups
+//   (compacting; with XCD placement: sl * X + q), X / q / sl as xcd_place_parts gives them (1 / 0 / j without placement).
+//   -> false: this workgroup has nothing to do.  tile: the tile it computes (unchanged when the model has < 2 zero samples).
+//   dups: the samples (bit mask) it must ALSO store its tile to, rows shifted by (d - rep) samples; 0 for any tile but the representative's.
+struct DupPlan { unsigned dups; int rep; };
+__device__ __forceinline__ unsigned dup_issue(const unsigned* zw, int B) {
+    const int lane = threadIdx.x & 63;
+    return (zw && lane < B) ? __hip_atomic_load(zw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+}
+__device__ __forceinline__ bool dup_resolve(unsigned word, unsigned zbps, int B, int tps, int mode, int X, int q, int sl, int& tile, DupPlan& pl) {
+    pl.dups = 0; pl.rep = 0;
+    const unsigned zmask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(word == zbps));     // (lanes >= B hold ~0: never equal, zbps <= 2^24)
+    if (__popc(zmask) < 2) return true;
+    const int rep = __ffs((int)zmask) - 1;
+    const unsigned dmask = zmask & ~(1u << rep);
+    int s;
+    if (mode == 1) {
+        s = tile / tps;
+        if ((dmask >> s) & 1u) return false;
+    } else {
+        const int ct = (B - __popc(dmask)) * tps;                      // computed tiles of the model
+        if (sl * X + q >= ct) return false;
+        const int t = q * (ct / X) + (q < ct % X ? q : ct % X) + sl;   // XCD q takes a contiguous range of them
+        int cs = t / tps;                                              // the cs-th sample that is no duplicate
+        for (s = 0; s < B; ++s) {
+            if ((dmask >> s) & 1u) continue;
+            if (cs == 0) break;
+            --cs;
+        }
+        tile = s * tps + t % tps;
+    }
+    if (s == rep) { pl.dups = dmask; pl.rep = rep; }
+    return true;
+}
+
 // Dead-backward skip (include/mmsurv.h MmsDnOpts.skip_dead_bwd): the backward kernels of a model return at once when the model's
 // "bwd_live" word -- written by the head launch, an earlier launch on the same stream, and by nothing else during the backward -- is 0.
 // The test is uniform over every workgroup of the model, so kernels whose workgroups wait for each other leave together.

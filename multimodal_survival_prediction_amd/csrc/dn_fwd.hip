@@ -17,7 +17,7 @@ __device__ __forceinline__ void store_tile(float* y, int ldy, int M, int N, int 
 }
 template <int TM, int TN>
 __device__ __forceinline__ void tile_col_stats(double* osum, double* osumsq, int M, int N, int m0, int n0,
-                                               const float* Cs, int tid) {
+                                               const float* Cs, int tid, double mul = 1.0) {      // mul: identical tiles this one stands for (dup_zero)
 #ifdef MMS_ABLATE_STATS
     return;
 #endif
@@ -30,8 +30,8 @@ __device__ __forceinline__ void tile_col_stats(double* osum, double* osumsq, int
         double v = Cs[r * (TN + 1) + tid];
         s += v; q += v * v;
     }
-    atomicAdd(&osum[n], s);
-    atomicAdd(&osumsq[n], q);
+    atomicAdd(&osum[n], s * mul);
+    atomicAdd(&osumsq[n], q * mul);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -344,6 +344,8 @@ __global__ __launch_bounds__(256) void conv3_fwd_reduce_kernel(const Grp<Conv3Fw
 // channel quarters, window 32 + 2(W+1) rows = 26 KB at W = 8): the block-1 launches of 2-3 fold models (512 / 768 tiles, 2-3 per CU).
 #define C3M_PITCH 132
 #define C3M_MAXHALO 17
+// Duplicate zero samples (MmsDnOpts.dup_zero; common.h dup_issue / dup_resolve): on = 0 off, 1 compacting, 2 masking; B samples of tps tiles
+struct DupArgs { int on, B, tps; };
 // -DC3M_TIMING (tools/c3m_timing.py): shader-clock stamps of the kernel's phases, one record of 8 words per workgroup
 #ifdef C3M_TIMING
 __device__ unsigned long long* c3m_ts_buf = nullptr;
@@ -370,13 +372,14 @@ extern "C" int mms_c3m_timing_buffer(void* buf) { return hipMemcpyToSymbol(HIP_S
 #define C3M_NTAPS 27          // timing-only ablation: fewer taps (tools/build_variant.sh)
 #endif
 template <int C3M_TM, bool PIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C3M_TM == 64 ? 1 : 3, C3M_TM == 64 ? 2 : 3))) void conv3_fwd_mt_kernel(const Grp<Conv3FwdP> grp) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C3M_TM == 64 ? 1 : 3, C3M_TM == 64 ? 2 : 3))) void conv3_fwd_mt_kernel(const Grp<Conv3FwdP> grp, const DupArgs da) {
     constexpr int RT = C3M_TM / 32, KS = 4 / RT, CW = 128 / KS, NQ = CW / 8, NH = NQ / 2;   // row tiles, channel splits, channels / float4 K-groups per wave, per half tap
-    int gi, bx;
+    int gi, bx, xX, xq, xsl;
     C3M_TS_DECL;
     C3M_STAMP(0);
-    xcd_place(gi, bx);           // XCD-contiguous row ranges; a fold group of 2 / 4 / 8 models: each model on its own XCDs
+    xcd_place_parts(gi, bx, xX, xq, xsl);   // XCD-contiguous row ranges; a fold group of 2 / 4 / 8 models: each model on its own XCDs
     const Conv3FwdP& p = grp.p[gi];
+    const unsigned zword = da.on ? dup_issue(p.zwords, da.B) : 0u;     // resolved below, behind the BatchNorm constants' loads
     // every kernel argument the loops need, read ONCE into registers (left as references into the kernarg segment the compiler re-loads them,
     // s_load + wait, inside each predicated load)
     const float* __restrict__ y1 = p.y1;
@@ -386,11 +389,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C3M_TM == 6
     float* img = smem;                                               // [nrows + 1][132]: the window and one row of zeros
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kq = lane >> 5;
     const int rt = wave / KS, kh2 = wave % KS;
-    const int m0 = bx * C3M_TM;
     const int halo = W + 1, nrows = C3M_TM + 2 * halo;
     const int c4 = (tid & 31) * 4;
     float mean[4], sc[4], beta[4];
     bn_consts4(p.bn, c4, mean, sc, beta);
+    DupPlan dup{0u, 0};
+    if (da.on && !dup_resolve(zword, (unsigned)p.zbps, da.B, da.tps, da.on - 1, xX, xq, xsl, bx, dup)) return;      // a duplicate's workgroup (uniform)
+    const int m0 = bx * C3M_TM;
     const int myrow = m0 + rt * 32 + li;
     const unsigned m9 = myrow < M ? tap_mask9(p.coords[myrow < M ? myrow : 0], p.g, false) : 0u;
     f32x16 acc, acc2;
@@ -515,7 +520,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C3M_TM == 6
     __syncthreads();
     C3M_STAMP(6);                 // channel splits added
     store_tile<C3M_TM, 32>(p.out, p.ldo, M, 32, m0, 0, Cs, tid);
-    tile_col_stats<C3M_TM, 32>(stat_rep(p.osum, p.srep, p.sstride), stat_rep(p.osumsq, p.srep, p.sstride), M, 32, m0, 0, Cs, tid);
+    for (unsigned dm = dup.dups; dm; dm &= dm - 1u)                  // the representative's tile: the same rows of every other zero sample
+        store_tile<C3M_TM, 32>(p.out, p.ldo, M, 32, m0 + (__ffs((int)dm) - 1 - dup.rep) * da.tps * C3M_TM, 0, Cs, tid);
+    tile_col_stats<C3M_TM, 32>(stat_rep(p.osum, p.srep, p.sstride), stat_rep(p.osumsq, p.srep, p.sstride), M, 32, m0, 0, Cs, tid,
+                               (double)(1 + __popc(dup.dups)));
     C3M_STAMPW(7);                // tile written, statistic atomics acknowledged
     C3M_TS_FLUSH();
 }
@@ -534,8 +542,19 @@ static inline int conv3_mt_tile(int M, int ng, const Dims3& g, const MmsDnOpts& 
     const double f32 = (double)n32 / (double)((n32 + 767) / 768 * 768), f64 = (double)n64 / (double)((n64 + 511) / 512 * 512);
     return n64 >= 512 && f64 > f32 + 0.1 ? 64 : 32;
 }
+// Duplicate zero samples: on for a launch whose samples are whole numbers of tiles, at most 32 of them, every model carrying its words.
+template <int TM>
+static DupArgs conv3_dup_args(const Conv3FwdP* pp, int ng, const MmsDnOpts& o) {
+    const Conv3FwdP& p = *pp;
+    const long rps = (long)p.g.D * p.g.H * p.g.W;
+    DupArgs da{0, 0, 0};
+    if (o.dup_zero < 0 || rps <= 0 || rps % TM != 0 || p.M % rps != 0 || p.M / rps > 32 || p.M / rps < 2) return da;
+    for (int g = 0; g < ng; ++g) if (!pp[g].zwords || pp[g].zbps <= 0) return da;
+    da.on = o.dup_zero == 1 ? 2 : 1; da.B = (int)(p.M / rps); da.tps = (int)(rps / TM);
+    return da;
+}
 template <int TM, bool PIN>
-static int launch_conv3_fwd_mt(const Conv3FwdP* pp, int ng, hipStream_t s) {
+static int launch_conv3_fwd_mt(const Conv3FwdP* pp, int ng, const MmsDnOpts& o, hipStream_t s) {
     const Conv3FwdP& p = *pp;
     constexpr int smem_max = (TM + 2 * C3M_MAXHALO + 1) * C3M_PITCH * (int)sizeof(float);
     constexpr int smem_epi = 4 / (TM / 32) * TM * 33 * (int)sizeof(float);                // the epilogue's partial tiles: 16.9 KB
@@ -545,7 +564,7 @@ static int launch_conv3_fwd_mt(const Conv3FwdP* pp, int ng, hipStream_t s) {
     std::call_once(attr_once, [&] { hipFuncSetAttribute((const void*)(conv3_fwd_mt_kernel<TM, PIN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_max); });
     Grp<Conv3FwdP> a;
     grp_fill(a, pp, ng, 1);
-    MMS_LAUNCH((conv3_fwd_mt_kernel<TM, PIN>), dim3((p.M + TM - 1) / TM, 1, ng), dim3(256), smem, s, a);
+    MMS_LAUNCH((conv3_fwd_mt_kernel<TM, PIN>), dim3((p.M + TM - 1) / TM, 1, ng), dim3(256), smem, s, a, conv3_dup_args<TM>(pp, ng, o));
     return mms_check_launch();
 }
 
@@ -562,9 +581,9 @@ extern "C" int mms_conv3_fwd_group(const Conv3FwdP* pp, int ng, const MmsDnOpts*
     for (int g = 0; g < ng; ++g) if (!mms_bn_aligned16(pp[g].bn) || pp[g].wfrag != p.wfrag) return MMS_ERR_ARG;   // BatchNorm blocks are read with 16-byte vector loads
     if (p.wfrag) return (!p.partial && mms_conv3_small_jn(p.M, ng, p.g, o)) ? mms_c3s_fwd(pp, ng, o, s) : MMS_ERR_ARG;       // fragment-ordered weights: the small-grid kernel only
     if (const int tm = p.partial ? 0 : conv3_mt_tile(p.M, ng, p.g, o)) {
-        if (tm == 64) return launch_conv3_fwd_mt<64, false>(pp, ng, s);
+        if (tm == 64) return launch_conv3_fwd_mt<64, false>(pp, ng, o, s);
         // pinned schedule while the launch is at most one round of three 32-row workgroups per CU
-        return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_fwd_mt<32, true>(pp, ng, s) : launch_conv3_fwd_mt<32, false>(pp, ng, s);
+        return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_fwd_mt<32, true>(pp, ng, o, s) : launch_conv3_fwd_mt<32, false>(pp, ng, o, s);
     }
     if (!p.partial && mms_conv3_small_jn(p.M, ng, p.g, o)) return mms_c3s_fwd(pp, ng, o, s);      // small grids: 16-row tiles, all taps, no reduce launch
     if (p.partial) {
@@ -651,11 +670,14 @@ struct Conv0FwdOp {
 // ------------------------------------------------------------------------------------------------------
 #define C0F_REG (13 * 13 * 13)      // 2197
 __host__ __device__ constexpr int c0f_koff(int tap) { return (tap / 49) * 169 + ((tap / 7) % 7) * 13 + tap % 7; }
-__global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP> grp, const int zskip) {
+struct ZwTab { unsigned* w[MMS_MAX_GROUP]; };        // the models' zero-sample words (mms_conv0_fwd_group_zw), by value beside the Grp<>
+__global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP> grp, const int zskip, const ZwTab zt) {
     __shared__ float xs[2][C0F_REG + 3];
     __shared__ float Cs[4][32 * 33];
     __shared__ __attribute__((aligned(16))) int zvote[2][4];
+    __shared__ int zcnt[32];            // zero boxes of each sample in this workgroup's current segment (ZwTab; thread 0 counts)
     int zpar = 0;
+    if (threadIdx.x < 32) zcnt[threadIdx.x] = 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kq = lane >> 5;
     const int vt = wave >> 1, ct = wave & 1;                       // voxel tile, channel tile
     const int D0 = grp.p[0].out.D, H0 = grp.p[0].out.H, W0 = grp.p[0].out.W, Di = grp.p[0].in.D, Hi = grp.p[0].in.H, Wi = grp.p[0].in.W;
@@ -674,6 +696,7 @@ __global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP>
         const int b0 = gs - model * nbox, b1 = seg_end - model * nbox;
         gs = seg_end;
         const Conv0FwdP& p = grp.p[model];
+        unsigned* const zwords = zt.w[model];
         float breg[172];                                       // W[32*ct + li][2s + kq], s = 0..171 (tap 343 = padding)
         {
             // through LDS: the 88 KB weight block is copied with coalesced loads, all in flight together, and each lane picks its row from
@@ -727,6 +750,7 @@ __global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP>
             if (more) gload(bx + 1);
             const int rb = bx / NB, b = bx - rb * NB, bz = rb / (bh * bw), r2 = rb - bz * (bh * bw), by = r2 / bw, bxw = r2 - by * bw;
             if (zero) {
+                if (tid == 0 && zwords) ++zcnt[b];          // (read behind the loop's last barrier, below)
                 // same addresses as the store below: voxel 2i + kq of this wave's tile, channel 32 ct + li
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -794,10 +818,14 @@ __global__ __launch_bounds__(256) void conv0_fwd_box_kernel(const Grp<Conv0FwdP>
                 atomicAdd(&stat_rep(p.osumsq, p.srep, p.sstride)[32 * ct + li], ssq);
             }
         }
+        if (zwords && tid < 32) {         // one atomic per sample with zero boxes, workgroup and model; the next segment counts behind its first barrier
+            const int n = zcnt[tid];
+            if (n) { atomicAdd(&zwords[tid], (unsigned)n); zcnt[tid] = 0; }
+        }
     }
 }
 
-extern "C" int mms_conv0_fwd_group(const Conv0FwdP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
+extern "C" int mms_conv0_fwd_group_zw(const Conv0FwdP* pp, unsigned* const* zwords, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const Conv0FwdP& p = *pp;
     if (p.M <= 0) return MMS_ERR_ARG;
@@ -812,6 +840,8 @@ extern "C" int mms_conv0_fwd_group(const Conv0FwdP* pp, int ng, const MmsDnOpts*
     if (!boxed) return launch_tile_gemm<Conv0FwdOp>(pp, ng, dim3((p.M + 63) / 64, 1, 1), s);
     Grp<Conv0FwdP> a;
     grp_fill(a, pp, ng, ng);
+    ZwTab zt{};
+    if (zwords && p.M / vox <= 32) for (int g = 0; g < ng; ++g) zt.w[g] = zwords[g];      // the kernel counts 32 samples at most; else the words stay 0 (= not zero)
     // one workgroup per CU at most: 342 VGPRs leave room for one wave per SIMD, so a second round would only pay the per-workgroup set-up
     // (weight rows into registers) again
     const long boxes = (long)ng * (p.M / 64);
@@ -821,9 +851,10 @@ extern "C" int mms_conv0_fwd_group(const Conv0FwdP* pp, int ng, const MmsDnOpts*
     static std::once_flag attr_once;
     std::call_once(attr_once, [&] { hipFuncSetAttribute((const void*)conv0_fwd_box_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem); });
     const int zskip = (opts && opts->c0_zero_skip < 0) ? 0 : 1;
-    MMS_LAUNCH(conv0_fwd_box_kernel, dim3(nwg, 1, 1), dim3(256), smem, s, a, zskip);
+    MMS_LAUNCH(conv0_fwd_box_kernel, dim3(nwg, 1, 1), dim3(256), smem, s, a, zskip, zt);
     return mms_check_launch();
 }
+extern "C" int mms_conv0_fwd_group(const Conv0FwdP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) { return mms_conv0_fwd_group_zw(pp, nullptr, ng, opts, s); }
 MMS_SINGLE_O(mms_conv0_fwd, Conv0FwdP)
 
 // ------------------------------------------------------------------------------------------------------

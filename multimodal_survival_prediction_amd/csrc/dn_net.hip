@@ -46,6 +46,7 @@ struct Plan {
     size_t cl_xa[NB], cl_xb[NB], cl_gst[NB], cl_tab[NB], cl_zero_begin, cl_ga, cl_gz;
     size_t b4_err;
     size_t bwd_live;                // one word: the head launch of the backward found a non-zero element in dout (MmsDnOpts.skip_dead_bwd)
+    size_t zw;                      // zero-box counts of the samples (MmsDnOpts.dup_zero), 64 words right behind hx (inside the per-step zeroed region)
     size_t hx;                      // arrival words of the fused block-3 forward launches, one per dense layer (inside the per-step zeroed region)
     size_t bb_y0, bb_y1[NLAYER], bb_in[NLAYER], bb_tr[3], bb_head;   // backward (s1 | s2)
     size_t total;
@@ -119,6 +120,7 @@ bool make_plan(Plan& P, int B, int D, int H, int W) {
     for (int i = 0; i < 3; ++i) P.bb_tr[i] = take((size_t)P.R[i] * 2 * 1024 * 8);
     P.bb_head = take((size_t)2 * 1024 * 8);
     P.hx = take(256);
+    P.zw = take(256);               // (contiguous with hx: an eval-mode forward zeroes both with one launch)
     P.cl_zero_begin = o;
     P.cl_ga = take((size_t)2 * 8 * 256 * 8);          // backward of a single-cluster block 4: hand-off A by layer parity, the dz broadcast
     P.cl_gz = take((size_t)512 * 8);
@@ -189,7 +191,7 @@ extern "C" int mms_pack_conv3_table_group_ex(const void* const*, int, int, uint6
 extern "C" int mms_unpack_conv3_grads(const void*, int, hipStream_t);
 extern "C" int mms_bn_running_update_group(const void* const*, int, int, float, hipStream_t);
 extern "C" int mms_zero_regions_group(void* const*, int, size_t, hipStream_t);
-extern "C" int mms_conv0_fwd_group(const Conv0FwdP*, int, const MmsDnOpts*, hipStream_t);
+extern "C" int mms_conv0_fwd_group_zw(const Conv0FwdP*, unsigned* const*, int, const MmsDnOpts*, hipStream_t);
 extern "C" int mms_pool_fwd_group(const PoolFwdP*, int, hipStream_t);
 extern "C" int mms_pool_act_group(const PoolActP*, int, hipStream_t);
 extern "C" int mms_conv1_fwd_group(const Conv1FwdP*, int, const MmsDnOpts*, hipStream_t);
@@ -255,6 +257,7 @@ extern "C" int mms_dn121_region(int B, int D, int H, int W, const char* name, in
     if (!strcmp(name, "stats")) return set(P.stats_begin, P.stats_end - P.stats_begin);
     if (!strcmp(name, "b4_err")) return set(P.b4_err, 1024);
     if (!strcmp(name, "hx")) return set(P.hx, 256);
+    if (!strcmp(name, "zero_words")) return set(P.zw, 256);
     if (!strcmp(name, "bwd_live")) return set(P.bwd_live, 4);
     return MMS_ERR_ARG;
 }
@@ -433,6 +436,17 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
     auto st = [&](void* ws, size_t off, int Ctot_, int coff, bool sq) -> double* {
         return train ? at<double>(ws, off) + (sq ? Ctot_ : 0) + coff : nullptr;
     };
+    // Duplicate zero samples (MmsDnOpts.dup_zero): conv0 counts every sample's zero boxes into the workspace words "zero_words" (zeroed with
+    // the statistics, or just below), and the multi-tap conv2 launches behind it compute one of a model's all-zero samples for all of them.
+    // Never under SyncBN or a statistics hook, by the rule of skip_dead_bwd: the ranks' statistics are summed between the launches.
+    const bool cl_ok = !dp.hook && dp.bn_world == 1;
+    const bool dupz = o.dup_zero >= 0 && cl_ok && B >= 2 && B <= 32;
+    const int zbps = (P.g0.D / 4) * (P.g0.H / 4) * (P.g0.W / 4);
+    if (!train && (dupz || (cl_ok && fuse_block(P, 2, ng, o)))) {       // the words, and the fused block-3 launches' arrival words (training: the zero-fill above)
+        void* regs[MMS_MAX_GROUP];
+        FOR_G regs[g] = at<void>(cx[g].ws, P.hx);
+        TRY(mms_zero_regions_group(regs, ng, 512, s));
+    }
     {   // stem
         Conv0FwdP c0[MMS_MAX_GROUP];
         PoolFwdP pf[MMS_MAX_GROUP];
@@ -446,22 +460,18 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
                              st(c.ws, P.st_slab[0], CTOT[0], 0, false), st(c.ws, P.st_slab[0], CTOT[0], 0, true)};
             pf[g].srep = P.R[0]; pf[g].sstride = 2 * CTOT[0];
         }
-        TRYS(28, mms_conv0_fwd_group(c0, ng, &o, s));
+        unsigned* zws[MMS_MAX_GROUP];
+        FOR_G zws[g] = at<unsigned>(cx[g].ws, P.zw);
+        TRYS(28, mms_conv0_fwd_group_zw(c0, dupz ? zws : nullptr, ng, &o, s));
         SYNC(at<double>(cx[0].ws, P.st_y0), P.R0, 2 * 64, 64, 64);
         TRYS(28, mms_pool_fwd_group(pf, ng, s));
         SYNC(at<double>(cx[0].ws, P.st_slab[0]), P.R[0], 2 * CTOT[0], 64, CTOT[0]);
     }
     // dense blocks with <= 32 voxels per sample as ONE launch (dn_cl.hip): block 4 (and block 3) of 64x64x32 volumes
-    const bool cl_ok = !dp.hook && dp.bn_world == 1;
     if (!train && cl_ok && (cluster_block(P, 2, o, 0) || cluster_block(P, 3, o, 0))) {      // granules + counters (training: the statistics zero-fill above covers them)
         void* regs[MMS_MAX_GROUP];
         FOR_G regs[g] = at<void>(cx[g].ws, P.cl_zero_begin);
         TRY(mms_zero_regions_group(regs, ng, P.stats_end - P.cl_zero_begin, s));
-    }
-    if (!train && cl_ok && fuse_block(P, 2, ng, o)) {       // the fused block-3 launches' arrival words (training: the zero-fill above)
-        void* regs[MMS_MAX_GROUP];
-        FOR_G regs[g] = at<void>(cx[g].ws, P.hx);
-        TRY(mms_zero_regions_group(regs, ng, 256, s));
     }
     int l = 0;
     for (int b = 0; b < NB; ++b) {
@@ -511,6 +521,7 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
                                       st(c.ws, P.st_slab[b], CTOT[b], C, false), st(c.ws, P.st_slab[b], CTOT[b], C, true),
                                       ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
                     c3[g].srep = P.R[b]; c3[g].sstride = 2 * CTOT[b]; c3[g].wfrag = frag3 ? 1 : 0;
+                    c3[g].zwords = dupz ? at<unsigned>(c.ws, P.zw) : nullptr; c3[g].zbps = zbps;
                 }
                 if (!fuse || i == 0) {          // (fused: this layer's conv1 ran in the previous layer's launch)
                     TRYS(b, mms_conv1_fwd_group(c1, ng, &o, s));
