@@ -126,6 +126,19 @@ typedef struct MmsDnOpts {
                               with more than 32 samples, and under SyncBN or a statistics hook.  Results: activations bit-identical; the
                               statistics differ in summation order only.  The one difference: a non-finite value reaches all zero samples
                               from the first one's computation -- which is what the full computation yields too */
+    int dup_zero_bwd;      /* the same in the backward of block 1's conv2.  The gradient rows of a model's zero samples are identical through the
+                              whole backward iff their rows of dout are equal; under a modality mask an absent CT's row is exactly zero.  So the
+                              head launch of mms_dn121_backward / _mt / _group leaves in the workspace word "bwd_dup" the bit mask of
+                              D = { b : zero_words[b] == boxes per sample and row b of dout compares equal to 0.0f in every element } (NaN
+                              counts as non-zero, -0.0f as zero), or 0 when |D| < 2, B > 32 or dout is too large for the live scan.  The
+                              multi-tap backward-data kernel then computes the tiles of the lowest sample of D only, stores them to the same
+                              rows of the others and multiplies its BatchNorm-backward partials by |D| (compacting form, as the forward); the
+                              multi-tap weight-gradient kernel takes its row chunks over the rows of the samples outside D \ {lowest} and
+                              scales the lowest one's dz rows by |D|.  0 = both kernels, 1 = backward-data only, 2 = weight gradient only,
+                              -1 = off.  On under the conditions of skip_dead_bwd AND of dup_zero (so never under SyncBN or a statistics
+                              hook, in backward stages, in mms_dn121_input_grad, or with dup_zero = -1), where rows per sample are a multiple
+                              of 32 and 2 <= B <= 32.  Every other kernel form ignores the word.  Results: dbn bit-identical, sums and weight
+                              gradients in another summation order (and |D| x row instead of |D| equal rows) */
 } MmsDnOpts;
 
 /* BatchNorm parameter source. train=1: batch statistics from the fp64 accumulators; train=0: running stats.
@@ -258,6 +271,9 @@ typedef struct Conv3BwdDataP {
     int wfrag;                      // 1: wpb is in MFMA-fragment order [tap][cin/16][cout/16][lane = ((cout/4)%4)*16 + cin%16][cout%4] (mms_pack_conv3_frag); as Conv3FwdP.wfrag
     const unsigned* live;           // optional (MmsDnOpts.skip_dead_bwd): device word; 0 = every workgroup of this member returns at once.  NULL = always run.
                                     // (PoolBwdP, HeadBwdP and MmsWgradModel keep their layouts: the drivers pass their words beside them, csrc/dn_ops.h)
+    const unsigned* dup;            // optional (MmsDnOpts.dup_zero_bwd): device word, the bit mask of the samples whose dz AND y1 rows are identical
+                                    // (mms_head_bwd_group_dup); fewer than two bits below M / (D*H*W) = nothing to share.  NULL = off.  Read by the
+                                    // multi-tap kernel only, and only with 2..32 samples of a multiple of 32 rows
 } Conv3BwdDataP;
 
 // conv3 backward-weight: dW[cout][cin][tap] += sum_m relu(bn(y1))[nbr(m,tap)][cin] * dz[m][cout]
@@ -273,6 +289,8 @@ typedef struct Conv3BwdWP {
                                     // 2: [32][27][128] (cout, tap, cin) -- the PACKED PRIMARY layout of MmsDnOpts.w2_packed: the same
                                     //    512-byte runs, and the buffer IS the parameter's gradient (no scratch, no unpack)
     const unsigned* live;           // optional, as Conv3BwdDataP.live
+    const unsigned* dup;            // optional, as Conv3BwdDataP.dup: the multi-tap kernel walks the rows of every sample but the mask's higher ones and
+                                    // counts the lowest one's rows once per sample of the mask.  NULL = off
 } Conv3BwdWP;
 
 /* Weight gradients of many (model, layer) members of ONE dense block as one launch per op (csrc/dn_bwd.hip): the members' parameter
@@ -800,7 +818,8 @@ int mms_dn121_workspace_bytes(int B, int D, int H, int W, size_t* bytes);
  * "stats" (the per-step zeroed region), "b4_err", "hx", and "bwd_live": ONE 32-bit word per workspace, written by the head launch of
  * every mms_dn121_backward / _mt / _group call with MmsDnOpts.skip_dead_bwd on -- 1 = this model's dout had an element unequal to 0.0f
  * (or was too large to scan), 0 = the later launches of that call returned at once.  Outside the per-step zeroed region; undefined
- * before the first such call, not touched by the staged / SyncBN / input-gradient drivers. */
+ * before the first such call, not touched by the staged / SyncBN / input-gradient drivers.  "bwd_dup": ONE word likewise, written by
+ * the same launch where MmsDnOpts.dup_zero_bwd is on: the bit mask of the samples whose gradient rows are identical, 0 = nothing to share. */
 int mms_dn121_region(int B, int D, int H, int W, const char* name, int index, size_t* off, size_t* bytes);
 int mms_dn121_init(void* ws, int B, int D, int H, int W, const void* const* params, const void* const* buffers, const MmsDnOpts* opts, hipStream_t s);
 /* which dense layers (bit l, l < 58) get their conv2 packs in MFMA-fragment order for this problem and these options (the layers whose
@@ -879,6 +898,13 @@ int mms_wgrad_tab_group(const MmsWgradModel* models, int nmodels, const MmsWgrad
                         const MmsWgradShape* shape, int which, hipStream_t s);
 int mms_bn_bwd_apply_group(const BnBwdApplyP* p, int ng, hipStream_t s);
 int mms_head_bwd_group(const HeadBwdP* p, int ng, hipStream_t s);
+/* The same, and the two words that the later launches of a backward read (the parameter block's layout is kept, so they travel beside it).
+ * live_out[g] (or NULL): model g's "bwd_live" word, MmsDnOpts.skip_dead_bwd.  dup_out[g] (or NULL): its "bwd_dup" word,
+ * MmsDnOpts.dup_zero_bwd, from zwords[g] = the model's [B] zero-box counts (mms_conv0_fwd_group_zw) and zbps = the boxes per sample: the bit
+ * mask of the samples b with zwords[g][b] == zbps whose row of dout compares equal to 0.0f in every element; 0 with fewer than two such
+ * samples, B > 32, more than 16384 elements of dout, zwords[g] NULL or zbps <= 0. */
+int mms_head_bwd_group_dup(const HeadBwdP* p, unsigned* const* live_out, const unsigned* const* zwords, int zbps, unsigned* const* dup_out,
+                           int ng, hipStream_t s);
 int mms_pool_bwd_group(const PoolBwdP* p, int ng, hipStream_t s);
 int mms_conv0_bwd_weight_group(const Conv0BwdWP* p, int ng, const MmsDnOpts* opts, hipStream_t s);
 int mms_pack_conv3_table_group(const void* const* tables_dev, int ng, int nlayers, hipStream_t s);

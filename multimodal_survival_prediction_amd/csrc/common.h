@@ -27,7 +27,11 @@ template <class P> static inline bool grp_fill(Grp<P>& a, const P* pp, int ng, i
 #define MMS_SINGLE(name, T) extern "C" int name(const T* p, hipStream_t s) { return name##_group(p, 1, s); }
 #define MMS_SINGLE_O(name, T) extern "C" int name(const T* p, hipStream_t s) { return name##_group(p, 1, nullptr, s); }      // (launch-shape options: defaults)
 // launch-shape options by value: a NULL pointer means "all defaults" (include/mmsurv.h: MmsDnOpts)
+#ifdef MMS_DUP_ZERO_BWD_DEFAULT      // A/B variant builds (tools/build_variant.sh): what dup_zero_bwd = 0 stands for
+static inline MmsDnOpts mms_opts(const MmsDnOpts* o) { MmsDnOpts r = o ? *o : MmsDnOpts{}; if (r.dup_zero_bwd == 0) r.dup_zero_bwd = MMS_DUP_ZERO_BWD_DEFAULT; return r; }
+#else
 static inline MmsDnOpts mms_opts(const MmsDnOpts* o) { return o ? *o : MmsDnOpts{}; }
+#endif
 
 
 // XCD-aware placement of an M-tiled launch whose grid is (tiles, *, models) (cdna_hip_programming.md T1; placement affects speed only,
@@ -77,9 +81,9 @@ __device__ __forceinline__ unsigned dup_issue(const unsigned* zw, int B) {
     const int lane = threadIdx.x & 63;
     return (zw && lane < B) ? __hip_atomic_load(zw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
 }
-__device__ __forceinline__ bool dup_resolve(unsigned word, unsigned zbps, int B, int tps, int mode, int X, int q, int sl, int& tile, DupPlan& pl) {
+// the plan from the bit mask of the identical samples (uniform; bits >= B must be clear)
+__device__ __forceinline__ bool dup_plan(unsigned zmask, int B, int tps, int mode, int X, int q, int sl, int& tile, DupPlan& pl) {
     pl.dups = 0; pl.rep = 0;
-    const unsigned zmask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(word == zbps));     // (lanes >= B hold ~0: never equal, zbps <= 2^24)
     if (__popc(zmask) < 2) return true;
     const int rep = __ffs((int)zmask) - 1;
     const unsigned dmask = zmask & ~(1u << rep);
@@ -101,6 +105,30 @@ __device__ __forceinline__ bool dup_resolve(unsigned word, unsigned zbps, int B,
     }
     if (s == rep) { pl.dups = dmask; pl.rep = rep; }
     return true;
+}
+__device__ __forceinline__ bool dup_resolve(unsigned word, unsigned zbps, int B, int tps, int mode, int X, int q, int sl, int& tile, DupPlan& pl) {
+    const unsigned zmask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(word == zbps));     // (lanes >= B hold ~0: never equal, zbps <= 2^24)
+    return dup_plan(zmask, B, tps, mode, X, q, sl, tile, pl);
+}
+
+// The backward's form (MmsDnOpts.dup_zero_bwd): the gradient rows of a model's zero samples are identical too where their rows of dout are
+// all zero, and the head launch of the backward leaves the bit mask of exactly those samples in the model's "bwd_dup" word (0 = fewer than
+// two).  dupm_issue requests the word (first thing in the kernel), dupm_mask gives the mask AFTER the kernel's own prologue loads have been
+// issued -- bits >= B dropped, 0 unless two samples are left -- and dup_resolve_mask is dup_resolve's compacting form on it.
+__device__ __forceinline__ unsigned dupm_issue(const unsigned* w) {
+    return w ? __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+}
+__device__ __forceinline__ unsigned dupm_mask(unsigned word, int B) {
+    const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)word) & (B >= 32 ? 0xffffffffu : (1u << B) - 1u);
+    return __popc(m) < 2 ? 0u : m;
+}
+__device__ __forceinline__ bool dup_resolve_mask(unsigned mask, int B, int tps, int X, int q, int sl, int& tile, DupPlan& pl) {
+    return dup_plan(mask, B, tps, 0, X, q, sl, tile, pl);
+}
+// the n-th (from 0) set bit of `keep` (uniform or per lane; n < popc(keep))
+__device__ __forceinline__ int nth_bit(unsigned keep, int n) {
+    for (; n > 0; --n) keep &= keep - 1u;
+    return __ffs((int)keep) - 1;
 }
 
 // Dead-backward skip (include/mmsurv.h MmsDnOpts.skip_dead_bwd): the backward kernels of a model return at once when the model's

@@ -208,12 +208,15 @@ __global__ __launch_bounds__(256) void conv3_bwd_data_reduce16_kernel(const Grp<
 #define C3D_BP 36
 #define C3D_MAXHALO 17
 #define C3D_PIN() do { if constexpr (PIN) { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } } while (0)
+// Identical samples (MmsDnOpts.dup_zero_bwd; common.h dupm_issue / dup_resolve_mask): on = 0 off, 1 on; B samples of tps tiles = rps rows
+struct DupBwdArgs { int on, B, tps, rps; };
 template <bool PIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv3_bwd_data_mt_kernel(const Grp<Conv3BwdDataP> grp) {
-    int gi, bx;
-    xcd_place(gi, bx);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv3_bwd_data_mt_kernel(const Grp<Conv3BwdDataP> grp, const DupBwdArgs da) {
+    int gi, bx, xX, xq, xsl;
+    xcd_place_parts(gi, bx, xX, xq, xsl);
     const Conv3BwdDataP& p = grp.p[gi];
     const unsigned alive = live_issue(p.live);
+    const unsigned dword = da.on ? dupm_issue(p.dup) : 0u;               // tested below, behind the prologue's loads
     const float* __restrict__ dz = p.dz;
     const float* __restrict__ wpb = p.wpb;
     const float* __restrict__ y1 = p.y1;
@@ -221,25 +224,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int M = p.M, lddz = p.lddz, W = p.g.W, HW = p.g.H * p.g.W;
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [3][nrows][36] + one row of zeros
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kq = lane >> 5;
-    const int m0 = bx * 32, halo = W + 1, nrows = 32 + 2 * halo;
+    const int halo = W + 1, nrows = 32 + 2 * halo;
+    int m0 = bx * 32;
     const int cin = 32 * wave + li;
     // ---- prologue: every load issued before the first use (constants of this lane's channel, the row's tap mask, the three windows)
     float mu, rstd, ga, be;
     bn_consts1(p.bn, cin, mu, rstd, ga, be);
-    const int myrow = m0 + li;
-    const int mycoord = p.coords[myrow < M ? myrow : 0];
+    int myrow, mycoord;
     constexpr int NR = (32 + 2 * C3D_MAXHALO + 31) / 32;               // row passes per window: 3
     float4 wv[3][NR];
     const int wr = tid >> 3, wc = (tid & 7) * 4;
+    auto wload = [&]() __attribute__((always_inline)) {                 // the tile's loads: its rows' coordinates and dz windows
+        myrow = m0 + li;
+        mycoord = p.coords[myrow < M ? myrow : 0];
 #pragma unroll
-    for (int kd = 0; kd < 3; ++kd)
+        for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = wr + 32 * i, src = m0 - (kd - 1) * HW - halo + r;
-            const bool ok = r < nrows && src >= 0 && src < M;
-            const float4 v = *(const float4*)(dz + (size_t)(ok ? src : 0) * lddz + wc);
-            wv[kd][i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+            for (int i = 0; i < NR; ++i) {
+                const int r = wr + 32 * i, src = m0 - (kd - 1) * HW - halo + r;
+                const bool ok = r < nrows && src >= 0 && src < M;
+                const float4 v = *(const float4*)(dz + (size_t)(ok ? src : 0) * lddz + wc);
+                wv[kd][i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+    };
+    wload();
     const float* wl = wpb + (size_t)cin * 864 + 4 * kq;
     float4 b[3][4];
     auto bload = [&](float4 (&bb)[4], int tap) __attribute__((always_inline)) {
@@ -249,6 +257,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     bload(b[0], 0);
     bload(b[1], 1);
     if (live_dead(alive)) return;                                      // (dead model: every load of the prologue is in flight, nothing stored yet)
+    // identical samples: the model's computed tiles are dealt over its XCDs anew; a workgroup whose tile moves loads that tile's rows
+    // (a second round trip, paid only by a batch that has rows to share: the word is 0 otherwise and was requested first)
+    DupPlan dup{0u, 0};
+    if (da.on) {
+        if (const unsigned dmask = dupm_mask(dword, da.B)) {
+            int tile = bx;
+            if (!dup_resolve_mask(dmask, da.B, da.tps, xX, xq, xsl, tile, dup)) return;      // beyond the computed tiles (uniform)
+            if (tile != bx) { m0 = tile * 32; wload(); }
+        }
+    }
 #pragma unroll
     for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
@@ -311,11 +329,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             const float pre = fmaf(ga, xh, be);
             const float g = pre > 0.f ? acc[r] + acc2[r] : 0.f;
             dbn[(size_t)m * 128 + cin] = g;
+            for (unsigned dm = dup.dups; dm; dm &= dm - 1u)           // the representative's tile: the same rows of every other sample of the mask
+                dbn[((size_t)m + (size_t)((__ffs((int)dm) - 1 - dup.rep) * da.rps)) * 128 + cin] = g;
             s1 += g; s2 += (double)g * xh;
         }
     }
     s1 += __shfl_xor(s1, 32);
     s2 += __shfl_xor(s2, 32);
+    if (dup.dups) { const double mul = (double)(1 + __popc(dup.dups)); s1 *= mul; s2 *= mul; }
     if (kq == 0) {
         atomicAdd(&stat_rep(p.s1, p.srep, p.sstride)[cin], s1);
         atomicAdd(&stat_rep(p.s2, p.srep, p.sstride)[cin], s2);
@@ -329,13 +350,26 @@ static inline bool conv3_bwd_data_mt_ok(int M, int ng, const Dims3& g, const Mms
     const int min32 = o.conv3_mt32_min > 0 ? o.conv3_mt32_min : 256;
     return M >= 1024 && (long)((M + 31) / 32) * ng >= min32;
 }
+// Identical samples: on for a launch whose samples are whole numbers of 32-row tiles, 2..32 of them, every member carrying its word.
+// which: the consumer's bit in MmsDnOpts.dup_zero_bwd (1 = backward-data, 2 = weight gradient; 0 = both)
+template <class P>
+static DupBwdArgs conv3_dup_bwd_args(const P* pp, int ng, const MmsDnOpts& o, int which) {
+    const P& p = *pp;
+    const long rps = (long)p.g.D * p.g.H * p.g.W;
+    DupBwdArgs da{0, 0, 0, 0};
+    if (o.dup_zero_bwd < 0 || (o.dup_zero_bwd != 0 && o.dup_zero_bwd != which)) return da;
+    if (rps <= 0 || rps % 32 != 0 || p.M % rps != 0 || p.M / rps > 32 || p.M / rps < 2) return da;
+    for (int g = 0; g < ng; ++g) if (!pp[g].dup) return da;
+    da.on = 1; da.B = (int)(p.M / rps); da.tps = (int)(rps / 32); da.rps = (int)rps;
+    return da;
+}
 template <bool PIN>
-static int launch_conv3_bwd_data_mt(const Conv3BwdDataP* pp, int ng, hipStream_t s) {
+static int launch_conv3_bwd_data_mt(const Conv3BwdDataP* pp, int ng, const MmsDnOpts& o, hipStream_t s) {
     const Conv3BwdDataP& p = *pp;
     const int smem = (3 * (32 + 2 * (p.g.W + 1)) + 1) * C3D_BP * (int)sizeof(float);      // W = 8: 21.7 KB, W = 16: 28.7 KB
     Grp<Conv3BwdDataP> a;
     grp_fill(a, pp, ng, 1);
-    MMS_LAUNCH((conv3_bwd_data_mt_kernel<PIN>), dim3((p.M + 31) / 32, 1, ng), dim3(256), smem, s, a);
+    MMS_LAUNCH((conv3_bwd_data_mt_kernel<PIN>), dim3((p.M + 31) / 32, 1, ng), dim3(256), smem, s, a, conv3_dup_bwd_args(pp, ng, o, 1));
     return mms_check_launch();
 }
 
@@ -364,7 +398,7 @@ extern "C" int mms_conv3_bwd_data_group(const Conv3BwdDataP* pp, int ng, const M
     if (conv3_bwd_data_mt_ok(p.M, ng, p.g, o)) {
         for (int g = 0; g < ng; ++g) if (pp[g].lddz % 4 != 0 || ((uintptr_t)pp[g].dz & 15) != 0) return MMS_ERR_ARG;     // dz rows are read with 16-byte loads
         // pinned schedule while the launch is at most one round of three workgroups per CU
-        return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_bwd_data_mt<true>(pp, ng, s) : launch_conv3_bwd_data_mt<false>(pp, ng, s);
+        return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_bwd_data_mt<true>(pp, ng, o, s) : launch_conv3_bwd_data_mt<false>(pp, ng, o, s);
     }
     if (mms_conv3_small_jn(p.M, ng, p.g, o)) return mms_c3s_bwd_data(pp, ng, o, s);      // small grids: 16-row tiles, all taps, no reduce launch
     return launch_tile_gemm<Conv3BwdDataOp<false>>(pp, ng, dim3((p.M + 31) / 32, 1, 1), s);
@@ -533,7 +567,7 @@ extern "C" int mms_unpack_conv3_grads(const void* table_host, int nlayers, hipSt
 #define C3W_AP 132                      // a2 image pitch (floats): [34][132]
 #define C3W_BP 36                       // dz image pitch: [32][36]
 #define C3W_STAGE (34 * C3W_AP + 32 * C3W_BP)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) void conv3_bwdw_mt_kernel(const Grp<Conv3BwdWP> grp) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) void conv3_bwdw_mt_kernel(const Grp<Conv3BwdWP> grp, const DupBwdArgs da) {
     // blockIdx.z = flat over (model, chunk, kd*3+kh); the 9 workgroups of a (model, chunk) pair share their rows: one XCD per pair
     int gi, z;
     {
@@ -546,6 +580,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     }
     const Conv3BwdWP& p = grp.p[gi];
     const unsigned alive = live_issue(p.live);
+    const unsigned dword = da.on ? dupm_issue(p.dup) : 0u;               // tested below, behind the BatchNorm constants' loads
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* vf = (float2*)(smem + 2 * C3W_STAGE);                      // per chunk row: 1/0 for "kw = 0 valid", "kw = 2 valid"
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
@@ -553,24 +588,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     const int offdh = ((kd - 1) * p.g.H + (kh - 1)) * p.g.W;
     int mc = (p.M + p.msplit - 1) / p.msplit;
     mc = (mc + 31) & ~31;
-    const int mb = chunk * mc, me = mb + mc < p.M ? mb + mc : p.M;
-    if (mb >= me) return;
+    int mb = chunk * mc, me = mb + mc < p.M ? mb + mc : p.M;
+    if (!da.on && mb >= me) return;
     const int c0 = (tid & 31) * 4;
     float mean[4], sc[4], beta[4];
     bn_consts4(p.bn, c0, mean, sc, beta);
     if (live_dead(alive)) return;
+    // Identical samples (MmsDnOpts.dup_zero_bwd): the chunks are taken over the COMPACTED row list -- the rows of every sample but the
+    // mask's higher ones (`keep`), whole samples of a multiple of 32 rows, so a 32-row step lies in one sample -- and the rows of the mask's
+    // lowest sample count once per sample of the mask (`mult`, on the staged dz rows).  mb / me are compacted row numbers then; rowof
+    // gives the actual row.  All of it uniform.
+    unsigned keep = 0u;                                                // 0 = off: compacted rows are the actual ones
+    int rep = -1;
+    float mult = 1.f;
+    if (da.on) {
+        if (const unsigned dmask = dupm_mask(dword, da.B)) {
+            rep = __ffs((int)dmask) - 1;
+            const unsigned dups = dmask & ~(1u << rep);
+            keep = (da.B >= 32 ? 0xffffffffu : (1u << da.B) - 1u) & ~dups;
+            mult = (float)__popc(dmask);
+            const int Mc = p.M - __popc(dups) * da.rps;
+            mc = (((Mc + p.msplit - 1) / p.msplit) + 31) & ~31;
+            mb = chunk * mc; me = mb + mc < Mc ? mb + mc : Mc;
+        }
+        if (mb >= me) return;                                          // (before any store)
+    }
+    auto rowof = [&](int c) __attribute__((always_inline)) { return keep ? nth_bit(keep, c / da.rps) * da.rps + c % da.rps : c; };
     // zero padding: the (kd, kh) part of a row's tap validity is common to the three taps and is folded into the staged dz
     // row; the kw part (kw = 1 is always valid) is a per-row factor pair read next to the dz fragment
     for (int j = tid; j < mc; j += 256) {
-        const unsigned mk = (mb + j < me) ? tap_mask9(p.coords[mb + j], p.g, false) : 0u;
+        const unsigned mk = (mb + j < me) ? tap_mask9(p.coords[rowof(mb + j)], p.g, false) : 0u;
         vf[j] = make_float2(mk & 64u ? 1.f : 0.f, mk & 256u ? 1.f : 0.f);
     }
     const unsigned selb = (1u << kd) | (8u << kh);
 
     float4 ra[5], rb;
     unsigned oka = 0;
-    bool okb = false;
-    auto gload = [&](int r0) __attribute__((always_inline)) {
+    float zb = 0.f;
+    auto gload = [&](int cr0) __attribute__((always_inline)) {         // the step at (compacted) row cr0
+        const int r0 = rowof(cr0), rend = r0 + (me - cr0);            // actual rows; the step's rows end with the chunk
+        const float scl = keep && r0 / da.rps == rep ? mult : 1.f;
         oka = 0;
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
@@ -580,8 +637,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
             ra[i] = ok ? *(const float4*)(p.y1 + (size_t)src * 128 + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         const int m = r0 + (tid >> 3);
-        rb = m < me ? *(const float4*)(p.dz + (size_t)m * p.lddz + (tid & 7) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        okb = m < me && (tap_mask9(p.coords[m], p.g, false) & selb) == selb;
+        rb = m < rend ? *(const float4*)(p.dz + (size_t)m * p.lddz + (tid & 7) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        zb = m < rend && (tap_mask9(p.coords[m], p.g, false) & selb) == selb ? scl : 0.f;
     };
     auto sstore = [&](float* st) __attribute__((always_inline)) {
 #pragma unroll
@@ -594,7 +651,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
                                 zf * fmaxf(bn_apply(ra[i].z, mean[2], sc[2], beta[2]), 0.f), zf * fmaxf(bn_apply(ra[i].w, mean[3], sc[3], beta[3]), 0.f));
             }
         }
-        const float zb = okb ? 1.f : 0.f;
         *(float4*)&st[34 * C3W_AP + (tid >> 3) * C3W_BP + (tid & 7) * 4] = make_float4(zb * rb.x, zb * rb.y, zb * rb.z, zb * rb.w);
     };
     f32x16 acc0, acc1, acc2;
@@ -695,7 +751,7 @@ extern "C" int mms_conv3_bwd_weight_group(const Conv3BwdWP* pp, int ng, const Mm
         constexpr int smem = (2 * C3W_STAGE + 2 * 1024) * (int)sizeof(float);        // 53.3 KB: 3 workgroups per CU
         Grp<Conv3BwdWP> a;
         if (!grp_fill(a, pp, ng, 9 * p.msplit)) return MMS_ERR_ARG;
-        MMS_LAUNCH(conv3_bwdw_mt_kernel, dim3(1, 1, 9 * p.msplit * ng), dim3(256), smem, s, a);
+        MMS_LAUNCH(conv3_bwdw_mt_kernel, dim3(1, 1, 9 * p.msplit * ng), dim3(256), smem, s, a, conv3_dup_bwd_args(pp, ng, o, 2));
         return mms_check_launch();
     }
     return launch_tile_gemm<Conv3BwdWOp>(pp, ng, dim3(1, 1, 27 * p.msplit), s);
@@ -1238,19 +1294,41 @@ __global__ __launch_bounds__(256) void head_bwd_feat_kernel(const Grp<HeadBwdP> 
     }
 }
 #define HEAD_LIVE_SCAN 16384
-__global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp, const LiveTab lt) {
+// the models' zero-sample words, the boxes per sample and the "bwd_dup" words to write (mms_head_bwd_group_dup), by value beside the Grp<>
+struct DupOutTab { const unsigned* zw[MMS_MAX_GROUP]; unsigned* out[MMS_MAX_GROUP]; unsigned zbps; };
+__global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp, const LiveTab lt, const DupOutTab dt) {
     const HeadBwdP& p = grp.p[blockIdx.z];
     // the model's "bwd_live" word (mms_head_bwd_group_live; read by every later launch of the backward): 1 if any of the B x N elements of
     // dout compares unequal to 0.0f.  Workgroup 0 scans dout -- a few loads per thread up to HEAD_LIVE_SCAN elements; a larger dout is
     // not scanned and counts as live.  The head launches themselves always do their work: with dout == 0 they write the zeros that the
     // later launches would read.
+    // The same scan gives the "bwd_dup" word (MmsDnOpts.dup_zero_bwd): every thread notes the rows (bit b & 31) in which it met a non-zero
+    // element, each wave ORs its notes and leaves them in its own LDS word ahead of the vote's barrier (no barrier of its own), and the word
+    // is the zero samples whose bit stayed clear -- if there are two of them.  The zero-sample words are requested before the scan.
     unsigned* const live_out = (unsigned*)lt.w[blockIdx.z];
-    if (blockIdx.x == 0 && live_out) {
+    unsigned* const dup_out = dt.out[blockIdx.z];
+    if (blockIdx.x == 0 && (live_out || dup_out)) {
+        __shared__ unsigned nzrows[4];
         const int n_el = p.B * p.N;
-        int any = n_el > HEAD_LIVE_SCAN;
-        if (!any) for (int i = threadIdx.x; i < n_el; i += 256) any |= p.dout[(i / p.N) * p.lddout + i % p.N] != 0.0f;      // NaN: unequal; -0.0f: equal
-        any = __syncthreads_or(any);
-        if (threadIdx.x == 0) __hip_atomic_store(live_out, any ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool scan = n_el <= HEAD_LIVE_SCAN;
+        const unsigned* zw = dt.zw[blockIdx.z];
+        const bool dup_ok = dup_out && zw && scan && p.B <= 32 && dt.zbps > 0;
+        const unsigned word = (dup_ok && (int)threadIdx.x < p.B) ? zw[threadIdx.x] : 0xffffffffu;
+        unsigned nz = 0;
+        if (scan) for (int i = threadIdx.x; i < n_el; i += 256) nz |= (p.dout[(i / p.N) * p.lddout + i % p.N] != 0.0f ? 1u : 0u) << ((i / p.N) & 31);   // NaN: unequal; -0.0f: equal
+        if (dup_ok) {
+            unsigned w = nz;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) w |= (unsigned)__shfl_xor((int)w, o, 64);
+            if ((threadIdx.x & 63) == 0) nzrows[threadIdx.x >> 6] = w;
+        }
+        const int any = __syncthreads_or(!scan || nz != 0u);
+        if (threadIdx.x == 0 && live_out) __hip_atomic_store(live_out, any ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x < 64 && dup_out) {                                // wave 0: lanes < B hold the samples' words
+            unsigned d = dup_ok ? (unsigned)__ballot(word == dt.zbps) & ~(nzrows[0] | nzrows[1] | nzrows[2] | nzrows[3]) : 0u;
+            if (__popc(d) < 2) d = 0u;
+            if (threadIdx.x == 0) __hip_atomic_store(dup_out, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.N * p.C) return;
@@ -1264,8 +1342,13 @@ __global__ __launch_bounds__(256) void head_bwd_w_kernel(const Grp<HeadBwdP> grp
         p.dbias[n] += d;
     }
 }
-extern "C" int mms_head_bwd_group(const HeadBwdP* pp, int ng, hipStream_t s) { return mms_head_bwd_group_live(pp, nullptr, ng, s); }
+static_assert(sizeof(Grp<HeadBwdP>) + sizeof(LiveTab) + sizeof(DupOutTab) <= 4096, "kernel-argument segment");
+extern "C" int mms_head_bwd_group(const HeadBwdP* pp, int ng, hipStream_t s) { return mms_head_bwd_group_dup(pp, nullptr, nullptr, 0, nullptr, ng, s); }
 extern "C" int mms_head_bwd_group_live(const HeadBwdP* pp, unsigned* const* live_out, int ng, hipStream_t s) {
+    return mms_head_bwd_group_dup(pp, live_out, nullptr, 0, nullptr, ng, s);
+}
+extern "C" int mms_head_bwd_group_dup(const HeadBwdP* pp, unsigned* const* live_out, const unsigned* const* zwords, int zbps, unsigned* const* dup_out,
+                                      int ng, hipStream_t s) {
     Grp<HeadBwdP> a;
     if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
     const HeadBwdP& p = *pp;
@@ -1274,8 +1357,11 @@ extern "C" int mms_head_bwd_group_live(const HeadBwdP* pp, unsigned* const* live
         const HeadBwdP& q = pp[g];
         if (q.B != p.B || q.C != p.C || q.N != p.N || q.V != p.V) return MMS_ERR_ARG;
     }
+    DupOutTab dt{};
+    dt.zbps = zbps > 0 ? (unsigned)zbps : 0u;
+    for (int g = 0; dup_out && g < ng; ++g) { dt.out[g] = dup_out[g]; dt.zw[g] = zwords ? zwords[g] : nullptr; }
     MMS_LAUNCH(head_bwd_feat_kernel, dim3((p.C + 63) / 64, 1, ng), dim3(256), 0, s, a);
-    MMS_LAUNCH(head_bwd_w_kernel, dim3((p.N * p.C + 255) / 256, 1, ng), dim3(256), 0, s, a, live_tab((const unsigned* const*)live_out, ng));
+    MMS_LAUNCH(head_bwd_w_kernel, dim3((p.N * p.C + 255) / 256, 1, ng), dim3(256), 0, s, a, live_tab((const unsigned* const*)live_out, ng), dt);
     return mms_check_launch();
 }
 MMS_SINGLE(mms_head_bwd, HeadBwdP)
@@ -1331,7 +1417,7 @@ extern "C" int mms_head_bwd_apply(const HeadBwdP* pp, hipStream_t s) {
     Grp<HeadBwdP> a;
     if (!grp_fill(a, pp, 1, 1)) return MMS_ERR_ARG;
     MMS_LAUNCH(head_bwd_apply_kernel, dim3((pp->C + 255) / 256), dim3(256), 0, s, *pp);
-    MMS_LAUNCH(head_bwd_w_kernel, dim3((pp->N * pp->C + 255) / 256, 1, 1), dim3(256), 0, s, a, LiveTab{});      // (SyncBN: no word)
+    MMS_LAUNCH(head_bwd_w_kernel, dim3((pp->N * pp->C + 255) / 256, 1, 1), dim3(256), 0, s, a, LiveTab{}, DupOutTab{});      // (SyncBN: no words)
     return mms_check_launch();
 }
 

@@ -46,6 +46,7 @@ struct Plan {
     size_t cl_xa[NB], cl_xb[NB], cl_gst[NB], cl_tab[NB], cl_zero_begin, cl_ga, cl_gz;
     size_t b4_err;
     size_t bwd_live;                // one word: the head launch of the backward found a non-zero element in dout (MmsDnOpts.skip_dead_bwd)
+    size_t bwd_dup;                 // one word: the samples whose gradient rows are identical, as the same launch found them (MmsDnOpts.dup_zero_bwd)
     size_t zw;                      // zero-box counts of the samples (MmsDnOpts.dup_zero), 64 words right behind hx (inside the per-step zeroed region)
     size_t hx;                      // arrival words of the fused block-3 forward launches, one per dense layer (inside the per-step zeroed region)
     size_t bb_y0, bb_y1[NLAYER], bb_in[NLAYER], bb_tr[3], bb_head;   // backward (s1 | s2)
@@ -146,6 +147,7 @@ bool make_plan(Plan& P, int B, int D, int H, int W) {
     P.counters = take(4096 * 4);
     P.b4_err = take(1024);
     P.bwd_live = take(4);           // outside the per-step zeroed region: written by every backward that reads it
+    P.bwd_dup = take(4);            // likewise
     for (int b = 0; b < NB; ++b) P.cl_tab[b] = take(sizeof(B4Layer) * LAYERS[b]);
     P.total = o;
     return true;
@@ -259,6 +261,7 @@ extern "C" int mms_dn121_region(int B, int D, int H, int W, const char* name, in
     if (!strcmp(name, "hx")) return set(P.hx, 256);
     if (!strcmp(name, "zero_words")) return set(P.zw, 256);
     if (!strcmp(name, "bwd_live")) return set(P.bwd_live, 4);
+    if (!strcmp(name, "bwd_dup")) return set(P.bwd_dup, 4);
     return MMS_ERR_ARG;
 }
 
@@ -601,15 +604,22 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
     auto lv = [&](const Ctx& c) -> unsigned* { return skip_dead ? at<unsigned>(c.ws, P.bwd_live) : nullptr; };
     const unsigned* lvs[MMS_MAX_GROUP];     // the same words as an array, for the launches that take them beside their parameter blocks
     FOR_G lvs[g] = lv(cx[g]);
+    // Identical samples (MmsDnOpts.dup_zero_bwd): the same head launch leaves the bit mask of the zero samples with a zero row of dout in
+    // the word "bwd_dup", and block 1's conv2 launches carry its address.  Under the conditions of the word above (this call's head launch
+    // writes it; no SyncBN, no hook, no stage) and of the forward's dup_zero, whose zero-sample words it is made from.
+    const bool dup_bwd = skip_dead && o.dup_zero_bwd >= 0 && o.dup_zero >= 0 && dp.bn_world == 1 && B >= 2 && B <= 32;
+    auto dv = [&](const Ctx& c) -> unsigned* { return dup_bwd ? at<unsigned>(c.ws, P.bwd_dup) : nullptr; };
     if (dp.b_hi == NB - 1) {
         HeadBwdP hb[MMS_MAX_GROUP];
         unsigned* hlive[MMS_MAX_GROUP];
+        unsigned* hdup[MMS_MAX_GROUP];
+        const unsigned* hzw[MMS_MAX_GROUP];
         FOR_G {
             const Ctx& c = cx[g];
             hb[g] = HeadBwdP{c.dout, lddout, at<float>(c.ws, P.pooled), at<float>(c.ws, P.slab[3]), CTOT[3], 1024, B, P.M[3] / B,
                              mk_bn(c.ws, P.st_slab[3], CTOT[3], c.prm, IDX.n5w, nullptr, 0, P.M[3] * bnw, 1, P.R[3]), c.prm[IDX.outw], nout,
                              c.grd[IDX.outw], c.grd[IDX.outb], c.grd[IDX.n5w], c.grd[IDX.n5b], at<float>(c.ws, P.dslab[3]), CTOT[3]};
-            hlive[g] = lv(c);
+            hlive[g] = lv(c); hdup[g] = dv(c); hzw[g] = at<unsigned>(c.ws, P.zw);
         }
         if (sync) {     // norm5's backward sums must span all ranks: sums kernel | all-reduce | apply kernel
             hb[0].ext_sums = at<double>(cx[0].ws, P.bb_head);
@@ -617,7 +627,7 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
             SYNC(at<double>(cx[0].ws, P.bb_head), 1, 2 * 1024, 1024, 1024);
             TRY(mms_head_bwd_apply(hb, s));
         } else {
-            TRY(mms_head_bwd_group_live(hb, hlive, ng, s));
+            TRY(mms_head_bwd_group_dup(hb, hlive, hzw, (P.g0.D / 4) * (P.g0.H / 4) * (P.g0.W / 4), dup_bwd ? hdup : nullptr, ng, s));
         }
     }
     // Weight gradients are off the backward's critical chain (nothing reads them before the optimiser).  In blocks 2-4 a
@@ -718,8 +728,9 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                                       at<double>(c.ws, P.bb_y1[l]), at<double>(c.ws, P.bb_y1[l]) + 128,
                                       ns3 > 1 ? at<float>(c.ws, P.partial) : nullptr, ns3};
                 bd[g].srep = P.R[b]; bd[g].sstride = 2 * 128; bd[g].wfrag = conv3_frag_block(P, b, ng, o) ? 1 : 0; bd[g].live = lv(c);
+                bd[g].dup = b == 0 ? dv(c) : nullptr;
                 bw[g] = Conv3BwdWP{at<float>(c.ws, P.y1[l]), at<int>(c.ws, P.coords[b]), P.g[b], M, bn2, dslab + C, CTOT[b],
-                                   packed ? c.grd[ip + 5] : at<float>(c.ws, P.dwp[l]), ms3, packed ? 2 : 1, lv(c)};
+                                   packed ? c.grd[ip + 5] : at<float>(c.ws, P.dwp[l]), ms3, packed ? 2 : 1, lv(c), b == 0 ? dv(c) : nullptr};
                 Conv1BwdP& q = c1[g];
                 q = Conv1BwdP{};
                 q.dyraw = dmid; q.lddy = 128;
