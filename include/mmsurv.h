@@ -510,6 +510,30 @@ typedef struct CindexP {
     unsigned long long* counts;     // [3], zeroed by the caller
 } CindexP;
 
+/* Weighted (bootstrap) Harrell-C pair counts of M models on R multiplicity vectors, exact integers (csrc/cindex_boot.hip).
+ * A replicate that drew patient i w_i times has  2*concordant + tied = sum_ij w_i w_j S[i][j]  and  comparable = sum_ij w_i w_j P[i][j],
+ * P[i][j] = [pair (i, j) is comparable, i the member with the observed earlier event], S = P o (2 [hrank_i > hrank_j] + [hrank_i == hrank_j]):
+ * what counting pairs on the literally resampled arrays gives.  The kernel forms W.S and W.P on the int8 matrix cores without ever storing
+ * an n x n matrix (memory: the arguments only) and compares integer ranks, so ties are exactly the caller's ties.
+ * Ranks: 0 <= rank < 2^31 - 1 (dense ranks as of numpy.unique(return_inverse=True)).  Limits: 1 <= n <= MMS_CBOOT_MAX_N, which keeps the
+ * int32 column sums (<= 2 * 127 * n) in range for every permitted w; 1 <= R <= MMS_CBOOT_MAX_R; 1 <= M <= MMS_CBOOT_MAX_M.  The input may be
+ * in any order (time-sorted input lets the kernel skip about half of its tiles).  w 16-byte, out 8-byte, the int arrays 4-byte aligned.
+ * A NULL required pointer, a size out of range, ldw < n or not a multiple of 64, ldh < n, a misaligned pointer or an unknown pair_rule:
+ * MMS_ERR_ARG before any launch.  The adds into `out` are integer atomics: two calls give the same numbers. */
+#define MMS_CBOOT_MAX_N 1048576
+#define MMS_CBOOT_MAX_R 1048576
+#define MMS_CBOOT_MAX_M 8
+typedef struct CbootP {
+    const int* hrank; int ldh; int M;   // [M][ldh] order-preserving dense integer ranks of the risk scores (higher = higher risk), 1 <= M <= 8
+    const int* trank;                   // [n] dense ranks of the survival times
+    const int* event;                   // [n] 0 / 1
+    const int* stratum;                 // [n] or NULL: pairs count only inside one stratum (out-of-fold predictions of different folds' models)
+    int n;
+    const signed char* w; int ldw; int R;  // [R][ldw] multiplicities 0..127; ldw % 64 == 0, bytes n..ldw-1 of every row zero
+    long long* out;                     // [M+1][R], zeroed by the caller: row m < M: 2*concordant + tied of model m; row M: comparable pairs
+    int pair_rule;                      // 0: e_i && t_j > t_i (mms_cindex_counts' rule); 1: lifelines' -- additionally e_i && !e_j && t_i == t_j
+} CbootP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -802,6 +826,7 @@ int mms_cox_fwd_bwd(const CoxP* p, hipStream_t s);
 int mms_moe_fwd(const MoeP* p, hipStream_t s);                 /* R/scripts/analysis/generate_km_curves.py:262-281 (MoeP above) */
 int mms_moe_bwd(const MoeP* p, hipStream_t s);
 int mms_cindex_counts(const CindexP* p, hipStream_t s);
+int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / weighted pair counts of M models x R replicates (CbootP above) */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */
 int mms_w2_pack(const AdamP* p, hipStream_t s);                /* the derived conv2 packs alone, from the current weights (after load_state_dict / any external update) */

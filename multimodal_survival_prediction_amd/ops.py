@@ -277,6 +277,31 @@ def cindex_counts(h, time, event):
     return counts
 
 
+def cindex_boot(hrank, trank, event, w, stratum=None, pair_rule=0):
+    """Weighted (bootstrap) Harrell-C pair counts (CbootP in mmsurv.h).  hrank: int32 [M, n] (or [n]) dense ranks of the risk scores, trank /
+    event / stratum: int32 [n], w: int8 [R, n] multiplicities 0..127 -> int64 [M + 1, R]: row m = 2*concordant + tied of model m, row M =
+    comparable pairs.  w is padded here to the 64-byte row length the kernel reads."""
+    hrank = hrank.reshape(1, -1) if hrank.dim() == 1 else hrank
+    M, n = hrank.shape
+    if w.dim() != 2 or w.shape[1] != n or w.dtype != torch.int8:
+        raise ValueError("w must be int8 [R, n]")
+    if trank.numel() != n or event.numel() != n or (stratum is not None and stratum.numel() != n):
+        raise ValueError("trank / event / stratum must have n = %d elements" % n)
+    dev = hrank.device
+    i32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.int32).contiguous()
+    hrank, trank, event, stratum = i32(hrank), i32(trank), i32(event), i32(stratum)
+    R, ldw = w.shape[0], (n + 63) // 64 * 64
+    if ldw == n and w.is_contiguous() and w.data_ptr() % 16 == 0:
+        wp = w
+    else:
+        wp = torch.zeros(R, ldw, dtype=torch.int8, device=dev)
+        wp[:, :n] = w
+    out = torch.zeros(M + 1, R, dtype=torch.int64, device=dev)
+    p = _S()["CbootP"](ptr(hrank), n, M, ptr(trank), ptr(event), ptr(stratum), n, ptr(wp), ldw, R, ptr(out), int(pair_rule))
+    call("mms_cindex_boot", p)
+    return out
+
+
 def adam_params(p_, g, m, v, hyper, sumsq, step, skip_flag=None, adamw=False, acc=None, cox_out=None, entropy=None,
                 rng=None, w2=None):
     """w2: None or dict(off=int64[n] device tensor, pack_b=ptr table (int64[n] device tensor of addresses), pack_f=the same,

@@ -13,11 +13,17 @@ and the Kaplan-Meier tables as CSV.
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute
     python scripts/analysis/evaluate_model.py --ensemble models/final/fold_*_best.pth --model final [--combine rank] [--attribute]
+    python scripts/analysis/evaluate_model.py --bootstrap 2000 [--seed 0] [--compare other_model/test_predictions.csv ...]
 
 --predict runs the checkpoint's eval-mode forward on the MI355X (the HIP path; no CPU fallback) over the validation split
 of that fold of the cohort the training entry points use (data/processed/* under MMS_DATA_ROOT when present, else the seeded
 synthetic cohort) and writes results/test_predictions.csv first.  lifelines/seaborn are not needed: the statistics are the
 numpy restatements in multimodal_survival_prediction_amd/survival_stats.py.
+
+--bootstrap R adds "c_index_bootstrap" to the summary: the percentile interval of the C-index over R patient resamples (on the MI355X:
+multimodal_survival_prediction_amd/bootstrap.py), for a file with risk_fold_* columns each member's C-index and the paired difference
+ensemble - member, and with --compare the paired difference of this file's risk_score against every other file's on the same patients.
+A `fold` column, when present, stratifies both the pairs and the resampling.  Without --bootstrap nothing changes.
 """
 import argparse
 import json
@@ -195,8 +201,34 @@ def predict_ensemble(checkpoints, kind, combine, batch_size, out_csv, attribute_
     return df
 
 
-def evaluate(df, outdir="results", plots=True):
-    """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics)."""
+def bootstrap_summary(df, replicates, seed=0, compare=(), alpha=0.05):
+    """-> the "c_index_bootstrap" entry: one paired bootstrap over risk_score, the risk_fold_* members and the --compare files' risk_score."""
+    from multimodal_survival_prediction_amd.bootstrap import cindex_bootstrap
+    members = sorted((c for c in df.columns if c.startswith("risk_fold_")), key=lambda c: int(c.rsplit("_", 1)[1]))
+    rows, others = [df["risk_score"].to_numpy(float)] + [df[c].to_numpy(float) for c in members], []
+    for path in compare:
+        if "patient_id" not in df.columns:
+            raise ValueError("--compare joins on patient_id, which the predictions file does not have")
+        o = pd.read_csv(path)
+        if o["patient_id"].duplicated().any() or df["patient_id"].duplicated().any() or set(o["patient_id"]) != set(df["patient_id"]):
+            raise ValueError(f"{path}: the patient sets differ (a paired comparison scores every model on the same patients)")
+        others.append(path)
+        rows.append(o.set_index("patient_id").loc[df["patient_id"], "risk_score"].to_numpy(float))
+    res = cindex_bootstrap(np.stack(rows), df["survival_time"].to_numpy(float), df["event"].to_numpy(int), R=replicates, seed=seed,
+                           strata=df["fold"].to_numpy() if "fold" in df.columns else None, pair_rule="lifelines", alpha=alpha)
+    paired = lambda a, b: {"delta": float(res.delta[a, b]), "low": float(res.delta_ci_low[a, b]), "high": float(res.delta_ci_high[a, b]),
+                           "p_value": float(res.p_value[a, b])}
+    out = {"replicates": int(replicates), "seed": int(seed), "alpha": float(alpha), "low": float(res.ci_low[0]), "high": float(res.ci_high[0]),
+           "se": float(res.se[0]), "n_degenerate": int(res.n_degenerate)}
+    if members:
+        out["members"] = {c: dict(c_index=float(res.c[1 + k]), **paired(0, 1 + k)) for k, c in enumerate(members)}
+    if others:
+        out["compare"] = {path: dict(c_index=float(res.c[1 + len(members) + k]), **paired(0, 1 + len(members) + k)) for k, path in enumerate(others)}
+    return out
+
+
+def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=()):
+    """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics; bootstrap > 0: + c_index_bootstrap)."""
     t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
     c_index = SS.concordance_index(t, -r, e)
     group = SS.risk_groups(r)
@@ -221,6 +253,8 @@ def evaluate(df, outdir="results", plots=True):
         times, surv, at_risk, deaths = SS.kaplan_meier(t[m], e[m])
         km_rows += [dict(group=name, time=a, survival=b, at_risk=int(c), events=int(d)) for a, b, c, d in zip(times, surv, at_risk, deaths)]
     pd.DataFrame(km_rows).to_csv(os.path.join(outdir, "kaplan_meier_table.csv"), index=False)
+    if bootstrap:
+        summary["c_index_bootstrap"] = bootstrap_summary(df, bootstrap, seed, compare)
     with open(os.path.join(outdir, "evaluation_summary.json"), "w") as f:
         json.dump(summary, f, indent=2)
     if plots:
@@ -280,7 +314,18 @@ def main(argv=None):
     ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv; "
                     "with --ensemble: the members' mean (<id>_ct.npy) and spread (<id>_ct_std.npy) and the mean gradient's gene_scores.csv")
     ap.add_argument("--top", type=int, default=50, help="rows of gene_scores.csv")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                    help="R bootstrap resamples of the patients (on the GPU): adds c_index_bootstrap {replicates, seed, alpha, low, high, se, "
+                         "n_degenerate} to the summary, and for risk_fold_* columns each member's C-index and ensemble - member with CI and p-value")
+    ap.add_argument("--seed", type=int, default=0, help="with --bootstrap: seed of numpy.random.default_rng")
+    ap.add_argument("--compare", metavar="OTHER.csv", nargs="+", default=[],
+                    help="with --bootstrap: other models' predictions of the SAME patients (joined on patient_id); adds the paired difference "
+                         "of this file's risk_score against each, with CI and p-value")
     a = ap.parse_args(argv)
+    if a.compare and not a.bootstrap:
+        ap.error("--compare needs --bootstrap R (the comparison is a paired bootstrap)")
+    if a.bootstrap < 0:
+        ap.error("--bootstrap needs a positive number of replicates")
     if a.attribute and not (a.predict or a.ensemble):
         ap.error("--attribute needs --predict CHECKPOINT (the gradients are taken on the checkpoint's model)")
     if a.predict and a.ensemble:
@@ -290,10 +335,16 @@ def main(argv=None):
         df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
     else:
         df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top) if a.predict else pd.read_csv(a.predictions)
-    s = evaluate(df, a.outdir, plots=not a.no_plots)
+    s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
           f"log-rank chi2 {s['logrank']['chi2']:.3f} p {s['logrank']['p_value']:.3g}")
+    if a.bootstrap:
+        b = s["c_index_bootstrap"]
+        print(f"C-index {s['c_index']:.4f}, {100 * (1 - b['alpha']):.0f} % CI {b['low']:.4f}-{b['high']:.4f} (SE {b['se']:.4f}; {b['replicates']} resamples, "
+              f"seed {b['seed']}, {b['n_degenerate']} degenerate)")
+        for name, m in list(b.get("members", {}).items()) + list(b.get("compare", {}).items()):
+            print(f"  vs {name}: C {m['c_index']:.4f}, difference {m['delta']:+.4f} (CI {m['low']:+.4f}..{m['high']:+.4f}, p = {m['p_value']:.3g})")
     print(f"saved {os.path.join(a.outdir, 'evaluation_summary.json')}, kaplan_meier_table.csv" + ("" if a.no_plots else ", figures"))
     return s
 
