@@ -534,6 +534,27 @@ typedef struct CbootP {
     int pair_rule;                      // 0: e_i && t_j > t_i (mms_cindex_counts' rule); 1: lifelines' -- additionally e_i && !e_j && t_i == t_j
 } CbootP;
 
+/* Univariate Cox score screen (csrc/gene_screen.hip): the partial-likelihood score test of every gene at beta = 0, Breslow ties, on P
+ * problems in one launch.  A problem p is the ordered list row[off[p] .. off[p+1]) of patient rows of x, TIME DESCENDING (a fold's
+ * training patients or a bootstrap resample of them: a row may repeat, a repeat is a tie).  With S1_k the running sum of the list's
+ * first k + 1 rows of gene j,   U[p][j] = sum_k a_k x_kj,   V[p][j] = sum_k b_k x_kj^2 - sum_k q_k S1_kj^2;   the statistic U^2 / V is
+ * chi-square with one degree of freedom.  coef[k] = {a_k, b_k, q_k} depend on the labels only and are computed by the host in fp64
+ * (gene_select.score_coefficients): b_k = sum over the event times u <= t_k of d_u / n_u, a_k = e_k - b_k, q_k = d_u / n_u^2 at the
+ * last position of event time u's tie group and 0 elsewhere (d_u events at u, n_u rows with t >= u).
+ * fp64 accumulation, no atomics, plain stores; a problem's bits do not depend on the other problems of the launch.  P = 0 and empty
+ * problems are valid (U = V = 0).  The launch cannot read row / off: the CALLER guarantees 0 <= row < N and off non-decreasing from 0
+ * (ops.gene_screen checks both on the host).  A NULL pointer, P < 0, G < 1, G > MMS_GENE_SCREEN_MAX_G, ld < G, N < 1 or a pointer not
+ * aligned to its element: MMS_ERR_ARG before any launch. */
+#define MMS_GENE_SCREEN_MAX_G 4194240  /* 65535 strips of 64 genes (grid y) */
+typedef struct GeneScreenP {
+    const float* x; int N; int ld;      // [N][ld] fp32 (device), the first G columns are screened
+    int G; int P;
+    const int* off;                     // [P+1] problem p = positions off[p] .. off[p+1]-1 of row / coef
+    const int* row;                     // [off[P]] patient rows in risk order
+    const double* coef;                 // [off[P]][3] a, b, q
+    double* U; double* V;               // [P][G] out (every element written)
+} GeneScreenP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -827,6 +848,7 @@ int mms_moe_fwd(const MoeP* p, hipStream_t s);                 /* R/scripts/anal
 int mms_moe_bwd(const MoeP* p, hipStream_t s);
 int mms_cindex_counts(const CindexP* p, hipStream_t s);
 int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / weighted pair counts of M models x R replicates (CbootP above) */
+int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox score test of G genes on P problems (GeneScreenP above) */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */
 int mms_w2_pack(const AdamP* p, hipStream_t s);                /* the derived conv2 packs alone, from the current weights (after load_state_dict / any external update) */

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import augment as _augment
+from .gene_select import fold_matrix as _fold_matrix
 
 COHORT_608 = dict(n=608, imaging=142, rnaseq=427, clinical=587, survival=348, complete=109)   # R/README.md:21-25
 
@@ -100,11 +101,15 @@ class BatchLoader:
     A lazy loader adds augment=<records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them inside its
     gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both yield the
     same augmented batches.  A spec with rot / zoom / noise (AugmentSpec.has_affine) draws a second, 16-word record per row: a lazy loader
-    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  augment_style: the model style ("partial", "final", ...) the spec is checked against."""
+    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  augment_style: the model style ("partial", "final", ...) the spec is checked against.
+    fold: which cross-validation fold the loader belongs to.  Only read over a cohort that carries per-fold gene matrices
+    (gene_select.GeneSelection.apply): the batches a loader materialises itself then take their rnaseq rows from that fold's [N, k]
+    matrix (a lazy loader names rows only; the fold group's gather launch picks the matrix, FoldGroupEngine(folds=))."""
 
     def __init__(self, cohort, indices, batch_size, shuffle=False, seed=0, style="final", lazy=False, with_valid=True, augment=None,
-                 augment_style=None):
+                 augment_style=None, fold=None):
         self.c, self.idx, self.bs, self.shuffle, self.style = cohort, torch.as_tensor(indices), batch_size, shuffle, style
+        self.fold = fold
         self.gen = torch.Generator().manual_seed(seed)
         self.lazy = lazy
         self.augment = _augment.as_spec(augment)
@@ -159,7 +164,8 @@ class BatchLoader:
                 yield b
                 continue
             j = idx[i:i + self.bs].to(dev)
-            b = dict(image=self.c["image"][j], rnaseq=self.c["rnaseq"][j], clinical=self.c["clinical"][j],
+            rna = self.c["rnaseq"] if "rnaseq_folds" not in self.c else _fold_matrix(self.c, self.fold)
+            b = dict(image=self.c["image"][j], rnaseq=rna[j], clinical=self.c["clinical"][j],
                      label=self.c["label"][j], mask=self.c["mask"][j], has_survival=self.c["has_survival"][j].tolist())
             if self.style == "simple":   # simple_fusion.py:152-153
                 b["time"] = self.c["label"][j, 0:1]

@@ -780,28 +780,29 @@ class SurvivalEngine:
         else:
             P.valid.copy_(valid.reshape(-1).to(torch.float32), non_blocking=True)
 
-    def gather_block(self, P, cohort, idx_dev):
+    def gather_block(self, P, cohort, idx_dev, fold=None):
         """GatherP (include/mmsurv.h) that assembles this plan's batch from a cohort dict (data.make_cohort) that lives in HBM
         (data.cohort_to) or in pinned host memory (data.cohort_pin: the gather launch then reads the rows over PCIe): image, rnaseq,
         clinical, mask, label[time, event] and, when present, a float per-patient `valid` column.  idx_dev: [B] int64 device tensor
         that the caller refills before each launch.  With a modality mask in the cohort, image / rnaseq rows of patients without that
         modality are zero-filled instead of read -- after checking once that they are all-zero in the cohort, as the reference's
-        dataset makes them (partial_modality_training.py:96-141)."""
-        G, _ = self._gather_sources(P, cohort, idx_dev)
+        dataset makes them (partial_modality_training.py:96-141).  fold: over a cohort with per-fold gene matrices
+        (gene_select.GeneSelection.apply) the rnaseq source -- pointer, pitch and width -- is that fold's [N, k] matrix."""
+        G, _ = self._gather_sources(P, cohort, idx_dev, fold)
         return G
 
-    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev, aff_dev=None):
+    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev, aff_dev=None, fold=None):
         """(GatherP, AugP) of mms_gather_aug_group: gather_block's sources plus what each of them is to the augmentation records
         rec_dev ([B, 8] int32 device tensor, augment.make_records) -- the CT volume, a row that modality j's drop bit zero-fills,
         a mask whose column j that bit clears.  time / event / valid are plain copies.  aff_dev ([B, 16] int32 device tensor,
         augment.affine_records): -> (GatherP, AugP, AffP), the blocks of mms_gather_affine_group."""
         from . import augment
-        G, roles = self._gather_sources(P, cohort, idx_dev)
+        G, roles = self._gather_sources(P, cohort, idx_dev, fold)
         dims = tuple(P.ct.shape[-3:]) if P.has_enc else None
         A = augment.aug_block(rec_dev, roles, dims, (0, 0, 0))
         return (G, A) if aff_dev is None else (G, A, augment.aff_block(aff_dev))
 
-    def _gather_sources(self, P, cohort, idx_dev):
+    def _gather_sources(self, P, cohort, idx_dev, fold=None):
         """-> (GatherP, per source (augment role, drop bit)).  A source is (cohort tensor, destination, width or None = all columns,
         availability flags or None, role, modality whose drop bit zero-fills it or -1)."""
         from .augment import ROLE_MASK, ROLE_PLAIN, ROLE_VOLUME
@@ -816,7 +817,15 @@ class SurvivalEngine:
                     chk[key] = bool((cohort[key][gone] == 0).all()) if bool(gone.any()) else True
                 if chk[key]:
                     flags[key] = cohort["mask"][:, j:]
-        srcs = [(cohort["rnaseq"], P.buf["rna"], None, flags.get("rnaseq"), ROLE_PLAIN, 1)] if "rna" in P.buf else []
+        srcs = []
+        if "rna" in P.buf:
+            rna = cohort["rnaseq"]
+            if "rnaseq_folds" in cohort:         # per-fold gene selection: this member's own [N, k] matrix (a zero row keeps zero columns)
+                from .gene_select import fold_matrix
+                rna = fold_matrix(cohort, fold)
+            if rna.shape[1] != P.buf["rna"].shape[1]:
+                raise ValueError("the model reads %d RNA-seq columns, the cohort's matrix has %d" % (P.buf["rna"].shape[1], rna.shape[1]))
+            srcs.append((rna, P.buf["rna"], None, flags.get("rnaseq"), ROLE_PLAIN, 1))
         if P.has_enc:
             srcs.append((cohort["image"].view(cohort["image"].shape[0], -1), P.ct.view(P.B, -1), None, flags.get("image"), ROLE_VOLUME, 0))
         if "clin" in P.buf:

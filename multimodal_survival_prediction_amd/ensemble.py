@@ -183,7 +183,10 @@ class FoldEnsemble:
         on N x K numbers)."""
         if combine not in ("mean", "rank"):
             raise ValueError("predict_cohort: combine is 'mean' or 'rank', got %r" % (combine,))
-        idx = torch.as_tensor(np.asarray(indices), dtype=torch.int64)
+        if "rnaseq_folds" in cohort:
+            raise NotImplementedError("predict_cohort: ensembles of selected-gene models are not supported -- the members share ONE batch, "
+                                      "and per-fold gene selection (gene_select.GeneSelection.apply) gives every member its own columns")
+        idx =torch.as_tensor(np.asarray(indices), dtype=torch.int64)
         parts = []
         for s in range(0, len(idx), max(1, int(batch_size))):
             j = idx[s:s + batch_size].to(cohort["image"].device)

@@ -42,9 +42,14 @@ class FoldGroupEngine:
     # the entry points' layout (sub-groups on three streams), more than that layout's spread (tools/bench_image_only.py)
     FUSED_IMG_TAIL = True
 
-    def __init__(self, models, fused_tail=None, **engine_kw):
+    def __init__(self, models, fused_tail=None, folds=None, **engine_kw):
         """models: 1..10 modules of the same class/shape, already on the GPU and not yet bound to an engine.
-        fused_tail: ImageOnlyModel's tail as one launch per pass (None: FUSED_IMG_TAIL); ignored by the other models."""
+        fused_tail: ImageOnlyModel's tail as one launch per pass (None: FUSED_IMG_TAIL); ignored by the other models.
+        folds: the cross-validation fold of each model (None: model g is fold g).  Only read by the indexed steps over a cohort that
+        carries per-fold gene matrices (gene_select.GeneSelection.apply): member g's RNA-seq rows are gathered from fold folds[g]'s matrix."""
+        self.folds = list(range(len(models))) if folds is None else [int(f) for f in folds]
+        if len(self.folds) != len(models):
+            raise ValueError("folds must name one fold per model")
         self.fused_tail = self.FUSED_IMG_TAIL if fused_tail is None else bool(fused_tail)
         if not 1 <= len(models) <= self.MAX:
             raise ValueError("a fold group holds 1..%d models" % self.MAX)
@@ -321,7 +326,7 @@ class FoldGroupEngine:
             # only rewritten after the event recorded behind its previous copy has completed
             pin = dict(bufs=[torch.zeros(len(members), B, dtype=torch.int64).pin_memory() for _ in range(4)],
                        evs=[None] * 4, k=0)
-            blocks = _arr([e.gather_block(P, cohort, dev_idx[g]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))])
+            blocks = _arr([e.gather_block(P, cohort, dev_idx[g], fold=self.folds[GP.members[g]]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))])
             for e, P in zip(GP.eng, GP.Ps):
                 if "valid" not in cohort:
                     P.valid.fill_(1.0)
@@ -374,7 +379,7 @@ class FoldGroupEngine:
         key = id(cohort)
         if key not in cache:
             dev = torch.zeros(len(GP.members), GP.B, A.REC_WORDS, dtype=torch.int32, device=self.device)
-            pairs = [e.gather_aug_blocks(P, cohort, dev_idx[g], dev[g]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))]
+            pairs = [e.gather_aug_blocks(P, cohort, dev_idx[g], dev[g], fold=self.folds[GP.members[g]]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))]
             cache[key] = dict(dev=dev, pin=[torch.zeros(dev.shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]],
                               gather=_arr([g for g, _ in pairs]), aug=_arr([a for _, a in pairs]))
         aug = cache[key]

@@ -302,6 +302,40 @@ def cindex_boot(hrank, trank, event, w, stratum=None, pair_rule=0):
     return out
 
 
+def gene_screen(x, off, row, coef, G=None, plan_only=False):
+    """Univariate Cox score screen (GeneScreenP in mmsurv.h).  x: fp32 [N, >= G] device matrix (row pitch x.stride(0)); off: [P + 1]
+    problem offsets, row: [off[P]] patient rows in risk order, coef: [off[P], 3] float64 (a, b, q) -- host arrays (numpy or CPU
+    tensors).  The launch cannot check row / off, so both are checked HERE, before the upload (as augment.check_records checks its
+    records): rows in [0, N), off non-decreasing from 0 and ending at len(row).  -> (U, V): two [P, G] float64 device tensors.
+    plan_only: upload and check, do not launch -> (GeneScreenP, the tensors it points to, U, V), for call("mms_gene_screen", p) by
+    the caller (tools/bench_gene_screen.py times the launch alone)."""
+    import numpy as np
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise TypeError("x must be a 2-D fp32 device tensor with unit column stride")
+    N, G = x.shape[0], x.shape[1] if G is None else int(G)
+    off, row = np.asarray(off, dtype=np.int64).reshape(-1), np.asarray(row, dtype=np.int64).reshape(-1)
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64)).reshape(-1, 3)
+    P = len(off) - 1
+    if N < 1 or not 1 <= G <= x.shape[1]:
+        raise ValueError("x must have N >= 1 rows and 1 <= G <= %d columns" % x.shape[1])
+    if P < 0 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != len(row) or len(coef) != len(row):
+        raise ValueError("off must be non-decreasing from 0 to len(row) = len(coef)")
+    if len(row) >= 2 ** 31:
+        raise ValueError("the problems' row lists together must stay below 2^31 entries")
+    if len(row) and (row.min() < 0 or row.max() >= N):
+        raise ValueError("rows must lie in [0, %d)" % N)
+    dev = x.device
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt) if len(a) else np.zeros(1, dt))).to(dev)       # (never a NULL pointer)
+    off_d, row_d = up(off, np.int32), up(row, np.int32)
+    coef_d = up(coef.reshape(-1), np.float64)
+    U, V = torch.empty(max(P, 1), G, dtype=torch.float64, device=dev), torch.empty(max(P, 1), G, dtype=torch.float64, device=dev)
+    p = _S()["GeneScreenP"](ptr(x), N, x.stride(0), G, P, ptr(off_d), ptr(row_d), ptr(coef_d), ptr(U), ptr(V))
+    if plan_only:
+        return p, (x, off_d, row_d, coef_d), U[:P], V[:P]
+    call("mms_gene_screen", p)
+    return U[:P], V[:P]
+
+
 def adam_params(p_, g, m, v, hyper, sumsq, step, skip_flag=None, adamw=False, acc=None, cox_out=None, entropy=None,
                 rng=None, w2=None):
     """w2: None or dict(off=int64[n] device tensor, pack_b=ptr table (int64[n] device tensor of addresses), pack_f=the same,

@@ -12,6 +12,7 @@ and the Kaplan-Meier tables as CSV.
     python scripts/analysis/evaluate_model.py                            # evaluates an existing results/test_predictions.csv
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute
+    python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --genes models/final/fold_1_genes.json
     python scripts/analysis/evaluate_model.py --ensemble models/final/fold_*_best.pth --model final [--combine rank] [--attribute]
     python scripts/analysis/evaluate_model.py --bootstrap 2000 [--seed 0] [--compare other_model/test_predictions.csv ...]
 
@@ -19,6 +20,10 @@ and the Kaplan-Meier tables as CSV.
 of that fold of the cohort the training entry points use (data/processed/* under MMS_DATA_ROOT when present, else the seeded
 synthetic cohort) and writes results/test_predictions.csv first.  lifelines/seaborn are not needed: the statistics are the
 numpy restatements in multimodal_survival_prediction_amd/survival_stats.py.
+
+--genes FILE (with --predict): the checkpoint was trained on per-fold selected genes (MMS_SELECT_GENES; the fold_k_genes.json written next
+to it): the model is built at that width and reads the fold's columns of the RNA-seq matrix; --attribute names the genes by their
+original identity.  Ensembles of selected-gene models are not supported (every member has its own columns) and are refused.
 
 --bootstrap R adds "c_index_bootstrap" to the summary: the percentile interval of the C-index over R patient resamples (on the MI355X:
 multimodal_survival_prediction_amd/bootstrap.py), for a file with risk_fold_* columns each member's C-index and the paired difference
@@ -74,7 +79,7 @@ def _cohort_of(kind, device, external=False):
     return cohort, keep
 
 
-def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50):
+def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
     labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth."""
@@ -89,6 +94,16 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     labelled = torch.nonzero(keep).reshape(-1).numpy()
     _, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
     idx = labelled[val]
+    gene_cols = None
+    if genes:                                          # per-fold gene selection: the fold's columns, read before the forward pass
+        from multimodal_survival_prediction_amd.gene_select import GeneSelection
+        if kind == "image_only":
+            raise SystemExit("--genes: ImageOnlyModel reads no RNA-seq")
+        sel = GeneSelection.load(genes)
+        gene_cols = np.asarray(sel.columns[0] if len(sel.columns) == 1 else sel.columns_of(fold - 1), dtype=np.int64)
+        if sel.n_genes != cohort["rnaseq"].shape[1]:
+            raise SystemExit(f"--genes: {genes} selects among {sel.n_genes} genes, the cohort has {cohort['rnaseq'].shape[1]}")
+        cohort = dict(cohort, rnaseq=cohort["rnaseq"][:, torch.as_tensor(gene_cols, device=cohort["rnaseq"].device)].contiguous())
     model = getattr(models, cls)(**ctor(cohort))
     model.load_state_dict(torch.load(checkpoint, map_location="cpu"))
     model.to(device).eval()
@@ -129,7 +144,10 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
                 gene_sum = g.sum(0) if gene_sum is None else gene_sum + g.sum(0)
                 gene_rows += len(g)
     if attribute_dir and gene_sum is not None:
-        names = cohort.get("gene_names") or [f"g{i}" for i in range(len(gene_sum))]
+        n_all = len(gene_sum) if gene_cols is None else sel.n_genes
+        names = cohort.get("gene_names") or [f"g{i}" for i in range(n_all)]
+        if gene_cols is not None:                      # the selected columns under their original names
+            names = [names[int(c)] for c in gene_cols]
         score = gene_sum / gene_rows
         order = np.argsort(-score, kind="stable")[:top]
         pd.DataFrame({"gene": [names[i] for i in order], "mean_abs_grad": score[order]}).to_csv(
@@ -313,6 +331,8 @@ def main(argv=None):
                     help="with --ensemble: risk_score = the members' mean log-hazard, or their mean midrank over the predicted patients / N")
     ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv; "
                     "with --ensemble: the members' mean (<id>_ct.npy) and spread (<id>_ct_std.npy) and the mean gradient's gene_scores.csv")
+    ap.add_argument("--genes", metavar="FILE", help="with --predict: the fold's selected gene columns (fold_k_genes.json written by a training entry "
+                    "point under MMS_SELECT_GENES); the model is built at that width")
     ap.add_argument("--top", type=int, default=50, help="rows of gene_scores.csv")
     ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
                     help="R bootstrap resamples of the patients (on the GPU): adds c_index_bootstrap {replicates, seed, alpha, low, high, se, "
@@ -330,11 +350,16 @@ def main(argv=None):
         ap.error("--attribute needs --predict CHECKPOINT (the gradients are taken on the checkpoint's model)")
     if a.predict and a.ensemble:
         ap.error("--predict scores one fold's validation split, --ensemble every labelled patient: give one of them")
+    if a.genes and a.ensemble:
+        ap.error("--genes with --ensemble: ensembles of selected-gene models are not supported (every fold's model reads its own columns; "
+                 "score each fold with --predict --genes)")
+    if a.genes and not a.predict:
+        ap.error("--genes needs --predict CHECKPOINT")
     adir = os.path.join(a.outdir, "attribution") if a.attribute else None
     if a.ensemble:
         df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
     else:
-        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top) if a.predict else pd.read_csv(a.predictions)
+        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes) if a.predict else pd.read_csv(a.predictions)
     s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "

@@ -41,6 +41,40 @@ def augment_hparams(spec):
     return {} if spec is None else {"augment": str(spec)}
 
 
+def select_genes(cohort, train_indices_per_fold, ckpt_path, fold_names=None, rank=0):
+    """MMS_SELECT_GENES=k (unset or 0 by default: off, nothing changes): per-fold gene selection by a univariate Cox score screen of each
+    fold's TRAINING patients (multimodal_survival_prediction_amd.gene_select), with MMS_SELECT_STABILITY=R bootstrap resamples per fold
+    (default 0) drawn from MMS_SELECT_SEED (default 0).  Selects for every fold, leaves the per-fold [N, k] matrices in the cohort
+    (GeneSelection.apply: loaders take fold=, the fold group folds=) and, on rank 0, writes fold_{name}_genes.json next to each
+    checkpoint ckpt_path(name) (name = fold_names[f], default f + 1).  -> GeneSelection, or None when off."""
+    k = env_int("MMS_SELECT_GENES", 0)
+    if k <= 0:
+        return None
+    from multimodal_survival_prediction_amd import gene_select
+    sel = gene_select.select_genes(cohort, train_indices_per_fold, k, stability=env_int("MMS_SELECT_STABILITY", 0),
+                                   seed=env_int("MMS_SELECT_SEED", 0))
+    sel.apply(cohort)
+    if rank == 0:
+        for f in range(len(sel.columns)):
+            name = f + 1 if fold_names is None else fold_names[f]
+            d = os.path.dirname(ckpt_path(name)) or "."
+            os.makedirs(d, exist_ok=True)
+            sel.save(os.path.join(d, f"fold_{name}_genes.json"), fold=f)
+        print(f"gene selection: top {k} of {sel.n_genes} genes per fold (stability {sel.stability}, seed {sel.seed}); "
+              f"rows screened {sel.rows_screened}", flush=True)
+    return sel
+
+
+def rna_width(sel, name="rna_dim"):
+    """Constructor keyword of a model that reads the selected genes: {name: k}; nothing when selection is off (the class default)."""
+    return {} if sel is None else {name: sel.k}
+
+
+def gene_hparams(sel):
+    """-> {"select_genes": k, ...} for cv_results.json's hyperparameters; nothing when selection is off (today's JSON unchanged)."""
+    return {} if sel is None else {"select_genes": sel.k, "select_stability": sel.stability, "select_seed": sel.seed}
+
+
 def setup_device():
     from multimodal_survival_prediction_amd import distributed as D
     world, rank, local = D.init()
@@ -82,16 +116,17 @@ def lockstep_enabled(n_local_folds, batch_size=None):
 
 
 def cv_lockstep(style, models, loaders, group_kw, num_epochs, patience, make_scheduler, ckpt_path, device, rank, fold_names,
-                log_every=5):
+                log_every=5, fold_ids=None):
     """The per-fold epoch loop of the three scripts (train, validate, scheduler, best-checkpoint, early stopping) run for
     all local folds at once: one FoldGroupEngine advances every still-active fold by one batch per launch sequence.
     loaders: [(train_loader, val_loader)] per fold; make_scheduler(optimizer) -> object with step(metric) or step();
-    patience None = no early stopping (simple_fusion.py).  -> per fold dict(best_c_index, best_epoch, patients_per_sec)."""
+    patience None = no early stopping (simple_fusion.py).  fold_ids: the 0-based cross-validation fold of each model (None: model g is
+    fold g) -- which per-fold gene matrix its batches are gathered from (select_genes above).  -> per fold dict(best_c_index, best_epoch, patients_per_sec)."""
     import inspect
     import time
     from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
     from multimodal_survival_prediction_amd.training import FusedOptimizer, has_named_validation, train_epoch_lockstep, validate_lockstep
-    group = FoldGroupEngine(models, **group_kw)
+    group = FoldGroupEngine(models, folds=fold_ids, **group_kw)
     for tl, vl in loaders:                     # cohort in HBM (or pinned host memory): name the batches, let the group gather them
         for ld in ((tl, vl) if has_named_validation(style) else (tl,)):      # (validate_lockstep's named-batch path)
             if env_int("MMS_LAZY_BATCHES", 1) and (ld.c["image"].is_cuda or ld.c["image"].is_pinned()):

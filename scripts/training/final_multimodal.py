@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, lockstep_enabled, save_json, setup_device
+from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, lockstep_enabled, rna_width, save_json, select_genes, setup_device
 
 from multimodal_survival_prediction_amd import data, distributed as D
 from multimodal_survival_prediction_amd.losses import calculate_cindex, cox_loss  # noqa: F401  (reference surface)
@@ -43,24 +43,26 @@ def main():
     cohort = data.cohort_to(data.make_cohort(n=N_PATIENTS, dims=env_dims(), seed=608, complete=True), device)
     folds = data.kfold_indices(cohort["n"], N_FOLDS, seed=SEED)
     os.makedirs("models/final", exist_ok=True)
+    ckpt = lambda name: f"models/final/fold_{name}_best.pth"
+    sel = select_genes(cohort, [tr for tr, _ in folds], ckpt, rank=rank)        # MMS_SELECT_GENES (unset: off)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
     if lockstep_enabled(len(my_folds), BATCH_SIZE):      # all local folds advance together, one launch sequence per batch position
-        loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=SEED + f, augment=AUGMENT, augment_style="final"),
-                    data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False)) for f in my_folds]
-        models = [MultiModalSurvivalNet().to(device) for _ in my_folds]
+        loaders = [(data.BatchLoader(cohort, folds[f][0], BATCH_SIZE, shuffle=True, seed=SEED + f, augment=AUGMENT, augment_style="final", fold=f),
+                    data.BatchLoader(cohort, folds[f][1], BATCH_SIZE, shuffle=False, fold=f)) for f in my_folds]
+        models = [MultiModalSurvivalNet(**rna_width(sel)).to(device) for _ in my_folds]
         res = cv_lockstep("final", models, loaders, dict(lr=LEARNING_RATE, weight_decay=1e-4, adamw=False), NUM_EPOCHS, PATIENCE,
                           lambda o: ReduceLROnPlateau(o, mode="max", factor=0.5, patience=5),
-                          lambda name: f"models/final/fold_{name}_best.pth", device, rank, [f + 1 for f in my_folds])
+                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds)
         local = [{"fold": f + 1, "best_c_index": r["best_c_index"], "patients_per_sec": r["patients_per_sec"], "epochs_run": r["epochs_run"]}
                  for f, r in zip(my_folds, res)]
         my_folds = []
     for fold in my_folds:
         train_idx, val_idx = folds[fold]
         train_loader = data.BatchLoader(cohort, train_idx, BATCH_SIZE, shuffle=True, seed=SEED + fold,
-                                        augment=AUGMENT, augment_style="final")
-        val_loader = data.BatchLoader(cohort, val_idx, BATCH_SIZE, shuffle=False)
-        model = MultiModalSurvivalNet().to(device)
+                                        augment=AUGMENT, augment_style="final", fold=fold)
+        val_loader = data.BatchLoader(cohort, val_idx, BATCH_SIZE, shuffle=False, fold=fold)
+        model = MultiModalSurvivalNet(**rna_width(sel)).to(device)
         optimizer = FusedOptimizer(model, lr=LEARNING_RATE, weight_decay=1e-4, adamw=False)      # optim.Adam (:350)
         scheduler = ReduceLROnPlateau(optimizer, mode="max", factor=0.5, patience=5)             # (:351)
         best_c_index, patience_counter, t_train, n_train, epochs_run = 0, 0, 0.0, 0, 0
@@ -89,7 +91,7 @@ def main():
             "model": "MultiModalSurvivalNet (Late Fusion)", "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)),
             "fold_results": cv_results,
             "hyperparameters": {"batch_size": BATCH_SIZE, "learning_rate": LEARNING_RATE, "epochs": NUM_EPOCHS, "n_folds": N_FOLDS,
-                                **augment_hparams(AUGMENT)}})
+                                **augment_hparams(AUGMENT), **gene_hparams(sel)}})
         print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f}; saved results/final/cv_results.json")
 
 
