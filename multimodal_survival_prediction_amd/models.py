@@ -38,6 +38,14 @@ def _fusion(d):
     return nn.Sequential(nn.Linear(d, 256), nn.BatchNorm1d(256), nn.ReLU(), nn.Dropout(0.3), nn.Linear(256, 128), nn.ReLU())
 
 
+def _next_dropout_masks(eng):
+    """End of a completed training backward on the autograd path: advance the dropout step counter engine.rng[1] (on the device, on the
+    current stream, no host sync), as mms_grad_sumsq does for the fused step.  The k-th backward since the engine was created draws
+    the masks of counter k -- the fused path's sequence; a forward and its own backward (which recomputes the masks) read the same
+    value; two forward/backward rounds before one optimiser step draw two masks, as torch's Dropout does."""
+    eng.rng[1:].add_(1)
+
+
 class _Net(torch.autograd.Function):
     """forward/backward of a whole network on the engine's eager path."""
 
@@ -73,6 +81,7 @@ class _Net(torch.autograd.Function):
             P.gate.ent_weight, P.gate.dgate_ext = old, None
         else:
             eng._backward_from_dhz(P)
+        _next_dropout_masks(eng)
         return None, None, None, None, None, None
 
 
@@ -266,6 +275,7 @@ class _MoeNet(torch.autograd.Function):
         P.moe_bwd[1].dgate_ext = ext.data_ptr() if ext is not None else None
         eng._backward_from_dhz(P)
         P.moe_bwd[1].dgate_ext = None
+        _next_dropout_masks(eng)
         return None, None, None, None, None, None
 
 

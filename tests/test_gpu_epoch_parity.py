@@ -10,7 +10,7 @@ a cohort that contains every special case of those loops:
   batch 3  2 labelled (1 event) + 2 unlabelled                -> Cox on the labelled subset only
   batch 4  all labelled
   batch 5  ragged tail of 2 patients
-Dropout is off (its RNG cannot be matched); DenseNet121-3D encoder on the headline 64x64x32 volumes.
+Dropout is off here (dropout-on parity, against the CPU replica of the hash masks, lives in tests/test_gpu_dropout.py); DenseNet121-3D encoder on the headline 64x64x32 volumes.
 
 Two variants per style.
   lr = 0 ("frozen weights"): everything but the weight update runs -- per-batch losses, skip rules, denominators, BatchNorm running
