@@ -555,6 +555,48 @@ typedef struct GeneScreenP {
     double* U; double* V;               // [P][G] out (every element written)
 } GeneScreenP;
 
+/* Elastic-net Cox regression ("Coxnet"), P problems in lock-step (csrc/coxnet.hip).  All problems share ONE list of patient rows of x in
+ * stable time-descending order (row, with an event flag per position and a flag at the last position of every group of equal times) and
+ * differ in their integer multiplicities mult[p] over that list (0 = not in this fit, > 1 = a bootstrap repeat, i.e. a tie), in lam, alpha
+ * and the optional per-gene scale, given as its reciprocal (the fit then runs on x_j inv_scale_j).  With n = sum m, eta = x beta, S0_u = sum_{t_k >= u} m_k exp(eta_k)
+ * and d_u = sum m_k e_k over the tie group of u, the objective is
+ *     F(beta) = (1/n) [ -sum_k m_k e_k eta_k + sum_u d_u log S0_u ] + lam ( alpha |beta|_1 + (1 - alpha)/2 |beta|^2 )
+ * (Breslow ties), computed after subtracting the problem's maximum eta over its rows with m > 0.  Residual r_k = m_k e_k -
+ * m_k exp(eta_k) c_k, c_k = sum_{u <= t_k} d_u / S0_u; a row with m = 0 has r = 0 exactly (a select).  The smooth part's gradient is
+ * -x'r / n + lam (1 - alpha) beta; a problem without rows or events has loss 0.
+ * mms_coxnet_eval: one evaluation at `beta` -> E (eta), R (r), loss (the bracket above, NOT divided by n), nsum (n), grad, f (the smooth
+ *   part), kkt and obj (F); the solver's state (trial, step, iters, status, counter) is not touched.
+ * mms_coxnet_iterate: `iters` rounds of monotone proximal gradient with a step per problem: trial = soft(beta - s g, s lam alpha) is
+ *   accepted iff f(trial) <= f + <g, D> + |D|^2 / (2 s) + 1e-12 max(1, |f|), then s *= 1.25, else s /= 2 and (beta, g) stay.  A problem
+ *   whose KKT residual (max_j |g_j + lam alpha sign beta_j| where beta_j != 0, max(|g_j| - lam alpha, 0) elsewhere) at the kept point is
+ *   <= tol gets status 1 and is frozen; one that has counted max_iter iterations gets status 2; both decrement *counter (integer atomic).
+ *   A NEW problem has status -1, its start in `trial`, step = 1, iters = 0 and *counter counts it: its first round evaluates the start,
+ *   keeps it without a test (status -> 0, or 1 if it is already optimal) and counts no iteration.
+ * fp64 throughout, both products on v_mfma_f64_16x16x4_f64, no float atomics, no waits inside a launch; a problem's bits do not depend on
+ * P or on its place among the problems.  The launch cannot check row / mult / lam / alpha / scale: the CALLER guarantees 0 <= row < N,
+ * mult >= 0, lam >= 0, 0 <= alpha <= 1, inv_scale > 0 (ops.coxnet_* check on the host).  A NULL pointer (inv_scale alone may be NULL), P < 0,
+ * G < 1, ld < G, N < 1, nrow < 0, P > 16 * 65535, a pointer not aligned to its element, tol outside (0, MMS_COXNET_MAX_TOL], max_iter
+ * outside [1, MMS_COXNET_MAX_ITER] or iters < 0: MMS_ERR_ARG before any launch.  P = 0, nrow = 0 or iters = 0: MMS_OK without a launch. */
+#define MMS_COXNET_MAX_TOL 1.0
+#define MMS_COXNET_MAX_ITER 100000000
+typedef struct CoxnetP {
+    const float* x; int N; int ld; int G;      // [N][ld] fp32 (device), the first G columns are used
+    int nrow;                                  // positions of the row list
+    const int* row; const int* event; const int* glast;   // [nrow] patient row, event flag, 1 at the last position of a tie group
+    int P;
+    const int* mult;                           // [P][nrow] multiplicities
+    const double* lam; const double* alpha;    // [P]
+    const double* inv_scale;                   // [P][G] or NULL (all 1): 1 / the per-gene scale
+    double* beta; double* trial; double* grad; // [P][G] kept point, trial point, the smooth part's gradient at the kept point
+    double* f; double* step;                   // [P] smooth objective at the kept point, step
+    int* iters; int* status;                   // [P] iterations counted; -1 new, 0 running, 1 converged, 2 max_iter reached
+    double* loss; double* nsum; double* kkt; double* obj;   // [P] out
+    double* E; double* R;                      // [P][nrow] eta and residual of the last evaluated point
+    double* Gr;                                // [P][G] workspace: the raw product x'r
+    int* counter;                              // [1] unfinished problems
+    double tol; int max_iter;
+} CoxnetP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -849,6 +891,8 @@ int mms_moe_bwd(const MoeP* p, hipStream_t s);
 int mms_cindex_counts(const CindexP* p, hipStream_t s);
 int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / weighted pair counts of M models x R replicates (CbootP above) */
 int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox score test of G genes on P problems (GeneScreenP above) */
+int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);         /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
+int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */
 int mms_w2_pack(const AdamP* p, hipStream_t s);                /* the derived conv2 packs alone, from the current weights (after load_state_dict / any external update) */

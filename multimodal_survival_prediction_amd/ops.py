@@ -336,6 +336,128 @@ def gene_screen(x, off, row, coef, G=None, plan_only=False):
     return U[:P], V[:P]
 
 
+COXNET_STATUS = {-1: "new", 0: "not converged", 1: "converged", 2: "not converged"}
+
+
+def coxnet_plan(x, row, event, glast, mult, lam, alpha, scale=None, beta=None, G=None, tol=1e-6, max_iter=5000):
+    """Upload and check the problems of one elastic-net Cox call (CoxnetP in mmsurv.h) -> (CoxnetP, dict of the device tensors it points
+    to).  x: fp32 [N, >= G] device matrix; row / event / glast: [n] the shared row list (time descending), its event flags and tie-group
+    end flags; mult: [P, n] integer multiplicities; lam, alpha: [P]; scale: None or [P, G]; beta: None (zeros) or [P, G] start / point of
+    evaluation -- host arrays.  The launch cannot check them, so they are checked HERE (as ops.gene_screen checks its rows): rows in
+    [0, N), mult >= 0, lam >= 0 and finite, alpha in [0, 1], scale > 0 and finite (the device gets its reciprocal).  The state is that of NEW problems: status -1,
+    trial = beta, step 1, iters 0, counter P."""
+    import numpy as np
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise TypeError("x must be a 2-D fp32 device tensor with unit column stride")
+    N, G = x.shape[0], x.shape[1] if G is None else int(G)
+    if N < 1 or not 1 <= G <= x.shape[1]:
+        raise ValueError("x must have N >= 1 rows and 1 <= G <= %d columns" % x.shape[1])
+    row = np.asarray(row, dtype=np.int64).reshape(-1)
+    n = len(row)
+    event, glast = np.asarray(event).reshape(-1) != 0, np.asarray(glast).reshape(-1) != 0
+    mult = np.asarray(mult)
+    if mult.ndim != 2 or mult.shape[1] != n or len(event) != n or len(glast) != n:
+        raise ValueError("mult must be [P, n] and event / glast [n] for the n = %d rows of the list" % n)
+    P = mult.shape[0]
+    if not np.array_equal(mult, np.floor(mult)) or (mult < 0).any() or (mult >= 2 ** 31).any():
+        raise ValueError("multiplicities must be integers >= 0")
+    if n and (row.min() < 0 or row.max() >= N):
+        raise ValueError("rows must lie in [0, %d)" % N)
+    if n and not glast[-1]:
+        raise ValueError("the last row of the list ends a tie group: glast[-1] must be set")
+    if P * max(n, G) >= 2 ** 31:
+        raise ValueError("P * max(rows, G) must stay below 2^31")
+    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (P,)).copy()
+    alpha = np.broadcast_to(np.asarray(alpha, dtype=np.float64), (P,)).copy()
+    if not (np.isfinite(lam).all() and (lam >= 0).all()):
+        raise ValueError("lambda must be finite and >= 0")
+    if not ((alpha >= 0).all() and (alpha <= 1).all()):
+        raise ValueError("alpha must lie in [0, 1]")
+    if scale is not None:
+        scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float64))
+        if scale.shape != (P, G) or not (np.isfinite(scale).all() and (scale > 0).all()):
+            raise ValueError("scale must be [P, G], finite and > 0")
+    beta = np.zeros((P, G)) if beta is None else np.ascontiguousarray(np.asarray(beta, dtype=np.float64))
+    if beta.shape != (P, G) or not np.isfinite(beta).all():
+        raise ValueError("beta must be [P, G] and finite")
+    if not (0 < float(tol) <= 1.0) or not 1 <= int(max_iter) <= 100000000:
+        raise ValueError("tol must lie in (0, 1] and max_iter in [1, 1e8]")
+    dev = x.device
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt)).reshape(-1) if a.size else np.zeros(1, dt)).to(dev)   # (never a NULL pointer)
+    f64 = lambda *s: torch.zeros(max(int(np.prod(s)), 1), dtype=torch.float64, device=dev)
+    i32 = lambda k: torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
+    t = dict(x=x, row=up(row, np.int32), event=up(event, np.int32), glast=up(glast, np.int32), mult=up(mult, np.int32),
+             lam=up(lam, np.float64), alpha=up(alpha, np.float64), scale=None if scale is None else up(1.0 / scale, np.float64),
+             beta=up(beta, np.float64), trial=up(beta, np.float64), grad=f64(P, G), f=f64(P), step=f64(P) + 1.0, iters=i32(P),
+             status=i32(P) - 1, loss=f64(P), nsum=f64(P), kkt=f64(P), obj=f64(P), E=f64(P, n), R=f64(P, n), Gr=f64(P, G),
+             counter=i32(1) + P)
+    p = _S()["CoxnetP"](ptr(x), N, x.stride(0), G, n, ptr(t["row"]), ptr(t["event"]), ptr(t["glast"]), P, ptr(t["mult"]), ptr(t["lam"]),
+                        ptr(t["alpha"]), ptr(t["scale"]), ptr(t["beta"]), ptr(t["trial"]), ptr(t["grad"]), ptr(t["f"]), ptr(t["step"]),
+                        ptr(t["iters"]), ptr(t["status"]), ptr(t["loss"]), ptr(t["nsum"]), ptr(t["kkt"]), ptr(t["obj"]), ptr(t["E"]),
+                        ptr(t["R"]), ptr(t["Gr"]), ptr(t["counter"]), float(tol), int(max_iter))
+    t.update(P=P, G=G, n=n)
+    return p, t
+
+
+def _coxnet_out(t, names):
+    P, G, n = t["P"], t["G"], t["n"]
+    shape = dict(beta=(P, G), grad=(P, G), E=(P, n), R=(P, n))
+    import math
+    return {k: t[k][:math.prod(shape.get(k, (P,)))].reshape(shape.get(k, (P,))).cpu().numpy() for k in names}
+
+
+def coxnet_eval(x, row, event, glast, mult, lam, alpha, beta, scale=None, G=None):
+    """One evaluation of P elastic-net Cox problems at beta (mms_coxnet_eval; arguments as coxnet_plan) -> dict of float64 numpy arrays:
+    eta, r [P, n]; grad [P, G] (the smooth part's gradient, on the scaled genes); loss (the negative partial log-likelihood, not divided
+    by n), n, f (smooth part), obj, kkt [P].  An empty row list launches nothing: loss 0 and gradient lam (1 - alpha) beta, by the same
+    rule as a problem without rows."""
+    p, t = coxnet_plan(x, row, event, glast, mult, lam, alpha, scale=scale, beta=beta, G=G)
+    if t["P"] and t["n"]:
+        _lib.check(_lib.load_library().mms_coxnet_eval(ctypes.byref(p), stream()), "mms_coxnet_eval")
+        o = _coxnet_out(t, ("E", "R", "grad", "loss", "nsum", "f", "obj", "kkt"))
+        return dict(eta=o["E"], r=o["R"], grad=o["grad"], loss=o["loss"], n=o["nsum"], f=o["f"], obj=o["obj"], kkt=o["kkt"])
+    return _coxnet_no_rows(t)
+
+
+def _coxnet_no_rows(t):
+    """What the definitions give a call without rows (nothing to launch): loss 0, gradient lam (1 - alpha) beta."""
+    import numpy as np
+    P, G = t["P"], t["G"]
+    o = _coxnet_out(t, ("beta", "lam", "alpha"))
+    b, l1, l2 = o["beta"], (o["lam"] * o["alpha"])[:, None], (o["lam"] * (1 - o["alpha"]))[:, None]
+    g = l2 * b
+    rho = np.where(b != 0, np.abs(g + l1 * np.sign(b)), np.maximum(np.abs(g) - l1, 0.0)).max(1) if P else np.zeros(0)
+    f = 0.5 * l2[:, 0] * (b * b).sum(1)
+    return dict(eta=np.zeros((P, 0)), r=np.zeros((P, 0)), grad=g, loss=np.zeros(P), n=np.zeros(P), f=f,
+                obj=f + l1[:, 0] * np.abs(b).sum(1), kkt=rho, beta=b)
+
+
+def coxnet_fit(x, row, event, glast, mult, lam, alpha, scale=None, beta=None, G=None, tol=1e-6, max_iter=5000, check_every=50):
+    """Fit P elastic-net Cox problems in lock-step (mms_coxnet_iterate; arguments as coxnet_plan, beta = the start, zeros by default):
+    enqueue check_every rounds, read the device counter of unfinished problems (one 4-byte copy), until it is zero; max_iter bounds every
+    problem's own count on the device.  -> dict of numpy arrays: beta, grad [P, G]; f, obj, kkt, step [P]; iters, status [P] (1 =
+    converged, 2 = max_iter reached without convergence: not a fit) and eta [P, n] of the last evaluated point."""
+    import numpy as np
+    p, t = coxnet_plan(x, row, event, glast, mult, lam, alpha, scale=scale, beta=beta, G=G, tol=tol, max_iter=max_iter)
+    check_every = max(1, int(check_every))
+    if t["P"] and t["n"]:
+        lib = _lib.load_library()
+        rounds = 0
+        while rounds <= int(max_iter) + 1:
+            _lib.check(lib.mms_coxnet_iterate(ctypes.byref(p), check_every, stream()), "mms_coxnet_iterate")
+            rounds += check_every
+            if int(t["counter"].item()) <= 0:
+                break
+        o = _coxnet_out(t, ("beta", "grad", "f", "obj", "kkt", "step", "iters", "status", "E"))
+        o["eta"] = o.pop("E")
+        return o
+    o = _coxnet_no_rows(t)
+    P = t["P"]
+    conv = o["kkt"] <= tol
+    return dict(beta=o["beta"], grad=o["grad"], f=o["f"], obj=o["obj"], kkt=o["kkt"], step=np.ones(P), iters=np.zeros(P, np.int32),
+                status=np.where(conv, 1, 2).astype(np.int32), eta=o["eta"])
+
+
 def adam_params(p_, g, m, v, hyper, sumsq, step, skip_flag=None, adamw=False, acc=None, cox_out=None, entropy=None,
                 rng=None, w2=None):
     """w2: None or dict(off=int64[n] device tensor, pack_b=ptr table (int64[n] device tensor of addresses), pack_f=the same,

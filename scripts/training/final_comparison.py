@@ -16,7 +16,14 @@ RESULTS_FILES = {          # display name -> file written by scripts/training/<e
     "Final Multimodal": "results/final/cv_results.json",
     "SimMLM": "results/simmim/cv_results.json",              # scripts/training/simmlm_training.py
     "Image-Only": "results/image_only/cv_results.json",      # scripts/training/image_only_training.py
+    "Cox elastic net": "results/cox_baseline/cv_results.json",   # scripts/training/cox_baseline.py
 }
+# The baseline's fold values are the OUTER validation C-index at a lambda chosen by inner cross-validation on the training patients (nested
+# CV); a network's best_c_index is its maximum over the epochs ON the validation fold.  The two are not on equal footing, and the baseline
+# is the one handicapped.
+NESTED = ("Cox elastic net",)
+NESTED_NOTE = ("(+) nested cross-validation: lambda chosen inside each fold's training patients, the validation fold not seen; the other "
+               "rows are maxima over epochs on the validation fold -- not on equal footing, the (+) row is the one handicapped")
 
 
 def collect(root="."):
@@ -62,7 +69,9 @@ def main(root="."):
     if not res:
         raise SystemExit("no results/*/cv_results.json found under %s" % os.path.abspath(root))
     for name, r in sorted(res.items(), key=lambda kv: -kv[1]["mean"]):
-        print(f"  {name:22s} C-index {r['mean']:.4f} +/- {r['std']:.4f}  folds {['%.3f' % v for v in r['fold_values']]}")
+        print(f"  {name + (' (+)' if name in NESTED else ''):22s} C-index {r['mean']:.4f} +/- {r['std']:.4f}  folds {['%.3f' % v for v in r['fold_values']]}")
+    if any(name in NESTED for name in res):
+        print("  " + NESTED_NOTE)
     best, tests = compare(res)
     print(f"best: {best} ({res[best]['mean']:.4f})")
     for name, t in tests.items():
