@@ -10,6 +10,9 @@ One `SurvivalEngine` per model instance.  It
     which is what `training.train_epoch_*` (one loop, `training._train_epoch`, over the per-style table there) and bench.py
     replay once per batch.
 
+The state roll-back around graph capture exists once, for this engine and for fold_group.FoldGroupEngine:
+`SurvivalEngine.snapshot` / `restore`, used by `capture`.
+
 PyTorch supplies device memory, streams and graph capture only; every numeric op is a kernel behind
 include/mmsurv.h.  Nothing here falls back to torch math.
 """
@@ -133,6 +136,44 @@ def head_program(model):
         bufs = dict(feats=w, f1=model.fc[0].out_features, hz=1)
         return dict(kind=kind, width=w, ct_cols=0, lins=lins, gate=None, bufs=bufs, encoder=model.encoder, n_pre=0, enc_width=w)
     raise TypeError("unsupported model %s" % kind)
+
+
+def capture(engines, body):
+    """-> HIP graph of body().  Warm-up on one fresh side stream (first-launch attribute calls, lazy module loads), roll the engines
+    back, capture, roll back again (capture does not execute, but keep state exact regardless)."""
+    snaps = [e.snapshot() for e in engines]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        body()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    for e, snap in zip(engines, snaps):
+        e.restore(snap)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        body()
+    for e, snap in zip(engines, snaps):
+        e.restore(snap)
+    return g
+
+
+def gate_out(P):
+    """The gate weights [B, 3] a forward leaves on plan P, or None for a model without a gate."""
+    return P.gatew if (P.gate is not None or P.moe is not None) else None
+
+
+def check_attribute(engines, wrt):
+    """The argument checks of SurvivalEngine.attribute / FoldGroupEngine.attribute_lockstep."""
+    if engines[0].prog["kind"] == "SimMLM_SurvivalNet":
+        raise RuntimeError("attribute: SimMLM_SurvivalNet is not supported -- its mixture-of-experts kernels (csrc/moe.hip) have no "
+                           "input-gradient form; supported: the five imaging classes and RNASeqSurvivalModel")
+    if any(e.model.training for e in engines):
+        raise RuntimeError("attribute needs the model in eval mode (call model.eval()): input gradients are taken with frozen "
+                           "BatchNorm statistics; train-mode (batch-statistic) input gradients are not computed")
+    bad = [w for w in wrt if w not in ("ct", "rna", "clinical")]
+    if bad:
+        raise ValueError("attribute: wrt takes 'ct', 'rna', 'clinical'; got %r" % (bad,))
 
 
 def fallback_widths(enc):
@@ -276,6 +317,20 @@ class SurvivalEngine:
         if force or self._packs_version != self.flat._version:
             _lib.check(self.lib.mms_w2_pack(ctypes.byref(self._w2_adam), ops.stream()), "mms_w2_pack")
             self._packs_version = self.flat._version
+
+    def _state(self):
+        """Every tensor a training or validation step changes: a state word added to the fused step is added here, nowhere else."""
+        return [self.flat, self.m, self.v, self.step_count, self.rng, self.acc, self.acc_eval] + list(self.model.buffers())
+
+    def snapshot(self):
+        """Copy of the engine's state for the roll-back around graph capture (`capture`, `_ddp_step`)."""
+        return [t.clone() for t in self._state()]
+
+    def restore(self, snap):
+        with torch.no_grad():
+            for t, t0 in zip(self._state(), snap):
+                t.copy_(t0)
+        self.sync_packs()          # (the roll-back changed the weights: rebuild the derived conv2 packs, outside any capture)
 
     def check_train_batch(self, B, dims=None, bn_world=1):
         """check_train_batch for THIS model: BatchNorm1d heads need more than one patient; a model without them (ImageOnlyModel) trains
@@ -880,31 +935,7 @@ class SurvivalEngine:
             return
         key = ("train", skip_if_unusable)
         if key not in P.graphs:
-            # warm-up on a side stream (first-launch attribute calls, lazy module loads), then capture
-            state = [self.flat.clone(), self.m.clone(), self.v.clone(), self.step_count.clone(), self.rng.clone(),
-                     self.acc.clone(), [b.clone() for b in self.model.buffers()]]
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._train_body(P, skip_if_unusable)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            with torch.no_grad():   # undo the warm-up step
-                self.flat.copy_(state[0]); self.m.copy_(state[1]); self.v.copy_(state[2])
-                self.step_count.copy_(state[3]); self.rng.copy_(state[4]); self.acc.copy_(state[5])
-                for b, b0 in zip(self.model.buffers(), state[6]):
-                    b.copy_(b0)
-            self.sync_packs()          # (the roll-back changed the weights: rebuild the derived conv2 packs, outside any capture)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._train_body(P, skip_if_unusable)
-            P.graphs[key] = g
-            with torch.no_grad():   # capture does not execute, but keep state exact regardless
-                self.flat.copy_(state[0]); self.m.copy_(state[1]); self.v.copy_(state[2])
-                self.step_count.copy_(state[3]); self.rng.copy_(state[4]); self.acc.copy_(state[5])
-                for b, b0 in zip(self.model.buffers(), state[6]):
-                    b.copy_(b0)
-            self.sync_packs()          # (the roll-back changed the weights: rebuild the derived conv2 packs, outside any capture)
+            P.graphs[key] = capture([self], lambda: self._train_body(P, skip_if_unusable))
         P.graphs[key].replay()
 
     # ---- data-parallel step (one process per GPU) --------------------------------------------------------
@@ -964,17 +995,12 @@ class SurvivalEngine:
         key0 = ("ddp", global_cox, world)
         if key0 not in P.graphs:
             # the parts depend on each other through the workspace (statistic accumulators are zeroed by the first part only), so
-            # they are warmed up as ONE eager step, rolled back, and then captured without being executed
-            state = [self.flat.clone(), self.m.clone(), self.v.clone(), self.step_count.clone(), self.rng.clone(),
-                     self.acc.clone(), [b.clone() for b in self.model.buffers()]]
+            # they are warmed up as ONE eager step (on the current stream: the collectives stay where they are), rolled back, and then
+            # captured without being executed
+            snap = self.snapshot()
             run(lambda part: self._train_body(P, False, part))
             torch.cuda.synchronize()
-            with torch.no_grad():
-                self.flat.copy_(state[0]); self.m.copy_(state[1]); self.v.copy_(state[2])
-                self.step_count.copy_(state[3]); self.rng.copy_(state[4]); self.acc.copy_(state[5])
-                for b, b0 in zip(self.model.buffers(), state[6]):
-                    b.copy_(b0)
-            self.sync_packs()          # (the roll-back changed the weights: rebuild the derived conv2 packs, outside any capture)
+            self.restore(snap)
             graphs = {}
             for part in [it[1] for it in seq if it[0] == "part"] + [upd]:
                 g = torch.cuda.CUDAGraph()
@@ -1082,20 +1108,11 @@ class SurvivalEngine:
         self.sync_packs()
         if use_graph:
             if "eval" not in P.graphs:
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._forward(P, False)
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._forward(P, False)
-                P.graphs["eval"] = g
+                P.graphs["eval"] = capture([self], lambda: self._forward(P, False))
             P.graphs["eval"].replay()
         else:
             self._forward(P, False)
-        return P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)
+        return P.buf["hz"][:, 0], gate_out(P)
 
     # ---- input-gradient attribution ----------------------------------------------------------------------
     def _attr_blocks(self, P):
@@ -1174,16 +1191,7 @@ class SurvivalEngine:
         backward with dhazard = 1 per row gives every row's gradient; more than 32 rows run in chunks of 32 (exact).  Eval forward ->
         heads' backward with eval-mode prologues and no weight gradients -> the encoder's input-gradient driver (mms_dn121_input_grad /
         mms_fb3_input_grad).  Touches no .grad, no optimiser state, no running statistic, no conv2 pack and no training graph."""
-        kind = self.prog["kind"]
-        if kind == "SimMLM_SurvivalNet":
-            raise RuntimeError("attribute: SimMLM_SurvivalNet is not supported -- its mixture-of-experts kernels (csrc/moe.hip) have no "
-                               "input-gradient form; supported: the five imaging classes and RNASeqSurvivalModel")
-        if self.model.training:
-            raise RuntimeError("attribute needs the model in eval mode (call model.eval()): input gradients are taken with frozen "
-                               "BatchNorm statistics; train-mode (batch-statistic) input gradients are not computed")
-        bad = [w for w in wrt if w not in ("ct", "rna", "clinical")]
-        if bad:
-            raise ValueError("attribute: wrt takes 'ct', 'rna', 'clinical'; got %r" % (bad,))
+        check_attribute([self], wrt)
         ref = rna if rna is not None else ct
         B = ref.shape[0]
         dims = tuple(ct.shape[-3:]) if (ct is not None and self.prog["encoder"] is not None) else None

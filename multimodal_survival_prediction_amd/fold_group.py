@@ -4,7 +4,8 @@ The reference trains fold after fold (final_multimodal.py:316-402, partial_modal
 simple_fusion.py:318-436).  The folds are independent models of identical architecture, and one batch-4 step of one
 of them is far too small for 256 CUs (most of its 570 kernels are launch/latency bound).  A `FoldGroupEngine` owns G
 `SurvivalEngine`s and issues every launch of the training step ONCE for the whole group through the `*_group` entry
-points of include/mmsurv.h: same kernels, same per-model arithmetic, G times the workgroups per launch.
+points of include/mmsurv.h: same kernels, same per-model arithmetic, G times the workgroups per launch.  The warm-up /
+roll-back / capture of a graph is the single engine's (engine.capture).
 
 Per-model state stays per model (parameters, Adam moments, BatchNorm buffers, learning rate, dropout counters,
 epoch accumulators): a fold trained in a group follows exactly the trajectory it follows alone.
@@ -17,7 +18,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
-from .engine import SurvivalEngine, group_widths_ok
+from .engine import SurvivalEngine, capture, check_attribute, gate_out, group_widths_ok
 
 _S = _lib.structs
 
@@ -85,7 +86,7 @@ class FoldGroupEngine:
 
     # ---- plans -----------------------------------------------------------------------------------
     def plan(self, B, dims, members=None):
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
+        members = self._members(members)
         key = (B,) + (tuple(dims) if dims is not None else ()) + (members,)
         if key in self.plans:
             return self.plans[key]
@@ -247,20 +248,6 @@ class FoldGroupEngine:
                 _lib.check(lib.mms_dn121_backward_group(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, self._opts_arg(GP), st),
                            "mms_dn121_backward_group")
 
-    # ---- state snapshot around graph warm-up ---------------------------------------------------------
-    def _snapshot(self, eng):
-        return [[e.flat.clone(), e.m.clone(), e.v.clone(), e.step_count.clone(), e.rng.clone(), e.acc.clone(),
-                 [b.clone() for b in e.model.buffers()], e.acc_eval.clone()] for e in eng]
-
-    def _restore(self, eng, snap):
-        with torch.no_grad():
-            for e, s in zip(eng, snap):
-                e.flat.copy_(s[0]); e.m.copy_(s[1]); e.v.copy_(s[2]); e.step_count.copy_(s[3]); e.rng.copy_(s[4])
-                e.acc.copy_(s[5]); e.acc_eval.copy_(s[7])
-                for b, b0 in zip(e.model.buffers(), s[6]):
-                    b.copy_(b0)
-                e.sync_packs()         # (the roll-back changed the weights: rebuild the derived conv2 packs, outside any capture)
-
     def _opts_arg(self, GP):
         """`const MmsDnOpts*` of the group's driver calls (the members share one block: same class, same options).  The persistent
         per-block kernels (csrc/dn_cl.hip, dn_b4.hip) hand data between co-resident workgroups and one such launch per worker stream
@@ -272,45 +259,44 @@ class FoldGroupEngine:
         return ctypes.byref(o)
 
     def _graph(self, GP, key, body):
+        """The plan's HIP graph of body(), captured on first use (engine.capture: warm-up, roll-back of every member, capture)."""
         if key not in GP.graphs:
-            snap = self._snapshot(GP.eng)
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            self._restore(GP.eng, snap)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
-            GP.graphs[key] = g
-            self._restore(GP.eng, snap)
+            GP.graphs[key] = capture(GP.eng, body)
         return GP.graphs[key]
 
-    # ---- public ------------------------------------------------------------------------------------------
-    def train_step(self, batches, members=None, skip_if_unusable=True, use_graph=True):
-        """One optimisation step of every member on its own batch.  batches: one dict per member with the keyword
-        arguments of SurvivalEngine.load_batch (ct, rna, clinical, mask, time, event, valid); all of one batch size."""
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
-        if len(batches) != len(members):
-            raise ValueError("one batch per member")
-        has_enc = self.engines[0].prog["encoder"] is not None
-        rows = lambda b: (b["rna"] if b.get("rna") is not None else b["ct"]).shape[0]       # (a CT-only model has no rna input)
-        B = rows(batches[0])
-        dims = tuple(batches[0]["ct"].shape[-3:]) if has_enc else None
-        self.engines[0].check_train_batch(B, dims)
-        for b in batches:
-            if rows(b) != B or (has_enc and tuple(b["ct"].shape[-3:]) != dims):
-                raise ValueError("fold-group batches must share one shape; split ragged tails into their own step")
-        GP = self.plan(B, dims, members)
-        for e, P, b in zip(GP.eng, GP.Ps, batches):
-            e.load_batch(P, **b)
+    def _members(self, members):
+        return tuple(range(len(self.engines))) if members is None else tuple(members)
+
+    @staticmethod
+    def _rows(batch):
+        return (batch["rna"] if batch.get("rna") is not None else batch["ct"]).shape[0]       # (a CT-only model has no rna input)
+
+    def _step(self, GP, skip_if_unusable, use_graph):
+        """The training step on the batches the plan's input buffers hold: eager launches, or the replay of their graph."""
         self._sync_packs(GP)
         if not use_graph:
             self._train_body(GP, skip_if_unusable)
             return
         self._graph(GP, ("train", bool(skip_if_unusable)), lambda: self._train_body(GP, skip_if_unusable)).replay()
+
+    # ---- public ------------------------------------------------------------------------------------------
+    def train_step(self, batches, members=None, skip_if_unusable=True, use_graph=True):
+        """One optimisation step of every member on its own batch.  batches: one dict per member with the keyword
+        arguments of SurvivalEngine.load_batch (ct, rna, clinical, mask, time, event, valid); all of one batch size."""
+        members = self._members(members)
+        if len(batches) != len(members):
+            raise ValueError("one batch per member")
+        has_enc = self.engines[0].prog["encoder"] is not None
+        B = self._rows(batches[0])
+        dims = tuple(batches[0]["ct"].shape[-3:]) if has_enc else None
+        self.engines[0].check_train_batch(B, dims)
+        for b in batches:
+            if self._rows(b) != B or (has_enc and tuple(b["ct"].shape[-3:]) != dims):
+                raise ValueError("fold-group batches must share one shape; split ragged tails into their own step")
+        GP = self.plan(B, dims, members)
+        for e, P, b in zip(GP.eng, GP.Ps, batches):
+            e.load_batch(P, **b)
+        self._step(GP, skip_if_unusable, use_graph)
 
     def _gather_indexed(self, GP, cohort, idx, augment=None, affine=None):
         """Index copy (pinned ring -> device) + the ONE gather launch that assembles the group's batches in the plans' input buffers.
@@ -401,7 +387,7 @@ class FoldGroupEngine:
         and intensity map, modality dropout); None: no augmentation, the plain gather.  augment_affine: [len(members)][B] affine records
         (augment.affine_records / augment.sample) of the same rows: the launch is mms_gather_affine_group (rotation / zoom resampling,
         additive noise; the flip / shift fields of `augment` are not read, they are folded into the matrices)."""
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
+        members = self._members(members)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if idx.dim() != 2 or idx.shape[0] != len(members):
             raise ValueError("indices must be [len(members)][B]")
@@ -411,11 +397,7 @@ class FoldGroupEngine:
         GP = self.plan(B, dims, members)
         self._gather_indexed(GP, cohort, idx, None if augment is None else torch.as_tensor(augment),
                              None if augment_affine is None else torch.as_tensor(augment_affine))
-        self._sync_packs(GP)
-        if not use_graph:
-            self._train_body(GP, skip_if_unusable)
-            return
-        self._graph(GP, ("train", bool(skip_if_unusable)), lambda: self._train_body(GP, skip_if_unusable)).replay()
+        self._step(GP, skip_if_unusable, use_graph)
 
     def _eval_loss_body(self, GP):
         """Eval-mode forward of every member + the Cox value of its batch (no gradient) + the validation accumulators."""
@@ -429,7 +411,7 @@ class FoldGroupEngine:
         """validate_*'s step with the batches named by patient indices (as train_step_indexed): gather + ONE graph (eval-mode forward,
         Cox value of each member's batch, accumulators SurvivalEngine.acc_eval).  -> per member (hazard [B], (loss | usable) [2]):
         views of static buffers, valid until the next step of this plan."""
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
+        members = self._members(members)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if idx.dim() != 2 or idx.shape[0] != len(members):
             raise ValueError("indices must be [len(members)][B]")
@@ -446,12 +428,8 @@ class FoldGroupEngine:
                            "form of mms_dn121_input_grad / mms_fb3_input_grad); call SurvivalEngine.attribute on each fold's model")
 
     # ---- one batch seen by every member (ensembles) ----------------------------------------------------------
-    @staticmethod
-    def _rows(batch):
-        return (batch["rna"] if batch.get("rna") is not None else batch["ct"]).shape[0]
-
     def _shared_plan(self, batch, members):
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
+        members = self._members(members)
         has_enc = self.engines[0].prog["encoder"] is not None
         dims = tuple(batch["ct"].shape[-3:]) if has_enc else None
         GP = self.plan(self._rows(batch), dims, members)
@@ -475,7 +453,7 @@ class FoldGroupEngine:
             self._graph(GP, "eval_shared", lambda: self._forward(GP, False, x=x)).replay()
         else:
             self._forward(GP, False, x=x)
-        return [(P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)) for P in GP.Ps]
+        return [(P.buf["hz"][:, 0], gate_out(P)) for P in GP.Ps]
 
     def _attr_group(self, GP):
         """The members' attribution blocks (SurvivalEngine._attr_blocks) as the arrays of the *_group entry points."""
@@ -495,16 +473,7 @@ class FoldGroupEngine:
         return AG
 
     def _check_attribute(self, wrt):
-        kind = self.engines[0].prog["kind"]
-        if kind == "SimMLM_SurvivalNet":
-            raise RuntimeError("attribute: SimMLM_SurvivalNet is not supported -- its mixture-of-experts kernels (csrc/moe.hip) have no "
-                               "input-gradient form; supported: the five imaging classes and RNASeqSurvivalModel")
-        if any(e.model.training for e in self.engines):
-            raise RuntimeError("attribute needs the model in eval mode (call model.eval()): input gradients are taken with frozen "
-                               "BatchNorm statistics; train-mode (batch-statistic) input gradients are not computed")
-        bad = [w for w in wrt if w not in ("ct", "rna", "clinical")]
-        if bad:
-            raise ValueError("attribute: wrt takes 'ct', 'rna', 'clinical'; got %r" % (bad,))
+        check_attribute(self.engines, wrt)
 
     def _attribute_lockstep_run(self, batch, members=None):
         """attribute_lockstep's launches -> (GP, AG): the members' hazards are in their plans' buffers, their input gradients in
@@ -567,10 +536,9 @@ class FoldGroupEngine:
 
     def forward_eval(self, batches, members=None, use_graph=True):
         """Eval-mode forward of every member -> list of (hazard [B] view, gate [B,3] or None) per member."""
-        members = tuple(range(len(self.engines))) if members is None else tuple(members)
-        B = (batches[0]["rna"] if batches[0].get("rna") is not None else batches[0]["ct"]).shape[0]
+        members = self._members(members)
         dims = tuple(batches[0]["ct"].shape[-3:]) if self.engines[0].prog["encoder"] is not None else None
-        GP = self.plan(B, dims, members)
+        GP = self.plan(self._rows(batches[0]), dims, members)
         for e, P, b in zip(GP.eng, GP.Ps, batches):
             e.load_batch(P, **b)
         self._sync_packs(GP)
@@ -578,7 +546,7 @@ class FoldGroupEngine:
             self._graph(GP, "eval", lambda: self._forward(GP, False)).replay()
         else:
             self._forward(GP, False)
-        return [(P.buf["hz"][:, 0], (P.gatew if (P.gate is not None or P.moe is not None) else None)) for P in GP.Ps]
+        return [(P.buf["hz"][:, 0], gate_out(P)) for P in GP.Ps]
 
     def reset_epoch_stats(self):
         for e in self.engines:
