@@ -597,6 +597,48 @@ typedef struct CoxnetP {
     double tol; int max_iter;
 } CoxnetP;
 
+/* Cut-point scan of the two-group log-rank statistic (csrc/logrank_scan.hip): the statistic of EVERY admissible cut of Q problems in one
+ * launch -- the maximally selected log-rank statistic of M models and of R relabellings of each (risk_strata.stratify).
+ * The n patients stand in TIME-DESCENDING order (any order inside a group of equal times); the labels are shared by all problems.  A
+ * problem q is the int32 rank vector rank[q][0..n) over those positions (a model's dense risk ranks, or a permutation of them) and a
+ * cut set s = cset[q] (q itself when cset is NULL): the ascending cut ranks cut[coff[s] .. coff[s+1]).  Position i is in the HIGH group
+ * of cut c iff rank[q][i] >= cut[c].  With d_u events and n_u positions at risk (t >= u) at event time u, G_i = the high-group members
+ * among positions 0..i and D the high group's events,
+ *     U = D - sum_i h_i G_i   (= sum_i [high_i] a_i with a_i = e_i - sum_{u <= t_i} d_u / n_u: observed - expected events),
+ *     V = sum_i c_i G_i (i + 1 - G_i)   (the hypergeometric variance of survival_stats.logrank_test),   chi2 = U^2 / V, 0 when V <= 0,
+ * coef[i] = {h_i, c_i}: h_i = d_u / n_u and c_i = d_u (n_u - d_u) / (n_u^2 (n_u - 1)) (c_i: when n_u >= 2, else 0) at the LAST position
+ * of event time u's tie group (where i + 1 = n_u), both 0 elsewhere; pflag[i] = [e_i] | 2 [coef[i] != {0, 0}].  The host computes both
+ * in fp64 (risk_strata.logrank_coefficients).  A time with n_u = 1 -- skipped by logrank_test -- adds 1 - 1 = 0 to U and nothing to V.
+ * Out, per problem: chi2_max = the largest chi2 over its cuts, arg_max = its cut index (the smallest on ties; a problem without cuts:
+ * 0 and -1), chi2_at = chi2 at cut index at[s] (0 when at is NULL or the index is outside the set).  U / V / n_high / d_high: optional
+ * full tables [Q][ldo], all four or none; n_high and d_high are the exact size and events of the high group.
+ * fp64 arithmetic, no atomics, plain stores; a problem's bits depend on its own rank vector and cut list only, not on Q, on its place
+ * in the launch or on whether the tables are asked for (a replicate with the identity permutation reproduces the observed chi2_max
+ * bit for bit).  Q = 0 and empty cut sets are valid; an event-free cohort gives zeros.  The launch cannot check that coff is
+ * non-decreasing from 0, that every cut list is ascending, that cset lies in [0, S), that maxc bounds every set or that pflag matches
+ * coef: the CALLER guarantees them (ops.logrank_scan checks on the host).  A NULL required pointer (cset, at and the tables may be
+ * NULL), n < 1, n > MMS_LRSCAN_MAX_N, ldr < n, Q < 0, Q > MMS_LRSCAN_MAX_Q, maxc < 0, maxc > MMS_LRSCAN_MAX_C, some but not all of
+ * the tables, ldo < maxc with tables, or a pointer not aligned to its element (coef: to its 16-byte pair): MMS_ERR_ARG before any
+ * launch. */
+#define MMS_LRSCAN_MAX_N 65535     /* a thread counts the high group and its events in the two 16-bit halves of one register */
+#define MMS_LRSCAN_MAX_C 65535     /* cuts lie between distinct ranks of at most MAX_N patients: never more than n - 1 are distinct */
+#define MMS_LRSCAN_MAX_Q 16777215  /* one workgroup of 256 threads per problem: the launch's thread count stays below 2^32 */
+typedef struct LogrankScanP {
+    int n; int ldr; int Q;              // positions, row pitch of rank, problems
+    int maxc;                           // the largest cut set's size (bounds ldo)
+    const int* rank;                    // [Q][ldr] ranks over the shared time-descending positions
+    const int* pflag;                   // [n] bit 0: event, bit 1: coef[i] is not {0, 0}
+    const double* coef;                 // [n][2] h, c
+    const int* coff;                    // [S+1] cut set s = cut[coff[s] .. coff[s+1])
+    const int* cut;                     // [coff[S]] ascending inside a set
+    const int* cset;                    // [Q] the problem's cut set, or NULL: set q
+    const int* at;                      // [S] the designated cut index of a set (the median split), or NULL
+    double* chi2_max; int* arg_max; double* chi2_at;    // [Q] out
+    double* U; double* V;               // [Q][ldo] out or NULL
+    int* n_high; int* d_high;           // [Q][ldo] out or NULL
+    int ldo;
+} LogrankScanP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -891,6 +933,7 @@ int mms_moe_bwd(const MoeP* p, hipStream_t s);
 int mms_cindex_counts(const CindexP* p, hipStream_t s);
 int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / weighted pair counts of M models x R replicates (CbootP above) */
 int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox score test of G genes on P problems (GeneScreenP above) */
+int mms_logrank_scan(const LogrankScanP* p, hipStream_t s);   /* log-rank statistic of every cut of Q problems (LogrankScanP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);         /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */

@@ -336,6 +336,75 @@ def gene_screen(x, off, row, coef, G=None, plan_only=False):
     return U[:P], V[:P]
 
 
+def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False, plan_only=False):
+    """Log-rank statistic of every cut of Q problems (LogrankScanP in mmsurv.h).  rank: int32 [Q, n] ranks over the shared time-descending
+    positions -- a device tensor (row pitch rank.stride(0)) or a host array; pflag: [n], coef: [n, 2] float64 (h, c) from
+    risk_strata.logrank_coefficients; coff: [S + 1] offsets of the S cut sets in cut; cset: [Q] the set of each problem (None: S = Q, set
+    q); at: [S] the designated cut index of each set, -1 = none (None: none) -- host arrays.  The launch cannot check them, so they are
+    checked HERE (as ops.gene_screen checks its rows): coff non-decreasing from 0 to len(cut), every set ascending, cset in [0, S), at in
+    [-1, the set's size), pflag's bits against coef.  -> dict of device tensors chi2_max, chi2_at (float64 [Q]), arg_max (int32 [Q]) and,
+    with tables, U, V (float64 [Q, C]), n_high, d_high (int32 [Q, C]), C = the largest set (columns past a problem's own cuts are not
+    written).  plan_only: upload and check, do not launch -> (LogrankScanP, the tensors it points to, the dict), for
+    call("mms_logrank_scan", p) by the caller (tools/bench_logrank_scan.py times the launch alone)."""
+    import numpy as np
+    dev = rank.device if torch.is_tensor(rank) and rank.is_cuda else torch.device("cuda")
+    if not torch.is_tensor(rank):
+        rank = torch.from_numpy(np.ascontiguousarray(np.asarray(rank, dtype=np.int32)))
+    if rank.dim() != 2 or rank.dtype != torch.int32 or (rank.shape[0] and rank.shape[1] and rank.stride(1) != 1):
+        raise TypeError("rank must be int32 [Q, n] with unit column stride")
+    rank = rank.to(dev)
+    Q, n = rank.shape
+    if Q > 1 and rank.stride(0) < n:                 # (an expanded view: rows that overlap have no pitch)
+        rank = rank.contiguous()
+    pflag = np.asarray(pflag, dtype=np.int64).reshape(-1)
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64)).reshape(-1, 2)
+    coff, cut = np.asarray(coff, dtype=np.int64).reshape(-1), np.asarray(cut, dtype=np.int64).reshape(-1)
+    S = len(coff) - 1
+    if n < 1 or len(pflag) != n or len(coef) != n:
+        raise ValueError("rank must have n >= 1 columns, pflag n entries and coef [n, 2]")
+    if ((pflag & ~3) != 0).any() or not np.array_equal((pflag & 2) != 0, (coef != 0).any(1)) or not np.isfinite(coef).all():
+        raise ValueError("pflag must be [event] | 2 [coef != 0] and coef finite")
+    if S < 0 or coff[0] != 0 or (np.diff(coff) < 0).any() or coff[-1] != len(cut):
+        raise ValueError("coff must be non-decreasing from 0 to len(cut)")
+    if len(cut) >= 2 ** 31 or (len(cut) and (np.abs(cut) >= 2 ** 31).any()):
+        raise ValueError("cuts must be int32 and fewer than 2^31")
+    inner = np.ones(len(cut), bool)
+    inner[coff[:-1][coff[:-1] < len(cut)]] = False                       # (the first cut of a set has no predecessor in it)
+    if len(cut) > 1 and ((np.diff(cut) < 0) & inner[1:]).any():
+        raise ValueError("every cut set must be ascending")
+    if cset is None:
+        if S != Q:
+            raise ValueError("without cset there is one cut set per problem: %d sets, %d problems" % (S, Q))
+    else:
+        cset = np.asarray(cset, dtype=np.int64).reshape(-1)
+        if len(cset) != Q or (Q and (cset.min() < 0 or cset.max() >= S)):
+            raise ValueError("cset must name one of the %d cut sets for each of the %d problems" % (S, Q))
+    sizes = np.diff(coff)
+    if at is not None:
+        at = np.asarray(at, dtype=np.int64).reshape(-1)
+        if len(at) != S or (at < -1).any() or (at >= sizes).any():
+            raise ValueError("at must hold one cut index per set (-1: none)")
+    maxc = int(sizes.max()) if S else 0
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt)).reshape(-1) if a.size else np.zeros(1, dt)).to(dev)   # (never a NULL pointer)
+    t = dict(rank=rank if rank.numel() else torch.zeros(1, dtype=torch.int32, device=dev), pflag=up(pflag, np.int32),
+             coef=up(coef, np.float64), coff=up(coff, np.int32), cut=up(cut, np.int32),
+             cset=None if cset is None else up(cset, np.int32), at=None if at is None else up(at, np.int32))
+    ldo = max(maxc, 1)
+    out = dict(chi2_max=torch.zeros(max(Q, 1), dtype=torch.float64, device=dev), arg_max=torch.zeros(max(Q, 1), dtype=torch.int32, device=dev),
+               chi2_at=torch.zeros(max(Q, 1), dtype=torch.float64, device=dev))
+    if tables:
+        out.update(U=torch.zeros(max(Q, 1), ldo, dtype=torch.float64, device=dev), V=torch.zeros(max(Q, 1), ldo, dtype=torch.float64, device=dev),
+                   n_high=torch.zeros(max(Q, 1), ldo, dtype=torch.int32, device=dev), d_high=torch.zeros(max(Q, 1), ldo, dtype=torch.int32, device=dev))
+    p = _S()["LogrankScanP"](n, max(rank.stride(0), n) if Q else n, Q, maxc, ptr(t["rank"]), ptr(t["pflag"]), ptr(t["coef"]), ptr(t["coff"]),
+                             ptr(t["cut"]), ptr(t["cset"]), ptr(t["at"]), ptr(out["chi2_max"]), ptr(out["arg_max"]), ptr(out["chi2_at"]),
+                             ptr(out.get("U")), ptr(out.get("V")), ptr(out.get("n_high")), ptr(out.get("d_high")), ldo)
+    res = {k: (v[:Q, :maxc] if v.dim() == 2 else v[:Q]) for k, v in out.items()}
+    if plan_only:
+        return p, (t, out), res
+    call("mms_logrank_scan", p)
+    return res
+
+
 COXNET_STATUS = {-1: "new", 0: "not converged", 1: "converged", 2: "not converged"}
 
 

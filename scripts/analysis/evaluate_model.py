@@ -29,6 +29,11 @@ original identity.  Ensembles of selected-gene models are not supported (every m
 multimodal_survival_prediction_amd/bootstrap.py), for a file with risk_fold_* columns each member's C-index and the paired difference
 ensemble - member, and with --compare the paired difference of this file's risk_score against every other file's on the same patients.
 A `fold` column, when present, stratifies both the pairs and the resampling.  Without --bootstrap nothing changes.
+
+--stratify R [--min-prop 0.1] adds "risk_stratification" to the summary: the log-rank statistic of EVERY admissible cut of risk_score
+(cutpoint_scan.csv), the median split's permutation p, the best cut with the ADJUSTED p of the maximally selected statistic over R random
+relabellings (on the MI355X: multimodal_survival_prediction_amd/risk_strata.py), Peto hazard ratios, and Greenwood bands on the
+Kaplan-Meier figure.  Without --stratify nothing changes.
 """
 import argparse
 import json
@@ -245,8 +250,25 @@ def bootstrap_summary(df, replicates, seed=0, compare=(), alpha=0.05):
     return out
 
 
-def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=()):
-    """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics; bootstrap > 0: + c_index_bootstrap)."""
+def stratification_summary(df, replicates, seed=0, min_prop=0.1, outdir="results", alpha=0.05):
+    """-> (the "risk_stratification" entry, the median split's Kaplan-Meier curves with bands); writes <outdir>/cutpoint_scan.csv, the
+    log-rank statistic of every admissible cut of risk_score (multimodal_survival_prediction_amd/risk_strata.py, on the GPU)."""
+    from multimodal_survival_prediction_amd import risk_strata as RS
+    t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
+    res = RS.stratify(r, t, e, R=replicates, seed=seed, min_prop=min_prop, alpha=alpha)
+    m = res.models[0]
+    pd.DataFrame({"threshold": m.threshold, "n_high": m.n_high, "d_high": m.d_high, "U": m.U, "V": m.V, "chi2": m.chi2,
+                  "p_unadjusted": m.p_unadjusted, "median_split": np.arange(len(m.threshold)) == m.median_index,
+                  "best": np.arange(len(m.threshold)) == m.best_index}).to_csv(os.path.join(outdir, "cutpoint_scan.csv"), index=False)
+    curves = RS.km_groups(t, e, m.high(r, "median"), alpha)
+    out = dict(replicates=res.replicates, seed=int(seed), min_prop=float(min_prop), alpha=float(alpha), **m.summary())
+    out["km"] = {c.group: {"median": c.median, "median_low": c.median_low, "median_high": c.median_high} for c in curves}
+    return out, curves
+
+
+def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), stratify=0, min_prop=0.1):
+    """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics; bootstrap > 0: + c_index_bootstrap;
+    stratify > 0: + risk_stratification and cutpoint_scan.csv)."""
     t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
     c_index = SS.concordance_index(t, -r, e)
     group = SS.risk_groups(r)
@@ -273,14 +295,17 @@ def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=()):
     pd.DataFrame(km_rows).to_csv(os.path.join(outdir, "kaplan_meier_table.csv"), index=False)
     if bootstrap:
         summary["c_index_bootstrap"] = bootstrap_summary(df, bootstrap, seed, compare)
+    bands = None
+    if stratify:
+        summary["risk_stratification"], bands = stratification_summary(df, stratify, seed, min_prop, outdir)
     with open(os.path.join(outdir, "evaluation_summary.json"), "w") as f:
         json.dump(summary, f, indent=2)
     if plots:
-        _plots(df.assign(risk_group=group), km_rows, summary, outdir)
+        _plots(df.assign(risk_group=group), km_rows, summary, outdir, bands)
     return summary
 
 
-def _plots(df, km_rows, summary, outdir):
+def _plots(df, km_rows, summary, outdir, bands=None):
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -294,6 +319,8 @@ def _plots(df, km_rows, summary, outdir):
         g = km[km["group"] == name]
         if len(g):
             ax.step(g["time"], g["survival"], where="post", label=name, color=colour)
+    for c in bands or ():                              # --stratify: Greenwood (log-log) bands of the same two groups
+        ax.fill_between(c.time, c.low, c.high, step="post", alpha=0.15, color="tab:red" if c.group == "High Risk" else "tab:blue", linewidth=0)
     ax.set_xlabel("Time (days)"); ax.set_ylabel("Survival Probability"); ax.set_ylim(0, 1.02)
     ax.set_title(f"Kaplan-Meier by risk group (log-rank p = {summary['logrank']['p_value']:.3g})")
     ax.legend(loc="best"); ax.grid(True, alpha=0.3)
@@ -337,7 +364,12 @@ def main(argv=None):
     ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
                     help="R bootstrap resamples of the patients (on the GPU): adds c_index_bootstrap {replicates, seed, alpha, low, high, se, "
                          "n_degenerate} to the summary, and for risk_fold_* columns each member's C-index and ensemble - member with CI and p-value")
-    ap.add_argument("--seed", type=int, default=0, help="with --bootstrap: seed of numpy.random.default_rng")
+    ap.add_argument("--seed", type=int, default=0, help="with --bootstrap / --stratify: seed of numpy.random.default_rng")
+    ap.add_argument("--stratify", type=int, default=0, metavar="R",
+                    help="scan every admissible cut of risk_score with R random relabellings (on the GPU): adds risk_stratification {median: chi2, "
+                         "p_asymptotic, p_permutation, hazard_ratio; best: threshold, chi2, p_adjusted, hazard_ratio; km} to the summary, writes "
+                         "cutpoint_scan.csv and draws Greenwood bands on the Kaplan-Meier figure")
+    ap.add_argument("--min-prop", type=float, default=0.1, help="with --stratify: every cut leaves ceil(min_prop n) patients on each side")
     ap.add_argument("--compare", metavar="OTHER.csv", nargs="+", default=[],
                     help="with --bootstrap: other models' predictions of the SAME patients (joined on patient_id); adds the paired difference "
                          "of this file's risk_score against each, with CI and p-value")
@@ -346,6 +378,8 @@ def main(argv=None):
         ap.error("--compare needs --bootstrap R (the comparison is a paired bootstrap)")
     if a.bootstrap < 0:
         ap.error("--bootstrap needs a positive number of replicates")
+    if a.stratify < 0 or not 0.0 <= a.min_prop <= 0.5:
+        ap.error("--stratify needs a positive number of relabellings and --min-prop a share in [0, 0.5]")
     if a.attribute and not (a.predict or a.ensemble):
         ap.error("--attribute needs --predict CHECKPOINT (the gradients are taken on the checkpoint's model)")
     if a.predict and a.ensemble:
@@ -360,7 +394,8 @@ def main(argv=None):
         df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
     else:
         df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes) if a.predict else pd.read_csv(a.predictions)
-    s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare)
+    s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare, stratify=a.stratify,
+                 min_prop=a.min_prop)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
           f"log-rank chi2 {s['logrank']['chi2']:.3f} p {s['logrank']['p_value']:.3g}")
@@ -370,6 +405,12 @@ def main(argv=None):
               f"seed {b['seed']}, {b['n_degenerate']} degenerate)")
         for name, m in list(b.get("members", {}).items()) + list(b.get("compare", {}).items()):
             print(f"  vs {name}: C {m['c_index']:.4f}, difference {m['delta']:+.4f} (CI {m['low']:+.4f}..{m['high']:+.4f}, p = {m['p_value']:.3g})")
+    if a.stratify:
+        rs = s["risk_stratification"]
+        print(f"median split: chi2 {rs['median']['chi2']:.3f}, p {rs['median']['p_asymptotic']:.3g} asymptotic / {rs['median']['p_permutation']:.3g} "
+              f"permutation, HR {rs['median']['hazard_ratio']:.2f} ({rs['median']['low']:.2f}-{rs['median']['high']:.2f}); best of {rs['n_cuts']} cuts: "
+              f"risk > {rs['best']['threshold']:.4f}, chi2 {rs['best']['chi2']:.3f}, adjusted p {rs['best']['p_adjusted']:.3g} "
+              f"({rs['replicates']} relabellings, seed {rs['seed']}); saved cutpoint_scan.csv")
     print(f"saved {os.path.join(a.outdir, 'evaluation_summary.json')}, kaplan_meier_table.csv" + ("" if a.no_plots else ", figures"))
     return s
 
