@@ -639,6 +639,45 @@ typedef struct LogrankScanP {
     int ldo;
 } LogrankScanP;
 
+/* Absolute-risk metrics under bootstrap multiplicities (csrc/td_metrics.hip): the IPCW Brier score and the cumulative/dynamic AUC
+ * numerator of M models at H horizons for R multiplicity rows in one launch (absolute_risk.prediction_error).
+ * The n patients stand in TIME-ASCENDING order, at equal times events before censorings; the labels are shared by all replicates:
+ * trank = dense ranks of the times (equal times share a rank), event = 0 / 1, hcut[h] = the number of positions with t <= tau_h
+ * (non-decreasing; always the end of a group of equal times).  rord[m][k] = 2 * position + [k is the last of its group of equal risk
+ * scores], the positions of model m in RISK-ASCENDING order.  surv[m][i][h] = model m's predicted S(tau_h) of position i.
+ * A replicate r is the multiplicity row w[r][0..n) (0..127; W = sum w).  Over the distinct times u ascending, with S_a = sum of w at
+ * t >= u, d_u = the w of the events at u, n_u = S_a - d_u and S_b = the w at t > u (all exact integers),
+ *     G(t)  = prod_{u <= t, n_u > 0} S_b / n_u      (reverse Kaplan-Meier: the censoring distribution; G(t-) the product over u < t),
+ *     KM(t) = prod_{u <= t, S_a > 0} n_u / S_a      (the replicate's own Kaplan-Meier estimate),
+ * every factor ONE fp64 division of two integers, multiplied in ascending time order.  At horizon h a position i is a case iff
+ * i < hcut[h] and e_i, a control iff i >= hcut[h]; a case weighs w_i / G(t_i-).  Out, [R][H]: G = G(tau_h), km = KM(tau_h), wcase = the
+ * cases' weight, wctrl = the controls' sum of w (an exact integer); [R][M][H]:
+ *     brier   = ( sum_cases w_i / G(t_i-) S_i^2 + [wctrl > 0] sum_controls w_i (1 - S_i)^2 / G(tau_h) ) / W,
+ *     auc_num = sum over case i, control j of (w_i / G(t_i-)) w_j ([eta_i > eta_j] + 1/2 [eta_i = eta_j])
+ * (the AUC is auc_num / (wcase wctrl); the host forms it, the null model's Brier score from km, and the integrals).
+ * fp64 accumulation, no atomics, plain stores; one workgroup per replicate: a replicate's bits depend on its own row and the shared
+ * inputs only, not on R, on its place in the launch or on M (G / km / wcase / wctrl) or the other models (brier / auc_num).
+ * R = 0 is valid and launches nothing.  The launch cannot check the tables' contents: the CALLER guarantees the order and the tie
+ * rule of the positions, dense trank, hcut as above, every rord row a permutation with consistent group flags, finite surv, w >= 0 and
+ * W >= 1 in every row (ops.td_metrics checks on the host).  A position of rord outside [0, n) is clamped: it cannot reach memory
+ * outside the arguments.  A NULL pointer, n < 1, n > MMS_TD_MAX_N, H < 1, H > MMS_TD_MAX_H, M < 1, M > MMS_TD_MAX_M, R < 0,
+ * R > MMS_TD_MAX_R, ldr < n, ldh < H, ldw < n or a pointer not aligned to its element: MMS_ERR_ARG before any launch. */
+#define MMS_TD_MAX_H 64            /* lane = horizon: one wave */
+#define MMS_TD_MAX_M 64
+#define MMS_TD_MAX_N 4096          /* 12 bytes of LDS a position */
+#define MMS_TD_MAX_R 16777215      /* one workgroup of 256 threads per replicate: the launch's thread count stays below 2^32 */
+typedef struct TdMetricsP {
+    int n; int H; int M; int R;         // positions, horizons, models, replicates
+    const int* trank; const int* event; // [n] dense time ranks and event flags of the time-ascending positions
+    const int* hcut;                    // [H] positions with t <= tau_h
+    const int* rord; int ldr;           // [M][ldr] 2 * position + [last of its risk tie group], risk ascending
+    const double* surv; int ldh;        // [M][n][ldh] predicted survival at the horizons, position-major
+    const signed char* w; int ldw;      // [R][ldw] multiplicities 0..127
+    double* G; double* km;              // [R][H] out
+    double* wcase; double* wctrl;       // [R][H] out
+    double* brier; double* auc_num;     // [R][M][H] out
+} TdMetricsP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -934,6 +973,7 @@ int mms_cindex_counts(const CindexP* p, hipStream_t s);
 int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / weighted pair counts of M models x R replicates (CbootP above) */
 int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox score test of G genes on P problems (GeneScreenP above) */
 int mms_logrank_scan(const LogrankScanP* p, hipStream_t s);   /* log-rank statistic of every cut of Q problems (LogrankScanP above) */
+int mms_td_metrics(const TdMetricsP* p, hipStream_t s);       /* IPCW Brier / dynamic AUC sums of M models x H horizons x R replicates (TdMetricsP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);         /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */

@@ -405,6 +405,62 @@ def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False,
     return res
 
 
+def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
+    """IPCW Brier / dynamic AUC sums of M models at H horizons under R multiplicity rows (TdMetricsP in mmsurv.h).  trank, event: [n] dense
+    time ranks and event flags of the TIME-ASCENDING positions (events before censorings at equal times), hcut: [H] positions with
+    t <= tau_h, rord: [M, n] 2 * position + [last of its risk tie group] in risk-ascending order -- host arrays
+    (absolute_risk.metric_inputs makes them); surv: float64 [M, n, H] predicted survival per position, w: int8 [R, n] multiplicities --
+    host arrays or device tensors.  The launch cannot check the tables, so they are checked HERE (as ops.logrank_scan checks its cuts):
+    trank dense and non-decreasing from 0, no event after a censoring inside a time group, hcut non-decreasing in [0, n] and on
+    group boundaries, every rord row a permutation whose last entry ends a group, surv finite, w in 0..127 with a positive sum in every
+    row.  -> dict of float64 device tensors G, km, wcase, wctrl [R, H], brier, auc_num [R, M, H].  plan_only: upload and check, do not
+    launch -> (TdMetricsP, the tensors it points to, the dict), for call("mms_td_metrics", p) by the caller (tools/bench_td_metrics.py
+    times the launch alone)."""
+    import numpy as np
+    dev = next((t.device for t in (surv, w) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda"))
+    trank, event = np.asarray(trank, dtype=np.int64).reshape(-1), np.asarray(event, dtype=np.int64).reshape(-1)
+    hcut, rord = np.asarray(hcut, dtype=np.int64).reshape(-1), np.asarray(rord, dtype=np.int64)
+    n, H = len(trank), len(hcut)
+    if n < 1 or H < 1 or len(event) != n or rord.ndim != 2 or rord.shape[0] < 1 or rord.shape[1] != n:
+        raise ValueError("trank / event must have n >= 1 entries, hcut H >= 1 and rord must be [M >= 1, n]")
+    M = rord.shape[0]
+    step = np.diff(trank)
+    if trank[0] != 0 or ((step != 0) & (step != 1)).any():
+        raise ValueError("trank must be dense ranks of ascending times: from 0, every step 0 or 1")
+    if ((event != 0) & (event != 1)).any() or ((step == 0) & (np.diff(event) > 0)).any():
+        raise ValueError("event must be 0 / 1 and, inside a group of equal times, events must precede censorings")
+    inner = hcut[(hcut > 0) & (hcut < n)]
+    if (hcut < 0).any() or (hcut > n).any() or (np.diff(hcut) < 0).any() or (trank[inner - 1] == trank[inner]).any():
+        raise ValueError("hcut must be non-decreasing in [0, n] and must not split a group of equal times")
+    if (rord < 0).any() or not (np.sort(rord >> 1, 1) == np.arange(n)).all() or not (rord[:, -1] & 1).all():
+        raise ValueError("every row of rord must be 2 * (a permutation of 0..n-1) + flag, the last entry flagged")
+    if not torch.is_tensor(surv):
+        surv = torch.from_numpy(np.ascontiguousarray(np.asarray(surv, dtype=np.float64)))
+    if not torch.is_tensor(w):
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(w)))
+    if surv.dtype != torch.float64 or tuple(surv.shape) != (M, n, H) or not bool(torch.isfinite(surv).all()):
+        raise ValueError("surv must be finite float64 [M, n, H] = [%d, %d, %d]" % (M, n, H))
+    if w.dtype != torch.int8 or w.dim() != 2 or w.shape[1] != n:
+        raise ValueError("w must be int8 [R, n]")
+    R = w.shape[0]
+    if R and (bool((w < 0).any()) or bool((w.sum(1, dtype=torch.int64) < 1).any())):
+        raise ValueError("w must hold multiplicities 0..127 and every row must draw a patient")
+    surv, w = surv.to(dev).contiguous(), w.to(dev).contiguous()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
+    t = dict(trank=up(trank), event=up(event), hcut=up(hcut), rord=up(rord), surv=surv,
+             w=w if R else torch.zeros(1, n, dtype=torch.int8, device=dev))               # (never a NULL pointer)
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+    out = dict(G=z(max(R, 1), H), km=z(max(R, 1), H), wcase=z(max(R, 1), H), wctrl=z(max(R, 1), H), brier=z(max(R, 1), M, H),
+               auc_num=z(max(R, 1), M, H))
+    p = _S()["TdMetricsP"](n, H, M, R, ptr(t["trank"]), ptr(t["event"]), ptr(t["hcut"]), ptr(t["rord"]), n, ptr(t["surv"]), H, ptr(t["w"]), n,
+                           ptr(out["G"]), ptr(out["km"]), ptr(out["wcase"]), ptr(out["wctrl"]), ptr(out["brier"]), ptr(out["auc_num"]))
+    res = {k: v[:R] for k, v in out.items()}
+    if plan_only:
+        return p, (t, out), res
+    call("mms_td_metrics", p)
+    return res
+
+
 COXNET_STATUS = {-1: "new", 0: "not converged", 1: "converged", 2: "not converged"}
 
 

@@ -34,6 +34,17 @@ A `fold` column, when present, stratifies both the pairs and the resampling.  Wi
 (cutpoint_scan.csv), the median split's permutation p, the best cut with the ADJUSTED p of the maximally selected statistic over R random
 relabellings (on the MI355X: multimodal_survival_prediction_amd/risk_strata.py), Peto hazard ratios, and Greenwood bands on the
 Kaplan-Meier figure.  Without --stratify nothing changes.
+
+--horizons H | t1,t2,... adds "prediction_error" to the summary: the risk score becomes a survival curve S(t | x) through the Breslow
+baseline hazard of the fit set (--baseline TRAIN.csv; with --predict the fold's training patients are scored into
+<outdir>/train_predictions.csv and used), written per patient to survival_curves.csv, and is judged at the horizons by the IPCW Brier
+score, its scaled form against the Kaplan-Meier null model (IPA), the cumulative/dynamic AUC (prediction_error.csv, with intervals when
+--bootstrap R is given, on the MI355X: multimodal_survival_prediction_amd/absolute_risk.py) and a calibration table at the middle
+horizon (calibration.csv).  --compare-curves adds paired IBS / iAUC differences against other runs' survival_curves.csv on the same
+patients and horizons.  A file with risk_fold_* member columns has its risk_score evaluated alone.  Without --horizons nothing changes.
+
+    python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --horizons 16 --bootstrap 2000
+    python scripts/analysis/evaluate_model.py --horizons 365,730,1095 --baseline results/train_predictions.csv
 """
 import argparse
 import json
@@ -84,10 +95,11 @@ def _cohort_of(kind, device, external=False):
     return cohort, keep
 
 
-def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None):
+def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None, train_csv=None):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
-    labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth."""
+    labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth.
+    train_csv: also score the fold's TRAINING patients into that file, same columns (the fit set of --horizons' Breslow baseline)."""
     import torch
     from _common import env_dims, env_int, load_or_make_cohort, setup_device
     from multimodal_survival_prediction_amd import data, models
@@ -97,7 +109,7 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     n_folds, batch_size = n_folds or env_int("MMS_FOLDS", folds_default), batch_size or env_int("MMS_BATCH_SIZE", batch_default)
     cohort, keep = _cohort_of(kind, device)
     labelled = torch.nonzero(keep).reshape(-1).numpy()
-    _, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
+    trn, val = data.kfold_indices(len(labelled), n_folds, seed=42)[fold - 1]
     idx = labelled[val]
     gene_cols = None
     if genes:                                          # per-fold gene selection: the fold's columns, read before the forward pass
@@ -120,21 +132,23 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     if attribute_dir:
         from multimodal_survival_prediction_amd import attribution
         os.makedirs(attribute_dir, exist_ok=True)
+    def forward(ct, rna, clin, mask):
+        if kind == "final":
+            return eng.forward_eval(ct, rna, clin)[0]
+        if kind in ("partial", "simmim"):
+            return eng.forward_eval(ct, rna, clin, mask=mask)[0]
+        if kind == "simple":
+            return eng.forward_eval(ct, rna)[0]
+        if kind == "flexible":
+            return eng.forward_eval(ct, rna, mask=mask[:, :2])[0]
+        if kind == "image_only":
+            return eng.forward_eval(ct)[0]
+        return eng.forward_eval(None, rna)[0]
+
     for s in range(0, len(idx), batch_size):
         j = torch.as_tensor(idx[s:s + batch_size], device=device)
         ct, rna, clin, mask = cohort["image"][j], cohort["rnaseq"][j], cohort["clinical"][j], cohort["mask"][j]
-        if kind == "final":
-            hz, _ = eng.forward_eval(ct, rna, clin)
-        elif kind in ("partial", "simmim"):
-            hz, _ = eng.forward_eval(ct, rna, clin, mask=mask)
-        elif kind == "simple":
-            hz, _ = eng.forward_eval(ct, rna)
-        elif kind == "flexible":
-            hz, _ = eng.forward_eval(ct, rna, mask=mask[:, :2])
-        elif kind == "image_only":
-            hz, _ = eng.forward_eval(ct)
-        else:
-            hz, _ = eng.forward_eval(None, rna)
+        hz = forward(ct, rna, clin, mask)
         risks.append(hz.clone().cpu())
         if attribute_dir:
             has = (mask != 0).cpu().numpy() if mask is not None else np.ones((len(j), 3), bool)
@@ -158,6 +172,12 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
         pd.DataFrame({"gene": [names[i] for i in order], "mean_abs_grad": score[order]}).to_csv(
             os.path.join(attribute_dir, "gene_scores.csv"), index=False)
         print(f"wrote {attribute_dir}: saliency volumes and gene_scores.csv ({len(order)} genes over {gene_rows} patients)")
+    train_risks = []
+    if train_csv:                                      # the fold's training patients, scored by the same forward (after the validation split)
+        tidx = labelled[trn]
+        for s in range(0, len(tidx), batch_size):
+            j = torch.as_tensor(tidx[s:s + batch_size], device=device)
+            train_risks.append(forward(cohort["image"][j], cohort["rnaseq"][j], cohort["clinical"][j], cohort["mask"][j]).clone().cpu())
     eng.check_b4()                                     # a timed-out block-4 hand-off must not end up in the predictions file
     lab = cohort["label"].cpu().numpy()[idx]
     df = pd.DataFrame({"patient_id": [pid(i) for i in idx],
@@ -165,6 +185,12 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     os.makedirs(os.path.dirname(out_csv) or ".", exist_ok=True)
     df.to_csv(out_csv, index=False)
     print(f"wrote {out_csv}: {len(df)} patients of fold {fold}/{n_folds} ({cls})")
+    if train_csv:
+        lab = cohort["label"].cpu().numpy()[tidx]
+        os.makedirs(os.path.dirname(train_csv) or ".", exist_ok=True)
+        pd.DataFrame({"patient_id": [pid(i) for i in tidx], "survival_time": lab[:, 0], "event": lab[:, 1].astype(int),
+                      "risk_score": torch.cat(train_risks).numpy()}).to_csv(train_csv, index=False)
+        print(f"wrote {train_csv}: {len(tidx)} training patients of fold {fold}/{n_folds}")
     return df
 
 
@@ -266,9 +292,84 @@ def stratification_summary(df, replicates, seed=0, min_prop=0.1, outdir="results
     return out, curves
 
 
-def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), stratify=0, min_prop=0.1):
+def parse_horizons(arg, time, event):
+    """--horizons: a count H (absolute_risk.default_horizons of this file's patients) or the horizons themselves, comma-separated"""
+    from multimodal_survival_prediction_amd import absolute_risk as AR
+    if str(arg).strip().isdigit():
+        return AR.default_horizons(time, event, int(arg))
+    return AR.check_horizons([float(x) for x in str(arg).split(",")])
+
+
+def curve_columns(horizons):
+    """one S_<tau> column name per horizon; repr keeps every digit, so --compare-curves reads the horizons back exactly"""
+    return [f"S_{float(x)!r}" for x in horizons]
+
+
+def prediction_error_summary(df, horizons, baseline, replicates=0, seed=0, compare_curves=(), outdir="results", alpha=0.05):
+    """-> (the "prediction_error" entry, what the figures need).  baseline: the fit-set predictions (survival_time, event, risk_score)
+    of the Breslow baseline.  Writes <outdir>/survival_curves.csv (S(tau | risk_score) per patient), prediction_error.csv (per horizon
+    Brier score, Kaplan-Meier null model, IPA and cumulative/dynamic AUC; with replicates > 0 their bootstrap intervals, on the GPU:
+    multimodal_survival_prediction_amd/absolute_risk.py) and calibration.csv (at the middle horizon)."""
+    from multimodal_survival_prediction_amd import absolute_risk as AR
+    t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
+    if any(c.startswith("risk_fold_") for c in df.columns):
+        print("--horizons: the file has risk_fold_* member columns; risk_score alone is evaluated")
+    tau = parse_horizons(horizons, t, e)
+    base = AR.breslow_baseline(baseline["risk_score"].to_numpy(float), baseline["survival_time"].to_numpy(float), baseline["event"].to_numpy(int))
+    surv, cols = base.survival(r, tau), curve_columns(tau)
+    keep = [c for c in ("patient_id", "survival_time", "event", "risk_score") if c in df.columns]
+    curves = pd.concat([df[keep].reset_index(drop=True), pd.DataFrame(surv, columns=cols)], axis=1)
+    curves.to_csv(os.path.join(outdir, "survival_curves.csv"), index=False)
+    survs, risks, others = [surv], [r], []
+    for path in compare_curves:
+        o = pd.read_csv(path)
+        if "patient_id" not in df.columns or "patient_id" not in o.columns:
+            raise ValueError(f"{path}: --compare-curves joins on patient_id")
+        if o["patient_id"].duplicated().any() or df["patient_id"].duplicated().any() or set(o["patient_id"]) != set(df["patient_id"]):
+            raise ValueError(f"{path}: the patient sets differ (a paired comparison scores every model on the same patients)")
+        if [c for c in o.columns if c.startswith("S_")] != cols:
+            raise ValueError(f"{path}: its horizons {[c[2:] for c in o.columns if c.startswith('S_')]} are not this run's {[c[2:] for c in cols]}")
+        o = o.set_index("patient_id").loc[df["patient_id"]]
+        if not (np.array_equal(o["survival_time"].to_numpy(float), t) and np.array_equal(o["event"].to_numpy(int), e)):
+            raise ValueError(f"{path}: survival_time / event differ from this run's for the same patient ids")
+        others.append(path); survs.append(o[cols].to_numpy(float)); risks.append(o["risk_score"].to_numpy(float))
+    res = AR.prediction_error(np.stack(survs), np.stack(risks), t, e, tau, R=replicates, seed=seed,
+                              strata=df["fold"].to_numpy() if "fold" in df.columns else None, alpha=alpha)
+    table = {"horizon": tau}
+    for name, est in (("brier", res.brier), ("brier_null", res.brier_null), ("ipa", res.ipa), ("auc", res.auc)):
+        table[name] = est.value if est.value.ndim == 1 else est.value[0]
+    if replicates:
+        for name, est in (("brier", res.brier), ("brier_null", res.brier_null), ("ipa", res.ipa), ("auc", res.auc)):
+            table[name + "_low"], table[name + "_high"] = (est.low, est.high) if est.low.ndim == 1 else (est.low[0], est.high[0])
+    table = pd.DataFrame(table)
+    table.to_csv(os.path.join(outdir, "prediction_error.csv"), index=False)
+    k = (len(tau) - 1) // 2
+    calib = pd.DataFrame(AR.calibration_table(surv[:, k], t, e, tau[k], groups=min(5, len(t)), alpha=alpha))
+    calib.insert(0, "horizon", tau[k])
+    calib.to_csv(os.path.join(outdir, "calibration.csv"), index=False)
+    out = {"horizons": [float(x) for x in tau], "replicates": int(replicates), "seed": int(seed), "alpha": float(alpha),
+           "baseline_patients": int(len(baseline)), "ibs": float(res.ibs.value[0]), "iauc": float(res.iauc.value[0]),
+           "brier": [float(x) for x in res.brier.value[0]], "brier_null": [float(x) for x in res.brier_null.value],
+           "ipa": [float(x) for x in res.ipa.value[0]], "auc": [float(x) for x in res.auc.value[0]], "calibration_horizon": float(tau[k])}
+    if replicates:
+        out.update(n_degenerate=int(res.n_degenerate), ibs_low=float(res.ibs.low[0]), ibs_high=float(res.ibs.high[0]), ibs_se=float(res.ibs.se[0]),
+                   iauc_low=float(res.iauc.low[0]), iauc_high=float(res.iauc.high[0]), iauc_se=float(res.iauc.se[0]))
+    if others:
+        def paired(d, m):
+            p = {"delta": float(d.delta[0, m])}
+            if replicates:
+                p.update(low=float(d.low[0, m]), high=float(d.high[0, m]), p_value=float(d.p_value[0, m]))
+            return p
+        out["compare"] = {path: {"ibs": float(res.ibs.value[1 + m]), "iauc": float(res.iauc.value[1 + m]), "ibs_difference": paired(res.ibs_diff, 1 + m),
+                                 "iauc_difference": paired(res.iauc_diff, 1 + m)} for m, path in enumerate(others)}
+    return out, (table, calib)
+
+
+def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), stratify=0, min_prop=0.1, horizons=None, baseline=None,
+             compare_curves=()):
     """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics; bootstrap > 0: + c_index_bootstrap;
-    stratify > 0: + risk_stratification and cutpoint_scan.csv)."""
+    stratify > 0: + risk_stratification and cutpoint_scan.csv; horizons: + prediction_error, survival_curves.csv, prediction_error.csv
+    and calibration.csv, with `baseline` the fit-set predictions of the Breslow baseline)."""
     t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
     c_index = SS.concordance_index(t, -r, e)
     group = SS.risk_groups(r)
@@ -298,11 +399,42 @@ def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), 
     bands = None
     if stratify:
         summary["risk_stratification"], bands = stratification_summary(df, stratify, seed, min_prop, outdir)
+    tables = None
+    if horizons:
+        summary["prediction_error"], tables = prediction_error_summary(df, horizons, baseline, bootstrap, seed, compare_curves, outdir)
     with open(os.path.join(outdir, "evaluation_summary.json"), "w") as f:
         json.dump(summary, f, indent=2)
     if plots:
         _plots(df.assign(risk_group=group), km_rows, summary, outdir, bands)
+        if tables:
+            _absolute_risk_plots(*tables, outdir)
     return summary
+
+
+def _absolute_risk_plots(table, calib, outdir):
+    """--horizons: Brier score / AUC against time (with the bootstrap intervals when present) and the calibration plot"""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return
+    fig, (a0, a1) = plt.subplots(1, 2, figsize=(11, 4.5))
+    for ax, names, title in ((a0, (("brier", "Model", "tab:red"), ("brier_null", "Kaplan-Meier null model", "tab:gray")), "IPCW Brier score"),
+                             (a1, (("auc", "Model", "tab:blue"),), "Cumulative/dynamic AUC")):
+        for col, label, colour in names:
+            ax.plot(table["horizon"], table[col], marker="o", label=label, color=colour)
+            if col + "_low" in table.columns:
+                ax.fill_between(table["horizon"], table[col + "_low"], table[col + "_high"], alpha=0.15, color=colour, linewidth=0)
+        ax.set_xlabel("Time (days)"); ax.set_title(title); ax.legend(loc="best"); ax.grid(True, alpha=0.3)
+    a1.axhline(0.5, color="black", linestyle="--", linewidth=0.8)
+    fig.tight_layout(); fig.savefig(os.path.join(outdir, "prediction_error.png"), dpi=150); plt.close(fig)
+    fig, ax = plt.subplots(figsize=(5.5, 5))
+    ax.errorbar(calib["predicted"], calib["observed"], yerr=[calib["observed"] - calib["low"], calib["high"] - calib["observed"]], marker="o", capsize=3)
+    ax.plot([0, 1], [0, 1], color="black", linestyle="--", linewidth=0.8)
+    ax.set_xlabel("Predicted event probability"); ax.set_ylabel("Observed (1 - Kaplan-Meier)")
+    ax.set_title(f"Calibration at {calib['horizon'].iloc[0]:g} days"); ax.grid(True, alpha=0.3)
+    fig.tight_layout(); fig.savefig(os.path.join(outdir, "calibration.png"), dpi=150); plt.close(fig)
 
 
 def _plots(df, km_rows, summary, outdir, bands=None):
@@ -373,7 +505,21 @@ def main(argv=None):
     ap.add_argument("--compare", metavar="OTHER.csv", nargs="+", default=[],
                     help="with --bootstrap: other models' predictions of the SAME patients (joined on patient_id); adds the paired difference "
                          "of this file's risk_score against each, with CI and p-value")
+    ap.add_argument("--horizons", metavar="H | t1,t2,...",
+                    help="absolute-risk evaluation at H default horizons (equally spaced between the 10th and 90th percentile of the observed event "
+                         "times) or at the given times: adds prediction_error {horizons, brier, brier_null, ipa, auc, ibs, iauc} to the summary and "
+                         "writes survival_curves.csv, prediction_error.csv and calibration.csv; with --bootstrap R (on the GPU) their intervals")
+    ap.add_argument("--baseline", metavar="TRAIN.csv",
+                    help="with --horizons: the fit set of the Breslow baseline hazard -- the TRAINING patients scored by the same model, in the "
+                         "columns of test_predictions.csv (default with --predict: <outdir>/train_predictions.csv, which --predict then writes)")
+    ap.add_argument("--compare-curves", metavar="OTHER/survival_curves.csv", nargs="+", default=[],
+                    help="with --horizons: other runs' survival_curves.csv on the SAME patient ids and horizons; adds the paired difference of "
+                         "IBS and iAUC against each (with --bootstrap R: interval and p-value)")
     a = ap.parse_args(argv)
+    if (a.baseline or a.compare_curves) and not a.horizons:
+        ap.error("--baseline and --compare-curves belong to --horizons")
+    if a.horizons and not (a.baseline or a.predict):
+        ap.error("--horizons needs the fit set of the baseline hazard: --baseline TRAIN.csv (or --predict, which scores the fold's training patients)")
     if a.compare and not a.bootstrap:
         ap.error("--compare needs --bootstrap R (the comparison is a paired bootstrap)")
     if a.bootstrap < 0:
@@ -392,10 +538,15 @@ def main(argv=None):
     adir = os.path.join(a.outdir, "attribution") if a.attribute else None
     if a.ensemble:
         df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
+    elif a.predict:
+        train_csv = os.path.join(a.outdir, "train_predictions.csv") if a.horizons and not a.baseline else None
+        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes, train_csv)
+        a.baseline = a.baseline or train_csv
     else:
-        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes) if a.predict else pd.read_csv(a.predictions)
+        df = pd.read_csv(a.predictions)
     s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare, stratify=a.stratify,
-                 min_prop=a.min_prop)
+                 min_prop=a.min_prop, horizons=a.horizons, baseline=pd.read_csv(a.baseline) if a.horizons else None,
+                 compare_curves=a.compare_curves)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
           f"log-rank chi2 {s['logrank']['chi2']:.3f} p {s['logrank']['p_value']:.3g}")
@@ -411,6 +562,15 @@ def main(argv=None):
               f"permutation, HR {rs['median']['hazard_ratio']:.2f} ({rs['median']['low']:.2f}-{rs['median']['high']:.2f}); best of {rs['n_cuts']} cuts: "
               f"risk > {rs['best']['threshold']:.4f}, chi2 {rs['best']['chi2']:.3f}, adjusted p {rs['best']['p_adjusted']:.3g} "
               f"({rs['replicates']} relabellings, seed {rs['seed']}); saved cutpoint_scan.csv")
+    if a.horizons:
+        pe = s["prediction_error"]
+        ci = lambda k: f" ({100 * (1 - pe['alpha']):.0f} % CI {pe[k + '_low']:.4f}-{pe[k + '_high']:.4f})" if a.bootstrap else ""
+        print(f"{len(pe['horizons'])} horizons {pe['horizons'][0]:g}..{pe['horizons'][-1]:g}, baseline on {pe['baseline_patients']} patients: "
+              f"IBS {pe['ibs']:.4f}{ci('ibs')}, iAUC {pe['iauc']:.4f}{ci('iauc')}; saved survival_curves.csv, prediction_error.csv, calibration.csv")
+        for name, m in pe.get("compare", {}).items():
+            tail = lambda d: f" (CI {d['low']:+.4f}..{d['high']:+.4f}, p = {d['p_value']:.3g})" if a.bootstrap else ""
+            print(f"  vs {name}: IBS {m['ibs']:.4f}, difference {m['ibs_difference']['delta']:+.4f}{tail(m['ibs_difference'])}; "
+                  f"iAUC {m['iauc']:.4f}, difference {m['iauc_difference']['delta']:+.4f}{tail(m['iauc_difference'])}")
     print(f"saved {os.path.join(a.outdir, 'evaluation_summary.json')}, kaplan_meier_table.csv" + ("" if a.no_plots else ", figures"))
     return s
 
