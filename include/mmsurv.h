@@ -678,6 +678,52 @@ typedef struct TdMetricsP {
     double* brier; double* auc_num;     // [R][M][H] out
 } TdMetricsP;
 
+/* Multivariable Cox regression by Newton-Raphson (csrc/cox_newton.hip): Q = R * S low-dimensional fits in one launch -- every bootstrap
+ * replicate of every nested covariate subset of one analysis (multivariable.analyse).
+ * The n patients stand in TIME-DESCENDING order (any order inside a group of equal times) with event[n] = 0 / 1 and glast[n] = 1 at the
+ * last position of a group of equal times (CoxnetP's convention); x[n][ldx] is the fp64 covariate table, position-major, of which the
+ * first p columns are used.  All of this is shared.  Problem q = r * S + s has the multiplicity row w[r][0..n) (0..127, a multiplicity
+ * is a repeat) and the column set cmask[s] (bit a: column a is in the model); coefficients outside the mask stay exactly 0 and their se
+ * is NaN.  Breslow ties.  With eta_k = sum_{a in A} x_ka beta_a shifted by its maximum over the rows with w > 0, r_k = w_k exp(eta_k)
+ * and the running sums S0 = sum r, S1 = sum r x, S2 = sum r x x' over the positions so far, every tie-group end with
+ * d = sum w_k e_k > 0 over the group adds
+ *     l += sum w e eta - d log S0,    g += sum w e x - d S1 / S0,    I += d (S2 / S0 - S1 S1' / S0^2).
+ * Solver, per problem:  (1) beta = 0, evaluate, loglik0 = l.  sum w e = 0: status 6 (beta = 0, loglik = 0).  (2) Every round factors
+ * I = L L' on the mask's columns; a pivot (the diagonal entry less the squares left of it) that is not > 1e-10 * the largest diagonal
+ * entry of I: status 3 (singular).  (3) delta = I^-1 g; max |delta| <= tol: status 1 (converged), beta is kept and
+ * se = sqrt(diag(I^-1)) from this factor.  (4) Else the first s = 1, 1/2, ..., 2^-20 with l(beta + s delta) >= l - 1e-12 max(1, |l|)
+ * is accepted (anything else, NaN included, is not); none: status 5.  (5) An accepted step counts one iteration; then
+ * max |beta| > beta_max: status 4 (monotone likelihood), else iters = max_iter: status 2.  Every status leaves a finite beta, the
+ * loglik of that beta and iters; se is NaN unless the status is 1.  An empty mask is the null model (status 1 after 0 iterations).
+ * Out: beta, se [Q][p], loglik, loglik0 [Q], iters, status [Q] and, unless NULL, info [Q][p][p] = the full symmetric information at the
+ * kept beta (zero outside the mask).
+ * fp64 throughout, no atomics, no waits, plain stores; one workgroup per problem: a problem's bits depend on its own row, its own mask
+ * and the shared inputs only, not on Q, on its place in the launch or on whether info is asked for.  Bits of a mask at or above p are
+ * ignored by the launch.  The launch cannot check the tables' contents: the CALLER guarantees the order of the positions, glast
+ * consistent with it (glast[n - 1] = 1), finite x, w >= 0 and valid, non-empty masks (ops.cox_newton checks on the host).  A NULL
+ * required pointer (info alone may be NULL), n < 1, n > MMS_COXNEWTON_MAX_N, p < 1, p > MMS_COXNEWTON_MAX_P, ldx < p, ldw < n, R < 0,
+ * S < 0, S > MMS_COXNEWTON_MAX_S, R * S > MMS_COXNEWTON_MAX_Q, tol outside (0, MMS_COXNEWTON_MAX_TOL], max_iter outside
+ * [1, MMS_COXNEWTON_MAX_ITER], beta_max not > 0 or a pointer not aligned to its element: MMS_ERR_ARG before any launch.  R = 0 or
+ * S = 0: MMS_OK without a launch. */
+#define MMS_COXNEWTON_MAX_P 16       /* 136 (a <= b) pairs: three waves of lanes */
+#define MMS_COXNEWTON_MAX_N 4096     /* 20 bytes of LDS a position */
+#define MMS_COXNEWTON_MAX_S 64
+#define MMS_COXNEWTON_MAX_Q 16777215 /* one workgroup of 256 threads per problem: the launch's thread count stays below 2^32 */
+#define MMS_COXNEWTON_MAX_TOL 1e-3
+#define MMS_COXNEWTON_MAX_ITER 1000
+typedef struct CoxNewtonP {
+    int n; int p; int R; int S;         // positions, covariate columns, replicates, subsets
+    const double* x; int ldx;           // [n][ldx] covariates of the time-descending positions
+    const int* event; const int* glast; // [n] event flag; 1 at the last position of a group of equal times
+    const signed char* w; int ldw;      // [R][ldw] multiplicities 0..127
+    const int* cmask;                   // [S] bit a: column a is in the model
+    double tol; int max_iter; double beta_max;
+    double* beta; double* se;           // [R * S][p] out
+    double* loglik; double* loglik0;    // [R * S] out
+    int* iters; int* status;            // [R * S] out
+    double* info;                       // [R * S][p][p] out, or NULL
+} CoxNewtonP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -974,7 +1020,8 @@ int mms_cindex_boot(const CbootP* p, hipStream_t s);           /* bootstrap / we
 int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox score test of G genes on P problems (GeneScreenP above) */
 int mms_logrank_scan(const LogrankScanP* p, hipStream_t s);   /* log-rank statistic of every cut of Q problems (LogrankScanP above) */
 int mms_td_metrics(const TdMetricsP* p, hipStream_t s);       /* IPCW Brier / dynamic AUC sums of M models x H horizons x R replicates (TdMetricsP above) */
-int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);         /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
+int mms_cox_newton(const CoxNewtonP* p, hipStream_t s);       /* Newton-Raphson Cox fits of R replicates x S covariate subsets (CoxNewtonP above) */
+int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);        /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */

@@ -461,6 +461,69 @@ def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     return res
 
 
+COX_NEWTON_STATUS = {1: "converged", 2: "max_iter", 3: "singular", 4: "monotone likelihood", 5: "no step accepted", 6: "no events"}
+
+
+def cox_newton(x, time, event, glast, w, cmask, tol=1e-9, max_iter=30, beta_max=30.0, info=False, plan_only=False):
+    """Newton-Raphson Cox fits of R multiplicity rows x S covariate subsets (CoxNewtonP in mmsurv.h).  x: float64 [n, p] covariates of
+    the TIME-DESCENDING positions, w: int8 [R, n] multiplicities -- host arrays or device tensors (a view's row pitch x.stride(0) /
+    w.stride(0) is passed on); time, event, glast: [n] the positions' times, event flags and 1 at the last position of each group of
+    equal times, cmask: [S] column sets (bit a = column a) -- host arrays.  The launch cannot check the tables, so they are checked
+    HERE (as ops.td_metrics checks its own): times
+    non-increasing, glast exactly the ends of the groups of equal times, x finite, w >= 0, every mask non-empty and below 2^p.
+    -> dict of device tensors beta, se (float64 [R, S, p]), loglik, loglik0 (float64 [R, S]), iters, status (int32 [R, S]) and, with
+    info, info (float64 [R, S, p, p]).  plan_only: upload and check, do not launch -> (CoxNewtonP, the tensors it points to, the dict),
+    for call("mms_cox_newton", p) by the caller (tools/bench_cox_newton.py times the launch alone)."""
+    import numpy as np
+    dev = next((t.device for t in (x, w) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda"))
+    time, event = np.asarray(time, dtype=np.float64).reshape(-1), np.asarray(event, dtype=np.int64).reshape(-1)
+    glast, cmask = np.asarray(glast, dtype=np.int64).reshape(-1), np.asarray(cmask, dtype=np.int64).reshape(-1)
+    n, S = len(time), len(cmask)
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+    if not torch.is_tensor(w):
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(w)))
+    if x.dtype != torch.float64 or x.dim() != 2 or x.shape[0] != n or n < 1 or x.shape[1] < 1 or x.stride(1) != 1:
+        raise ValueError("x must be float64 [n, p] with n = len(time) >= 1, p >= 1 and unit column stride")
+    p = x.shape[1]
+    if len(event) != n or len(glast) != n or ((event != 0) & (event != 1)).any():
+        raise ValueError("event and glast must have n entries and event must be 0 / 1")
+    if not np.isfinite(time).all() or (np.diff(time) > 0).any():
+        raise ValueError("the positions must stand in time-descending order (finite times)")
+    if not np.array_equal(glast != 0, np.concatenate([time[1:] != time[:-1], [True]])):
+        raise ValueError("glast must be 1 exactly at the last position of every group of equal times")
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("x must be finite")
+    if w.dtype != torch.int8 or w.dim() != 2 or w.shape[1] != n or (w.shape[0] > 1 and w.stride(1) != 1):
+        raise ValueError("w must be int8 [R, n]")
+    R = w.shape[0]
+    if R and bool((w < 0).any()):
+        raise ValueError("w must hold multiplicities 0..127")
+    if ((cmask <= 0) | (cmask >= (1 << p))).any():
+        raise ValueError("every mask must name at least one of the %d columns and none beyond them" % p)
+    x, w = x.to(dev), w.to(dev)
+    if n > 1 and x.stride(0) < p:
+        x = x.contiguous()
+    if R == 0 or (R > 1 and w.stride(0) < n) or w.stride(1) != 1:
+        w = w.contiguous() if R else torch.zeros(1, n, dtype=torch.int8, device=dev)          # (never a NULL pointer)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)) if a.size else np.zeros(1, np.int32)).to(dev)
+    t = dict(x=x, w=w, event=up(event), glast=up((glast != 0)), cmask=up(cmask))
+    Q = max(R * S, 1)
+    zd = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+    zi = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+    out = dict(beta=zd(Q, p), se=zd(Q, p), loglik=zd(Q), loglik0=zd(Q), iters=zi(Q), status=zi(Q))
+    if info:
+        out["info"] = zd(Q, p, p)
+    P = _S()["CoxNewtonP"](n, p, R, S, ptr(x), max(x.stride(0), p) if n > 1 else p, ptr(t["event"]), ptr(t["glast"]), ptr(w),
+                           max(w.stride(0), n) if R > 1 else n, ptr(t["cmask"]), float(tol), int(max_iter), float(beta_max), ptr(out["beta"]),
+                           ptr(out["se"]), ptr(out["loglik"]), ptr(out["loglik0"]), ptr(out["iters"]), ptr(out["status"]), ptr(out.get("info")))
+    res = {k: v[:R * S].reshape((R, S) + tuple(v.shape[1:])) for k, v in out.items()}
+    if plan_only:
+        return P, (t, out), res
+    call("mms_cox_newton", P)
+    return res
+
+
 COXNET_STATUS = {-1: "new", 0: "not converged", 1: "converged", 2: "not converged"}
 
 

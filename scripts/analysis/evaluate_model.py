@@ -45,6 +45,16 @@ patients and horizons.  A file with risk_fold_* member columns has its risk_scor
 
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --horizons 16 --bootstrap 2000
     python scripts/analysis/evaluate_model.py --horizons 365,730,1095 --baseline results/train_predictions.csv
+
+--adjust [COVARIATES.csv] adds "multivariable" to the summary: is risk_score an INDEPENDENT prognostic factor once the covariates of
+that file (patient_id plus numeric columns; --adjust-columns a,b takes those alone) are in a Cox model?  The file's columns are the base
+model, risk_score is added to it, and every --compare file's risk_score is added under that file's stem: adjusted hazard ratios (per
+standard deviation and per unit) with Wald intervals, likelihood-ratio tests of base + covariate against base, and with --bootstrap R
+percentile intervals over the same patient resamples as the C-index (on the MI355X: multimodal_survival_prediction_amd/multivariable.py);
+multivariable.csv has one row per model and coefficient.  With --predict a bare --adjust writes <outdir>/covariates.csv (age of the
+predicted patients, empty where the clinical record is missing) and uses it.  Without --adjust nothing changes.
+
+    python scripts/analysis/evaluate_model.py --adjust data/covariates.csv --compare rnaseq/test_predictions.csv --bootstrap 2000
 """
 import argparse
 import json
@@ -95,11 +105,12 @@ def _cohort_of(kind, device, external=False):
     return cohort, keep
 
 
-def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None, train_csv=None):
+def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None, train_csv=None, cov_csv=None):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
     labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth.
-    train_csv: also score the fold's TRAINING patients into that file, same columns (the fit set of --horizons' Breslow baseline)."""
+    train_csv: also score the fold's TRAINING patients into that file, same columns (the fit set of --horizons' Breslow baseline).
+    cov_csv: also write the predicted patients' covariates there (patient_id, age = clinical * 100, empty without a clinical record)."""
     import torch
     from _common import env_dims, env_int, load_or_make_cohort, setup_device
     from multimodal_survival_prediction_amd import data, models
@@ -185,6 +196,12 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     os.makedirs(os.path.dirname(out_csv) or ".", exist_ok=True)
     df.to_csv(out_csv, index=False)
     print(f"wrote {out_csv}: {len(df)} patients of fold {fold}/{n_folds} ({cls})")
+    if cov_csv:
+        age = cohort["clinical"].cpu().numpy()[idx, 0].astype(np.float64) * 100.0
+        os.makedirs(os.path.dirname(cov_csv) or ".", exist_ok=True)
+        pd.DataFrame({"patient_id": [pid(i) for i in idx],
+                      "age": np.where(cohort["mask"].cpu().numpy()[idx, 2] != 0, age, np.nan)}).to_csv(cov_csv, index=False)
+        print(f"wrote {cov_csv}: age of {len(idx)} patients")
     if train_csv:
         lab = cohort["label"].cpu().numpy()[tidx]
         os.makedirs(os.path.dirname(train_csv) or ".", exist_ok=True)
@@ -365,11 +382,48 @@ def prediction_error_summary(df, horizons, baseline, replicates=0, seed=0, compa
     return out, (table, calib)
 
 
+def multivariable_summary(df, adjust, adjust_columns=None, compare=(), replicates=0, seed=0, outdir="results", alpha=0.05):
+    """-> the "multivariable" entry; writes <outdir>/multivariable.csv (one row per model and coefficient).  adjust: the covariates file
+    (or its DataFrame): patient_id plus numeric columns = the base model (adjust_columns: those alone); risk_score and every compare
+    file's risk_score (under the file's stem) are the added covariates (multimodal_survival_prediction_amd/multivariable.py, on the GPU)."""
+    from multimodal_survival_prediction_amd import multivariable as MV
+    cov = pd.read_csv(adjust) if isinstance(adjust, (str, os.PathLike)) else adjust
+    if "patient_id" not in df.columns or "patient_id" not in cov.columns:
+        raise ValueError("--adjust joins on patient_id, which both files must have")
+    if cov["patient_id"].duplicated().any() or df["patient_id"].duplicated().any() or not set(df["patient_id"]) <= set(cov["patient_id"]):
+        raise ValueError("--adjust: the covariates must list every predicted patient once")
+    cov = cov.set_index("patient_id").loc[df["patient_id"]]
+    base = list(adjust_columns) if adjust_columns else [c for c in cov.columns if pd.api.types.is_numeric_dtype(cov[c])]
+    missing = [c for c in base if c not in cov.columns or not pd.api.types.is_numeric_dtype(cov[c])]
+    if missing or not base:
+        raise ValueError(f"--adjust: no numeric column(s) {missing or ''} in the covariates file")
+    columns = {c: cov[c].to_numpy(float) for c in base}
+    columns["risk_score"] = df["risk_score"].to_numpy(float)
+    for path in compare:
+        o = pd.read_csv(path)
+        if o["patient_id"].duplicated().any() or set(o["patient_id"]) != set(df["patient_id"]):
+            raise ValueError(f"{path}: the patient sets differ (a paired comparison scores every model on the same patients)")
+        stem = os.path.splitext(os.path.basename(path))[0]
+        if stem in columns:
+            raise ValueError(f"{path}: the name {stem!r} is taken (a covariate is named after its file's stem)")
+        columns[stem] = o.set_index("patient_id").loc[df["patient_id"], "risk_score"].to_numpy(float)
+    add = [c for c in columns if c not in base]
+    res = MV.analyse(columns, df["survival_time"].to_numpy(float), df["event"].to_numpy(int), base, add, R=replicates, seed=seed,
+                     strata=df["fold"].to_numpy() if "fold" in df.columns else None, alpha=alpha)
+    rows = []
+    for m in res["models"]:
+        for name, c in m["coefficients"].items():
+            rows.append(dict(model=m["model"], covariate=name, **c, loglik=m["loglik"], aic=m["aic"], c_index=m["c_index"], status=m["status"]))
+    pd.DataFrame(rows).to_csv(os.path.join(outdir, "multivariable.csv"), index=False)
+    return res
+
+
 def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), stratify=0, min_prop=0.1, horizons=None, baseline=None,
-             compare_curves=()):
+             compare_curves=(), adjust=None, adjust_columns=None):
     """-> the evaluation_summary.json dictionary (reference keys + log-rank + per-group statistics; bootstrap > 0: + c_index_bootstrap;
     stratify > 0: + risk_stratification and cutpoint_scan.csv; horizons: + prediction_error, survival_curves.csv, prediction_error.csv
-    and calibration.csv, with `baseline` the fit-set predictions of the Breslow baseline)."""
+    and calibration.csv, with `baseline` the fit-set predictions of the Breslow baseline; adjust: + multivariable and multivariable.csv,
+    with `adjust` the covariates file)."""
     t, e, r = df["survival_time"].to_numpy(float), df["event"].to_numpy(int), df["risk_score"].to_numpy(float)
     c_index = SS.concordance_index(t, -r, e)
     group = SS.risk_groups(r)
@@ -402,6 +456,8 @@ def evaluate(df, outdir="results", plots=True, bootstrap=0, seed=0, compare=(), 
     tables = None
     if horizons:
         summary["prediction_error"], tables = prediction_error_summary(df, horizons, baseline, bootstrap, seed, compare_curves, outdir)
+    if adjust is not None:
+        summary["multivariable"] = multivariable_summary(df, adjust, adjust_columns, compare, bootstrap, seed, outdir)
     with open(os.path.join(outdir, "evaluation_summary.json"), "w") as f:
         json.dump(summary, f, indent=2)
     if plots:
@@ -515,13 +571,23 @@ def main(argv=None):
     ap.add_argument("--compare-curves", metavar="OTHER/survival_curves.csv", nargs="+", default=[],
                     help="with --horizons: other runs' survival_curves.csv on the SAME patient ids and horizons; adds the paired difference of "
                          "IBS and iAUC against each (with --bootstrap R: interval and p-value)")
+    ap.add_argument("--adjust", metavar="COVARIATES.csv", nargs="?", const=True, default=None,
+                    help="multivariable Cox analysis (on the GPU): patient_id plus numeric columns = the base model, to which risk_score and every "
+                         "--compare file's risk_score are added; adds multivariable {models, lr_tests, n_degenerate, status_counts} to the summary and "
+                         "writes multivariable.csv; with --bootstrap R percentile intervals.  Bare, with --predict: <outdir>/covariates.csv (age), "
+                         "which --predict then writes")
+    ap.add_argument("--adjust-columns", metavar="a,b", help="with --adjust: the columns of the base model (default: every numeric column)")
     a = ap.parse_args(argv)
+    if a.adjust is True and not a.predict:
+        ap.error("--adjust needs a covariates file (bare --adjust belongs to --predict, which writes <outdir>/covariates.csv)")
+    if a.adjust_columns and a.adjust is None:
+        ap.error("--adjust-columns belongs to --adjust")
     if (a.baseline or a.compare_curves) and not a.horizons:
         ap.error("--baseline and --compare-curves belong to --horizons")
     if a.horizons and not (a.baseline or a.predict):
         ap.error("--horizons needs the fit set of the baseline hazard: --baseline TRAIN.csv (or --predict, which scores the fold's training patients)")
-    if a.compare and not a.bootstrap:
-        ap.error("--compare needs --bootstrap R (the comparison is a paired bootstrap)")
+    if a.compare and not (a.bootstrap or a.adjust is not None):
+        ap.error("--compare needs --bootstrap R (the comparison is a paired bootstrap) or --adjust")
     if a.bootstrap < 0:
         ap.error("--bootstrap needs a positive number of replicates")
     if a.stratify < 0 or not 0.0 <= a.min_prop <= 0.5:
@@ -540,13 +606,15 @@ def main(argv=None):
         df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
     elif a.predict:
         train_csv = os.path.join(a.outdir, "train_predictions.csv") if a.horizons and not a.baseline else None
-        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes, train_csv)
+        cov_csv = os.path.join(a.outdir, "covariates.csv") if a.adjust is True else None
+        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes, train_csv, cov_csv)
         a.baseline = a.baseline or train_csv
+        a.adjust = cov_csv or a.adjust
     else:
         df = pd.read_csv(a.predictions)
     s = evaluate(df, a.outdir, plots=not a.no_plots, bootstrap=a.bootstrap, seed=a.seed, compare=a.compare, stratify=a.stratify,
                  min_prop=a.min_prop, horizons=a.horizons, baseline=pd.read_csv(a.baseline) if a.horizons else None,
-                 compare_curves=a.compare_curves)
+                 compare_curves=a.compare_curves, adjust=a.adjust, adjust_columns=a.adjust_columns.split(",") if a.adjust_columns else None)
     print(f"patients {s['test_patients']} (deaths {s['deaths']}, censored {s['censored']}); C-index {s['c_index']:.4f}; "
           f"median risk {s['median_risk_score']:.4f}; low/high {s['risk_groups']['low_risk']}/{s['risk_groups']['high_risk']}; "
           f"log-rank chi2 {s['logrank']['chi2']:.3f} p {s['logrank']['p_value']:.3g}")
@@ -571,6 +639,17 @@ def main(argv=None):
             tail = lambda d: f" (CI {d['low']:+.4f}..{d['high']:+.4f}, p = {d['p_value']:.3g})" if a.bootstrap else ""
             print(f"  vs {name}: IBS {m['ibs']:.4f}, difference {m['ibs_difference']['delta']:+.4f}{tail(m['ibs_difference'])}; "
                   f"iAUC {m['iauc']:.4f}, difference {m['iauc_difference']['delta']:+.4f}{tail(m['iauc_difference'])}")
+    if a.adjust is not None:
+        mv = s["multivariable"]
+        full = mv["models"][-1]
+        print(f"multivariable Cox on {mv['patients']} complete cases ({mv['n_dropped']} dropped), model {' + '.join(full['columns'])}:")
+        for name, c in full["coefficients"].items():
+            boot = f", bootstrap {c['hr_boot_low']:.3f}-{c['hr_boot_high']:.3f}" if a.bootstrap else ""
+            print(f"  {name}: HR {c['hr']:.3f} per SD (Wald {c['hr_low']:.3f}-{c['hr_high']:.3f}{boot}), p = {c['p']:.3g}")
+        for name, lr in mv["lr_tests"].items():
+            print(f"  likelihood-ratio test, base + {name} against base: chi2 {lr['chi2']:.3f} on {lr['df']} df, p = {lr['p']:.3g}")
+        if a.bootstrap:
+            print(f"  {mv['replicates']} resamples, seed {mv['seed']}, {mv['n_degenerate']} degenerate; saved multivariable.csv")
     print(f"saved {os.path.join(a.outdir, 'evaluation_summary.json')}, kaplan_meier_table.csv" + ("" if a.no_plots else ", figures"))
     return s
 
