@@ -54,18 +54,34 @@ def _build_features():
 
 
 class _Encode(torch.autograd.Function):
+    """The activations and BatchNorm statistics of a forward live in the module's one workspace (`_eng`), not in the autograd graph:
+    every forward of the module stamps a serial number on it (_run_forward), and a backward runs only while its forward is the latest
+    one there, and only once (the backward adds into BatchNorm-backward accumulators that only a training forward zeroes)."""
+
     @staticmethod
     def forward(ctx, x, anchor, net):
         ctx.net = net
         ctx.save_for_backward(x)
         ctx.train = net.training
-        return net._run_forward(x)
+        out = net._run_forward(x)
+        ctx.eng, ctx.serial = net._eng, net._eng["fwd_serial"]
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         if not ctx.train:
             raise RuntimeError("DenseNet121 (HIP): backward needs a training-mode forward (BN batch statistics)")
         (x,) = ctx.saved_tensors
+        e = ctx.net._eng
+        if e is not ctx.eng or e["fwd_serial"] != ctx.serial:
+            raise RuntimeError("DenseNet121 (HIP) backward: another forward ran on this model's workspace since the forward being "
+                               "differentiated (eval-mode and no_grad forwards included); its activations and BatchNorm statistics are "
+                               "gone -- run each backward before the next forward")
+        if e["bwd_serial"] == ctx.serial:
+            raise RuntimeError("DenseNet121 (HIP) backward: a second backward over the same forward is not supported (the first one "
+                               "consumed the workspace's BatchNorm-backward accumulators, which only a training forward zeroes); run "
+                               "the forward again")
+        e["bwd_serial"] = ctx.serial
         ctx.net._run_backward(x, dout)
         return None, None, None
 
@@ -117,7 +133,7 @@ class DenseNet121(nn.Module):
         btab = (ctypes.c_void_p * 363)(*[b.data_ptr() for b in bufs])
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.mms_dn121_init(ws.data_ptr(), B, D, H, W, ptab, btab, None, st), "mms_dn121_init")      # (torch-layout conv2 weights)
-        self._eng = dict(key=key, ws=ws, ptab=ptab, btab=btab, dims=(B, D, H, W), lib=lib)
+        self._eng = dict(key=key, ws=ws, ptab=ptab, btab=btab, dims=(B, D, H, W), lib=lib, fwd_serial=0, bwd_serial=0)
         return self._eng
 
     def _check_input(self, x):
@@ -129,6 +145,7 @@ class DenseNet121(nn.Module):
 
     def _run_forward(self, x):
         e = self._tables(x)
+        e["fwd_serial"] += 1         # (what _Encode.backward checks: this forward now owns the workspace)
         B, D, H, W = e["dims"]
         nout = self.class_layers.out.out_features
         out = torch.empty(B, nout, device=x.device, dtype=torch.float32)
@@ -180,6 +197,7 @@ class DenseNet121(nn.Module):
         from . import ops
         x = self._check_input(x)
         e = self._tables(x)
+        e["fwd_serial"] += 1
         B, D, H, W = e["dims"]
         nout = self.class_layers.out.out_features
         opts = ops.dn_opts(self.dn_opts, out_features=nout, persist_b3=-1, persist_b4=-1, fuse_layers=-1)

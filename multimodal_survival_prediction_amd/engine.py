@@ -205,6 +205,14 @@ def group_widths_ok(widths):
     return all(w % 64 != 48 for w in widths)
 
 
+def _weights_token(params, flat):
+    """What torch knows about the last change of `params` (parameters whose .data are views of `flat`) and of `flat` itself: their
+    version counters.  `p.data = view` gives the parameter a counter of its own, so an in-place change of p (p.mul_(), p.copy_(),
+    load_state_dict, a torch optimiser's step) bumps p._version and NOT flat._version; a write to flat (restore) bumps flat's only.
+    A write through p.data bumps neither.  Pure host code."""
+    return tuple(p._version for p in params) + (flat._version,)
+
+
 class _Plan:
     """Everything that depends on the batch size B (and the volume dims)."""
     pass
@@ -276,6 +284,7 @@ class SurvivalEngine:
             w2ids = {id(p) for k, p in self.prog["encoder"].named_parameters() if k.endswith("layers.conv2.weight")}
             assert len(w2ids) == 58
         self.w2_offsets = []
+        self._w2_params = []              # the conv2 parameters, in the order of w2_offsets (sync_packs watches their version counters)
 
         def view(buf, o, p):
             if id(p) in w2ids:
@@ -286,6 +295,7 @@ class SurvivalEngine:
                 if id(p) in w2ids:
                     assert tuple(p.shape) == (32, 128, 3, 3, 3) and o % 4 == 0
                     self.w2_offsets.append(o)
+                    self._w2_params.append(p)
                 v = view(self.flat, o, p)
                 v.copy_(p.data)
                 p.data = v
@@ -310,13 +320,18 @@ class SurvivalEngine:
 
     def sync_packs(self, force=False):
         """Packed primary conv2 storage: the derived packs are written by the fused optimiser step (mms_clip_adam); after ANY other
-        change of the weights -- load_state_dict, a torch optimiser, the roll-back around graph capture -- they are rebuilt here
-        (mms_w2_pack).  Detected through the version counter torch keeps for the flat buffer (its views share it); cheap to call."""
+        change of the weights -- load_state_dict, a torch optimiser, an in-place edit of a parameter, the roll-back around graph
+        capture -- they are rebuilt here (mms_w2_pack).  Detected through `_weights_token`: the version counters torch keeps for the 58
+        conv2 parameters and for the flat buffer.  Host-side attribute reads only: no synchronisation, and no launch when nothing
+        changed (so none inside a graph capture: every eager entry point calls this before it captures or replays).
+        NOT detected: writes through `p.data` (`p.data.mul_()`, optimisers written in the old `.data` style) -- they bump no version
+        counter at all.  After such a write call `sync_packs(force=True)`."""
         if self.w2 is None or self.w2["fragmask"] is None:
             return
-        if force or self._packs_version != self.flat._version:
+        token = _weights_token(self._w2_params, self.flat)
+        if force or self._packs_version != token:
             _lib.check(self.lib.mms_w2_pack(ctypes.byref(self._w2_adam), ops.stream()), "mms_w2_pack")
-            self._packs_version = self.flat._version
+            self._packs_version = token
 
     def _state(self):
         """Every tensor a training or validation step changes: a state word added to the fused step is added here, nowhere else."""
@@ -367,6 +382,9 @@ class SurvivalEngine:
         self._check_params()
         P = _Plan()
         P.B, P.dims = B, dims
+        # which forward the plan's one workspace holds (stamped by every forward on it), and which of them a backward has consumed:
+        # what the autograd path (models._Net) checks before it runs a backward
+        P.fwd_serial = P.bwd_serial = 0
         dev = self.device
         prog = self.prog
         P.has_enc = prog["encoder"] is not None and not heads_only
@@ -636,6 +654,7 @@ class SurvivalEngine:
     def _forward(self, P, train, enc_opts=None):
         """enc_opts: `const MmsDnOpts*` of the DenseNet121 driver call instead of _opts_arg's (attribute: the per-layer forms)."""
         self.sync_packs()
+        P.fwd_serial += 1
         st = ops.stream()
         lib, prog = self.lib, self.prog
         B, (D, H, W) = P.B, (P.dims if P.has_enc else (1, 1, 1))
@@ -917,6 +936,7 @@ class SurvivalEngine:
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None, bn_world=ddp_world if (sync_bn and ddp_world > 1) else 1)
         self.load_batch(P, ct, rna, clinical, mask, time, event, valid)
         self.sync_packs()
+        P.fwd_serial += 1           # (a graph replay does not pass through _forward)
         if ddp_world > 1 and P.big and self.prog["encoder"] is not None:
             raise RuntimeError("the data-parallel steps of the imaging models are limited to 32 rows per rank (their staged graphs are "
                                "built and tested on the small-batch head kernels); got %d -- lower the per-rank batch (the global batch is "
@@ -1106,6 +1126,7 @@ class SurvivalEngine:
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None)
         self.load_batch(P, ct, rna, clinical, mask)
         self.sync_packs()
+        P.fwd_serial += 1           # (a graph replay does not pass through _forward)
         if use_graph:
             if "eval" not in P.graphs:
                 P.graphs["eval"] = capture([self], lambda: self._forward(P, False))

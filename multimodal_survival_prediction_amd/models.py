@@ -6,6 +6,18 @@ flexible_multimodal.py:157-256, train_rnaseq_only.py:126-151; MONAI branch).  Th
 autograd leaves: `torch.optim.Adam(model.parameters())`, `clip_grad_norm_`, `state_dict()/load_state_dict()` keep
 working (the autograd-compatible path), while `training.train_epoch_*` drive the fused HIP-graph step (what each model's loop feeds
 it is that style's row of `training._STYLES`).
+
+Weight changes from outside the fused step: the DenseNet121 encoder keeps derived packs of its 58 conv2 weights, and the engine rebuilds
+them before its next launch when torch's version counters show a change -- `load_state_dict`, a torch optimiser's `step()`, any in-place
+edit of a parameter under `no_grad` (`p.mul_()`, `p.copy_()`).  A write through `p.data` (`p.data.mul_()`, optimisers written in the old
+`.data` style) moves no version counter and cannot be seen: call `engine_of(model).sync_packs(force=True)` after one.
+
+One workspace per (batch size, volume size): the forward's activations and BatchNorm statistics live in the engine's plan, not in the
+autograd graph.  Every forward at the same batch size and volume size -- training or eval mode, with or without gradients, through the
+module or through the engine (`forward_eval`, `train_step`) -- overwrites it; a forward at another batch size or volume size has a
+workspace of its own and disturbs nothing.  A backward whose forward is no longer the latest on its workspace raises, and so does a
+second backward over the same forward (the first consumed the workspace's BatchNorm-backward accumulators, which only a training
+forward zeroes: csrc/dn_net.hip, DESIGN.md "Weight changes and the module surface").
 """
 import torch
 import torch.nn as nn
@@ -46,6 +58,19 @@ def _next_dropout_masks(eng):
     eng.rng[1:].add_(1)
 
 
+def _claim_backward(P, serial):
+    """The backward of the forward that stamped `serial` on plan P may run only while that forward is the latest on P's workspace,
+    and only once."""
+    if P.fwd_serial != serial:
+        raise RuntimeError("backward: another forward ran on this model's workspace since the forward being differentiated (same batch "
+                           "size and volume size share one workspace, eval-mode and no_grad forwards included); its activations and "
+                           "BatchNorm statistics are gone -- run each backward before the next forward")
+    if P.bwd_serial == serial:
+        raise RuntimeError("backward: a second backward over the same forward is not supported (the first one consumed the workspace's "
+                           "BatchNorm-backward accumulators, which only a training forward zeroes); run the forward again")
+    P.bwd_serial = serial
+
+
 class _Net(torch.autograd.Function):
     """forward/backward of a whole network on the engine's eager path."""
 
@@ -55,7 +80,7 @@ class _Net(torch.autograd.Function):
         P = eng.plan((rna if rna is not None else ct).shape[0], tuple(ct.shape[-3:]) if ct is not None else None)
         eng.load_batch(P, ct, rna, clinical, mask)
         eng._forward(P, model.training)
-        ctx.eng, ctx.P, ctx.train = eng, P, model.training
+        ctx.eng, ctx.P, ctx.train, ctx.serial = eng, P, model.training, P.fwd_serial
         hz = P.buf["hz"][:, 0].clone()
         if P.gate is not None:
             return hz, P.gatew.clone()
@@ -66,6 +91,7 @@ class _Net(torch.autograd.Function):
         if not ctx.train:
             raise RuntimeError("backward through an eval-mode forward is not supported (BN batch statistics)")
         eng, P = ctx.eng, ctx.P
+        _claim_backward(P, ctx.serial)
         if eng.params[0].grad is None:
             eng.gflat.zero_()
             eng.attach_grads()
@@ -253,7 +279,7 @@ class _MoeNet(torch.autograd.Function):
         P = eng.plan(rna.shape[0], tuple(ct.shape[-3:]))
         eng.load_batch(P, ct, rna, clinical, mask)
         eng._forward(P, model.training)
-        ctx.eng, ctx.P, ctx.train = eng, P, model.training
+        ctx.eng, ctx.P, ctx.train, ctx.serial = eng, P, model.training, P.fwd_serial
         hz = P.buf["hz"]
         return hz[:, 0].clone(), hz[:, 1].clone(), hz[:, 2].clone(), hz[:, 3].clone(), P.gatew.clone()
 
@@ -262,6 +288,7 @@ class _MoeNet(torch.autograd.Function):
         if not ctx.train:
             raise RuntimeError("backward through an eval-mode forward is not supported (BN batch statistics)")
         eng, P = ctx.eng, ctx.P
+        _claim_backward(P, ctx.serial)
         if eng.params[0].grad is None:
             eng.gflat.zero_()
             eng.attach_grads()

@@ -149,3 +149,8 @@ def test_packed_model_surface():
     ref.eval(); net.eval()
     with torch.no_grad():
         assert_close(net(ct.to(DEV), rna.to(DEV), clin.to(DEV)), ref(ct, rna, clin), 1e-4, "eval hazards after an in-place update by torch")
+    # (halved weights shrink the encoder's share of the hazards below that tolerance: the packs themselves, all 58 layers, bit for bit --
+    # tests/test_gpu_module_surface.py has the cases whose hazards move)
+    from gpu_util import assert_conv2_packs_current
+    assert eng.w2["fragmask"] != 0
+    assert_conv2_packs_current(eng)
