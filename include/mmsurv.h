@@ -503,6 +503,11 @@ typedef struct CoxP {
     float* tie_frac;                // [n] workspace (tie_mode 1): l/m of each event
 } CoxP;
 
+/* One span of mms_zero_spans_group: `bytes` > 0 bytes at p, any alignment. */
+typedef struct MmsZeroSpan {
+    void* p; size_t bytes;
+} MmsZeroSpan;
+
 /* Harrell C, pair counting (R/scripts/training/simple_fusion.py:59-73): counts[0]=concordant (h_i>h_j),
  * counts[1]=tied hazards, counts[2]=permissible pairs (e_i==1, t_j>t_i). */
 typedef struct CindexP {
@@ -1139,13 +1144,30 @@ int mms_gather_affine_group(const GatherP* p, const AugP* a, const AffP* f, int 
 int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s);  /* scratch[g]: model g's [nlayers][27][32][128] tap-major scratch; dw[g][i]: canonical gradient of layer i; nlayers <= 58 */
 int mms_zero_regions_group(void* const* regions_dev, int ng, size_t bytes, hipStream_t s);   /* 16-B aligned regions of equal size, zero-filled by one launch */
 int mms_linear_fwd_group(const LinearFwdP* p, int ng, hipStream_t s);
+/* Precondition since the two roles of a layer share one launch: dx must not overlap dy, y or x (the weight role may still be reading them
+ * while the input role writes dx; the engines keep activations and their gradients in separate buffers). */
 int mms_linear_bwd_group(const LinearBwdP* p, int ng, hipStream_t s);
+/* The same with the launch form chosen by the caller: 0 = what mms_linear_bwd_group does (a layer with both dw and dx: ONE launch whose
+ * workgroups split into the weight and the input role); 1 = one launch per role.  Same values per element in both.  Other forms: MMS_ERR_ARG. */
+int mms_linear_bwd_group_form(const LinearBwdP* p, int ng, int form, hipStream_t s);
 int mms_gate_fwd_group(const GateP* p, int ng, hipStream_t s);
 int mms_gate_bwd_group(const GateP* p, int ng, hipStream_t s);
 int mms_cox_fwd_bwd_group(const CoxP* p, int ng, hipStream_t s);
+/* The same with the launch form chosen by the caller: 0 = what mms_cox_fwd_bwd_group does (n <= 256: both passes in ONE launch of one
+ * workgroup per model; larger n: two launches); 1 = always the two launches.  Same bits in lse, tie_frac, out and dh.  Other forms: MMS_ERR_ARG. */
+int mms_cox_fwd_bwd_group_form(const CoxP* p, int ng, int form, hipStream_t s);
+/* Zero-fill of n spans (1 <= n <= 3 * MMS_MAX_GROUP; a step's gradient buffers, sums of squares and entropy words of a fold group) by ONE
+ * kernel launch -- no memset node, so the call orders like any other launch in a captured graph.  n outside the range, a NULL span pointer
+ * or an empty span: MMS_ERR_ARG and nothing is launched. */
+int mms_zero_spans_group(const MmsZeroSpan* spans, int n, hipStream_t s);
 int mms_moe_fwd_group(const MoeP* p, int ng, hipStream_t s);   /* SimMLM heads: MoeP.stage of the forward */
 int mms_moe_bwd_group(const MoeP* p, int ng, hipStream_t s);   /* ... and of the backward */
 int mms_grad_sumsq_group(const AdamP* p, int ng, hipStream_t s);
+/* The same with the launch form chosen by the caller: 0 = what mms_grad_sumsq_group does (where the grid of 256-thread workgroups is a
+ * multiple of four -- always from 4.2 M floats on -- a quarter as many workgroups of 1024 threads: a quarter of the fp64 atomics that end
+ * the launch); 1 = always 256 threads, at most 1024 workgroups.  Every thread's fp32 partial is the same in both; the sums differ by the
+ * order of the fp64 additions; the bookkeeping (step, acc, rng) is the same.  Other forms: MMS_ERR_ARG. */
+int mms_grad_sumsq_group_form(const AdamP* p, int ng, int form, hipStream_t s);
 int mms_clip_adam_group(const AdamP* p, int ng, hipStream_t s);
 int mms_w2_pack_group(const AdamP* p, int ng, hipStream_t s);
 /* whole-encoder drivers: entry g of every array describes model g (arguments as mms_dn121_forward / _backward) */

@@ -158,9 +158,8 @@ MMS_SINGLE(mms_linear_fwd, LinearFwdP)
 
 // ---- backward: weight/bias (one wave per output feature n) ---------------------------------------------------
 template <int MM, bool KS4>
-__global__ __launch_bounds__(256) void linear_bwd_w_kernel(const Grp<LinearBwdP> grp) {
-    const LinearBwdP& p = grp.p[blockIdx.z];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = KS4 ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;      // KS4: as linear_fwd_kernel
+__device__ __forceinline__ void linear_bwd_w_body(const LinearBwdP& p, const int bx) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = KS4 ? bx : bx * 4 + wave;      // KS4: as linear_fwd_kernel
     if (n >= p.N) return;
     constexpr int KSTEP = KS4 ? 256 : 64;
     float dz[MM], db = 0.f;
@@ -216,12 +215,9 @@ __global__ __launch_bounds__(256) void linear_bwd_w_kernel(const Grp<LinearBwdP>
 // time before their first use: one thread per column over ALL N rows was a chain of N dependent-latency loads on two CUs (K = 512, N = 256:
 // 18.6 us per launch; 47 us with an 8-deep unroll hint).
 template <int MM>
-__global__ __launch_bounds__(256) void linear_bwd_x_kernel(const Grp<LinearBwdP> grp) {
-    const LinearBwdP& p = grp.p[blockIdx.z];
-    __shared__ float dzs[MM][128];
-    __shared__ float red[3][MM][64];
+__device__ __forceinline__ void linear_bwd_x_body(const LinearBwdP& p, const int bx, float (&dzs)[MM][128], float (&red)[3][MM][64]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k = blockIdx.x * 64 + lane;
+    const int k = bx * 64 + lane;
     const int N = p.N, K = p.K;
     const float* __restrict__ wk = p.w + (k < K ? k : K - 1);        // clamped: branch-free loads
     float acc[MM];
@@ -289,30 +285,63 @@ __global__ __launch_bounds__(256) void linear_bwd_x_kernel(const Grp<LinearBwdP>
     for (int m = 0; m < MM; ++m) if (m < p.M) p.dx[(size_t)m * p.lddx + k] = dxv[m];
 }
 
+template <int MM, bool KS4>
+__global__ __launch_bounds__(256) void linear_bwd_w_kernel(const Grp<LinearBwdP> grp) {
+    linear_bwd_w_body<MM, KS4>(grp.p[blockIdx.z], (int)blockIdx.x);
+}
 template <int MM>
-static int launch_linear_bwd(const Grp<LinearBwdP>& a, int ng, hipStream_t s) {
+__global__ __launch_bounds__(256) void linear_bwd_x_kernel(const Grp<LinearBwdP> grp) {
+    __shared__ float dzs[MM][128];
+    __shared__ float red[3][MM][64];
+    linear_bwd_x_body<MM>(grp.p[blockIdx.z], (int)blockIdx.x, dzs, red);
+}
+// Both roles of a layer in ONE launch: the weight / bias gradient and the input gradient read the same dy, y and x and write disjoint outputs
+// (dw, dbias | dx, dgamma, dbeta), so neither has to wait for the other.  Workgroups blockIdx.x < wgrid take the weight role, the rest the
+// input role (uniform per workgroup); every element's arithmetic is that of the two single-role kernels above.
+template <int MM, bool KS4>
+__global__ __launch_bounds__(256) void linear_bwd_kernel(const Grp<LinearBwdP> grp, const int wgrid) {
+    const LinearBwdP& p = grp.p[blockIdx.z];
+    // the input role's LDS is every workgroup's: 5 KB at MM = 4 (the timed shapes), 40 KB at MM = 32, where it holds the weight role to 4
+    // workgroups per CU -- a launch has N / 4 + K / 64 workgroups per model (tens; a full group of 10 stays under two per CU), so that limit is not reached
+    __shared__ float dzs[MM][128];
+    __shared__ float red[3][MM][64];
+    if ((int)blockIdx.x < wgrid) linear_bwd_w_body<MM, KS4>(p, (int)blockIdx.x);
+    else linear_bwd_x_body<MM>(p, (int)blockIdx.x - wgrid, dzs, red);
+}
+
+// form: 0 = a layer that has both roles takes the merged launch; 1 = always one launch per role (the form before the merge: tests, timing)
+template <int MM>
+static int launch_linear_bwd(const Grp<LinearBwdP>& a, int ng, int form, hipStream_t s) {
     const LinearBwdP& p = a.p[0];
-    if (p.dw) {
-        if (p.K >= 2048) MMS_LAUNCH((linear_bwd_w_kernel<MM, true>), dim3(p.N, 1, ng), dim3(256), 0, s, a);
-        else MMS_LAUNCH((linear_bwd_w_kernel<MM, false>), dim3((p.N + 3) / 4, 1, ng), dim3(256), 0, s, a);
+    const bool ks4 = p.K >= 2048;
+    const int wgrid = ks4 ? p.N : (p.N + 3) / 4, xgrid = (p.K + 63) / 64;
+    if (p.dw && p.dx && form == 0) {
+        if (ks4) MMS_LAUNCH((linear_bwd_kernel<MM, true>), dim3(wgrid + xgrid, 1, ng), dim3(256), 0, s, a, wgrid);
+        else MMS_LAUNCH((linear_bwd_kernel<MM, false>), dim3(wgrid + xgrid, 1, ng), dim3(256), 0, s, a, wgrid);
+        return mms_check_launch();
     }
-    if (p.dx) MMS_LAUNCH(linear_bwd_x_kernel<MM>, dim3((p.K + 63) / 64, 1, ng), dim3(256), 0, s, a);
+    if (p.dw) {
+        if (ks4) MMS_LAUNCH((linear_bwd_w_kernel<MM, true>), dim3(wgrid, 1, ng), dim3(256), 0, s, a);
+        else MMS_LAUNCH((linear_bwd_w_kernel<MM, false>), dim3(wgrid, 1, ng), dim3(256), 0, s, a);
+    }
+    if (p.dx) MMS_LAUNCH(linear_bwd_x_kernel<MM>, dim3(xgrid, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
-extern "C" int mms_linear_bwd_group(const LinearBwdP* pp, int ng, hipStream_t s) {
+extern "C" int mms_linear_bwd_group_form(const LinearBwdP* pp, int ng, int form, hipStream_t s) {
     Grp<LinearBwdP> a;
-    if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
+    if (!grp_fill(a, pp, ng, 1) || form < 0 || form > 1) return MMS_ERR_ARG;
     const LinearBwdP& p = *pp;
     if (p.M <= 0 || p.M > 32 || p.N <= 0 || p.K <= 0) return MMS_ERR_ARG;
     for (int g = 1; g < ng; ++g) {
         const LinearBwdP& q = pp[g];
         if (q.M != p.M || q.N != p.N || q.K != p.K || (q.dw == nullptr) != (p.dw == nullptr) || (q.dx == nullptr) != (p.dx == nullptr)) return MMS_ERR_ARG;
     }
-    if (p.M <= 4) return launch_linear_bwd<4>(a, ng, s);
-    if (p.M <= 8) return launch_linear_bwd<8>(a, ng, s);
-    if (p.M <= 16) return launch_linear_bwd<16>(a, ng, s);
-    return launch_linear_bwd<32>(a, ng, s);
+    if (p.M <= 4) return launch_linear_bwd<4>(a, ng, form, s);
+    if (p.M <= 8) return launch_linear_bwd<8>(a, ng, form, s);
+    if (p.M <= 16) return launch_linear_bwd<16>(a, ng, form, s);
+    return launch_linear_bwd<32>(a, ng, form, s);
 }
+extern "C" int mms_linear_bwd_group(const LinearBwdP* pp, int ng, hipStream_t s) { return mms_linear_bwd_group_form(pp, ng, 0, s); }
 MMS_SINGLE(mms_linear_bwd, LinearBwdP)
 
 // ------------------------------------------------------------------------------------------------------
@@ -322,24 +351,54 @@ MMS_SINGLE(mms_linear_bwd, LinearBwdP)
 #define GATE_IN 291
 __device__ __forceinline__ int gate_seg(int t) { return t < 128 ? 0 : (t < 256 ? 1 : 2); }
 
+// Every global load of the kernel is requested before the first FMA: a wave's 16 x 5 w1 values (its 16 hidden units, k = lane + 64 i), b1,
+// w2, b2 and the row's features ride on ONE memory round trip (a unit at a time was 16 dependent trips: 40.8 us per launch at 4 rows).  Per
+// element the arithmetic and its order are unchanged: lane-strided k in ascending order, wave_sum, + b1.
 __global__ __launch_bounds__(256) void gate_fwd_kernel(const Grp<GateP> grp) {
     const GateP& p = grp.p[blockIdx.z];
     __shared__ float G[GATE_IN + 1], h[64], g[3];
     const int m = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    for (int i = t; i < GATE_IN; i += 256)
-        G[i] = i < GATE_F ? p.feats[(size_t)m * GATE_F + i] * p.mask[m * 3 + gate_seg(i)] : p.mask[m * 3 + (i - GATE_F)];
-    __syncthreads();
-    for (int j = wave * 16; j < wave * 16 + 16; ++j) {
-        float a = 0.f;
-        for (int k = lane; k < GATE_IN; k += 64) a = fmaf(p.w1[j * GATE_IN + k], G[k], a);
-        a = wave_sum(a);
-        if (lane == 0) { h[j] = fmaxf(a + p.b1[j], 0.f); p.hidden[m * 64 + j] = h[j]; }
+    constexpr int NK = (GATE_IN + 63) / 64;                          // 5 (the last one: lanes < GATE_IN - 256 only)
+    float wv[16][NK];
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+#pragma unroll
+        for (int i = 0; i < NK; ++i) {
+            const int k = lane + 64 * i;
+            wv[u][i] = p.w1[(wave * 16 + u) * GATE_IN + (k < GATE_IN ? k : GATE_IN - 1)];       // clamped: branch-free loads, not used
+        }
+    const float b1v = p.b1[wave * 16 + (lane & 15)];                 // lane u < 16 finishes unit wave * 16 + u
+    float w2v[3], b2v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { w2v[c] = p.w2[c * 64 + lane]; b2v[c] = p.b2[c]; }
+    {
+        const int i1 = t + 256;                                      // t < GATE_IN always; i1 < GATE_IN for t < 35: mask columns or features
+        const float f0 = p.feats[(size_t)m * GATE_F + t], m0 = p.mask[m * 3 + gate_seg(t)];
+        const float f1 = p.feats[(size_t)m * GATE_F + (i1 < GATE_F ? i1 : 0)];
+        const float m1 = p.mask[m * 3 + (i1 < GATE_F ? gate_seg(i1) : (i1 < GATE_IN ? i1 - GATE_F : 0))];
+        G[t] = f0 * m0;
+        if (i1 < GATE_IN) G[i1] = i1 < GATE_F ? f1 * m1 : m1;
+        else if (i1 == GATE_IN) G[i1] = 0.f;                         // the pad word that out-of-range lanes read (and do not use)
     }
+    __syncthreads();
+    float gk[NK];
+#pragma unroll
+    for (int i = 0; i < NK; ++i) gk[i] = G[lane + 64 * i < GATE_IN ? lane + 64 * i : GATE_IN];
+    float mine = 0.f;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < NK; ++i) if (lane + 64 * i < GATE_IN) a = fmaf(wv[u][i], gk[i], a);
+        a = wave_sum(a);
+        if (lane == u) mine = a;
+    }
+    if (lane < 16) { const float hv = fmaxf(mine + b1v, 0.f); h[wave * 16 + lane] = hv; p.hidden[m * 64 + wave * 16 + lane] = hv; }
     __syncthreads();
     if (wave == 0) {
         float l[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) l[c] = wave_sum(p.w2[c * 64 + lane] * h[lane]) + p.b2[c];
+        for (int c = 0; c < 3; ++c) l[c] = wave_sum(w2v[c] * h[lane]) + b2v[c];
         if (lane == 0) {
             const float mx = fmaxf(l[0], fmaxf(l[1], l[2]));
             const float e0 = expf(l[0] - mx), e1 = expf(l[1] - mx), e2 = expf(l[2] - mx), inv = 1.f / (e0 + e1 + e2);
@@ -539,59 +598,85 @@ MMS_SINGLE(mms_gate_bwd, GateP)
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool cox_valid(const CoxP& p, int i) { return p.valid == nullptr || p.valid[i] != 0.f; }
 
-__global__ __launch_bounds__(256) void cox_lse_kernel(const Grp<CoxP> grp) {
-    const CoxP& p = grp.p[blockIdx.z];
-    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= p.n) return;
-    if (!cox_valid(p, i)) { if (lane == 0) { p.lse[i] = 0.f; if (p.tie_mode == 1) p.tie_frac[i] = -1.f; } return; }
-    const float ti = p.time[i];
+// Where the two passes read the batch and the first pass's results: global memory (one launch per pass), or the LDS copy of the one-launch
+// form (n <= COX_ONE_N; lse / tie_frac still go to memory as well).  The same values through the same arithmetic: the same bits.
+struct CoxMem {
+    const CoxP& p;
+    __device__ __forceinline__ bool valid(int i) const { return cox_valid(p, i); }
+    __device__ __forceinline__ float time(int i) const { return p.time[i]; }
+    __device__ __forceinline__ float event(int i) const { return p.event[i]; }
+    __device__ __forceinline__ float h(int i) const { return p.h[(size_t)i * p.ldh]; }
+    __device__ __forceinline__ float lse(int i) const { return p.lse[i]; }
+    __device__ __forceinline__ float frac(int i) const { return p.tie_frac[i]; }
+    __device__ __forceinline__ void put_lse(int i, float v) const { p.lse[i] = v; }
+    __device__ __forceinline__ void put_frac(int i, float v) const { p.tie_frac[i] = v; }
+};
+#define COX_ONE_N 256
+struct CoxLds {
+    const CoxP& p;
+    float (&t)[COX_ONE_N]; float (&e)[COX_ONE_N]; float (&hh)[COX_ONE_N]; float (&v)[COX_ONE_N]; float (&l)[COX_ONE_N]; float (&f)[COX_ONE_N];
+    __device__ __forceinline__ bool valid(int i) const { return v[i] != 0.f; }
+    __device__ __forceinline__ float time(int i) const { return t[i]; }
+    __device__ __forceinline__ float event(int i) const { return e[i]; }
+    __device__ __forceinline__ float h(int i) const { return hh[i]; }
+    __device__ __forceinline__ float lse(int i) const { return l[i]; }
+    __device__ __forceinline__ float frac(int i) const { return f[i]; }
+    __device__ __forceinline__ void put_lse(int i, float x) const { l[i] = x; p.lse[i] = x; }
+    __device__ __forceinline__ void put_frac(int i, float x) const { f[i] = x; p.tie_frac[i] = x; }
+};
+
+// pass 1 of row i (one wave)
+template <class S>
+__device__ __forceinline__ void cox_lse_row(const CoxP& p, const S& src, const int i, const int lane) {
+    if (!src.valid(i)) { if (lane == 0) { src.put_lse(i, 0.f); if (p.tie_mode == 1) src.put_frac(i, -1.f); } return; }
+    const float ti = src.time(i);
     float mx = -INFINITY;
     for (int j = lane; j < p.n; j += 64)
-        if (cox_valid(p, j) && p.time[j] >= ti) mx = fmaxf(mx, p.h[(size_t)j * p.ldh]);
+        if (src.valid(j) && src.time(j) >= ti) mx = fmaxf(mx, src.h(j));
     mx = wave_max(mx);
     float s = 0.f;
     if (p.tie_mode != 1) {
         for (int j = lane; j < p.n; j += 64)
-            if (cox_valid(p, j) && p.time[j] >= ti) s += expf(p.h[(size_t)j * p.ldh] - mx);
+            if (src.valid(j) && src.time(j) >= ti) s += expf(src.h(j) - mx);
         s = wave_sum(s);
-        if (lane == 0) p.lse[i] = mx + logf(s);
+        if (lane == 0) src.put_lse(i, mx + logf(s));
         return;
     }
     // Efron (torchsurv _partial_likelihood_efron): the m events tied at t_i take the denominators D - (l/m) T, l = 0..m-1,
     // D = sum over the risk set, T = sum over the tied events; event i takes l = its rank (by index) among them.
     float st = 0.f, m = 0.f, l = 0.f;
     for (int j = lane; j < p.n; j += 64)
-        if (cox_valid(p, j)) {
-            const float tj = p.time[j];
+        if (src.valid(j)) {
+            const float tj = src.time(j);
             if (tj >= ti) {
-                const float e = expf(p.h[(size_t)j * p.ldh] - mx);
+                const float e = expf(src.h(j) - mx);
                 s += e;
-                if (tj == ti && p.event[j] != 0.f) { st += e; m += 1.f; l += j < i ? 1.f : 0.f; }
+                if (tj == ti && src.event(j) != 0.f) { st += e; m += 1.f; l += j < i ? 1.f : 0.f; }
             }
         }
     s = wave_sum(s); st = wave_sum(st); m = wave_sum(m); l = wave_sum(l);
     if (lane == 0) {
-        const bool ev = p.event[i] != 0.f;
+        const bool ev = src.event(i) != 0.f;
         const float f = ev ? l / m : 0.f;            // (censored rows: lse unused)
-        p.lse[i] = mx + logf(s - f * st);
-        p.tie_frac[i] = ev ? f : -1.f;
+        src.put_lse(i, mx + logf(s - f * st));
+        src.put_frac(i, ev ? f : -1.f);
     }
 }
 
-__global__ __launch_bounds__(256) void cox_grad_kernel(const Grp<CoxP> grp) {
-    const CoxP& p = grp.p[blockIdx.z];
-    __shared__ float red[8];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = blockIdx.x * 4 + wave;
+// pass 2: the batch counts (whole workgroup, 256 threads; red: 8 floats of LDS), the loss (`first`: this workgroup writes out) ...
+template <class S>
+__device__ __forceinline__ void cox_counts(const CoxP& p, const S& src, float* red, const bool first, bool& usable, float& denom) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool efron = p.tie_mode == 1;
     // batch counts (every block recomputes them: n is small).  ne = events (Breslow / untied: mean over events);
     // Efron: nd = distinct event times = events of tie rank 0 (torchsurv averages its per-time terms)
     float nv = 0.f, ne = 0.f, ls = 0.f, nd = 0.f;
     for (int j = threadIdx.x; j < p.n; j += 256)
-        if (cox_valid(p, j)) {
+        if (src.valid(j)) {
             nv += 1.f;
-            if (p.event[j] != 0.f) {
-                ne += 1.f; ls += p.h[(size_t)j * p.ldh] - p.lse[j];
-                if (efron && p.tie_frac[j] == 0.f) nd += 1.f;
+            if (src.event(j) != 0.f) {
+                ne += 1.f; ls += src.h(j) - src.lse(j);
+                if (efron && src.frac(j) == 0.f) nd += 1.f;
             }
         }
     nv = wave_sum(nv); ne = wave_sum(ne); ls = wave_sum(ls); nd = wave_sum(nd);
@@ -602,22 +687,26 @@ __global__ __launch_bounds__(256) void cox_grad_kernel(const Grp<CoxP> grp) {
     if (lane == 0) { red[wave] = ls; red[4 + wave] = nd; }
     __syncthreads();
     ls = red[0] + red[1] + red[2] + red[3]; nd = red[4] + red[5] + red[6] + red[7];
-    const bool usable = nv >= 2.f && ne > 0.f;      // final_multimodal.py:173-176
-    const float denom = efron ? nd : ne + 1e-8f;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    usable = nv >= 2.f && ne > 0.f;      // final_multimodal.py:173-176
+    denom = efron ? nd : ne + 1e-8f;
+    if (first && threadIdx.x == 0) {
         p.out[0] = usable ? -ls / denom : 0.f;
         p.out[1] = usable ? 1.f : 0.f;
     }
-    if (k >= p.n || p.dh == nullptr) return;
+}
+// ... and the gradient of row k (one wave)
+template <class S>
+__device__ __forceinline__ void cox_grad_row(const CoxP& p, const S& src, const int k, const int lane, const bool usable, const float denom) {
+    const bool efron = p.tie_mode == 1;
     float gsum = 0.f;
-    if (usable && cox_valid(p, k)) {
-        const float tk = p.time[k], hk = p.h[(size_t)k * p.ldh];
-        const bool ek = p.event[k] != 0.f;
+    if (usable && src.valid(k)) {
+        const float tk = src.time(k), hk = src.h(k);
+        const bool ek = src.event(k) != 0.f;
         for (int i = lane; i < p.n; i += 64)
-            if (cox_valid(p, i) && p.event[i] != 0.f && p.time[i] <= tk) {
+            if (src.valid(i) && src.event(i) != 0.f && src.time(i) <= tk) {
                 float w = 1.f;
-                if (efron && ek && p.time[i] == tk) w -= p.tie_frac[i];      // d/dh_k of D_i - f_i T_i
-                gsum += w * expf(hk - p.lse[i]);
+                if (efron && ek && src.time(i) == tk) w -= src.frac(i);      // d/dh_k of D_i - f_i T_i
+                gsum += w * expf(hk - src.lse(i));
             }
         gsum = wave_sum(gsum);
         if (lane == 0) p.dh[(size_t)k * p.lddh] = -p.scale * ((ek ? 1.f : 0.f) - gsum) / denom;
@@ -625,17 +714,112 @@ __global__ __launch_bounds__(256) void cox_grad_kernel(const Grp<CoxP> grp) {
         p.dh[(size_t)k * p.lddh] = 0.f;
     }
 }
-extern "C" int mms_cox_fwd_bwd_group(const CoxP* pp, int ng, hipStream_t s) {
+
+__global__ __launch_bounds__(256) void cox_lse_kernel(const Grp<CoxP> grp) {
+    const CoxP& p = grp.p[blockIdx.z];
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= p.n) return;
+    cox_lse_row(p, CoxMem{p}, i, lane);
+}
+__global__ __launch_bounds__(256) void cox_grad_kernel(const Grp<CoxP> grp) {
+    const CoxP& p = grp.p[blockIdx.z];
+    __shared__ float red[8];
+    const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    bool usable; float denom;
+    cox_counts(p, CoxMem{p}, red, blockIdx.x == 0, usable, denom);
+    if (k >= p.n || p.dh == nullptr) return;
+    cox_grad_row(p, CoxMem{p}, k, lane, usable, denom);
+}
+// n <= COX_ONE_N: ONE launch, one workgroup per model.  The batch is read once into LDS, the rows' first pass leaves lse / tie_frac there
+// (and in memory, as before), a barrier, then the second pass: one dependent launch and three memory round trips less on the step's chain
+// (the pair was 2 x 4.9 us at n = 4, which is the floor of a dependent launch).  A row is one wave's work in both passes, as in the
+// two kernels above.
+__global__ __launch_bounds__(256) void cox_one_kernel(const Grp<CoxP> grp) {
+    const CoxP& p = grp.p[blockIdx.z];
+    __shared__ float st[COX_ONE_N], se[COX_ONE_N], sh[COX_ONE_N], sv[COX_ONE_N], sl[COX_ONE_N], sf[COX_ONE_N], red[8];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t < p.n) {
+        st[t] = p.time[t]; se[t] = p.event[t]; sh[t] = p.h[(size_t)t * p.ldh];
+        sv[t] = p.valid ? p.valid[t] : 1.f;
+    }
+    __syncthreads();
+    const CoxLds src{p, st, se, sh, sv, sl, sf};
+    for (int i = wave; i < p.n; i += 4) cox_lse_row(p, src, i, lane);
+    __syncthreads();
+    bool usable; float denom;
+    cox_counts(p, src, red, true, usable, denom);
+    if (p.dh == nullptr) return;
+    for (int k = wave; k < p.n; k += 4) cox_grad_row(p, src, k, lane, usable, denom);
+}
+// form: 0 = the one-launch kernel where it applies (n <= COX_ONE_N); 1 = always the two kernels (tests, timing)
+extern "C" int mms_cox_fwd_bwd_group_form(const CoxP* pp, int ng, int form, hipStream_t s) {
     Grp<CoxP> a;
-    if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
+    if (!grp_fill(a, pp, ng, 1) || form < 0 || form > 1) return MMS_ERR_ARG;
     const CoxP& p = *pp;
     for (int g = 0; g < ng; ++g)
         if (pp[g].n != p.n || pp[g].n <= 0 || !pp[g].lse || !pp[g].out || pp[g].tie_mode < 0 || pp[g].tie_mode > 1 || (pp[g].tie_mode == 1 && !pp[g].tie_frac)) return MMS_ERR_ARG;
+    if (form == 0 && p.n <= COX_ONE_N) {
+        MMS_LAUNCH(cox_one_kernel, dim3(1, 1, ng), dim3(256), 0, s, a);
+        return mms_check_launch();
+    }
     MMS_LAUNCH(cox_lse_kernel, dim3((p.n + 3) / 4, 1, ng), dim3(256), 0, s, a);
     MMS_LAUNCH(cox_grad_kernel, dim3((p.n + 3) / 4, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
+extern "C" int mms_cox_fwd_bwd_group(const CoxP* pp, int ng, hipStream_t s) { return mms_cox_fwd_bwd_group_form(pp, ng, 0, s); }
 MMS_SINGLE(mms_cox_fwd_bwd, CoxP)
+
+// ------------------------------------------------------------------------------------------------------
+// zero-fill of a step's accumulators (every member's flat gradient, sum of squares, gate entropy): all spans in ONE launch
+// ------------------------------------------------------------------------------------------------------
+// The spans travel by value in the kernel argument.  A span is [head bytes up to the first 16-byte boundary][16-byte words][tail bytes]; it
+// gets ceil(words / ZS_WORDS) workgroups (at least one), each storing ZS_WORDS consecutive 16-byte words, ZS_U per thread (16 KB per workgroup:
+// more workgroups than fit the chip at once, so that they balance over the CUs); the span's first workgroup also stores the head and tail bytes.  first[i]: the first workgroup of span i (first[n] = the grid).
+#define ZS_MAX (3 * MMS_MAX_GROUP)
+#define ZS_U 4
+#define ZS_WORDS (256 * ZS_U)
+struct ZeroSpans { MmsZeroSpan s[ZS_MAX]; unsigned first[ZS_MAX + 1]; int n; };
+__global__ __launch_bounds__(256) void zero_spans_kernel(const ZeroSpans a) {
+    int i = 0;
+    while (i + 1 < a.n && blockIdx.x >= a.first[i + 1]) ++i;         // (uniform: n <= 30 scalar compares; measured ahead of a branch-free scan of the table)
+    const unsigned lb = blockIdx.x - a.first[i];
+    unsigned char* const p = (unsigned char*)a.s[i].p;
+    const size_t bytes = a.s[i].bytes;
+    size_t head = (size_t)((16 - ((uintptr_t)p & 15)) & 15);
+    if (head > bytes) head = bytes;
+    const size_t words = (bytes - head) >> 4, tail = (bytes - head) & 15;
+    float4* const body = (float4*)(p + head);
+    const size_t w0 = (size_t)lb * ZS_WORDS + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < ZS_U; ++u) {
+        const size_t w = w0 + (size_t)u * 256;
+        if (w < words) body[w] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (lb == 0) {
+        if (threadIdx.x < head) p[threadIdx.x] = 0;
+        else if (threadIdx.x >= 16 && threadIdx.x - 16 < tail) p[head + (words << 4) + (threadIdx.x - 16)] = 0;
+    }
+}
+extern "C" int mms_zero_spans_group(const MmsZeroSpan* spans, int n, hipStream_t s) {
+    if (!spans || n < 1 || n > ZS_MAX) return MMS_ERR_ARG;
+    ZeroSpans a{};
+    unsigned long long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!spans[i].p || spans[i].bytes == 0) return MMS_ERR_ARG;
+        a.s[i] = spans[i];
+        a.first[i] = (unsigned)blocks;
+        size_t head = (size_t)((16 - ((uintptr_t)spans[i].p & 15)) & 15);
+        if (head > spans[i].bytes) head = spans[i].bytes;
+        const size_t words = (spans[i].bytes - head) >> 4;
+        const size_t nb = (words + ZS_WORDS - 1) / ZS_WORDS;
+        blocks += nb ? nb : 1;
+        if (blocks > 0x7fffffffull) return MMS_ERR_ARG;
+    }
+    for (int i = n; i <= ZS_MAX; ++i) a.first[i] = (unsigned)blocks;
+    a.n = n;
+    MMS_LAUNCH(zero_spans_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    return mms_check_launch();
+}
 
 // ------------------------------------------------------------------------------------------------------
 // Harrell's C pair counts: one wave per event row i
@@ -668,12 +852,17 @@ extern "C" int mms_cindex_counts(const CindexP* pp, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------------
 // clip_grad_norm_ + Adam / AdamW over a flat buffer
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const Grp<AdamP> grp) {
+// T threads per workgroup.  Every workgroup ends in ONE fp64 atomic on the model's sum, and those serialise at about 9 ns each behind the
+// reads (tools/micro/sumsq_forms.hip: 2 x 56 MB in 28.9 us with 1024 workgroups of 256 threads, 19.3 us with the atomic left out, 47 and
+// 69 us with 2048 and 3443 workgroups; 18.2 us = 6.2 TB/s with a quarter of them).  T = 1024 is four workgroups of the T = 256 form in one:
+// the same threads, the same stride, the same loads in flight and so the same fp32 partial in every thread, and a quarter of the atomics.
+template <int T>
+__global__ __launch_bounds__(T) void grad_sumsq_kernel(const Grp<AdamP> grp) {
     const AdamP& p = grp.p[blockIdx.z];
-    __shared__ double red[4];
-    const long long n4 = p.n >> 2, stride = (long long)gridDim.x * 256;
+    __shared__ double red[T / 64];
+    const long long n4 = p.n >> 2, stride = (long long)gridDim.x * T;
     float a = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long i = (long long)blockIdx.x * T + threadIdx.x;
     for (; i + 3 * stride < n4; i += 4 * stride) {          // 4 independent 16-B loads in flight per thread
         const float4 g0 = ((const float4*)p.g)[i], g1 = ((const float4*)p.g)[i + stride], g2 = ((const float4*)p.g)[i + 2 * stride],
                      g3 = ((const float4*)p.g)[i + 3 * stride];
@@ -858,15 +1047,20 @@ static bool adam_group(Grp<AdamP>& a, const AdamP* pp, int ng) {
     }
     return true;
 }
-extern "C" int mms_grad_sumsq_group(const AdamP* pp, int ng, hipStream_t s) {
+// form: 0 = where the 256-thread grid is a multiple of four workgroups (always at its cap of 1024: from 4.2 M floats on), a quarter as many
+// workgroups of 1024 threads -- every thread's fp32 partial is unchanged, only the order of their fp64 sum differs; other sizes, and form 1
+// (tests, timing): the 256-thread workgroups of before round 11.
+extern "C" int mms_grad_sumsq_group_form(const AdamP* pp, int ng, int form, hipStream_t s) {
     Grp<AdamP> a;
-    if (!adam_group(a, pp, ng)) return MMS_ERR_ARG;
+    if (!adam_group(a, pp, ng) || form < 0 || form > 1) return MMS_ERR_ARG;
     long long blocks = (pp->n / 16 + 255) / 256;          // 4 float4 per thread and trip
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-    MMS_LAUNCH(grad_sumsq_kernel, dim3((unsigned)blocks, 1, ng), dim3(256), 0, s, a);
+    if (form == 0 && (blocks & 3) == 0) MMS_LAUNCH(grad_sumsq_kernel<1024>, dim3((unsigned)(blocks >> 2), 1, ng), dim3(1024), 0, s, a);
+    else MMS_LAUNCH(grad_sumsq_kernel<256>, dim3((unsigned)blocks, 1, ng), dim3(256), 0, s, a);
     return mms_check_launch();
 }
+extern "C" int mms_grad_sumsq_group(const AdamP* pp, int ng, hipStream_t s) { return mms_grad_sumsq_group_form(pp, ng, 0, s); }
 extern "C" int mms_clip_adam_group(const AdamP* pp, int ng, hipStream_t s) {
     Grp<AdamP> a;
     if (!adam_group(a, pp, ng)) return MMS_ERR_ARG;

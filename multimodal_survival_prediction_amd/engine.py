@@ -651,8 +651,15 @@ class SurvivalEngine:
         self._opts_live = o          # (keeps the block alive for the duration of the call)
         return ctypes.byref(o)
 
-    def _forward(self, P, train, enc_opts=None):
-        """enc_opts: `const MmsDnOpts*` of the DenseNet121 driver call instead of _opts_arg's (attribute: the per-layer forms)."""
+    def _zero_step(self):
+        """The step's accumulators (flat gradient, sum of squares, gate entropy) zeroed by ONE launch (mms_zero_spans_group)."""
+        if getattr(self, "_zspans", None) is None:
+            self._zspans = ops.zero_spans([self.gflat, self.sumsq, self.entropy])
+        _lib.check(self.lib.mms_zero_spans_group(self._zspans, len(self._zspans), ops.stream()), "mms_zero_spans_group")
+
+    def _forward(self, P, train, enc_opts=None, entropy_zeroed=False):
+        """enc_opts: `const MmsDnOpts*` of the DenseNet121 driver call instead of _opts_arg's (attribute: the per-layer forms);
+        entropy_zeroed: the caller has zeroed the gate-entropy word on this stream (_zero_step)."""
         self.sync_packs()
         P.fwd_serial += 1
         st = ops.stream()
@@ -676,7 +683,8 @@ class SurvivalEngine:
             for q in bl[:n_pre]:
                 _lib.check(lib.mms_linear_big_fwd(ctypes.byref(q), st), "mms_linear_big_fwd")
             if P.gate is not None:
-                self.entropy.zero_()
+                if not entropy_zeroed:
+                    self.entropy.zero_()
                 _lib.check(lib.mms_gate_fwd(ctypes.byref(P.gate), st), "mms_gate_fwd")
             if P.mix is not None:
                 _lib.check(lib.mms_missing_mix_fwd(ctypes.byref(P.mix), st), "mms_missing_mix_fwd")
@@ -690,7 +698,8 @@ class SurvivalEngine:
         if P.moe is not None:
             _lib.check(lib.mms_moe_fwd(ctypes.byref(P.moe[0]), st), "mms_moe_fwd")
         if P.gate is not None:
-            self.entropy.zero_()
+            if not entropy_zeroed:
+                self.entropy.zero_()
             _lib.check(lib.mms_gate_fwd(ctypes.byref(P.gate), st), "mms_gate_fwd")
         if P.mix is not None:
             _lib.check(lib.mms_missing_mix_fwd(ctypes.byref(P.mix), st), "mms_missing_mix_fwd")
@@ -793,9 +802,8 @@ class SurvivalEngine:
         st = ops.stream()
         lib = self.lib
         if part == "fwd":                      # DDP with the global risk set: first third
-            self.gflat.zero_()
-            self.sumsq.zero_()
-            self._forward(P, True)
+            self._zero_step()
+            self._forward(P, True, entropy_zeroed=True)
             return
         if part in ("coxbwd", "coxheads"):     # ... loss over the gathered world*B hazards, own slice of dL/dh [, heads only]
             G = P.gcox
@@ -807,9 +815,8 @@ class SurvivalEngine:
                 self._backward_from_dhz(P)
             return
         if part == "gradheads":                # rank-local risk set: zero-grad, forward, Cox, heads' backward
-            self.gflat.zero_()
-            self.sumsq.zero_()
-            self._forward(P, True)
+            self._zero_step()
+            self._forward(P, True, entropy_zeroed=True)
             _lib.check(lib.mms_cox_fwd_bwd(ctypes.byref(P.cox), st), "mms_cox_fwd_bwd")
             self._backward_heads(P)
             return
@@ -821,9 +828,8 @@ class SurvivalEngine:
                 self.gflat.mul_(part[1])
             part = "update"
         if part in ("all", "grad"):
-            self.gflat.zero_()
-            self.sumsq.zero_()
-            self._forward(P, True)
+            self._zero_step()
+            self._forward(P, True, entropy_zeroed=True)
             self._cox_step(P)
             self._backward_from_dhz(P)
             if part == "grad":

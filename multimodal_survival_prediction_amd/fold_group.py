@@ -62,7 +62,7 @@ class FoldGroupEngine:
         n += (-n) % 4
         G = len(models)
         self.device = dev
-        # group-wide buffers so that zeroing the step's accumulators is three memsets for the whole group
+        # group-wide buffers: zeroing the step's accumulators of the whole group is three contiguous spans of the one zeroing launch
         self.gflat_all = torch.zeros(G, n, device=dev)
         self.sumsq_all = torch.zeros(G, dtype=torch.float64, device=dev)
         self.entropy_all = torch.zeros(G, device=dev)
@@ -193,11 +193,14 @@ class FoldGroupEngine:
             e.sync_packs()
 
     def _zero(self, GP):
-        if GP.full:
-            self.gflat_all.zero_(); self.sumsq_all.zero_(); self.entropy_all.zero_()
-        else:
-            for e in GP.eng:
-                e.gflat.zero_(); e.sumsq.zero_(); e.entropy.zero_()
+        """The members' step accumulators (flat gradient, sum of squares, gate entropy) zeroed by ONE launch (mms_zero_spans_group)."""
+        if getattr(GP, "zero_spans", None) is None:
+            if GP.full:        # the whole group: its three buffers are contiguous
+                ts = [self.gflat_all, self.sumsq_all, self.entropy_all]
+            else:
+                ts = [t for e in GP.eng for t in (e.gflat, e.sumsq, e.entropy)]
+            GP.zero_spans = ops.zero_spans(ts)
+        _lib.check(self.lib.mms_zero_spans_group(GP.zero_spans, len(GP.zero_spans), ops.stream()), "mms_zero_spans_group")
 
     def _train_body(self, GP, skip_if_unusable):
         """zero-grad -> forward -> Cox -> backward -> clip -> Adam for every member, one launch sequence."""

@@ -239,6 +239,15 @@ def gate_params(feats, mask, w1, b1, w2, b2, hidden, gate, fused, dfused=None, e
                          ptr(dw2), ptr(db2), ptr(entropy))
 
 
+def zero_spans(tensors):
+    """-> the MmsZeroSpan array of mms_zero_spans_group over `tensors` (contiguous device tensors; the caller keeps them alive)."""
+    S = _S()["MmsZeroSpan"]
+    for t in tensors:
+        if not t.is_contiguous():
+            raise ValueError("zero_spans: contiguous tensors only")
+    return (S * len(tensors))(*[S(t.data_ptr(), t.numel() * t.element_size()) for t in tensors])
+
+
 TIE_MODES = {"breslow": 0, "efron": 1}
 
 
