@@ -1091,6 +1091,58 @@ int mms_dn121_backward_mt(void* ws, int B, int D, int H, int W, const float* x, 
 int mms_ct_preprocess(const float* x, int inD, int inH, int inW, float* out, int oD, int oH, int oW, float* scratch, hipStream_t s);
 int mms_rna_log_zscore(const float* counts, float* out, int n, int g, hipStream_t s);
 
+/* mms_ct_preprocess_raw_batch (csrc/ct_ingest.hip): mms_ct_preprocess for V volumes of different sizes and STORED types in one call,
+ * straight from the bytes of their files (NIfTI-1 data sections, nifti.py): no host conversion and no fp32 copy of a scan.
+ * The volumes stand in one device staging buffer `base` of base_bytes bytes, volume v at byte `offset` (16-byte aligned) as D x H x W
+ * elements of `dtype` (x fastest), byte-swapped when `swap` != 0.  A stored element r stands for slope * r + inter (NIfTI scl_slope /
+ * scl_inter; slope 0 means "no scaling": 1, 0).  Row out_row of out[n_rows][oD][oH][oW] receives
+ *     zoom_order1( ((slope r + inter) - lo) / (hi - lo + 1e-8) ),   lo / hi the extremes of slope r + inter over the volume,
+ * computed as (r - rmin) * |slope| / (|slope| (rmax - rmin) + 1e-8) on the raw extremes ((rmax - r) for a negative slope), so nothing
+ * cancels and a constant volume gives exact zeros.  Output coordinates as mms_ct_preprocess: o * (in - 1) / (out - 1) in fp64, upper
+ * neighbour clamped, scale 0 where out == 1; interpolation in fp32.
+ * Precision: int8 / uint8 / int16 / uint16 / float32 elements are exact in fp32; int32, uint32 and float64 elements are rounded to the
+ * nearest fp32 at the load (what a host astype(float32) does).  NaN elements are not supported (the extremes drop them, the voxels
+ * they touch come out NaN).
+ * `vols` is a HOST array, read during the call only: the kernels get the descriptors by value, MMS_CT_RAW_CHUNK volumes per launch
+ * pair (pass 1: per-volume partial extremes into scratch, plain stores; pass 2: reduce them, resample, normalise).  A volume's bits do
+ * not depend on what else is in the call.  scratch: >= MMS_CT_RAW_SCRATCH_FLOATS floats, whatever V.
+ * p, base, out, scratch or (V > 0) vols NULL; base not 16-byte or out / scratch not 4-byte aligned; V < 0 or > MMS_CT_RAW_MAX_VOLS;
+ * base_bytes < 0; n_rows < 1; a target dim < 1 or oD * oH * oW > MMS_CT_RAW_MAX_VOXELS; per volume: offset negative or not a multiple
+ * of 16, a dim < 1, D * H * W > MMS_CT_RAW_MAX_VOXELS, the volume's end past base_bytes, an unknown dtype, slope or inter not finite,
+ * out_row outside [0, n_rows), or an out_row given twice; passes outside 0..2, or != 0 with V > MMS_CT_RAW_CHUNK: MMS_ERR_ARG before
+ * any launch.  V = 0: MMS_OK without a launch. */
+#define MMS_CT_U8 2                     /* dtype codes = the NIfTI-1 datatype codes */
+#define MMS_CT_I16 4
+#define MMS_CT_I32 8
+#define MMS_CT_F32 16
+#define MMS_CT_F64 64
+#define MMS_CT_I8 256
+#define MMS_CT_U16 512
+#define MMS_CT_U32 768
+#define MMS_CT_RAW_CHUNK 32             /* volumes per launch pair: 32 descriptors by value stay well under the 4 KB kernarg limit */
+#define MMS_CT_RAW_PARTS 256            /* partial extremes (workgroups of pass 1) per volume, at most */
+#define MMS_CT_RAW_SCRATCH_FLOATS 16384 /* 2 * MMS_CT_RAW_PARTS * MMS_CT_RAW_CHUNK: the chunks of a call follow each other on the stream */
+#define MMS_CT_RAW_MAX_VOLS 4096        /* volumes per call */
+#define MMS_CT_RAW_MAX_VOXELS 2147483647 /* voxels per volume: element indices are 32-bit */
+typedef struct CtRawVol {
+    long long offset;                   // byte offset of the volume in base, a multiple of 16
+    int D; int H; int W;                // stored dims, W fastest
+    int dtype; int swap;                // MMS_CT_*; != 0: elements are in the other byte order
+    int out_row;                        // row of out
+    float slope; float inter;           // value = slope * stored + inter; slope 0 = (1, 0)
+} CtRawVol;
+typedef struct CtRawBatchP {
+    const void* base; long long base_bytes;
+    const CtRawVol* vols; int V;        // HOST array [V]
+    int n_rows;
+    float* out;                         // [n_rows][oD][oH][oW]
+    int oD; int oH; int oW;
+    int passes;                         // 0 = both (every caller but a timer); 1 / 2 = that pass alone, for V <= MMS_CT_RAW_CHUNK
+                                        // (tools/bench_ingest.py: pass 2 alone reads the partials an earlier call left in scratch)
+    float* scratch;                     // [MMS_CT_RAW_SCRATCH_FLOATS]
+} CtRawBatchP;
+int mms_ct_preprocess_raw_batch(const CtRawBatchP* p, hipStream_t s);
+
 /* =========================== fold groups =====================================================================
  * The reference trains its K fold models one after the other (R/scripts/training/final_multimodal.py:316-402,
  * partial_modality_training.py:482-560, simple_fusion.py:318-436); they are independent, so this library can advance

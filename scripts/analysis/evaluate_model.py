@@ -11,7 +11,7 @@ and the Kaplan-Meier tables as CSV.
 
     python scripts/analysis/evaluate_model.py                            # evaluates an existing results/test_predictions.csv
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1
-    python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute
+    python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --attribute [--attribute-format nii]
     python scripts/analysis/evaluate_model.py --predict models/final/fold_1_best.pth --model final --fold 1 --genes models/final/fold_1_genes.json
     python scripts/analysis/evaluate_model.py --ensemble models/final/fold_*_best.pth --model final [--combine rank] [--attribute]
     python scripts/analysis/evaluate_model.py --bootstrap 2000 [--seed 0] [--compare other_model/test_predictions.csv ...]
@@ -105,7 +105,22 @@ def _cohort_of(kind, device, external=False):
     return cohort, keep
 
 
-def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None, train_csv=None, cov_csv=None):
+def save_saliency(attribute_dir, stem, vol, cohort, i, fmt="npy"):
+    """One saliency volume (tD, tH, tW) of patient i -> <stem>.npy on the network grid, or (fmt "nii") <stem>.nii.gz: float32 NIfTI whose
+    affine is the scan's (cohort["geometry"], kept by load_cohort for NIfTI volumes) times the per-axis scale of the loader's
+    align-corners resample (nifti.saliency_affine), so a viewer overlays the map on the scan; identity without geometry."""
+    if fmt == "npy":
+        np.save(os.path.join(attribute_dir, stem + ".npy"), vol)
+        return
+    from multimodal_survival_prediction_amd import nifti
+    geometry = cohort.get("geometry")
+    geo = geometry[i] if geometry is not None else None
+    A = nifti.saliency_affine(geo[0], geo[1], vol.shape) if geo is not None else np.eye(4)
+    nifti.write_nifti(os.path.join(attribute_dir, stem + ".nii.gz"), np.ascontiguousarray(vol, dtype=np.float32), affine=A)
+
+
+def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=None, top=50, genes=None, train_csv=None, cov_csv=None,
+            attribute_format="npy"):
     """Eval-mode log-hazards of the fold's validation patients -> results/test_predictions.csv.  The cohort and the fold split
     are rebuilt exactly as the model's training entry point builds them (scripts/training/<name>.py: same seeds, K-fold over the
     labelled patients with random_state 42), so fold k here is the held-out split of models/<name>/fold_k_best.pth.
@@ -168,7 +183,7 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
                 vols = res["ct"][:, 0].cpu().numpy()
                 for r, i in enumerate(idx[s:s + batch_size]):
                     if has[r, 0]:
-                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct.npy"), vols[r])
+                        save_saliency(attribute_dir, f"{pid(i)}_ct", vols[r], cohort, int(i), attribute_format)
             if res["rna"] is not None and has[:, 1].any():
                 g = res["rna"].abs().double().cpu().numpy()[has[:, 1]]
                 gene_sum = g.sum(0) if gene_sum is None else gene_sum + g.sum(0)
@@ -211,7 +226,7 @@ def predict(checkpoint, kind, fold, n_folds, batch_size, out_csv, attribute_dir=
     return df
 
 
-def predict_ensemble(checkpoints, kind, combine, batch_size, out_csv, attribute_dir=None, top=50):
+def predict_ensemble(checkpoints, kind, combine, batch_size, out_csv, attribute_dir=None, top=50, attribute_format="npy"):
     """The K fold checkpoints as one predictor (multimodal_survival_prediction_amd.ensemble.FoldEnsemble) over EVERY labelled patient of
     the loaded cohort -> results/test_predictions.csv with predict's columns (risk_score = the combined score) plus risk_std and
     risk_fold_1..K.  On the cohort the folds were trained on the score is optimistic: each patient was seen by K - 1 members."""
@@ -241,8 +256,8 @@ def predict_ensemble(checkpoints, kind, combine, batch_size, out_csv, attribute_
                 vols, stds = att["ct"][:, 0].cpu().numpy(), att["ct_std"][:, 0].cpu().numpy()
                 for r, i in enumerate(idx[s:s + batch_size]):
                     if has[r, 0]:
-                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct.npy"), vols[r])
-                        np.save(os.path.join(attribute_dir, f"{pid(i)}_ct_std.npy"), stds[r])
+                        save_saliency(attribute_dir, f"{pid(i)}_ct", vols[r], cohort, int(i), attribute_format)
+                        save_saliency(attribute_dir, f"{pid(i)}_ct_std", stds[r], cohort, int(i), attribute_format)
             if att["rna"] is not None and has[:, 1].any():
                 g = att["rna"].abs().double().cpu().numpy()[has[:, 1]]
                 gene_sum = g.sum(0) if gene_sum is None else gene_sum + g.sum(0)
@@ -546,6 +561,9 @@ def main(argv=None):
                     help="with --ensemble: risk_score = the members' mean log-hazard, or their mean midrank over the predicted patients / N")
     ap.add_argument("--attribute", action="store_true", help="with --predict: write <outdir>/attribution/<patient_id>_ct.npy and gene_scores.csv; "
                     "with --ensemble: the members' mean (<id>_ct.npy) and spread (<id>_ct_std.npy) and the mean gradient's gene_scores.csv")
+    ap.add_argument("--attribute-format", choices=("npy", "nii"), default="npy",
+                    help="with --attribute: npy = arrays on the network grid; nii = <patient_id>_ct.nii.gz (and _ct_std.nii.gz for ensembles) "
+                         "carrying the scan's geometry, for a medical viewer to overlay on the scan")
     ap.add_argument("--genes", metavar="FILE", help="with --predict: the fold's selected gene columns (fold_k_genes.json written by a training entry "
                     "point under MMS_SELECT_GENES); the model is built at that width")
     ap.add_argument("--top", type=int, default=50, help="rows of gene_scores.csv")
@@ -603,11 +621,12 @@ def main(argv=None):
         ap.error("--genes needs --predict CHECKPOINT")
     adir = os.path.join(a.outdir, "attribution") if a.attribute else None
     if a.ensemble:
-        df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top)
+        df = predict_ensemble(a.ensemble, a.model, a.combine, a.batch_size, a.predictions, adir, a.top, a.attribute_format)
     elif a.predict:
         train_csv = os.path.join(a.outdir, "train_predictions.csv") if a.horizons and not a.baseline else None
         cov_csv = os.path.join(a.outdir, "covariates.csv") if a.adjust is True else None
-        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes, train_csv, cov_csv)
+        df = predict(a.predict, a.model, a.fold, a.n_folds, a.batch_size, a.predictions, adir, a.top, a.genes, train_csv, cov_csv,
+                     a.attribute_format)
         a.baseline = a.baseline or train_csv
         a.adjust = cov_csv or a.adjust
     else:

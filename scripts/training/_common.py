@@ -92,8 +92,9 @@ def save_json(path, obj):
 
 def load_or_make_cohort(device, **make_kw):
     """The reference reads data/processed/{full_matching_table.csv, rnaseq_normalized_mapped.csv} relative to the cwd.  If that
-    contract is present (e.g. written by cohort_io.write_cohort, or real data converted to .npy volumes) it is loaded ONCE
-    into an HBM-resident store with the volume preprocessing done on the GPU; otherwise a seeded synthetic cohort is built."""
+    contract is present (real data as it is -- nifti_path naming the .nii.gz volumes of convert_dicom_to_nifti.py, relative paths
+    resolved against the cwd, then MMS_DATA_ROOT -- or a cohort written by cohort_io.write_cohort, .npy volumes included) it is loaded
+    ONCE into an HBM-resident store with the volume preprocessing done on the GPU; otherwise a seeded synthetic cohort is built."""
     from multimodal_survival_prediction_amd import cohort_io, data
     root = os.environ.get("MMS_DATA_ROOT", ".")
     if os.path.exists(os.path.join(root, cohort_io.TABLE)):
