@@ -22,10 +22,9 @@ Definitions (n patients (t_i, e_i), integer multiplicities w_i, horizons tau_1 <
 These are the conventions of lifelines / scikit-survival with ONE difference: a case is weighted by the LEFT limit G(t_i-), after Graf
 et al. (1999); scikit-survival uses G(t_i).
 
-All replicates of all models at all horizons are ONE launch of mms_td_metrics (include/mmsurv.h: TdMetricsP); an all-ones row is
-prepended, so the point estimates come out of the same launch.  Everything after it (ratios, integrals, quantiles, p-values:
-prediction_error_statistics) is float64 host arithmetic.  There is no CPU fallback for the launch, like the rest of the package.  The
-draws are bootstrap.bootstrap_weights(n, R, seed, strata): the same seed resamples the same patients as bootstrap.cindex_bootstrap.
+All replicates of all models at all horizons are ONE launch of mms_td_metrics (include/mmsurv.h: TdMetricsP) under the multiplicity
+rows of bootstrap.replicate_rows.  Everything after it (ratios and integrals: prediction_error_statistics; intervals and p-values:
+bootstrap.estimate / paired) is float64 host arithmetic.  There is no CPU fallback for the launch, like the rest of the package.
 
 With strata (pooled out-of-fold predictions) only the RESAMPLING is stratified.  The pooled Brier score is meaningful when each fold's
 predictions came from that fold's own baseline; the pooled AUC assumes that the folds' risk scores are on a comparable scale.  Out of
@@ -34,7 +33,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .bootstrap import _to_numpy, bootstrap_weights
+from .bootstrap import Estimate, Paired, estimate, paired, replicate_rows
+from .risk_sets import risk_matrix, run_flags, to_numpy
 
 
 # ---- Breslow baseline ---------------------------------------------------------------------------------------------------------------
@@ -60,15 +60,15 @@ class Baseline:
 
     def survival(self, risk, horizons):
         """S(tau | eta) = exp(-H0(tau) e^eta) -> [..., H] for risk [...]"""
-        eta = np.asarray(_to_numpy(risk, "risk"), dtype=np.float64)
+        eta = np.asarray(to_numpy(risk, "risk"), dtype=np.float64)
         return np.exp(-self._steps(horizons) * np.exp(eta - self.shift)[..., None])
 
 
 def breslow_baseline(risk, time, event):
     """Breslow's estimate of the cumulative baseline hazard on a fit set (a fold's training patients scored by the model that predicts):
     H0(t) = sum over the event times u <= t of d_u / sum_{j: t_j >= u} exp(eta_j), d_u the events at u; computed on eta - max eta."""
-    eta = np.asarray(_to_numpy(risk, "risk"), dtype=np.float64).reshape(-1)
-    t, e = np.asarray(_to_numpy(time, "time"), dtype=np.float64).reshape(-1), np.asarray(_to_numpy(event, "event")).reshape(-1) != 0
+    eta = np.asarray(to_numpy(risk, "risk"), dtype=np.float64).reshape(-1)
+    t, e = np.asarray(to_numpy(time, "time"), dtype=np.float64).reshape(-1), np.asarray(to_numpy(event, "event")).reshape(-1) != 0
     if len(eta) < 1 or len(t) != len(eta) or len(e) != len(eta):
         raise ValueError("risk, time and event must have the same n >= 1 entries")
     shift = float(eta.max())
@@ -100,18 +100,17 @@ def default_horizons(time, event, H=16):
 def metric_inputs(risk, time, event, horizons):
     """-> (order, trank, event, hcut, rord) of TdMetricsP: order = the patients time ascending, events before censorings at equal
     times (stable); trank / event per position of that order; hcut[h] = positions with t <= tau_h; rord[m] = 2 * position + [last of
-    its group of equal risks], the positions of model m (risk: [M, n]) in risk-ascending order."""
+    its group of equal risks], the positions of model m (risk: [M, n]) in risk-ascending order.  (Tie flags: risk_sets.run_flags.)"""
     t, e = np.asarray(time, dtype=np.float64).reshape(-1), (np.asarray(event).reshape(-1) != 0).astype(np.int32)
     order = np.lexsort((1 - e, t))
     ts = t[order]
-    trank = np.concatenate([[0], np.cumsum(ts[1:] != ts[:-1])]).astype(np.int32)
+    trank = (np.cumsum(run_flags(ts)[0]) - 1).astype(np.int32)
     hcut = np.searchsorted(ts, np.asarray(horizons, dtype=np.float64), side="right").astype(np.int32)
     rord = []
     for r in np.asarray(risk):
         rp = r[order]
         ro = np.argsort(rp, kind="stable")
-        rs = rp[ro]
-        rord.append(2 * ro + np.concatenate([rs[1:] != rs[:-1], [True]]))
+        rord.append(2 * ro + run_flags(rp[ro])[1])
     return order, trank, e[order], hcut, np.stack(rord).astype(np.int32)
 
 
@@ -123,23 +122,6 @@ def _trapezoid_mean(y, x):
 
 
 # ---- statistics layer ---------------------------------------------------------------------------------------------------------------
-@dataclass
-class Estimate:
-    value: np.ndarray            # point estimate (the all-ones row)
-    low: np.ndarray              # percentile interval over the non-degenerate replicates
-    high: np.ndarray
-    se: np.ndarray               # their standard deviation (ddof 1)
-    boot: np.ndarray = None      # [..., R] replicate values (NaN where undefined)
-
-
-@dataclass
-class Paired:
-    delta: np.ndarray            # [M, M] value[a] - value[b]
-    low: np.ndarray              # percentile interval of the paired replicate differences
-    high: np.ndarray
-    p_value: np.ndarray          # two-sided, min(1, 2 min((#{d <= 0} + 1) / (R' + 1), (#{d >= 0} + 1) / (R' + 1)))
-
-
 @dataclass
 class PredictionErrorResult:
     horizons: np.ndarray         # [H]
@@ -155,34 +137,6 @@ class PredictionErrorResult:
     replicates: int = 0
     seed: int = 0
     alpha: float = 0.05
-
-
-def _estimate(all_, ok, alpha):
-    """all_: [..., 1 + R] (index 0 = the point estimate) -> Estimate over the replicates ok [R]"""
-    value, boot = all_[..., 0].copy(), all_[..., 1:].copy()
-    good = boot[..., ok]
-    nan = np.full(value.shape, np.nan)
-    lo, hi, se = nan.copy(), nan.copy(), nan.copy()
-    if good.shape[-1] > 0:
-        lo, hi = np.quantile(good, alpha / 2, axis=-1), np.quantile(good, 1 - alpha / 2, axis=-1)
-        if good.shape[-1] > 1:
-            se = good.std(axis=-1, ddof=1)
-    return Estimate(value=value, low=lo, high=hi, se=se, boot=boot)
-
-
-def _paired(est, ok, alpha):
-    """the paired differences of an [M] Estimate: bootstrap_statistics' formulas"""
-    M = len(est.value)
-    good = est.boot[:, ok]
-    Rp = good.shape[1]
-    lo, hi, pv = np.full((M, M), np.nan), np.full((M, M), np.nan), np.full((M, M), np.nan)
-    if Rp > 0:
-        for a in range(M):
-            for b in range(M):
-                d = good[a] - good[b]
-                lo[a, b], hi[a, b] = np.quantile(d, alpha / 2), np.quantile(d, 1 - alpha / 2)
-                pv[a, b] = min(1.0, 2.0 * min((np.count_nonzero(d <= 0) + 1) / (Rp + 1), (np.count_nonzero(d >= 0) + 1) / (Rp + 1)))
-    return Paired(delta=est.value[:, None] - est.value[None, :], low=lo, high=hi, p_value=pv)
 
 
 def prediction_error_statistics(raw, horizons, alpha=0.05, seed=0):
@@ -203,10 +157,10 @@ def prediction_error_statistics(raw, horizons, alpha=0.05, seed=0):
     ibs, iauc = _trapezoid_mean(brier, tau), _trapezoid_mean(auc, tau)           # [1 + R, M]
     ok = ~np.isnan(auc[1:]).any(axis=(1, 2))
     mv = lambda x: np.moveaxis(x, 0, -1)                                         # replicates last
-    e_ibs, e_iauc = _estimate(mv(ibs), ok, alpha), _estimate(mv(iauc), ok, alpha)
-    return PredictionErrorResult(horizons=tau, brier=_estimate(mv(brier), ok, alpha), brier_null=_estimate(mv(null), ok, alpha),
-                                 ipa=_estimate(mv(ipa), ok, alpha), ibs=e_ibs, auc=_estimate(mv(auc), ok, alpha), iauc=e_iauc,
-                                 ibs_diff=_paired(e_ibs, ok, alpha), iauc_diff=_paired(e_iauc, ok, alpha), n_degenerate=int(R - ok.sum()),
+    e_ibs, e_iauc = estimate(mv(ibs), ok, alpha), estimate(mv(iauc), ok, alpha)
+    return PredictionErrorResult(horizons=tau, brier=estimate(mv(brier), ok, alpha), brier_null=estimate(mv(null), ok, alpha),
+                                 ipa=estimate(mv(ipa), ok, alpha), ibs=e_ibs, auc=estimate(mv(auc), ok, alpha), iauc=e_iauc,
+                                 ibs_diff=paired(e_ibs, ok, alpha), iauc_diff=paired(e_iauc, ok, alpha), n_degenerate=int(R - ok.sum()),
                                  replicates=int(R), seed=seed, alpha=float(alpha))
 
 
@@ -215,29 +169,20 @@ def prediction_error(surv, risk, time, event, horizons, R=2000, seed=0, strata=N
     model comparison -> PredictionErrorResult (the module docstring has the definitions and the caveats of pooled predictions).
 
     surv: [n, H] or [M, n, H] predicted survival probabilities at the horizons (Baseline.survival), risk: [n] or [M, n] (higher = higher
-    risk; orders the AUC), time / event: [n], horizons: [H] finite, positive, strictly ascending.  The R draws are
-    bootstrap.bootstrap_weights(n, R, seed, strata); weights: int8 [R, n] multiplicities to use instead.  R = 0 gives the point estimates
-    alone.  One all-ones row is prepended, so the point estimates come out of the same launch.  Runs on the current GPU."""
+    risk; orders the AUC), time / event: [n], horizons: [H] finite, positive, strictly ascending.  The multiplicity rows are
+    bootstrap.replicate_rows(n, R, seed, strata, weights); R = 0 gives the point estimates alone.  Runs on the current GPU."""
     from . import ops
     tau = check_horizons(horizons)
-    risk = np.asarray(_to_numpy(risk, "risk"), dtype=np.float64)
-    risk = risk.reshape(1, -1) if risk.ndim == 1 else risk
-    surv = np.asarray(_to_numpy(surv, "surv"), dtype=np.float64)
+    risk, t, e = risk_matrix(risk, time, event)
+    risk = np.asarray(risk, dtype=np.float64)
+    surv = np.asarray(to_numpy(surv, "surv"), dtype=np.float64)
     surv = surv[None] if surv.ndim == 2 else surv
-    t, e = _to_numpy(time, "time").reshape(-1), _to_numpy(event, "event").reshape(-1)
-    M, n = risk.shape if risk.ndim == 2 else (0, 0)
-    if M < 1 or n < 1 or len(t) != n or len(e) != n or surv.shape != (M, n, len(tau)):
-        raise ValueError("risk must be [n] or [M, n], time / event [n] and surv [n, H] or [M, n, H] with H = len(horizons)")
+    M, n = risk.shape
+    if surv.shape != (M, n, len(tau)):
+        raise ValueError("surv must be [n, H] or [M, n, H] with H = len(horizons)")
     if not np.isfinite(surv).all() or surv.min() < 0 or surv.max() > 1:
         raise ValueError("surv must hold probabilities in [0, 1]")
-    if weights is None:
-        w = bootstrap_weights(n, R, seed, strata) if R else np.zeros((0, n), np.int8)
-    else:
-        w = _to_numpy(weights, "weights")
-        if w.ndim != 2 or w.shape[1] != n or (w.size and (w.min() < 0 or w.max() > 127)):
-            raise ValueError("weights must be [R, n] multiplicities in 0..127")
-        w = w.astype(np.int8)
-    w = np.concatenate([np.ones((1, n), np.int8), w])
+    w = replicate_rows(n, R, seed, strata, weights)
     order, trank, es, hcut, rord = metric_inputs(risk, t, e, tau)
     out = ops.td_metrics(trank, es, hcut, rord, np.ascontiguousarray(surv[:, order, :]), np.ascontiguousarray(w[:, order]))
     raw = {k: v.cpu().numpy() for k, v in out.items()}
@@ -252,7 +197,7 @@ def calibration_table(surv_tau, time, event, tau, groups=5, alpha=0.05):
     predicted event probability, observed = 1 - KM(tau) of the group, low, high = the Greenwood log-log band of risk_strata.km_curve).
     Host arithmetic, point estimates only."""
     from .risk_strata import km_curve
-    p = 1.0 - np.asarray(_to_numpy(surv_tau, "surv_tau"), dtype=np.float64).reshape(-1)
+    p = 1.0 - np.asarray(to_numpy(surv_tau, "surv_tau"), dtype=np.float64).reshape(-1)
     t, e = np.asarray(time, dtype=np.float64).reshape(-1), np.asarray(event).reshape(-1) != 0
     groups = int(groups)
     if not 1 <= groups <= len(p) or len(t) != len(p) or len(e) != len(p):

@@ -14,6 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .risk_sets import risk_matrix, to_numpy
+
 PAIR_RULES = {"harrell": 0, "lifelines": 1, 0: 0, 1: 1}
 
 
@@ -53,22 +55,31 @@ def bootstrap_weights(n, R, seed, strata=None):
     return w.astype(np.int8)
 
 
+def multiplicity_rows(weights, n):
+    """The one check of a caller's own multiplicities -> int8 [R, n]: 2-D with n columns, integral, 0..127 (NaN raises); R = 0 is fine."""
+    w = to_numpy(weights, "weights")
+    if w.ndim != 2 or w.shape[1] != n or (w.size and (w.min() < 0 or w.max() > 127 or (w != np.round(w)).any())):
+        raise ValueError("weights must be [R, %d] integer multiplicities in 0..127" % n)
+    return w.astype(np.int8)
+
+
+def replicate_rows(n, R, seed, strata=None, weights=None):
+    """-> int8 [1 + R, n], the multiplicity rows of one launch: an all-ones row (the point estimates come out of the same launch), then
+    bootstrap_weights(n, R, seed, strata) -- or the caller's own `weights` [R, n] (multiplicity_rows).  R = 0 gives the ones row alone.
+    Every analysis of an evaluation calls this, so the same seed and strata resample the same patients in all of them."""
+    if weights is not None:
+        w = multiplicity_rows(weights, n)
+    else:
+        w = bootstrap_weights(n, R, seed, strata) if R else np.zeros((0, n), np.int8)
+    return np.concatenate([np.ones((1, n), np.int8), w])
+
+
 def dense_ranks(x):
     """-> int32 dense ranks (0 = smallest) of x along its last axis, at x's OWN precision: equal values share a rank, nothing is rounded."""
     x = np.asarray(x)
     if x.ndim == 1:
         return np.unique(x, return_inverse=True)[1].reshape(-1).astype(np.int32)
     return np.stack([dense_ranks(row) for row in x])
-
-
-def _to_numpy(x, what):
-    if hasattr(x, "detach"):            # a torch tensor; bfloat16 has no numpy type: float32 holds it exactly
-        x = x.detach().cpu()
-        x = (x.float() if str(x.dtype) == "torch.bfloat16" else x).numpy()
-    x = np.asarray(x)
-    if x.dtype.kind == "f" and np.isnan(x).any():
-        raise ValueError("%s contains NaN" % what)
-    return x
 
 
 @dataclass
@@ -89,61 +100,86 @@ class BootstrapResult:
     seed: int = 0
 
 
+@dataclass
+class Estimate:
+    value: np.ndarray            # point estimate (the all-ones row)
+    low: np.ndarray              # percentile interval over the non-degenerate replicates
+    high: np.ndarray
+    se: np.ndarray               # their standard deviation (ddof 1)
+    boot: np.ndarray = None      # [..., R] replicate values (NaN where undefined)
+
+
+@dataclass
+class Paired:
+    delta: np.ndarray            # [M, M] value[a] - value[b]
+    low: np.ndarray              # percentile interval of the paired replicate differences
+    high: np.ndarray
+    p_value: np.ndarray          # two-sided, min(1, 2 min((#{d <= 0} + 1) / (R' + 1), (#{d >= 0} + 1) / (R' + 1)))
+
+
+def estimate(all_, ok, alpha):
+    """all_: [..., 1 + R] (index 0 = the point estimate) -> Estimate over the R' replicates ok [R]: NaN intervals for R' = 0, a NaN se
+    for R' = 1"""
+    value, boot = all_[..., 0].copy(), all_[..., 1:].copy()
+    good = boot[..., ok]
+    nan = np.full(value.shape, np.nan)
+    lo, hi, se = nan.copy(), nan.copy(), nan.copy()
+    if good.shape[-1] > 0:
+        lo, hi = np.quantile(good, [alpha / 2, 1 - alpha / 2], axis=-1)
+        if good.shape[-1] > 1:
+            se = good.std(axis=-1, ddof=1)
+    return Estimate(value=value, low=lo, high=hi, se=se, boot=boot)
+
+
+def paired(est, ok, alpha):
+    """the paired differences of an [M] Estimate over the same replicates ok [R] -> Paired"""
+    M = len(est.value)
+    good = est.boot[:, ok]
+    Rp = good.shape[1]
+    lo, hi, pv = np.full((M, M), np.nan), np.full((M, M), np.nan), np.full((M, M), np.nan)
+    if Rp > 0:
+        for a in range(M):
+            for b in range(M):
+                d = good[a] - good[b]
+                lo[a, b], hi[a, b] = np.quantile(d, [alpha / 2, 1 - alpha / 2])
+                pv[a, b] = min(1.0, 2.0 * min((np.count_nonzero(d <= 0) + 1) / (Rp + 1), (np.count_nonzero(d >= 0) + 1) / (Rp + 1)))
+    return Paired(delta=est.value[:, None] - est.value[None, :], low=lo, high=hi, p_value=pv)
+
+
 def bootstrap_statistics(counts, alpha=0.05, seed=0):
     """The statistics layer on raw counts: int64 [M + 1, 1 + R], column 0 the point estimate's, rows m < M = 2*concordant + tied of model m,
-    row M = comparable pairs.  Pure float64 host arithmetic; replicates with zero comparable pairs are NaN in c_boot, counted in
-    n_degenerate and left out of every quantile; when all are degenerate every statistic is NaN."""
+    row M = comparable pairs.  Pure float64 host arithmetic (estimate / paired); replicates with zero comparable pairs are NaN in c_boot,
+    counted in n_degenerate and left out of every quantile; when all are degenerate every statistic is NaN."""
     counts = np.asarray(counts, dtype=np.int64)
     M, R = counts.shape[0] - 1, counts.shape[1] - 1
     num, den = counts[:M].astype(np.float64), counts[M].astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         c_all = np.where(den > 0, num / (2.0 * den), np.nan)
-    c, c_boot = c_all[:, 0].copy(), c_all[:, 1:].copy()
     ok = den[1:] > 0
-    Rp = int(ok.sum())
-    nan1, nan2 = np.full(M, np.nan), np.full((M, M), np.nan)
-    se, lo, hi = nan1.copy(), nan1.copy(), nan1.copy()
-    dlo, dhi, pv = nan2.copy(), nan2.copy(), nan2.copy()
-    good = c_boot[:, ok]
-    if Rp > 0:
-        lo, hi = np.quantile(good, alpha / 2, axis=1), np.quantile(good, 1 - alpha / 2, axis=1)
-        if Rp > 1:
-            se = good.std(axis=1, ddof=1)
-        for a in range(M):
-            for b in range(M):
-                d = good[a] - good[b]
-                dlo[a, b], dhi[a, b] = np.quantile(d, alpha / 2), np.quantile(d, 1 - alpha / 2)
-                pv[a, b] = min(1.0, 2.0 * min((np.count_nonzero(d <= 0) + 1) / (Rp + 1), (np.count_nonzero(d >= 0) + 1) / (Rp + 1)))
-    return BootstrapResult(c=c, c_boot=c_boot, se=se, ci_low=lo, ci_high=hi, delta=c[:, None] - c[None, :], delta_ci_low=dlo,
-                           delta_ci_high=dhi, p_value=pv, n_degenerate=R - Rp, counts=counts, alpha=float(alpha), replicates=R, seed=seed)
+    c = estimate(c_all, ok, alpha)
+    d = paired(c, ok, alpha)
+    return BootstrapResult(c=c.value, c_boot=c.boot, se=c.se, ci_low=c.low, ci_high=c.high, delta=d.delta, delta_ci_low=d.low,
+                           delta_ci_high=d.high, p_value=d.p_value, n_degenerate=R - int(ok.sum()), counts=counts, alpha=float(alpha),
+                           replicates=R, seed=seed)
 
 
 def cindex_bootstrap(risk, time, event, R=2000, seed=0, strata=None, pair_rule="lifelines", alpha=0.05, weights=None):
     """Bootstrap distribution of Harrell's C of M models scored on the same n patients.
 
-    risk: [n] or [M, n] (numpy or torch, any float dtype; higher = higher risk; NaN raises), time / event: [n].  strata: [n] labels --
-    pairs count only inside one stratum and the resampling keeps every stratum's size (out-of-fold predictions of K folds' models).
-    pair_rule: "lifelines" (survival_stats.concordance_index: at equal times an (event, censored) pair is comparable) or "harrell"
-    (ops.cindex_counts: strictly later times only).  weights: int8 [R, n] multiplicities to use instead of bootstrap_weights(n, R, seed,
-    strata).  One all-ones row is prepended, so the point estimates come out of the same launch.  Runs on the current GPU."""
+    risk: [n] or [M, n] (numpy or torch, any float dtype; higher = higher risk; NaN raises), time / event: [n] (risk_sets.risk_matrix).
+    strata: [n] labels -- pairs count only inside one stratum and the resampling keeps every stratum's size (out-of-fold predictions of
+    K folds' models).  pair_rule: "lifelines" (survival_stats.concordance_index: at equal times an (event, censored) pair is comparable)
+    or "harrell" (ops.cindex_counts: strictly later times only).  The multiplicity rows are replicate_rows(n, R, seed, strata, weights),
+    R >= 1.  Runs on the current GPU."""
     import torch
     from . import ops
     if pair_rule not in PAIR_RULES:
         raise ValueError("pair_rule must be one of %s" % sorted(map(str, PAIR_RULES)))
-    risk = _to_numpy(risk, "risk")
-    risk = risk.reshape(1, -1) if risk.ndim == 1 else risk
-    t, e = _to_numpy(time, "time").reshape(-1), _to_numpy(event, "event").reshape(-1)
+    risk, t, e = risk_matrix(risk, time, event)
     n = risk.shape[1]
-    if risk.ndim != 2 or len(t) != n or len(e) != n:
-        raise ValueError("risk must be [n] or [M, n] and time / event [n]")
-    if weights is None:
-        w = bootstrap_weights(n, R, seed, strata)
-    else:
-        w = _to_numpy(weights, "weights")
-        if w.ndim != 2 or w.shape[1] != n or w.min() < 0 or w.max() > 127:
-            raise ValueError("weights must be [R, n] multiplicities in 0..127")
-        w = w.astype(np.int8)
-    w = np.concatenate([np.ones((1, n), np.int8), w])
+    if weights is None and int(R) < 1:
+        raise ValueError("n and R must be >= 1")
+    w = replicate_rows(n, R, seed, strata, weights)
     trank = dense_ranks(t)
     order = np.argsort(trank, kind="stable")          # time-sorted columns let the kernel skip the tiles without comparable pairs
     dev = torch.device("cuda")

@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import gene_select
-from .gene_select import _to_numpy
+from .risk_sets import descending_groups, to_numpy
 
 TOL = 1e-6
 MAX_ITER = 5000
@@ -45,14 +45,13 @@ class RiskRows:
 
 def risk_rows(cohort, indices=None):
     """The row list of a call: cohort's eligible patients (gene_select.eligible_rows; of `indices` when given) in stable time-descending
-    order, their event flags and the tie-group end flags."""
-    label = _to_numpy(cohort["label"]).astype(np.float64)
+    order (risk_sets.descending_groups), their event flags and the tie-group end flags."""
+    label = to_numpy(cohort["label"]).astype(np.float64)
     idx = np.arange(len(label)) if indices is None else indices
     rows = gene_select.eligible_rows(cohort, idx)
-    rows = rows[np.argsort(-label[rows, 0], kind="stable")]
-    t = label[rows, 0]
-    glast = np.concatenate([t[1:] != t[:-1], [True]]) if len(t) else np.zeros(0, bool)
-    return RiskRows(rows.astype(np.int64), t, label[rows, 1] != 0, glast)
+    order, _, _, _, glast = descending_groups(label[rows, 0])
+    rows = rows[order]
+    return RiskRows(rows.astype(np.int64), label[rows, 0], label[rows, 1] != 0, glast)
 
 
 def rows_as_list(rows):
@@ -76,7 +75,7 @@ class HipBackend:
 def problem_scales(x, rr, mults):
     """Per-problem, per-gene weighted standard deviation over the problem's own m > 0 rows (no centring of the data: the partial
     likelihood is shift-invariant) -> (scale float64 [F, G], constant bool [F, G]).  A constant gene gets scale 1."""
-    X = _to_numpy(x[_index(x, rr.rows)] if hasattr(x, "detach") else np.asarray(x)[rr.rows]).astype(np.float64)
+    X = to_numpy(x[_index(x, rr.rows)] if hasattr(x, "detach") else np.asarray(x)[rr.rows]).astype(np.float64)
     m = np.asarray(mults, dtype=np.float64)
     n = np.maximum(m.sum(1, keepdims=True), 1.0)
     mean = (m @ X) / n
@@ -109,7 +108,7 @@ def log_path(lam_max, n_lambda=30, ratio=0.05):
 def lambda_path(x, cohort, rr, mults, alpha, n_lambda=30, ratio=0.05, scale=None):
     """lambda_max of every multiplicity vector from gene_select.cox_score_screen's U (one launch: a problem is its rows repeated by their
     multiplicity) -> (lambdas [F, L] descending, lambda_max [F])."""
-    label = _to_numpy(cohort["label"])
+    label = to_numpy(cohort["label"])
     mults = np.asarray(mults)
     U, _, _ = gene_select.cox_score_screen(x, label[:, 0], label[:, 1], [np.repeat(rr.rows, m) for m in mults])
     lmax = lambda_max_from_score(U, scale, mults.sum(1), alpha)
@@ -193,7 +192,7 @@ def nested_problems(cohort, folds, inner, seed, rr=None):
     in the fit that is scored on it."""
     from . import data
     rr = risk_rows(cohort) if rr is None else rr
-    N = int(_to_numpy(cohort["label"]).shape[0])
+    N = int(to_numpy(cohort["label"]).shape[0])
     J = int(inner)
     mults, plan = np.zeros((len(folds), J + 1, len(rr)), np.int32), []
     for f, (tr, va) in enumerate(folds):
@@ -225,7 +224,7 @@ def nested_cv(cohort, folds, alpha=0.5, n_lambda=30, inner=5, criterion="cindex"
     if criterion not in ("cindex", "pl"):
         raise ValueError("criterion must be 'cindex' or 'pl'")
     be = backend or HipBackend()
-    label = _to_numpy(cohort["label"]).astype(np.float64)
+    label = to_numpy(cohort["label"]).astype(np.float64)
     rr, mults, plan = nested_problems(cohort, folds, inner, seed)
     K, J1, n = mults.shape
     J, L = J1 - 1, int(n_lambda)

@@ -7,9 +7,9 @@ runs once per fold, and with stability selection once per bootstrap resample of 
 
 The statistic is the Cox partial-likelihood score test of one gene at beta = 0 with Breslow ties, in closed form (include/mmsurv.h:
 GeneScreenP): for an ordered list of patient rows (time descending) U = sum_k a_k x_k, V = sum_k b_k x_k^2 - sum_k q_k S1_k^2 with S1
-the running column sum, stat = U^2 / V (chi-square, 1 dof).  a, b, q depend on the labels only: score_coefficients computes them on the
-host in float64; the sums over the patients for all genes of all problems are ONE launch of mms_gene_screen over the device-resident
-matrix.  A row listed twice is a tie, so a bootstrap resample is an index list with repeats and needs no weights.  There is no CPU
+the running column sum, stat = U^2 / V (chi-square, 1 dof).  a, b, q depend on the labels only (score_coefficients, on
+risk_sets.risk_set_table, in float64); the sums over the patients for all genes of all problems are ONE launch of mms_gene_screen over
+the device-resident matrix.  A row listed twice is a tie, so a bootstrap resample is an index list with repeats and needs no weights.  There is no CPU
 fallback for the sums, like the rest of the package.
 
 Reproducibility contract of the resamples (select_genes(stability=R)): fold f's multiplicities are
@@ -20,33 +20,17 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .risk_sets import risk_set_table, score_chi2 as score_statistic, to_numpy
+
 
 def score_coefficients(time, event, rows=None):
     """-> (order, a, b, q) of one problem.  time / event: per-patient arrays; rows: the problem's patient rows (repeats allowed; None =
     all patients once).  order: positions into `rows`, time descending (stable: equal times keep their order in `rows`) -- the problem's
     risk order is rows[order]; a, b, q: float64 per position of that order (GeneScreenP in include/mmsurv.h)."""
-    t_all, e_all = np.asarray(time, dtype=np.float64).reshape(-1), np.asarray(event, dtype=np.float64).reshape(-1)
-    rows = np.arange(len(t_all)) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
-    order = np.argsort(-t_all[rows], kind="stable")
-    t, e = t_all[rows][order], (e_all[rows][order] != 0).astype(np.float64)
-    n = len(t)
-    if n == 0:
-        z = np.zeros(0)
-        return order, z, z.copy(), z.copy()
-    first = np.concatenate([[True], t[1:] != t[:-1]])           # tie groups of equal times, in descending order
-    gid = np.cumsum(first) - 1
-    last = np.concatenate([np.nonzero(first)[0][1:] - 1, [n - 1]])
-    n_u = (last + 1).astype(np.float64)                         # rows with t >= u: everything up to the group's last position
-    d_u = np.bincount(gid, weights=e, minlength=len(last))
-    h = d_u / n_u
-    b = np.cumsum(h[::-1])[::-1][gid]                           # event times u <= t_k are the groups from k's own onwards
-    q = np.zeros(n)
-    q[last] = d_u / (n_u * n_u)
-    return order, e - b, b, q
-
-
-def _to_numpy(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    T = risk_set_table(time, event, rows)
+    q = np.zeros(len(T.e))
+    q[T.last] = T.d_u / (T.n_u * T.n_u)
+    return T.order, T.e - T.b, T.b, q
 
 
 def cox_score_screen(x_dev, time, event, index_lists):
@@ -54,7 +38,7 @@ def cox_score_screen(x_dev, time, event, index_lists):
     a list of patient rows, repeats allowed) in ONE launch -> (U, V, stat): float64 numpy [P, G]; stat = U^2 / V, and 0 wherever V <= 0
     (a constant gene, a problem without events, a single-row problem)."""
     from . import ops
-    time, event = _to_numpy(time), _to_numpy(event)
+    time, event = to_numpy(time), to_numpy(event)
     off, rows, coefs = [0], [], []
     for lst in index_lists:
         lst = np.asarray(lst, dtype=np.int64).reshape(-1)
@@ -69,11 +53,6 @@ def cox_score_screen(x_dev, time, event, index_lists):
     return U, V, score_statistic(U, V)
 
 
-def score_statistic(U, V):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(V > 0, U * U / np.where(V > 0, V, 1.0), 0.0)
-
-
 def top_k(stat, k):
     """The k largest of stat, the lower gene index winning ties -> their indices in rank order."""
     return np.argsort(-np.asarray(stat, dtype=np.float64), kind="stable")[:k]
@@ -81,10 +60,10 @@ def top_k(stat, k):
 
 def eligible_rows(cohort, indices):
     """The patients of `indices` that have RNA-seq and a survival label, in the order given."""
-    idx = np.asarray(_to_numpy(indices), dtype=np.int64).reshape(-1)
-    ok = _to_numpy(cohort["has_survival"]).astype(bool)
+    idx = np.asarray(to_numpy(indices), dtype=np.int64).reshape(-1)
+    ok = to_numpy(cohort["has_survival"]).astype(bool)
     if "mask" in cohort:
-        ok = ok & (_to_numpy(cohort["mask"])[:, 1] != 0)
+        ok = ok & (to_numpy(cohort["mask"])[:, 1] != 0)
     return idx[ok[idx]]
 
 
@@ -92,7 +71,7 @@ def fold_problems(cohort, train_indices_per_fold, stability=0, seed=0):
     """-> (problems, rows per fold): the index lists of select_genes' launch, fold after fold, a fold's full sample first and its
     `stability` resamples behind it (the module docstring's contract)."""
     from .bootstrap import bootstrap_weights
-    event = _to_numpy(cohort["label"])[:, 1]
+    event = to_numpy(cohort["label"])[:, 1]
     problems, rows_f = [], []
     for f, idx in enumerate(train_indices_per_fold):
         rows = eligible_rows(cohort, idx)
@@ -217,7 +196,7 @@ def select_genes(cohort, train_indices_per_fold, k, stability=0, seed=0):
     if stability < 0:
         raise ValueError("stability must be >= 0 resamples")
     problems, rows_f = fold_problems(cohort, train_indices_per_fold, stability, seed)
-    label = _to_numpy(cohort["label"])
+    label = to_numpy(cohort["label"])
     _, _, stat = cox_score_screen(x, label[:, 0], label[:, 1], problems)
     cols, freqs, stats = [], [], []
     for f in range(len(rows_f)):

@@ -4,10 +4,10 @@ models.
 
 The fit is the classical low-dimensional one -- Newton-Raphson on the Breslow partial likelihood with the observed information
 (include/mmsurv.h: CoxNewtonP) -- and it runs many times: every bootstrap replicate of every nested covariate subset is its own fit.
-All of them are ONE launch of mms_cox_newton, one workgroup per fit, under an all-ones multiplicity row (the point estimates) plus the
-R rows of bootstrap.bootstrap_weights -- the draws cindex_bootstrap and absolute_risk.prediction_error use, so the intervals of one
-evaluation describe the same resamples.  Everything after the launch (z, p-values, quantiles, likelihood-ratio tests) is float64 host
-arithmetic on a few thousand numbers.  There is no CPU fallback for the fits, like the rest of the package.
+All of them are ONE launch of mms_cox_newton, one workgroup per fit, under the multiplicity rows of bootstrap.replicate_rows -- the rows
+cindex_bootstrap and absolute_risk.prediction_error use, so the intervals of one evaluation describe the same resamples.  Everything
+after the launch (z, p-values, likelihood-ratio tests; bootstrap intervals: bootstrap.estimate) is float64 host arithmetic on a few
+thousand numbers.  There is no CPU fallback for the fits, like the rest of the package.
 
 A fit's status (ops.COX_NEWTON_STATUS): 1 converged, 2 max_iter, 3 singular information (a column constant in the resample, or
 collinear), 4 monotone likelihood (a separating covariate: |beta| passed beta_max; reported, not repaired), 5 no step accepted,
@@ -18,7 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 from scipy import stats
 
-from .bootstrap import _to_numpy, bootstrap_weights
+from .bootstrap import estimate, multiplicity_rows, replicate_rows
+from .risk_sets import descending_groups, to_numpy
 
 MAX_P, MAX_S = 16, 64          # MMS_COXNEWTON_MAX_P / _MAX_S of include/mmsurv.h
 
@@ -41,7 +42,7 @@ def design(columns, standardize=True):
     names = list(columns)
     if not names:
         raise ValueError("no columns")
-    raw = np.stack([np.asarray(_to_numpy_nan(columns[k]), dtype=np.float64).reshape(-1) for k in names], axis=1)
+    raw = np.stack([np.asarray(to_numpy(columns[k]), dtype=np.float64).reshape(-1) for k in names], axis=1)
     if np.isinf(raw).any():
         raise ValueError("non-finite values in column(s) %s" % [k for k, c in zip(names, raw.T) if np.isinf(c).any()])
     keep = ~np.isnan(raw).any(axis=1)
@@ -58,18 +59,11 @@ def design(columns, standardize=True):
     return Design(X=(X - center) / scale, names=names, keep=keep, n_dropped=int((~keep).sum()), center=center, scale=scale)
 
 
-def _to_numpy_nan(x):
-    if hasattr(x, "detach"):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x)
-
-
 def launch_order(time):
-    """-> (order, glast): the patients in time-descending order (stable) and the flag at the last position of every group of equal times"""
-    t = np.asarray(time, dtype=np.float64).reshape(-1)
-    order = np.argsort(-t, kind="stable")
-    ts = t[order]
-    return order, np.concatenate([ts[1:] != ts[:-1], [True]]).astype(np.int32)
+    """-> (order, glast): the patients in time-descending order (stable) and the flag at the last position of every group of equal times
+    (risk_sets.descending_groups)"""
+    order, _, _, _, glast = descending_groups(time)
+    return order, glast.astype(np.int32)
 
 
 def subset_masks(subsets, p):
@@ -117,9 +111,9 @@ def _run(X, time, event, w, masks, tol, max_iter, beta_max):
 
 
 def _checked(X, time, event):
-    X = np.asarray(_to_numpy(X, "X"), dtype=np.float64)
+    X = np.asarray(to_numpy(X, "X"), dtype=np.float64)
     X = X.reshape(len(X), -1)
-    t, e = np.asarray(_to_numpy(time, "time"), dtype=np.float64).reshape(-1), _to_numpy(event, "event").reshape(-1)
+    t, e = np.asarray(to_numpy(time, "time"), dtype=np.float64).reshape(-1), to_numpy(event, "event").reshape(-1)
     n, p = X.shape
     if n < 1 or not 1 <= p <= MAX_P or len(t) != n or len(e) != n or not np.isfinite(X).all() or not np.isfinite(t).all():
         raise ValueError("X must be finite [n, p] with 1 <= p <= %d and time / event [n], finite" % MAX_P)
@@ -160,7 +154,8 @@ def point_fits(raw_point, X, time, event, subsets, alpha=0.05):
 
 def cox_fit(X, time, event, weights=None, subsets=None, tol=1e-9, max_iter=30, beta_max=30.0, alpha=0.05):
     """Cox regression of (time, event) on the columns of X [n, p] (p <= 16), one fit per subset of columns (lists of column indices;
-    None: all columns).  weights: [n] integer multiplicities 0..127 (a multiplicity is a repeat; None: all ones).  Breslow ties.
+    None: all columns).  weights: [n] integer multiplicities 0..127 (a multiplicity is a repeat; None: all ones; checked by
+    bootstrap.multiplicity_rows).  Breslow ties.
     -> list, per subset, of dict(columns, beta, se, z, p (Wald, two-sided), hr, hr_low, hr_high (Wald, level 1 - alpha), loglik,
     loglik0, aic = 2 k - 2 loglik, status, iters, c_index = the apparent C-index of X beta, survival_stats.concordance_index on the
     patients as given).  Runs on the current GPU."""
@@ -168,13 +163,7 @@ def cox_fit(X, time, event, weights=None, subsets=None, tol=1e-9, max_iter=30, b
     n, p = X.shape
     subsets = [list(range(p))] if subsets is None else [list(s) for s in subsets]
     masks = subset_masks(subsets, p)
-    if weights is None:
-        w = np.ones((1, n), np.int8)
-    else:
-        w = np.asarray(_to_numpy(weights, "weights")).reshape(1, -1)
-        if w.shape[1] != n or w.min() < 0 or w.max() > 127 or (w != np.round(w)).any():
-            raise ValueError("weights must be [n] integer multiplicities in 0..127")
-        w = w.astype(np.int8)
+    w = np.ones((1, n), np.int8) if weights is None else multiplicity_rows(to_numpy(weights).reshape(1, -1), n)
     raw = _run(X, t, e, w, masks, tol, max_iter, beta_max)
     return point_fits({k: v[0] for k, v in raw.items()}, X, t, e, subsets, alpha)
 
@@ -198,6 +187,9 @@ def analyse_statistics(raw, X, time, event, names, models, base, add, alpha=0.05
     scale = np.ones(len(names)) if scale is None else np.asarray(scale, dtype=np.float64)
     ok = (status[1:] == 1).all(axis=1)
     fits = point_fits({k: np.asarray(v)[0] for k, v in raw.items()}, X, time, event, subsets, alpha)
+    fitted = [(s, col[k]) for s, m in enumerate(models) for k in m[1]]                        # the coefficients that exist, in output order
+    rl = np.ascontiguousarray(np.moveaxis(beta, 0, -1)[tuple(zip(*fitted))])                  # [len(fitted), 1 + R]: replicates last and contiguous
+    b_est, hr_est = estimate(rl, ok, alpha), estimate(np.exp(rl), ok, alpha)
     out_models = []
     for s, ((label, cols), f) in enumerate(zip(models, fits)):
         coefs = {}
@@ -206,11 +198,9 @@ def analyse_statistics(raw, X, time, event, names, models, base, add, alpha=0.05
             c["scale"] = float(scale[col[k]])
             c["hr_per_unit"] = float(np.exp(f["beta"][j] / scale[col[k]]))
             if R:
-                b = beta[1:, s, col[k]][ok]
-                lo, hi = (np.quantile(b, [alpha / 2, 1 - alpha / 2]) if len(b) else (np.nan, np.nan))
-                hlo, hhi = (np.quantile(np.exp(b), [alpha / 2, 1 - alpha / 2]) if len(b) else (np.nan, np.nan))
-                c.update(beta_boot_low=float(lo), beta_boot_high=float(hi), hr_boot_low=float(hlo), hr_boot_high=float(hhi),
-                         beta_boot_se=float(b.std(ddof=1)) if len(b) > 1 else float("nan"))
+                a = fitted.index((s, col[k]))
+                c.update(beta_boot_low=float(b_est.low[a]), beta_boot_high=float(b_est.high[a]), hr_boot_low=float(hr_est.low[a]),
+                         hr_boot_high=float(hr_est.high[a]), beta_boot_se=float(b_est.se[a]))
             coefs[k] = c
         out_models.append(dict(model=label, columns=list(cols), coefficients=coefs, loglik=f["loglik"], loglik0=f["loglik0"], aic=f["aic"],
                                status=f["status"], iters=f["iters"], c_index=f["c_index"]))
@@ -231,9 +221,8 @@ def analyse(columns, time, event, base, add, R=2000, seed=0, strata=None, alpha=
 
     columns: dict name -> [n] numbers holding every name of base and add (design: complete cases, standardised; a hazard ratio is per
     standard deviation, hr_per_unit per unit of the column).  The models are model_subsets(base, add).  One launch fits all of them
-    under an all-ones row plus the R rows of bootstrap.bootstrap_weights(n, R, seed, strata) over the complete cases (weights: int8
-    [R, n] multiplicities over the complete cases to use instead); R = 0 gives the point estimates alone.  -> the dictionary of
-    analyse_statistics plus n_dropped, seed and the design's center / scale.  Runs on the current GPU."""
+    under bootstrap.replicate_rows(n, R, seed, strata, weights) over the n complete cases; R = 0 gives the point estimates alone.
+    -> the dictionary of analyse_statistics plus n_dropped, seed and the design's center / scale.  Runs on the current GPU."""
     models = model_subsets(base, add)
     names = list(base) + list(add)
     missing = [k for k in names if k not in columns]
@@ -241,23 +230,15 @@ def analyse(columns, time, event, base, add, R=2000, seed=0, strata=None, alpha=
         raise ValueError("columns has no %s" % missing)
     if len(names) > MAX_P or len(models) > MAX_S:
         raise ValueError("at most %d covariates and %d models in one analysis" % (MAX_P, MAX_S))
-    t_all, e_all = np.asarray(_to_numpy_nan(time), dtype=np.float64).reshape(-1), np.asarray(_to_numpy_nan(event), dtype=np.float64).reshape(-1)
-    cols = {k: np.asarray(_to_numpy_nan(columns[k]), dtype=np.float64).reshape(-1) for k in names}
+    t_all, e_all = np.asarray(to_numpy(time), dtype=np.float64).reshape(-1), np.asarray(to_numpy(event), dtype=np.float64).reshape(-1)
+    cols = {k: np.asarray(to_numpy(columns[k]), dtype=np.float64).reshape(-1) for k in names}
     if any(len(c) != len(t_all) for c in cols.values()) or len(e_all) != len(t_all):
         raise ValueError("every column, time and event must have the same n entries")
     keep = ~np.isnan(np.stack(list(cols.values()) + [t_all, e_all], axis=1)).any(axis=1)      # (a patient without a label is no complete case)
     d = design({k: c[keep] for k, c in cols.items()})
     X, t, e = _checked(d.X, t_all[keep], e_all[keep])
     n = len(X)
-    if weights is None:
-        st = None if strata is None else np.asarray(strata).reshape(-1)[keep]
-        w = bootstrap_weights(n, R, seed, st) if R else np.zeros((0, n), np.int8)
-    else:
-        w = np.asarray(_to_numpy(weights, "weights"))
-        if w.ndim != 2 or w.shape[1] != n or (w.size and (w.min() < 0 or w.max() > 127)):
-            raise ValueError("weights must be [R, n] multiplicities in 0..127 over the %d complete cases" % n)
-        w = w.astype(np.int8)
-    w = np.concatenate([np.ones((1, n), np.int8), w])
+    w = replicate_rows(n, R, seed, None if strata is None else np.asarray(strata).reshape(-1)[keep], weights)      # (over the complete cases)
     col = {k: a for a, k in enumerate(names)}
     masks = subset_masks([[col[k] for k in m[1]] for m in models], len(names))
     raw = _run(X, t, e, w, masks, tol, max_iter, beta_max)

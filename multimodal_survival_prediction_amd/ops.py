@@ -311,6 +311,22 @@ def cindex_boot(hrank, trank, event, w, stratum=None, pair_rule=0):
     return out
 
 
+def _upload(a, dtype, dev):
+    """a host array -> flat device tensor of dtype; an empty one becomes a single zero (never a NULL pointer)"""
+    import numpy as np
+    a = np.asarray(a)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).reshape(-1) if a.size else np.zeros(1, dtype)).to(dev)
+
+
+def _launch_or_plan(name, p, keep, res, plan_only):
+    """The tail of the evaluation wrappers: launch `name` on p -> res.  plan_only: launch nothing -> (p, keep = whatever p points to,
+    res; a tuple res is spliced in), for call(name, p) by the caller (the tools/bench_*.py time the launch alone)."""
+    if plan_only:
+        return (p, keep) + (res if isinstance(res, tuple) else (res,))
+    call(name, p)
+    return res
+
+
 def gene_screen(x, off, row, coef, G=None, plan_only=False):
     """Univariate Cox score screen (GeneScreenP in mmsurv.h).  x: fp32 [N, >= G] device matrix (row pitch x.stride(0)); off: [P + 1]
     problem offsets, row: [off[P]] patient rows in risk order, coef: [off[P], 3] float64 (a, b, q) -- host arrays (numpy or CPU
@@ -334,15 +350,10 @@ def gene_screen(x, off, row, coef, G=None, plan_only=False):
     if len(row) and (row.min() < 0 or row.max() >= N):
         raise ValueError("rows must lie in [0, %d)" % N)
     dev = x.device
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt) if len(a) else np.zeros(1, dt))).to(dev)       # (never a NULL pointer)
-    off_d, row_d = up(off, np.int32), up(row, np.int32)
-    coef_d = up(coef.reshape(-1), np.float64)
+    off_d, row_d, coef_d = _upload(off, np.int32, dev), _upload(row, np.int32, dev), _upload(coef, np.float64, dev)
     U, V = torch.empty(max(P, 1), G, dtype=torch.float64, device=dev), torch.empty(max(P, 1), G, dtype=torch.float64, device=dev)
     p = _S()["GeneScreenP"](ptr(x), N, x.stride(0), G, P, ptr(off_d), ptr(row_d), ptr(coef_d), ptr(U), ptr(V))
-    if plan_only:
-        return p, (x, off_d, row_d, coef_d), U[:P], V[:P]
-    call("mms_gene_screen", p)
-    return U[:P], V[:P]
+    return _launch_or_plan("mms_gene_screen", p, (x, off_d, row_d, coef_d), (U[:P], V[:P]), plan_only)
 
 
 def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False, plan_only=False):
@@ -394,10 +405,8 @@ def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False,
         if len(at) != S or (at < -1).any() or (at >= sizes).any():
             raise ValueError("at must hold one cut index per set (-1: none)")
     maxc = int(sizes.max()) if S else 0
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt)).reshape(-1) if a.size else np.zeros(1, dt)).to(dev)   # (never a NULL pointer)
-    t = dict(rank=rank if rank.numel() else torch.zeros(1, dtype=torch.int32, device=dev), pflag=up(pflag, np.int32),
-             coef=up(coef, np.float64), coff=up(coff, np.int32), cut=up(cut, np.int32),
-             cset=None if cset is None else up(cset, np.int32), at=None if at is None else up(at, np.int32))
+    t = {k: None if a is None else _upload(a, np.int32, dev) for k, a in dict(pflag=pflag, coff=coff, cut=cut, cset=cset, at=at).items()}
+    t.update(rank=rank if rank.numel() else torch.zeros(1, dtype=torch.int32, device=dev), coef=_upload(coef, np.float64, dev))
     ldo = max(maxc, 1)
     out = dict(chi2_max=torch.zeros(max(Q, 1), dtype=torch.float64, device=dev), arg_max=torch.zeros(max(Q, 1), dtype=torch.int32, device=dev),
                chi2_at=torch.zeros(max(Q, 1), dtype=torch.float64, device=dev))
@@ -408,10 +417,7 @@ def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False,
                              ptr(t["cut"]), ptr(t["cset"]), ptr(t["at"]), ptr(out["chi2_max"]), ptr(out["arg_max"]), ptr(out["chi2_at"]),
                              ptr(out.get("U")), ptr(out.get("V")), ptr(out.get("n_high")), ptr(out.get("d_high")), ldo)
     res = {k: (v[:Q, :maxc] if v.dim() == 2 else v[:Q]) for k, v in out.items()}
-    if plan_only:
-        return p, (t, out), res
-    call("mms_logrank_scan", p)
-    return res
+    return _launch_or_plan("mms_logrank_scan", p, (t, out), res, plan_only)
 
 
 def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
@@ -455,19 +461,15 @@ def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     if R and (bool((w < 0).any()) or bool((w.sum(1, dtype=torch.int64) < 1).any())):
         raise ValueError("w must hold multiplicities 0..127 and every row must draw a patient")
     surv, w = surv.to(dev).contiguous(), w.to(dev).contiguous()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
-    t = dict(trank=up(trank), event=up(event), hcut=up(hcut), rord=up(rord), surv=surv,
-             w=w if R else torch.zeros(1, n, dtype=torch.int8, device=dev))               # (never a NULL pointer)
+    t = {k: _upload(a, np.int32, dev) for k, a in dict(trank=trank, event=event, hcut=hcut, rord=rord).items()}
+    t.update(surv=surv, w=w if R else torch.zeros(1, n, dtype=torch.int8, device=dev))               # (never a NULL pointer)
     z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
     out = dict(G=z(max(R, 1), H), km=z(max(R, 1), H), wcase=z(max(R, 1), H), wctrl=z(max(R, 1), H), brier=z(max(R, 1), M, H),
                auc_num=z(max(R, 1), M, H))
     p = _S()["TdMetricsP"](n, H, M, R, ptr(t["trank"]), ptr(t["event"]), ptr(t["hcut"]), ptr(t["rord"]), n, ptr(t["surv"]), H, ptr(t["w"]), n,
                            ptr(out["G"]), ptr(out["km"]), ptr(out["wcase"]), ptr(out["wctrl"]), ptr(out["brier"]), ptr(out["auc_num"]))
     res = {k: v[:R] for k, v in out.items()}
-    if plan_only:
-        return p, (t, out), res
-    call("mms_td_metrics", p)
-    return res
+    return _launch_or_plan("mms_td_metrics", p, (t, out), res, plan_only)
 
 
 COX_NEWTON_STATUS = {1: "converged", 2: "max_iter", 3: "singular", 4: "monotone likelihood", 5: "no step accepted", 6: "no events"}
@@ -515,8 +517,7 @@ def cox_newton(x, time, event, glast, w, cmask, tol=1e-9, max_iter=30, beta_max=
         x = x.contiguous()
     if R == 0 or (R > 1 and w.stride(0) < n) or w.stride(1) != 1:
         w = w.contiguous() if R else torch.zeros(1, n, dtype=torch.int8, device=dev)          # (never a NULL pointer)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)) if a.size else np.zeros(1, np.int32)).to(dev)
-    t = dict(x=x, w=w, event=up(event), glast=up((glast != 0)), cmask=up(cmask))
+    t = dict(x=x, w=w, event=_upload(event, np.int32, dev), glast=_upload(glast != 0, np.int32, dev), cmask=_upload(cmask, np.int32, dev))
     Q = max(R * S, 1)
     zd = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
     zi = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
@@ -527,10 +528,7 @@ def cox_newton(x, time, event, glast, w, cmask, tol=1e-9, max_iter=30, beta_max=
                            max(w.stride(0), n) if R > 1 else n, ptr(t["cmask"]), float(tol), int(max_iter), float(beta_max), ptr(out["beta"]),
                            ptr(out["se"]), ptr(out["loglik"]), ptr(out["loglik0"]), ptr(out["iters"]), ptr(out["status"]), ptr(out.get("info")))
     res = {k: v[:R * S].reshape((R, S) + tuple(v.shape[1:])) for k, v in out.items()}
-    if plan_only:
-        return P, (t, out), res
-    call("mms_cox_newton", P)
-    return res
+    return _launch_or_plan("mms_cox_newton", P, (t, out), res, plan_only)
 
 
 COXNET_STATUS = {-1: "new", 0: "not converged", 1: "converged", 2: "not converged"}
@@ -580,13 +578,12 @@ def coxnet_plan(x, row, event, glast, mult, lam, alpha, scale=None, beta=None, G
     if not (0 < float(tol) <= 1.0) or not 1 <= int(max_iter) <= 100000000:
         raise ValueError("tol must lie in (0, 1] and max_iter in [1, 1e8]")
     dev = x.device
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt)).reshape(-1) if a.size else np.zeros(1, dt)).to(dev)   # (never a NULL pointer)
     f64 = lambda *s: torch.zeros(max(int(np.prod(s)), 1), dtype=torch.float64, device=dev)
     i32 = lambda k: torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
-    t = dict(x=x, row=up(row, np.int32), event=up(event, np.int32), glast=up(glast, np.int32), mult=up(mult, np.int32),
-             lam=up(lam, np.float64), alpha=up(alpha, np.float64), scale=None if scale is None else up(1.0 / scale, np.float64),
-             beta=up(beta, np.float64), trial=up(beta, np.float64), grad=f64(P, G), f=f64(P), step=f64(P) + 1.0, iters=i32(P),
-             status=i32(P) - 1, loss=f64(P), nsum=f64(P), kkt=f64(P), obj=f64(P), E=f64(P, n), R=f64(P, n), Gr=f64(P, G),
+    t = {k: _upload(a, np.int32, dev) for k, a in dict(row=row, event=event, glast=glast, mult=mult).items()}
+    t.update({k: _upload(a, np.float64, dev) for k, a in dict(lam=lam, alpha=alpha, beta=beta, trial=beta).items()})
+    t.update(x=x, scale=None if scale is None else _upload(1.0 / scale, np.float64, dev), grad=f64(P, G), f=f64(P), step=f64(P) + 1.0,
+             iters=i32(P), status=i32(P) - 1, loss=f64(P), nsum=f64(P), kkt=f64(P), obj=f64(P), E=f64(P, n), R=f64(P, n), Gr=f64(P, G),
              counter=i32(1) + P)
     p = _S()["CoxnetP"](ptr(x), N, x.stride(0), G, n, ptr(t["row"]), ptr(t["event"]), ptr(t["glast"]), P, ptr(t["mult"]), ptr(t["lam"]),
                         ptr(t["alpha"]), ptr(t["scale"]), ptr(t["beta"]), ptr(t["trial"]), ptr(t["grad"]), ptr(t["f"]), ptr(t["step"]),

@@ -28,7 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 from scipy import stats
 
-from .bootstrap import _to_numpy, dense_ranks
+from .risk_sets import risk_matrix, risk_set_table, score_chi2 as chi2_of, to_numpy
 
 
 def logrank_coefficients(time, event):
@@ -37,26 +37,13 @@ def logrank_coefficients(time, event):
     n_u >= 2, else 0) at the LAST position of time u's tie group, 0 elsewhere;  a = e - sum_{u <= t} d_u / n_u (the per-patient term of
     observed - expected: U = sum over the high group of a);  pflag = [e] | 2 [h or c is not 0] (LogrankScanP).  logrank_test skips a
     time with n_u < 2; its O - E term is identically 0 there (the one patient at risk is the one event: a's two parts cancel), and it
-    has no variance term (c = 0)."""
-    t, e = np.asarray(time, dtype=np.float64).reshape(-1), np.asarray(event).reshape(-1) != 0
-    order = np.argsort(-t, kind="stable")
-    t, e = t[order], e[order].astype(np.float64)
-    n = len(t)
-    if n == 0:
-        z = np.zeros(0)
-        return order, z, z.copy(), z.copy(), np.zeros(0, np.int32)
-    first = np.concatenate([[True], t[1:] != t[:-1]])
-    gid = np.cumsum(first) - 1
-    last = np.concatenate([np.nonzero(first)[0][1:] - 1, [n - 1]])
-    n_u = (last + 1).astype(np.float64)
-    d_u = np.bincount(gid, weights=e, minlength=len(last))
-    hu = d_u / n_u
+    has no variance term (c = 0).  (n_u, d_u, h and the sum inside a: risk_sets.risk_set_table.)"""
+    order, e, _, last, n_u, d_u, h_u, b = risk_set_table(time, event)
     cu = np.where((d_u > 0) & (n_u >= 2), d_u * (n_u - d_u) / (n_u * n_u * np.maximum(n_u - 1.0, 1.0)), 0.0)
-    h, c = np.zeros(n), np.zeros(n)
-    h[last], c[last] = hu, cu
-    a = e - np.cumsum(hu[::-1])[::-1][gid]
+    h, c = np.zeros(len(e)), np.zeros(len(e))
+    h[last], c[last] = h_u, cu
     pflag = (e != 0).astype(np.int32) | (((h != 0) | (c != 0)).astype(np.int32) << 1)
-    return order, a, h, c, pflag
+    return order, e - b, h, c, pflag
 
 
 def prefix_statistic(high, a, c):
@@ -118,12 +105,6 @@ def permutation_p(obs, perm):
     perm = np.asarray(perm, dtype=np.float64)
     obs = np.asarray(obs, dtype=np.float64)
     return (1.0 + np.count_nonzero(perm >= obs[..., None], axis=-1)) / (perm.shape[-1] + 1.0)
-
-
-def chi2_of(U, V):
-    U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.where(V > 0, U * U / np.where(V > 0, V, 1.0), 0.0)
 
 
 def first_argmax(x):
@@ -243,18 +224,14 @@ def stratify(risk, time, event, R=10000, seed=0, min_prop=0.1, permutations=None
     mms_logrank_scan for the M observed rank vectors (with the cut tables) and one for the M R replicates."""
     import torch
     from . import ops
-    risk = _to_numpy(risk, "risk")
-    risk = risk.reshape(1, -1) if risk.ndim == 1 else risk
-    t, e = _to_numpy(time, "time").reshape(-1), _to_numpy(event, "event").reshape(-1)
-    if risk.ndim != 2 or risk.shape[1] < 1 or len(t) != risk.shape[1] or len(e) != risk.shape[1]:
-        raise ValueError("risk must be [n] or [M, n] with n >= 1 and time / event [n]")
+    risk, t, e = risk_matrix(risk, time, event)
     if not 0.0 <= float(min_prop) <= 0.5:
         raise ValueError("min_prop must lie in [0, 0.5]")
     M, n = risk.shape
     if permutations is None:
         perm = draw_permutations(n, R, seed)
     else:
-        perm = np.asarray(_to_numpy(permutations, "permutations"))
+        perm = np.asarray(to_numpy(permutations, "permutations"))
         if perm.ndim != 2 or perm.shape[1] != n or perm.dtype.kind not in "iu" or not (np.sort(perm, 1) == np.arange(n)).all():
             raise ValueError("permutations must be integer [R, n], every row a permutation of 0..n-1")
         perm = perm.astype(np.int64)
