@@ -1167,6 +1167,34 @@ int mms_conv3_bwd_weight_group(const Conv3BwdWP* p, int ng, const MmsDnOpts* opt
 /* Conv3BwdWP.msplit the whole-encoder drivers use for a launch of `members` (model, layer) members of M rows each (0: bad arguments) --
    so that a caller timing the launch alone (bench.py's roofline leg) shapes it exactly as the step does */
 int mms_conv3_bwd_weight_msplit(int M, int members, const MmsDnOpts* opts);
+/* The kernel form a *_group entry point takes for a launch of ng members shaped like `p0` under `opts` -- host only: no launch, no device
+   access; of the block's pointers only their being NULL and their alignment are read, as the launchers do.  op: MMS_OP_*, p0: member 0's
+   parameter block of that op.  Decided by the launchers' own predicates (csrc/dn_ops.h), so a test that must reach one form can assert
+   that it does.  -> MMS_FORM_* of the op (> 0), or MMS_ERR_ARG for an unknown op, a NULL block, ng outside 1..MMS_MAX_GROUP or a block
+   the entry point refuses for its own fields.  Each launcher switches on the same function, so the answer is what runs for members that
+   pass the launcher's comparison with member 0; one answer depends on the other members: MMS_FORM_C1_FUSED_WHOLEM needs every member to
+   qualify (else the launch takes MMS_FORM_C1_FUSED_TILE). */
+#define MMS_OP_CONV1_FWD 1            /* Conv1FwdP     */
+#define MMS_OP_CONV1_BWD_DATA 2       /* Conv1BwdP     */
+#define MMS_OP_CONV3_FWD 3            /* Conv3FwdP     */
+#define MMS_OP_CONV3_BWD_DATA 4       /* Conv3BwdDataP */
+#define MMS_OP_CONV3_BWD_WEIGHT 5     /* Conv3BwdWP    */
+#define MMS_FORM_C1_WHOLEK8 1         /* conv1 forward: 16x16 whole-K kernel, K <= 512 */
+#define MMS_FORM_C1_WHOLEK16 2        /*                16x16 whole-K kernel, K > 512 */
+#define MMS_FORM_C1_TILE32 3          /* conv1 forward / backward-data: 32x32 tile GEMM */
+#define MMS_FORM_C1_TILE64 4          /*                                64x64 tile GEMM */
+#define MMS_FORM_C1_KSPLIT 5          /* conv1 forward: 32x32 tiles, K split over workgroups, last-arriver fix-up */
+#define MMS_FORM_C1_FUSED_WHOLEM 6    /* conv1 backward-data with norm1's backward: whole-M kernel (csrc/dn_c1s.hip) */
+#define MMS_FORM_C1_FUSED_TILE 7      /*                                            tile-GEMM epilogue */
+#define MMS_FORM_C3_SMALL1 1          /* conv2 forward / backward-data: small-grid kernel, one 16-column tile per wave (JN = 1) */
+#define MMS_FORM_C3_SMALL2 2          /*                                small-grid kernel, two (JN = 2) */
+#define MMS_FORM_C3_MT32 3            /*                                multi-tap kernel, 32-row tiles */
+#define MMS_FORM_C3_MT64 4            /* conv2 forward: multi-tap kernel, 64-row tiles */
+#define MMS_FORM_C3_TAPSPLIT 5        /* conv2 forward / backward-data: taps split over workgroups + reduce launch */
+#define MMS_FORM_C3_TAPGEMM 6         /*                                one-tap-per-step tile GEMM */
+#define MMS_FORM_C3W_TAPGEMM 1        /* conv2 weight gradient: one-tap tile GEMM */
+#define MMS_FORM_C3W_MT 2             /*                        multi-tap kernel */
+int mms_dn_launch_form(int op, const void* p0, int ng, const MmsDnOpts* opts);
 int mms_conv1_bwd_data_group(const Conv1BwdP* p, int ng, const MmsDnOpts* opts, hipStream_t s);
 int mms_conv1_bwd_weight_group(const Conv1BwdP* p, int ng, hipStream_t s);
 /* The table-fed form of the two weight-gradient launches above (MmsWgradModel): which = 1 conv2, 2 conv1, 3 both.  MMS_ERR_ARG and no

@@ -77,6 +77,12 @@ def protos():
     return _PROTOS
 
 
+def defines(prefix):
+    """-> {name without the prefix: value} of the header's integer `#define <prefix>NAME value` lines"""
+    src = _strip_comments(open(HEADER).read())
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+%s(\w+)\s+\(?(-?\d+)\)?\s*$" % re.escape(prefix), src, flags=re.M)}
+
+
 def load_library():
     """Load the HIP library; raises (never falls back) when it is missing."""
     global _LIB

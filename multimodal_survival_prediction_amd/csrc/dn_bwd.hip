@@ -373,20 +373,32 @@ static int launch_conv3_bwd_data_mt(const Conv3BwdDataP* pp, int ng, const MmsDn
     return mms_check_launch();
 }
 
+// The kernel form of a conv2 backward-data launch of ng members shaped like p (MMS_FORM_C3_*; mms_dn_launch_form answers with it), or
+// MMS_ERR_ARG for a block the entry point refuses for its own fields.  The launcher below switches on it: what it says is what runs.
+static int form_conv3_bwd_data(const Conv3BwdDataP& p, int ng, const MmsDnOpts& o) {
+    if (p.M <= 0 || p.lddz % 4 != 0) return MMS_ERR_ARG;
+    const int jn = p.partial ? 0 : mms_conv3_small_jn(p.M, ng, p.g, o);
+    const int small = jn == 2 ? MMS_FORM_C3_SMALL2 : MMS_FORM_C3_SMALL1;
+    if (p.wfrag) return jn ? small : MMS_ERR_ARG;                 // fragment-ordered weights: the small-grid kernel only
+    if (p.partial) return (p.nsplit < 1 || p.nsplit > 27 || (p.nsplit - 1) * ((27 + p.nsplit - 1) / p.nsplit) >= 27) ? MMS_ERR_ARG : MMS_FORM_C3_TAPSPLIT;
+    if (conv3_bwd_data_mt_ok(p.M, ng, p.g, o)) return ((uintptr_t)p.dz & 15) != 0 ? MMS_ERR_ARG : MMS_FORM_C3_MT32;      // dz rows are read with 16-byte loads
+    return jn ? small : MMS_FORM_C3_TAPGEMM;                      // small grids: 16-row tiles, all taps, no reduce launch
+}
 extern "C" int mms_conv3_bwd_data_group(const Conv3BwdDataP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const MmsDnOpts o = mms_opts(opts);
     const Conv3BwdDataP& p = *pp;
-    if (p.M <= 0 || p.lddz % 4 != 0) return MMS_ERR_ARG;
+    const int form = form_conv3_bwd_data(p, ng, o);
+    if (form < 0) return form;
     for (int g = 1; g < ng; ++g) {
         const Conv3BwdDataP& q = pp[g];
         if (q.M != p.M || q.lddz % 4 != 0 || q.g.D != p.g.D || q.g.H != p.g.H || q.g.W != p.g.W ||
-            (q.partial == nullptr) != (p.partial == nullptr) || q.nsplit != p.nsplit) return MMS_ERR_ARG;
+            (q.partial == nullptr) != (p.partial == nullptr) || q.nsplit != p.nsplit || q.wfrag != p.wfrag) return MMS_ERR_ARG;
     }
-    for (int g = 1; g < ng; ++g) if (pp[g].wfrag != p.wfrag) return MMS_ERR_ARG;
-    if (p.wfrag) return (!p.partial && mms_conv3_small_jn(p.M, ng, p.g, o)) ? mms_c3s_bwd_data(pp, ng, o, s) : MMS_ERR_ARG;   // fragment-ordered weights: the small-grid kernel only
-    if (p.partial) {
-        if (p.nsplit < 1 || p.nsplit > 27 || (p.nsplit - 1) * ((27 + p.nsplit - 1) / p.nsplit) >= 27) return MMS_ERR_ARG;
+    switch (form) {
+    case MMS_FORM_C3_SMALL1:
+    case MMS_FORM_C3_SMALL2: return mms_c3s_bwd_data(pp, ng, o, s);
+    case MMS_FORM_C3_TAPSPLIT: {
         int rc = launch_tile_gemm<Conv3BwdDataOp<true>>(pp, ng, dim3((p.M + 31) / 32, 1, p.nsplit), s);
         if (rc != MMS_OK) return rc;
         Grp<Conv3BwdDataP> a;
@@ -395,13 +407,13 @@ extern "C" int mms_conv3_bwd_data_group(const Conv3BwdDataP* pp, int ng, const M
         else MMS_LAUNCH(conv3_bwd_data_reduce_kernel, dim3((p.M + 3) / 4, 1, ng), dim3(256), 0, s, a);
         return mms_check_launch();
     }
-    if (conv3_bwd_data_mt_ok(p.M, ng, p.g, o)) {
-        for (int g = 0; g < ng; ++g) if (pp[g].lddz % 4 != 0 || ((uintptr_t)pp[g].dz & 15) != 0) return MMS_ERR_ARG;     // dz rows are read with 16-byte loads
+    case MMS_FORM_C3_MT32:
+        for (int g = 1; g < ng; ++g) if (((uintptr_t)pp[g].dz & 15) != 0) return MMS_ERR_ARG;
         // pinned schedule while the launch is at most one round of three workgroups per CU
         return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_bwd_data_mt<true>(pp, ng, o, s) : launch_conv3_bwd_data_mt<false>(pp, ng, o, s);
+    case MMS_FORM_C3_TAPGEMM: return launch_tile_gemm<Conv3BwdDataOp<false>>(pp, ng, dim3((p.M + 31) / 32, 1, 1), s);
+    default: return MMS_ERR_ARG;
     }
-    if (mms_conv3_small_jn(p.M, ng, p.g, o)) return mms_c3s_bwd_data(pp, ng, o, s);      // small grids: 16-row tiles, all taps, no reduce launch
-    return launch_tile_gemm<Conv3BwdDataOp<false>>(pp, ng, dim3((p.M + 31) / 32, 1, 1), s);
 }
 MMS_SINGLE_O(mms_conv3_bwd_data, Conv3BwdDataP)
 
@@ -735,19 +747,27 @@ static inline bool conv3w_mt_ok(int rows_per_chunk, int msplit, int ng, const Mm
     return rows_per_chunk >= 512 && mms_conv3w_mt_fills((long)msplit * ng * 9);
 }
 
+// The kernel form of a conv2 weight-gradient launch of ng members shaped like p (MMS_FORM_C3W_*; mms_dn_launch_form answers with it), or
+// MMS_ERR_ARG for a block the entry point refuses for its own fields.  The launcher below switches on it: what it says is what runs.
+static int form_conv3_bwd_weight(const Conv3BwdWP& p, int ng, const MmsDnOpts& o) {
+    if (p.M <= 0 || p.msplit <= 0 || p.lddz % 4 != 0 || p.dw_layout < 0 || p.dw_layout > 2) return MMS_ERR_ARG;
+    const int chunk = ((p.M + p.msplit - 1) / p.msplit + 31) & ~31;
+    if (chunk > 1024) return MMS_ERR_ARG;    // row chunk must fit the LDS mask table
+    return conv3w_mt_ok(chunk, p.msplit, ng, o) ? MMS_FORM_C3W_MT : MMS_FORM_C3W_TAPGEMM;
+}
 extern "C" int mms_conv3_bwd_weight_group(const Conv3BwdWP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const MmsDnOpts o = mms_opts(opts);
     const Conv3BwdWP& p = *pp;
-    if (p.M <= 0 || p.msplit <= 0 || p.lddz % 4 != 0 || p.dw_layout < 0 || p.dw_layout > 2) return MMS_ERR_ARG;
-    if ((((p.M + p.msplit - 1) / p.msplit + 31) & ~31) > 1024) return MMS_ERR_ARG;    // row chunk must fit the LDS mask table
+    const int form = form_conv3_bwd_weight(p, ng, o);
+    if (form < 0) return form;
     for (int g = 0; g < ng; ++g) if (!mms_bn_aligned16(pp[g].bn)) return MMS_ERR_ARG;   // BatchNorm blocks are read with 16-byte vector loads
     for (int g = 1; g < ng; ++g) {
         const Conv3BwdWP& q = pp[g];
         if (q.M != p.M || q.msplit != p.msplit || q.lddz % 4 != 0 || q.g.D != p.g.D || q.g.H != p.g.H || q.g.W != p.g.W ||
             q.dw_layout != p.dw_layout) return MMS_ERR_ARG;
     }
-    if (conv3w_mt_ok(((p.M + p.msplit - 1) / p.msplit + 31) & ~31, p.msplit, ng, o)) {
+    if (form == MMS_FORM_C3W_MT) {
         constexpr int smem = (2 * C3W_STAGE + 2 * 1024) * (int)sizeof(float);        // 53.3 KB: 3 workgroups per CU
         Grp<Conv3BwdWP> a;
         if (!grp_fill(a, pp, ng, 9 * p.msplit)) return MMS_ERR_ARG;
@@ -937,36 +957,63 @@ static bool conv1_bwd_same(const Conv1BwdP* pp, int ng, bool same_k = true) {
     }
     return true;
 }
+// The kernel form of a conv1 backward-data launch of ng members shaped like p (MMS_FORM_C1_*; mms_dn_launch_form answers with it), or
+// MMS_ERR_ARG for a block the entry point refuses for its own fields.  The launcher below switches on it (the whole-M fused kernel needs EVERY
+// member to qualify, else the launch takes the tile-GEMM epilogue: the one answer that depends on the other members).
+static int form_conv1_bwd_data(const Conv1BwdP& p, int ng, const MmsDnOpts& o) {
+    if (p.M <= 0 || p.K % 32 != 0 || p.N % 32 != 0 || p.ldx % 4 != 0 || p.lddy % 4 != 0) return MMS_ERR_ARG;
+    if (p.has_bn_out && p.N != 128) return MMS_ERR_ARG;
+    if (p.fuse_dx) {      // norm1 backward fused into the epilogue: one workgroup must own every row of its 32 channels
+        if (p.pool || p.M > 128 || p.fuse_lddx % 4 != 0) return MMS_ERR_ARG;
+        return mms_conv1_small_bwd_ok(p, o) ? MMS_FORM_C1_FUSED_WHOLEM : MMS_FORM_C1_FUSED_TILE;
+    }
+    // tile shape from the whole group's work (MmsDnOpts.big_ng = -1: from one model's -- tests that need ng-independent arithmetic)
+    return mms_conv1_bwd_data_big(p, ng, o) ? MMS_FORM_C1_TILE64 : MMS_FORM_C1_TILE32;
+}
 extern "C" int mms_conv1_bwd_data_group(const Conv1BwdP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const MmsDnOpts o = mms_opts(opts);
     const Conv1BwdP& p = *pp;
-    if (p.M <= 0 || p.K % 32 != 0 || p.N % 32 != 0 || p.ldx % 4 != 0 || p.lddy % 4 != 0) return MMS_ERR_ARG;
-    if (p.has_bn_out && p.N != 128) return MMS_ERR_ARG;
+    int form = form_conv1_bwd_data(p, ng, o);
+    if (form < 0) return form;
     if (!conv1_bwd_same(pp, ng)) return MMS_ERR_ARG;
     for (int g = 0; g < ng; ++g) if ((pp[g].fuse_dx != nullptr) != (p.fuse_dx != nullptr)) return MMS_ERR_ARG;
-    if (p.fuse_dx) {      // norm1 backward fused into the epilogue: one workgroup must own every row of its 32 channels
-        if (p.pool || p.M > 128 || p.fuse_lddx % 4 != 0) return MMS_ERR_ARG;
-        bool small = true;
-        for (int g = 0; g < ng; ++g) small = small && mms_conv1_small_bwd_ok(pp[g], o);
-        if (small) return mms_c1s_bwd(pp, ng, s);
+    for (int g = 1; g < ng && form == MMS_FORM_C1_FUSED_WHOLEM; ++g) if (!mms_conv1_small_bwd_ok(pp[g], o)) form = MMS_FORM_C1_FUSED_TILE;
+    switch (form) {
+    case MMS_FORM_C1_FUSED_WHOLEM: return mms_c1s_bwd(pp, ng, s);
+    case MMS_FORM_C1_FUSED_TILE: {
         dim3 g(1, (p.K + 31) / 32, 1);
         return p.M <= 32 ? launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, false>>(pp, ng, g, s)
                          : launch_tile_gemm<Conv1BwdDataOp<4, 1, 1, false>>(pp, ng, g, s);
     }
-    // tile shape from the whole group's work (MmsDnOpts.big_ng = -1: from one model's -- tests that need ng-independent arithmetic)
-    const bool big = (long)p.M * p.K * (o.big_ng < 0 ? 1 : ng) >= 256L * 64 * 64;
-    if (big) {
+    case MMS_FORM_C1_TILE64: {
         dim3 g((p.M + 63) / 64, (p.K + 63) / 64, 1);
         return p.pool ? launch_tile_gemm<Conv1BwdDataOp<2, 2, 1, true>>(pp, ng, g, s)
                       : launch_tile_gemm<Conv1BwdDataOp<2, 2, 1, false>>(pp, ng, g, s);
     }
-    dim3 g((p.M + 31) / 32, (p.K + 31) / 32, 1);
-    if (!p.pool && p.N <= 128) return launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, false, true>>(pp, ng, g, s);     // one K tile: single LDS buffer
-    return p.pool ? launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, true>>(pp, ng, g, s)
-                  : launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, false>>(pp, ng, g, s);
+    default: {
+        dim3 g((p.M + 31) / 32, (p.K + 31) / 32, 1);
+        if (!p.pool && p.N <= 128) return launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, false, true>>(pp, ng, g, s);     // one K tile: single LDS buffer
+        return p.pool ? launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, true>>(pp, ng, g, s)
+                      : launch_tile_gemm<Conv1BwdDataOp<1, 1, 4, false>>(pp, ng, g, s);
+    }
+    }
 }
 MMS_SINGLE_O(mms_conv1_bwd_data, Conv1BwdP)
+
+// The form a *_group launcher takes (include/mmsurv.h): the launchers' own form functions, which they switch on.  Host only.
+extern "C" int mms_dn_launch_form(int op, const void* p0, int ng, const MmsDnOpts* opts) {
+    if (!p0 || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
+    const MmsDnOpts o = mms_opts(opts);
+    switch (op) {
+    case MMS_OP_CONV1_FWD: return mms_form_conv1_fwd(*(const Conv1FwdP*)p0, ng, o);
+    case MMS_OP_CONV1_BWD_DATA: return form_conv1_bwd_data(*(const Conv1BwdP*)p0, ng, o);
+    case MMS_OP_CONV3_FWD: return mms_form_conv3_fwd(*(const Conv3FwdP*)p0, ng, o);
+    case MMS_OP_CONV3_BWD_DATA: return form_conv3_bwd_data(*(const Conv3BwdDataP*)p0, ng, o);
+    case MMS_OP_CONV3_BWD_WEIGHT: return form_conv3_bwd_weight(*(const Conv3BwdWP*)p0, ng, o);
+    default: return MMS_ERR_ARG;
+    }
+}
 
 // ---- weight: dW[n][k] += sum_m dy[m][n] * a[m][k] ; rows n, cols k, reduce over m (split over grid.z)
 template <bool POOL>

@@ -192,7 +192,7 @@ int mms_c1s_fwd(const Conv1FwdP* pp, int ng, hipStream_t s) {
     Grp<Conv1FwdP> a;
     if (!grp_fill(a, pp, ng, 1)) return MMS_ERR_ARG;
     const dim3 grid((p.M + 15) / 16, (p.N + 15) / 16, ng);
-    if (p.K <= 512) {
+    if (mms_conv1_small_np(p.K) == 8) {
         const auto kern = conv1s_fwd_kernel<8>;        // 16 x 516 + 3 x 512 floats = 39 KB: below the default dynamic-LDS limit
         MMS_LAUNCH(kern, grid, dim3(256), smem, s, a);
     } else {

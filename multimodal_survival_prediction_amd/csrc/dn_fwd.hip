@@ -181,38 +181,51 @@ extern "C" int mms_pool_act_group(const PoolActP* pp, int ng, hipStream_t s) {
     return mms_check_launch();
 }
 
+// The kernel form of a conv1 forward launch of ng members shaped like p (MMS_FORM_C1_*; mms_dn_launch_form answers with it), or MMS_ERR_ARG for
+// a block the entry point refuses for its own fields.  The launcher below switches on it: what it says is what runs.
+int mms_form_conv1_fwd(const Conv1FwdP& p, int ng, const MmsDnOpts& o) {
+    if (p.K % 32 != 0 || p.K > 1024 || p.ldx % 4 != 0 || p.M <= 0) return MMS_ERR_ARG;
+    if (p.pool && ((p.in.D | p.in.H | p.in.W) & 1)) return MMS_ERR_ARG;
+    if (mms_conv1_small_ok(p, ng, o)) {      // few rows: 16 x 16 tiles over the whole K range from LDS-resident panels (dn_c1s.hip)
+        if (((uintptr_t)p.x | (uintptr_t)p.w) & 15) return MMS_ERR_ARG;
+        return mms_conv1_small_np(p.K) == 8 ? MMS_FORM_C1_WHOLEK8 : MMS_FORM_C1_WHOLEK16;
+    }
+    // big M: 64x64 tiles, no in-workgroup K split; small M: 32x32 tiles with the 4 waves splitting K
+    // tile shape from the whole group's work (MmsDnOpts.big_ng = -1: from one model's -- tests that need ng-independent arithmetic)
+    if (mms_conv1_fwd_big(p, ng, o)) return MMS_FORM_C1_TILE64;
+    if (!mms_conv1_fwd_ksplit(p)) return MMS_FORM_C1_TILE32;
+    if (p.ksplit > 8 || (long)(p.ksplit - 1) * ((((p.K + 127) / 128 + p.ksplit - 1) / p.ksplit) * 128) >= p.K) return MMS_ERR_ARG;   // every slice owns >= 1 channel
+    return MMS_FORM_C1_KSPLIT;
+}
 extern "C" int mms_conv1_fwd_group(const Conv1FwdP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const MmsDnOpts o = mms_opts(opts);
     const Conv1FwdP& p = *pp;
-    if (p.K % 32 != 0 || p.K > 1024 || p.ldx % 4 != 0 || p.M <= 0) return MMS_ERR_ARG;
-    if (p.pool && ((p.in.D | p.in.H | p.in.W) & 1)) return MMS_ERR_ARG;
+    const int form = mms_form_conv1_fwd(p, ng, o);
+    if (form < 0) return form;
     for (int g = 1; g < ng; ++g) {
         const Conv1FwdP& q = pp[g];
         if (q.M != p.M || q.N != p.N || q.K != p.K || q.ldx % 4 != 0 || q.pool != p.pool || q.in.D != p.in.D || q.in.H != p.in.H ||
             q.in.W != p.in.W) return MMS_ERR_ARG;
     }
-    if (mms_conv1_small_ok(p, ng, o)) {      // few rows: 16 x 16 tiles over the whole K range from LDS-resident panels (dn_c1s.hip)
-        for (int g = 0; g < ng; ++g) if (((uintptr_t)pp[g].x | (uintptr_t)pp[g].w) & 15) return MMS_ERR_ARG;
+    dim3 g((p.M + 31) / 32, (p.N + 31) / 32, 1);
+    switch (form) {
+    case MMS_FORM_C1_WHOLEK8:
+    case MMS_FORM_C1_WHOLEK16:
+        for (int i = 1; i < ng; ++i) if (((uintptr_t)pp[i].x | (uintptr_t)pp[i].w) & 15) return MMS_ERR_ARG;
         return mms_c1s_fwd(pp, ng, s);
-    }
-    // big M: 64x64 tiles, no in-workgroup K split; small M: 32x32 tiles with the 4 waves splitting K
-    // tile shape from the whole group's work (MmsDnOpts.big_ng = -1: from one model's -- tests that need ng-independent arithmetic)
-    const bool big = (long)p.M * p.N * (o.big_ng < 0 ? 1 : ng) >= 256L * 64 * 64;
-    if (big) {
-        dim3 g((p.M + 63) / 64, (p.N + 63) / 64, 1);
+    case MMS_FORM_C1_TILE64:
+        g = dim3((p.M + 63) / 64, (p.N + 63) / 64, 1);
         return p.pool ? launch_tile_gemm<Conv1FwdOp<2, 2, 1, true>>(pp, ng, g, s)
                       : launch_tile_gemm<Conv1FwdOp<2, 2, 1, false>>(pp, ng, g, s);
-    }
-    dim3 g((p.M + 31) / 32, (p.N + 31) / 32, 1);
-    if (p.partial && p.counters && p.ksplit > 1 && !p.pool) {
-        if (p.ksplit > 8 || (long)(p.ksplit - 1) * ((((p.K + 127) / 128 + p.ksplit - 1) / p.ksplit) * 128) >= p.K) return MMS_ERR_ARG;   // every slice owns >= 1 channel
+    case MMS_FORM_C1_KSPLIT:
         for (int i = 1; i < ng; ++i) if (pp[i].ksplit != p.ksplit || !pp[i].partial || !pp[i].counters) return MMS_ERR_ARG;
         g.z = p.ksplit;
         return launch_tile_gemm<Conv1FwdOp<1, 1, 4, false, true>>(pp, ng, g, s);
+    default:
+        return p.pool ? launch_tile_gemm<Conv1FwdOp<1, 1, 4, true>>(pp, ng, g, s)
+                      : launch_tile_gemm<Conv1FwdOp<1, 1, 4, false>>(pp, ng, g, s);
     }
-    return p.pool ? launch_tile_gemm<Conv1FwdOp<1, 1, 4, true>>(pp, ng, g, s)
-                  : launch_tile_gemm<Conv1FwdOp<1, 1, 4, false>>(pp, ng, g, s);
 }
 MMS_SINGLE_O(mms_conv1_fwd, Conv1FwdP)
 
@@ -568,28 +581,39 @@ static int launch_conv3_fwd_mt(const Conv3FwdP* pp, int ng, const MmsDnOpts& o, 
     return mms_check_launch();
 }
 
+// The kernel form of a conv2 forward launch of ng members shaped like p (MMS_FORM_C3_*; mms_dn_launch_form answers with it), or MMS_ERR_ARG for
+// a block the entry point refuses for its own fields.  The launcher below switches on it: what it says is what runs.
+int mms_form_conv3_fwd(const Conv3FwdP& p, int ng, const MmsDnOpts& o) {
+    if (p.M <= 0 || p.ldo % 4 != 0) return MMS_ERR_ARG;
+    const int jn = p.partial ? 0 : mms_conv3_small_jn(p.M, ng, p.g, o);
+    const int small = jn == 2 ? MMS_FORM_C3_SMALL2 : MMS_FORM_C3_SMALL1;
+    if (p.wfrag) return jn ? small : MMS_ERR_ARG;                 // fragment-ordered weights: the small-grid kernel only
+    if (const int tm = p.partial ? 0 : conv3_mt_tile(p.M, ng, p.g, o)) return tm == 64 ? MMS_FORM_C3_MT64 : MMS_FORM_C3_MT32;
+    if (jn) return small;                                          // small grids: 16-row tiles, all taps, no reduce launch
+    if (!p.partial) return MMS_FORM_C3_TAPGEMM;
+    if (p.nsplit < 1 || p.nsplit > 27) return MMS_ERR_ARG;
+    if ((p.nsplit - 1) * ((27 + p.nsplit - 1) / p.nsplit) >= 27) return MMS_ERR_ARG;       // every workgroup must own at least one tap
+    return MMS_FORM_C3_TAPSPLIT;
+}
 extern "C" int mms_conv3_fwd_group(const Conv3FwdP* pp, int ng, const MmsDnOpts* opts, hipStream_t s) {
     if (!pp || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     const MmsDnOpts o = mms_opts(opts);
     const Conv3FwdP& p = *pp;
-    if (p.M <= 0 || p.ldo % 4 != 0) return MMS_ERR_ARG;
+    const int form = mms_form_conv3_fwd(p, ng, o);
+    if (form < 0) return form;
     for (int g = 1; g < ng; ++g) {
         const Conv3FwdP& q = pp[g];
         if (q.M != p.M || q.ldo % 4 != 0 || q.g.D != p.g.D || q.g.H != p.g.H || q.g.W != p.g.W || (q.partial == nullptr) != (p.partial == nullptr) ||
             q.nsplit != p.nsplit) return MMS_ERR_ARG;
     }
     for (int g = 0; g < ng; ++g) if (!mms_bn_aligned16(pp[g].bn) || pp[g].wfrag != p.wfrag) return MMS_ERR_ARG;   // BatchNorm blocks are read with 16-byte vector loads
-    if (p.wfrag) return (!p.partial && mms_conv3_small_jn(p.M, ng, p.g, o)) ? mms_c3s_fwd(pp, ng, o, s) : MMS_ERR_ARG;       // fragment-ordered weights: the small-grid kernel only
-    if (const int tm = p.partial ? 0 : conv3_mt_tile(p.M, ng, p.g, o)) {
-        if (tm == 64) return launch_conv3_fwd_mt<64, false>(pp, ng, o, s);
-        // pinned schedule while the launch is at most one round of three 32-row workgroups per CU
+    switch (form) {
+    case MMS_FORM_C3_SMALL1:
+    case MMS_FORM_C3_SMALL2: return mms_c3s_fwd(pp, ng, o, s);
+    case MMS_FORM_C3_MT64: return launch_conv3_fwd_mt<64, false>(pp, ng, o, s);
+    case MMS_FORM_C3_MT32:      // pinned schedule while the launch is at most one round of three 32-row workgroups per CU
         return (long)((p.M + 31) / 32) * ng <= 768 ? launch_conv3_fwd_mt<32, true>(pp, ng, o, s) : launch_conv3_fwd_mt<32, false>(pp, ng, o, s);
-    }
-    if (!p.partial && mms_conv3_small_jn(p.M, ng, p.g, o)) return mms_c3s_fwd(pp, ng, o, s);      // small grids: 16-row tiles, all taps, no reduce launch
-    if (p.partial) {
-        if (p.nsplit < 1 || p.nsplit > 27) return MMS_ERR_ARG;
-        const int tpw = (27 + p.nsplit - 1) / p.nsplit;
-        if ((p.nsplit - 1) * tpw >= 27) return MMS_ERR_ARG;       // every workgroup must own at least one tap
+    case MMS_FORM_C3_TAPSPLIT: {
         int rc = launch_tile_gemm<Conv3FwdOp<true>>(pp, ng, dim3((p.M + 31) / 32, 1, p.nsplit), s);
         if (rc != MMS_OK) return rc;
         Grp<Conv3FwdP> a;
@@ -597,7 +621,9 @@ extern "C" int mms_conv3_fwd_group(const Conv3FwdP* pp, int ng, const MmsDnOpts*
         MMS_LAUNCH(conv3_fwd_reduce_kernel, dim3((p.M + 7) / 8, 1, ng), dim3(256), 0, s, a);
         return mms_check_launch();
     }
-    return launch_tile_gemm<Conv3FwdOp<false>>(pp, ng, dim3((p.M + 31) / 32, 1, 1), s);
+    case MMS_FORM_C3_TAPGEMM: return launch_tile_gemm<Conv3FwdOp<false>>(pp, ng, dim3((p.M + 31) / 32, 1, 1), s);
+    default: return MMS_ERR_ARG;
+    }
 }
 MMS_SINGLE_O(mms_conv3_fwd, Conv3FwdP)
 

@@ -58,6 +58,21 @@ static inline bool mms_conv1_small_ok(const Conv1FwdP& p, int ng, const MmsDnOpt
     const long maxwg = o.c1s_max_wgs > 0 ? o.c1s_max_wgs : 640;
     return (long)((p.M + 15) / 16) * ((p.N + 15) / 16) * ng <= maxwg;
 }
+// its operand pieces per thread and panel (the kernel's template argument, dn_c1s.hip)
+static inline int mms_conv1_small_np(int K) { return K <= 512 ? 8 : 16; }
+// Tile shape of the tile-GEMM 1x1x1 kernels: 64x64 tiles (no in-workgroup K split) when the WHOLE GROUP's output has >= 256 of them, else
+// 32x32 tiles with the four waves splitting K (MmsDnOpts.big_ng = -1: from one model's work -- tests that need ng-independent arithmetic).
+static inline bool mms_conv1_fwd_big(const Conv1FwdP& p, int ng, const MmsDnOpts& o) {
+    return (long)p.M * p.N * (o.big_ng < 0 ? 1 : ng) >= 256L * 64 * 64;
+}
+static inline bool mms_conv1_bwd_data_big(const Conv1BwdP& p, int ng, const MmsDnOpts& o) {
+    return (long)p.M * p.K * (o.big_ng < 0 ? 1 : ng) >= 256L * 64 * 64;
+}
+// the forward's K split over workgroups (32x32 tiles only): what the caller's block asks for
+static inline bool mms_conv1_fwd_ksplit(const Conv1FwdP& p) { return p.partial && p.counters && p.ksplit > 1 && !p.pool; }
+// Kernel forms of the two forward launchers (include/mmsurv.h mms_dn_launch_form, dn_bwd.hip): the functions the launchers of dn_fwd.hip switch on
+int mms_form_conv1_fwd(const Conv1FwdP& p, int ng, const MmsDnOpts& o);
+int mms_form_conv3_fwd(const Conv3FwdP& p, int ng, const MmsDnOpts& o);
 int mms_c1s_fwd(const Conv1FwdP* pp, int ng, hipStream_t s);
 // whole-M backward-data + fused norm1 backward (dn_c1s.hip): MmsDnOpts.conv1_small_bwd = -1 keeps the tile-GEMM forms
 bool mms_conv1_small_bwd_ok(const Conv1BwdP& p, const MmsDnOpts& o);

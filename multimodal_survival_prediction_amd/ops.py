@@ -61,6 +61,21 @@ def call(name, p, opts=None):
         _lib.check(getattr(lib, name + "_group")(ctypes.byref(p), 1, ctypes.byref(opts), stream()), name + "_group")
 
 
+# mms_dn_launch_form: the header's MMS_OP_* by lower-case name ("conv1_fwd", ...) and, per op, its MMS_FORM_<family>_* values by lower-case
+# name ("wholek8", "tile32", "small2", "mt", ...) -- read from include/mmsurv.h like every layout, not typed again
+LAUNCH_OPS = {k.lower(): v for k, v in _lib.defines("MMS_OP_").items()}
+_FORM_FAMILY = {"conv1_fwd": "C1_", "conv1_bwd_data": "C1_", "conv3_fwd": "C3_", "conv3_bwd_data": "C3_", "conv3_bwd_weight": "C3W_"}
+LAUNCH_FORMS = {op: {v: k.lower() for k, v in _lib.defines("MMS_FORM_" + fam).items()} for op, fam in _FORM_FAMILY.items()}
+
+
+def launch_form(op, p, ng, opts=None):
+    """The kernel form the op's *_group entry point takes for ng members shaped like the parameter block p (host only, no launch):
+    a name from LAUNCH_FORMS[op]; raises for a block the entry point would refuse."""
+    rc = _lib.load_library().mms_dn_launch_form(LAUNCH_OPS[op], ctypes.byref(p), int(ng), opts_ref(opts))
+    _lib.check(min(rc, 0), "mms_dn_launch_form")
+    return LAUNCH_FORMS[op][rc]
+
+
 def init_coords(B, dims, device):
     D, H, W = dims
     out = torch.empty(B * D * H * W, dtype=torch.int32, device=device)
