@@ -909,6 +909,47 @@ typedef struct AffP {
                                     // global loads instead (direct form: a small value forces it everywhere -- tests, A/B timing)
 } AffP;
 
+/* Batch assembly with ELASTIC deformation (mms_gather_elastic_group): mms_gather_affine_group with, per batch row, a third record that
+ * names a free-form displacement field d, added to the destination voxel BEFORE the affine map.  The field is a pure function of the
+ * record: a coarse lattice of control displacements from the counter hash, interpolated by uniform cubic B-splines; the kernel builds the
+ * lattice in LDS, no field is stored in memory.  Contract, volume extents n = (D, H, W), axis a = 0 / 1 / 2:
+ *   lattice   spacing s_a = 1 << log2_spacing[a] voxels, K_a = ((n_a - 1) >> log2_spacing[a]) + 4 control planes; plane j stands at lattice
+ *             position j - 1, so the planes k .. k + 3 exist for every voxel.  3 K_D K_H K_W <= MMS_ELA_LATTICE_MAX, else MMS_ERR_ARG.
+ *   control   component a at (jz, jy, jx), k = 3 ((jz K_H + jy) K_W + jx) + a:  c = amp_a * u(seed, k),
+ *             u = (float)((int)(h >> 8) - 8388608) * 2^-23 in [-1, 1),  h = hash(k * 0x9E3779B9 + hash(seed ^ 0x85ebca6b))  (hash: the mixer
+ *             above, uint32 arithmetic; the salt keeps the field independent of the noise of a row whose two seeds are equal).  u is exact
+ *             in fp32, c is rounded once.  amp_a is the record's amp[a] CLAMPED by the kernel into [0, max_amp[a]], NaN -> 0.
+ *   field     at destination voxel p = (z, y, x): k_a = p_a >> log2_spacing[a], r_a = (p_a & (s_a - 1)) / s_a (exact),
+ *             d_a = sum_{i,j,m in 0..3} B_i(r_z) B_j(r_y) B_m(r_x) c_a[k_z + i, k_y + j, k_x + m],  B the uniform cubic B-spline basis
+ *             B_0 = (1-r)^3 / 6, B_1 = (3r^3 - 6r^2 + 4) / 6, B_2 = (-3r^3 + 3r^2 + 3r + 1) / 6, B_3 = r^3 / 6: non-negative, sum 1, so
+ *             |d_a| <= amp_a up to rounding.  The order of evaluation is the kernel's (gather_elastic.hip: numerators 6 B exact in fp32,
+ *             z then y then x, one multiplication by fp32(1/216)): |d - exact| <= 16 * 2^-24 * amp_a.  amp bounds the CONTROL POINTS; the
+ *             realised max |d| is typically 0.5 .. 0.7 amp.
+ *   coords    cz = fmaf(m[0], z + d_z, fmaf(m[1], y + d_y, fmaf(m[2], x + d_x, m[3]))), cy, cx likewise; each p_a + d_a is one fp32 add.
+ *             Everything after that -- clamp, zero-padded trilinear sample, intensity map, noise indexed by the DESTINATION voxel, absent
+ *             and dropped rows, the other sources -- is mms_gather_affine_group's, unchanged.
+ * Bit identities: a row whose clamped amplitudes are all 0 yields the bits of mms_gather_affine_group for the same records; the staged
+ * and the direct form yield equal bits (AffP.stage_floats: 0, the library default, is the direct form for rows that deform -- the
+ * faster one by measurement, their source boxes being widened by the amplitude -- and the affine launch's staged form for rows that do
+ * not; a positive value is the staging budget of every row, as in the affine launch); a row's bits do not depend
+ * on ng, the member position or what else shares the launch.  The kernel is memory-safe for any record contents.
+ * No folding: p -> p + d(p) is injective when amp_a <= 0.4 s_a (Choi & Lee 2000); that check is the caller's, on the host
+ * (augment.check_elastic_records), as the records live on the device.
+ * mms_elastic_field writes d itself, out[b][a][z][y][x], through the device function the gather kernel calls (inspection, tests). */
+#define MMS_ELA_LATTICE_MAX 6144    /* floats of the control lattice in LDS (24 KB beside the 32 KB staging box: two workgroups per CU).  Sized for the
+                                       finest spacing (2) on the small volumes of quick runs and tests: 16 x 16 x 16 takes 5184, 8 x 24 x 32 takes 5985; the
+                                       flagship 64 x 64 x 32 takes 735 at spacing 16.  A third workgroup per CU (16 KB) would buy nothing: the launch has at
+                                       most 64 x B x ng workgroups for 256 CUs and is latency-bound */
+typedef struct ElaRec {
+    float amp[3];                   // control-point amplitude along D / H / W, voxels
+    unsigned seed;                  // of this row's lattice
+} ElaRec;
+typedef struct ElaP {
+    const ElaRec* rec;              // [B] records of this member's batch rows (device)
+    int log2_spacing[3];            // control spacing 1 << log2_spacing[a] voxels along D / H / W; each in 1..6, else MMS_ERR_ARG
+    float max_amp[3];               // bound the CALLER declares for its records' amp: finite, 0 <= max_amp[a] <= 64, else MMS_ERR_ARG
+} ElaP;
+
 /* ---- ABI self-description ---- */
 int mms_abi_sizeof(const char* name);      /* sizeof(struct <name>) as compiled, -1 if unknown */
 int mms_abi_version(void);
@@ -1221,6 +1262,8 @@ int mms_missing_mix_bwd_group(const MixP* p, int ng, hipStream_t s);
 int mms_gather_rows_group(const GatherP* p, int ng, hipStream_t s);
 int mms_gather_aug_group(const GatherP* p, const AugP* a, int ng, hipStream_t s);   /* gather + per-row augmentation records */
 int mms_gather_affine_group(const GatherP* p, const AugP* a, const AffP* f, int ng, hipStream_t s);   /* ... + affine resampling and noise records */
+int mms_gather_elastic_group(const GatherP* p, const AugP* a, const AffP* f, const ElaP* e, int ng, hipStream_t s);   /* ... + elastic deformation records */
+int mms_elastic_field(const ElaP* p, int B, int D, int H, int W, float* out, hipStream_t s);   /* the displacement field of B records, out [B][3][D][H][W] */
 int mms_unpack_conv3_grads_group(const float* const* scratch, float* const* const* dw, int ng, int nlayers, hipStream_t s);  /* scratch[g]: model g's [nlayers][27][32][128] tap-major scratch; dw[g][i]: canonical gradient of layer i; nlayers <= 58 */
 int mms_zero_regions_group(void* const* regions_dev, int ng, size_t bytes, hipStream_t s);   /* 16-B aligned regions of equal size, zero-filled by one launch */
 int mms_linear_fwd_group(const LinearFwdP* p, int ng, hipStream_t s);

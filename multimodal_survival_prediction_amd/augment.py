@@ -24,12 +24,25 @@ R = R_D(a0) R_H(a1) R_W(a2) (R_D turns the (H, W) plane about the D axis, R_H th
 counter-clockwise for a positive angle); the 8-word records handed on have flip and shift zeroed.  The rotation acts in VOXEL-INDEX
 space: the cohort tensors do not carry the voxel spacing, so on anisotropic grids an angle is not a physical angle.  The noise g is a
 counter hash of (seed, voxel index) summed over eight bytes (an Irwin-Hall approximation of a unit Gaussian, |g| <= 4.88) that a CPU
-reproduces bit for bit; the interpolation has a derived tolerance instead of bit equality (tests/test_gpu_augment_affine.py).  Elastic
-deformation is left out: it needs a displacement field per row, not a record.
+reproduces bit for bit; the interpolation has a derived tolerance instead of bit equality (tests/test_gpu_augment_affine.py).
+
+Elastic (free-form) deformation (spec key elastic; mms_gather_elastic_group, include/mmsurv.h: ElaRec / ElaP) rides a THIRD record of 4
+words per row
+
+    [amp_D, amp_H, amp_W (fp32), seed]
+
+and still the same single launch: the destination voxel p is moved to p + d(p) BEFORE the affine map, d the cubic B-spline interpolant
+of a coarse lattice (one control point every `spacing` voxels, a power of two) of control displacements amp_a * u, u in [-1, 1) a
+counter hash of (seed, lattice index).  The field is a pure function of the record -- the kernel builds the lattice in LDS and never
+stores a field -- so a row still carries a record, not a field.  amp bounds the CONTROL POINTS: |d| <= amp always, the realised largest
+|d| is typically 0.5 .. 0.7 amp.  The host refuses amp > 0.4 * spacing, the bound below which a cubic B-spline deformation cannot fold
+(Choi & Lee 2000); as the deformation comes before the affine map the bound does not depend on a row's rotation or zoom.  Air moves in
+at the borders, as with shifts.  displacement_field() returns d itself for inspection.
 
 AugmentSpec names the distribution, sample_records draws one epoch's records in ONE vectorised call from a generator of its own
 (turning augmentation on leaves the batch order of a seeded run unchanged; a spec with rot / zoom / noise makes a second call, after
-the first, so the first call's fields are the same with and without them), apply() runs the kernel over an already materialised batch.
+the first, so the first call's fields are the same with and without them; a spec with elastic makes a third, after those), apply() runs
+the kernel over an already materialised batch.
 """
 import ctypes
 import dataclasses
@@ -46,6 +59,31 @@ AFF_WORDS = 16                               # include/mmsurv.h: AffRec
 AFF_SIGMA, AFF_SEED = 12, 13                 # words 0..11: the 3 x 4 matrix
 MASKLESS_STYLES = styles_without_mask()      # (training's style table) their models take no modality mask: nothing can tell them a row is hidden
 ROLE_PLAIN, ROLE_VOLUME, ROLE_MASK = 0, 1, 2                     # include/mmsurv.h: MMS_AUG_*
+ELA_WORDS = 4                                # include/mmsurv.h: ElaRec
+ELA_SEED = 3                                 # words 0..2: the amplitudes along D / H / W
+ELA_FOLD = 0.4                               # amp <= ELA_FOLD * spacing: no folding (Choi & Lee 2000)
+ELA_MAX_AMP = 64.0                           # include/mmsurv.h: ElaP.max_amp
+
+
+def lattice_max():
+    """Floats of the control lattice the kernel keeps in LDS (include/mmsurv.h: MMS_ELA_LATTICE_MAX)."""
+    from . import _lib
+    return _lib.defines("MMS_ELA_")["LATTICE_MAX"]
+
+
+def lattice_floats(dims, spacing):
+    """3 K_D K_H K_W of the contract: K_a = (n_a - 1) // spacing + 4 control planes along axis a."""
+    return 3 * math.prod((int(n) - 1) // int(spacing) + 4 for n in dims)
+
+
+def _check_spacing(spacing, dims=None):
+    if not isinstance(spacing, int) or spacing < 2 or spacing > 64 or spacing & (spacing - 1):
+        raise ValueError("augment: the elastic spacing must be a power of two in 2..64 (voxels between control points), got %r" % (spacing,))
+    if dims is not None and lattice_floats(dims, spacing) > lattice_max():
+        fits = [s for s in (2, 4, 8, 16, 32, 64) if lattice_floats(dims, s) <= lattice_max()]
+        raise ValueError("augment: an elastic lattice of spacing %d over a %s volume takes %d floats, the kernel keeps %d; %s"
+                         % (spacing, "x".join(str(int(d)) for d in dims), lattice_floats(dims, spacing), lattice_max(),
+                            "the smallest spacing that fits is %d" % fits[0] if fits else "no spacing fits this volume"))
 
 
 def make_records(n, flip=0, shift=(0, 0, 0), scale=1.0, offset=0.0, drop=0):
@@ -79,7 +117,9 @@ class AugmentSpec:
     uniform on the integers [-max_shift, max_shift]; scale_range / offset_range: uniform fp32 intensity map; modality_drop_p: each
     modality the patient HAS is hidden with this probability (never the last one left); seed: of the sampler's own generator.
     rot_max: the angle about axis D / H / W is uniform in +-rot_max degrees; zoom_range: isotropic zoom, uniform (above 1 enlarges the
-    anatomy); noise_range: sigma of the additive noise, uniform per row."""
+    anatomy); noise_range: sigma of the additive noise, uniform per row.  elastic_range: amplitude of the elastic deformation's control
+    points in voxels, uniform per row, one value for the three axes (at most 0.4 * elastic_spacing); elastic_spacing: voxels between
+    control points, one power of two in 2..64 for all axes."""
     flip_p: tuple = (0.0, 0.0, 0.0)
     max_shift: tuple = (0, 0, 0)
     scale_range: tuple = (1.0, 1.0)
@@ -89,6 +129,8 @@ class AugmentSpec:
     rot_max: tuple = (0.0, 0.0, 0.0)
     zoom_range: tuple = (1.0, 1.0)
     noise_range: tuple = (0.0, 0.0)
+    elastic_range: tuple = (0.0, 0.0)
+    elastic_spacing: int = 16
 
     def __post_init__(self):
         object.__setattr__(self, "flip_p", _triple(self.flip_p, float))
@@ -102,7 +144,8 @@ class AugmentSpec:
         object.__setattr__(self, "rot_max", _triple(self.rot_max, float))
         object.__setattr__(self, "zoom_range", tuple(float(x) for x in self.zoom_range))
         object.__setattr__(self, "noise_range", tuple(float(x) for x in self.noise_range))
-        for name in ("scale_range", "offset_range", "zoom_range", "noise_range"):
+        object.__setattr__(self, "elastic_range", tuple(float(x) for x in self.elastic_range))
+        for name in ("scale_range", "offset_range", "zoom_range", "noise_range", "elastic_range"):
             r = getattr(self, name)
             if len(r) != 2 or not r[0] <= r[1] or not all(math.isfinite(x) for x in r):
                 raise ValueError("augment: %s must be lo:hi with lo <= hi" % name)
@@ -112,16 +155,31 @@ class AugmentSpec:
             raise ValueError("augment: zoom must be > 0")
         if self.noise_range[0] < 0:
             raise ValueError("augment: noise sigma must be >= 0")
+        self._check_elastic()
+
+    def _check_elastic(self, dims=None):
+        if self.elastic_range[0] < 0:
+            raise ValueError("augment: the elastic amplitude must be >= 0")
+        _check_spacing(self.elastic_spacing, dims if self.has_elastic else None)
+        if self.elastic_range[1] > ELA_FOLD * self.elastic_spacing:
+            raise ValueError("augment: elastic amplitude %g exceeds %g * spacing = %g voxels, above which the deformation can fold "
+                             "(raise the spacing or lower the amplitude)"
+                             % (self.elastic_range[1], ELA_FOLD, ELA_FOLD * self.elastic_spacing))
 
     @property
     def has_affine(self):
         """The spec asks for resampling or noise: its rows carry a second record and the launch is mms_gather_affine_group."""
         return any(a > 0 for a in self.rot_max) or self.zoom_range != (1.0, 1.0) or self.noise_range != (0.0, 0.0)
 
+    @property
+    def has_elastic(self):
+        """The spec asks for elastic deformation: its rows carry a third record and the launch is mms_gather_elastic_group."""
+        return self.elastic_range[1] > 0
+
     @classmethod
     def parse(cls, text):
-        """"flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=7,rot=10,zoom=0.9:1.1,noise=0:0.03" -- every key
-        optional; flip, shift and rot take one value for all axes or D:H:W."""
+        """"flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2,seed=7,rot=10,zoom=0.9:1.1,noise=0:0.03,elastic=0:3:16"
+        -- every key optional; flip, shift and rot take one value for all axes or D:H:W; elastic is lo:hi[:spacing]."""
         kw, seen = {}, set()
         for item in str(text).split(","):
             item = item.strip()
@@ -143,6 +201,13 @@ class AugmentSpec:
                 elif key in ("scale", "offset", "zoom", "noise"):
                     lo, hi = val.split(":")
                     kw[key + "_range"] = (float(lo), float(hi))
+                elif key == "elastic":
+                    parts = val.split(":")
+                    if len(parts) not in (2, 3):
+                        raise ValueError(val)
+                    kw["elastic_range"] = (float(parts[0]), float(parts[1]))
+                    if len(parts) == 3:
+                        kw["elastic_spacing"] = int(parts[2])
                 elif key == "moddrop":
                     kw["modality_drop_p"] = float(val)
                 elif key == "seed":
@@ -150,7 +215,7 @@ class AugmentSpec:
                 else:
                     raise KeyError(key)
             except KeyError:
-                raise ValueError("augment: unknown key %r (flip, shift, scale, offset, moddrop, seed, rot, zoom, noise)" % key) from None
+                raise ValueError("augment: unknown key %r (flip, shift, scale, offset, moddrop, seed, rot, zoom, noise, elastic)" % key) from None
             except ValueError:
                 raise ValueError("augment: cannot read %r" % item) from None
         return cls(**kw)
@@ -161,10 +226,14 @@ class AugmentSpec:
                                                                         c(self.offset_range), self.modality_drop_p, self.seed)
         if self.has_affine:                  # (a spec without the new keys prints as it always did)
             s += ",rot=%s,zoom=%s,noise=%s" % (c(self.rot_max), c(self.zoom_range), c(self.noise_range))
+        if self.has_elastic:
+            s += ",elastic=%s:%d" % (c(self.elastic_range), self.elastic_spacing)
         return s
 
     def validate(self, style=None, dims=None):
-        """Refuse what cannot work: hiding modalities from a model that takes no mask, shifts that move the whole volume out."""
+        """Refuse what cannot work: hiding modalities from a model that takes no mask, shifts that move the whole volume out, an
+        elastic spacing that is no power of two, an amplitude that can fold, a control lattice over the kernel's budget for dims."""
+        self._check_elastic(dims)
         if style is not None and self.modality_drop_p > 0 and style in MASKLESS_STYLES:
             raise ValueError("augment: moddrop=%g cannot be used with style %r: its model takes no modality mask, a hidden modality "
                              "would look like real zeros (styles with a mask: partial, simmlm, flexible)" % (self.modality_drop_p, style))
@@ -220,9 +289,38 @@ def sample_affine(spec, gen, recs, dims):
 
 
 def sample(spec, gen, mask, dims, style=None):
-    """sample_records, then sample_affine when the spec asks for it -> (records [n, 8], affine records [n, 16] or None)."""
+    """sample_records, then sample_affine when the spec asks for it -> (records [n, 8], affine records [n, 16] or None).  A spec with
+    elastic draws three records per row: sample_all."""
+    if spec.has_elastic:
+        raise ValueError("augment.sample returns two record arrays; a spec with elastic= needs the third: augment.sample_all")
     recs = sample_records(spec, gen, mask, dims, style)
     return sample_affine(spec, gen, recs, dims) if spec.has_affine else (recs, None)
+
+
+def sample_elastic(spec, gen, n):
+    """The third draw of a spec that `has_elastic`, made after the affine one on the same generator -> [n, 4] int32 elastic records.
+    One torch.rand(n, 4) call: column 0 the amplitude (one value for the three axes), 1 and 2 the two 16-bit halves of the lattice
+    seed, 3 spare."""
+    u = torch.rand(n, 4, generator=gen).double()
+    amp = spec.elastic_range[0] + (spec.elastic_range[1] - spec.elastic_range[0]) * u[:, 0]
+    seed = (torch.floor(u[:, 1] * 65536.0).long() << 16) | torch.floor(u[:, 2] * 65536.0).long()
+    return elastic_records(n, amp, seed)
+
+
+def sample_all(spec, gen, mask, dims, style=None):
+    """sample() plus the elastic draw -> (records [n, 8], affine records [n, 16] or None, elastic records [n, 4] or None).  For a spec
+    without elastic the first two are sample()'s and the third is None.  The elastic launch takes affine records: a spec with elastic
+    but no rot / zoom / noise composes them from the flips and shifts alone (sigma 0) and does not consume the second draw."""
+    if not spec.has_elastic:
+        return sample(spec, gen, mask, dims, style) + (None,)
+    recs = sample_records(spec, gen, mask, dims, style)
+    if spec.has_affine:
+        recs, aff = sample_affine(spec, gen, recs, dims)
+    else:
+        aff = affine_records(recs, dims=dims)
+        recs = recs.clone()
+        recs[:, FLIP:DX + 1] = 0
+    return recs, aff, sample_elastic(spec, gen, recs.shape[0])
 
 
 def rotation(angles_deg):
@@ -282,6 +380,42 @@ def check_affine_records(aff, n=None):
         raise ValueError("augment: noise sigma must be finite and >= 0")
 
 
+def elastic_records(n, amp=0.0, seed=0):
+    """-> [n, 4] int32 elastic records (words 0..2 hold fp32 bit patterns; ElaRec).  amp: scalar, [n] (one value for the three axes)
+    or [n, 3] (D / H / W) control-point amplitudes in voxels; seed: scalar or [n], the low 32 bits are kept."""
+    amp = np.asarray(torch.as_tensor(amp).double().numpy() if torch.is_tensor(amp) else amp, dtype=np.float64)
+    if amp.ndim == 1:
+        amp = amp[:, None]
+    amp = np.broadcast_to(amp, (n, 3))
+    seed = np.broadcast_to(np.asarray(torch.as_tensor(seed).numpy() if torch.is_tensor(seed) else seed, dtype=np.int64), (n,))
+    out = np.zeros((n, ELA_WORDS), dtype=np.int32)
+    out.view(np.float32)[:, :3] = amp.astype(np.float32)
+    out[:, ELA_SEED] = (seed & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    return torch.from_numpy(out)
+
+
+def check_elastic_records(ela, n=None, spacing=None):
+    """Host-side validation of elastic records before they reach the kernel (which clamps what it is given; the no-folding bound is
+    checked HERE): shape, dtype, finite amplitudes in [0, min(64, 0.4 * spacing)] -> per-axis max amplitude (ElaP.max_amp)."""
+    ela = torch.as_tensor(ela)
+    if ela.dtype != torch.int32 or ela.shape[-1] != ELA_WORDS or ela.is_cuda:
+        raise ValueError("elastic records must be a host int32 array of %d words per row (augment.elastic_records)" % ELA_WORDS)
+    rows = ela.reshape(-1, ELA_WORDS)
+    if n is not None and rows.shape[0] != n:
+        raise ValueError("augment: one elastic record per row, got %d for %d rows" % (rows.shape[0], n))
+    amp = rows.view(torch.float32)[:, :3]
+    if not bool(torch.isfinite(amp).all()) or not bool((amp >= 0).all()):
+        raise ValueError("augment: elastic amplitudes must be finite and >= 0")
+    mx = [float(x) for x in amp.amax(0)] if rows.shape[0] else [0.0, 0.0, 0.0]
+    if spacing is not None:
+        _check_spacing(spacing)
+    top = ELA_MAX_AMP if spacing is None else min(ELA_MAX_AMP, float(np.float32(ELA_FOLD * spacing)))
+    if max(mx) > top:
+        raise ValueError("augment: an elastic record's amplitude %g exceeds %g voxels%s" % (
+            max(mx), top, "" if spacing is None else " (%g * spacing %d: above it the deformation can fold)" % (ELA_FOLD, spacing)))
+    return mx
+
+
 def check_records(rec, dims=None, has_mask=True):
     """Host-side validation of a record array before it reaches the kernel -> per-axis max |shift|."""
     rec = torch.as_tensor(rec)
@@ -321,12 +455,44 @@ def aff_block(aff_dev, stage_floats=0):
     return F
 
 
-def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0):
+def ela_block(ela_dev, spacing, max_amp):
+    """ElaP (include/mmsurv.h).  spacing: voxels between control points, one power of two for the three axes; max_amp: per-axis bound
+    of the records' amplitudes (check_elastic_records)."""
+    from . import _lib
+    _check_spacing(spacing)
+    E = _lib.structs()["ElaP"]()
+    E.rec = ela_dev.data_ptr()
+    for a in range(3):
+        E.log2_spacing[a] = int(spacing).bit_length() - 1
+        E.max_amp[a] = float(max_amp[a])
+    return E
+
+
+def displacement_field(records, dims, spacing):
+    """The displacement field d of elastic records (mms_elastic_field: the device function the gather kernel calls) ->
+    [n, 3, D, H, W] fp32 on the GPU; d[i, a] is the displacement along axis a (D / H / W) in voxels."""
+    from . import _lib, ops
+    ela = torch.as_tensor(records).reshape(-1, ELA_WORDS)
+    dims = tuple(int(d) for d in dims)
+    mx = check_elastic_records(ela, spacing=spacing)
+    _check_spacing(spacing, dims)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ela_dev = ela.to(dev)
+    out = torch.empty((ela.shape[0], 3) + dims, dtype=torch.float32, device=dev)
+    if ela.shape[0]:
+        E = ela_block(ela_dev, spacing, mx)
+        _lib.check(_lib.load_library().mms_elastic_field(ctypes.byref(E), ela.shape[0], dims[0], dims[1], dims[2], out.data_ptr(), ops.stream()),
+                   "mms_elastic_field")
+    return out
+
+
+def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0, elastic=None, elastic_spacing=16):
     """The augmenting gather over an already materialised batch (device tensors image / rnaseq / clinical / mask as
     data.BatchLoader yields them), out of place, identity indices: -> the batch dict with those four replaced.  present_ok: per
     (image, rnaseq) whether rows whose mask column is 0 are known to be all-zero in the cohort (then they are not read, as in
     SurvivalEngine.gather_block).  affine: [B, 16] affine records (affine_records): the launch is then mms_gather_affine_group, which
-    ignores the records' flip / shift."""
+    ignores the records' flip / shift.  elastic: [B, 4] elastic records (elastic_records) over a lattice of elastic_spacing voxels: the
+    launch is mms_gather_elastic_group; without `affine` the matrices are composed from the records' flips and shifts."""
     from . import _lib, ops
     img, rna, clin, mask = batch["image"], batch["rnaseq"], batch["clinical"], batch["mask"]
     B, dims = img.shape[0], tuple(img.shape[-3:])
@@ -337,6 +503,12 @@ def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0):
     if affine is not None:
         affine = torch.as_tensor(affine)
         check_affine_records(affine, B)
+    if elastic is not None:
+        elastic = torch.as_tensor(elastic)
+        ela_mx = check_elastic_records(elastic, B, elastic_spacing)
+        _check_spacing(elastic_spacing, dims)
+        if affine is None:
+            affine = affine_records(rec, dims=dims)
     S = _lib.structs()
     dev = img.device
     mask = mask.contiguous()
@@ -361,6 +533,12 @@ def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0):
     if affine is not None:
         aff_dev = affine.reshape(B, AFF_WORDS).to(dev)
         F = aff_block(aff_dev, stage_floats)
+    if elastic is not None:
+        ela_dev = elastic.reshape(B, ELA_WORDS).to(dev)
+        E = ela_block(ela_dev, elastic_spacing, ela_mx)
+        _lib.check(_lib.load_library().mms_gather_elastic_group(ctypes.byref(G), ctypes.byref(A), ctypes.byref(F), ctypes.byref(E), 1,
+                                                                ops.stream()), "mms_gather_elastic_group")
+    elif affine is not None:
         _lib.check(_lib.load_library().mms_gather_affine_group(ctypes.byref(G), ctypes.byref(A), ctypes.byref(F), 1, ops.stream()),
                    "mms_gather_affine_group")
     else:

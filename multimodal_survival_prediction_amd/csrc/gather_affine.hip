@@ -13,48 +13,12 @@
 //                global loads per voxel.  Merely correct.
 // Which form a tile takes depends on (tile, record, argument) only: uniform per workgroup, as every branch around a barrier here.
 // No atomics, no in-launch waits.
-#include "common.h"
-#include "gather_rows.h"
+#include "gather_affine.h"       // tile, staging budget, aff_coord / aff_noise / aff_trilerp: shared with gather_elastic.hip
 
-#define AFT_Z 4
-#define AFT_Y 8
-#define AFT_X 32
-#define AFF_STAGE_MAX 8192                  // floats of the LDS staging box: 32 KB of the CU's 160 KB -- five such workgroups per CU, and 128 KB
-                                            // left for the kernels of the step's other streams that share the CU
-
-struct AffK { const AugRec* rec; const AffRec* aff; unsigned meta; int stage; };
-struct AffGrp { AffK k[MMS_MAX_GROUP]; int D, H, W; };
-
-// source coordinate of one axis (the contract's chain), clamped to [-2, n + 1]: nothing inside (-1, n) -- the only coordinates with a
-// corner in the volume -- moves, NaN becomes -2 (fmaxf returns its non-NaN operand), and the int conversion cannot overflow
-__device__ __forceinline__ float aff_coord(const float* m, float z, float y, float x, int n) {
-    const float c = fmaf(m[0], z, fmaf(m[1], y, fmaf(m[2], x, m[3])));
-    return fminf(fmaxf(c, -2.f), (float)n + 1.f);
-}
-
-// Irwin-Hall noise of the contract: the byte sum of two hashed words, centred and scaled to unit variance
-__device__ __forceinline__ float aff_noise(uint32_t hseed, uint32_t i) {
-    const uint32_t h0 = hash_u32((2u * i) * 0x9E3779B9U + hseed), h1 = hash_u32((2u * i + 1u) * 0x9E3779B9U + hseed);
-    const uint32_t lo = (h0 & 0x00FF00FFu) + ((h0 >> 8) & 0x00FF00FFu) + (h1 & 0x00FF00FFu) + ((h1 >> 8) & 0x00FF00FFu);
-    const int S = (int)((lo & 0xFFFFu) + (lo >> 16));
-    return (float)(S - 1020) * 0x1.39897ep-8f;
-}
-
-// trilinear sample from a corner fetcher at(z, y, x): x first, then y, then z; a weight of exactly 0 returns the lower corner's bits
-template <class F>
-__device__ __forceinline__ float aff_trilerp(F at, float cz, float cy, float cx) {
-    const float fz0 = floorf(cz), fy0 = floorf(cy), fx0 = floorf(cx);
-    const int iz = (int)fz0, iy = (int)fy0, ix = (int)fx0;
-    const float wz = cz - fz0, wy = cy - fy0, wx = cx - fx0;
-    float q[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float a = at(iz + (c >> 1), iy + (c & 1), ix), b = at(iz + (c >> 1), iy + (c & 1), ix + 1);
-        q[c] = fmaf(wx, b - a, a);
-    }
-    const float r0 = fmaf(wy, q[1] - q[0], q[0]), r1 = fmaf(wy, q[3] - q[2], q[2]);
-    return fmaf(wz, r1 - r0, r0);
-}
+// The kernel's body is kept as it was written: its box computation, staging loop and corner fetchers below are the ORIGINALS of
+// aff_box / aff_stage_box / aff_at_box / aff_at_global in gather_affine.h, which only gather_elastic_kernel calls.  Calling those
+// helpers from here compiles to a differently scheduled kernel (compare order, branch sense), and this kernel's instructions are
+// what the measurements of DESIGN.md section 5 were taken on; a fix to the staging has to be made in both places.
 
 __global__ __launch_bounds__(256) void gather_affine_kernel(const Grp<GatherP> grp, const AffGrp ag) {
     __shared__ float4 box4[AFF_STAGE_MAX / 4];

@@ -101,7 +101,10 @@ class BatchLoader:
     A lazy loader adds augment=<records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them inside its
     gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both yield the
     same augmented batches.  A spec with rot / zoom / noise (AugmentSpec.has_affine) draws a second, 16-word record per row: a lazy loader
-    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  augment_style: the model style ("partial", "final", ...) the spec is checked against.
+    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  A spec with elastic
+    (AugmentSpec.has_elastic) draws a third, 4-word record per row: a lazy loader adds augment_elastic=<rows> and
+    augment_elastic_spacing=<voxels> (and always augment_affine: the elastic launch takes matrices), a materialising one hands them to
+    augment.apply(elastic=).  augment_style: the model style ("partial", "final", ...) the spec is checked against.
     fold: which cross-validation fold the loader belongs to.  Only read over a cohort that carries per-fold gene matrices
     (gene_select.GeneSelection.apply): the batches a loader materialises itself then take their rnaseq rows from that fold's [N, k]
     matrix (a lazy loader names rows only; the fold group's gather launch picks the matrix, FoldGroupEngine(folds=))."""
@@ -149,10 +152,10 @@ class BatchLoader:
     def __iter__(self):
         idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
         dev = self.c["image"].device
-        recs = aff = None
-        if self.augment is not None:         # one vectorised draw per epoch (a second one for rot / zoom / noise)
-            recs, aff = _augment.sample(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
-                                        self.augment_style)
+        recs = aff = ela = None
+        if self.augment is not None:         # one vectorised draw per epoch (a second one for rot / zoom / noise, a third for elastic)
+            recs, aff, ela = _augment.sample_all(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
+                                                 self.augment_style)
         for i in range(0, len(idx), self.bs):
             if self.lazy:
                 jj = idx[i:i + self.bs]
@@ -161,6 +164,8 @@ class BatchLoader:
                     b["augment"] = recs[i:i + self.bs]
                 if aff is not None:
                     b["augment_affine"] = aff[i:i + self.bs]
+                if ela is not None:
+                    b["augment_elastic"], b["augment_elastic_spacing"] = ela[i:i + self.bs], self.augment.elastic_spacing
                 yield b
                 continue
             j = idx[i:i + self.bs].to(dev)
@@ -171,7 +176,8 @@ class BatchLoader:
                 b["time"] = self.c["label"][j, 0:1]
                 b["event"] = self.c["label"][j, 1:2].long()
             if recs is not None:
-                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok(), affine=None if aff is None else aff[i:i + self.bs])
+                kw = {} if ela is None else dict(elastic=ela[i:i + self.bs], elastic_spacing=self.augment.elastic_spacing)
+                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok(), affine=None if aff is None else aff[i:i + self.bs], **kw)
             yield b
 
 

@@ -301,11 +301,12 @@ class FoldGroupEngine:
             e.load_batch(P, **b)
         self._step(GP, skip_if_unusable, use_graph)
 
-    def _gather_indexed(self, GP, cohort, idx, augment=None, affine=None):
+    def _gather_indexed(self, GP, cohort, idx, augment=None, affine=None, elastic=None, elastic_spacing=16):
         """Index copy (pinned ring -> device) + the ONE gather launch that assembles the group's batches in the plans' input buffers.
         augment: [len(members)][B] records (augment.make_records) -- they ride the same pinned ring as the indices and the launch
         is mms_gather_aug_group; affine: [len(members)][B] affine records (augment.affine_records) beside them -- the launch is
-        mms_gather_affine_group; None: today's path."""
+        mms_gather_affine_group; elastic: [len(members)][B] elastic records (augment.elastic_records) over a lattice of
+        elastic_spacing voxels, a third ring beside those two -- the launch is mms_gather_elastic_group; None: today's path."""
         members, B = GP.members, GP.B
         key = id(cohort)
         cache = GP.__dict__.setdefault("gather", {})
@@ -323,8 +324,11 @@ class FoldGroupEngine:
         dev_idx, pin, blocks, _ = cache[key]
         if affine is not None and augment is None:
             raise ValueError("affine records come with the 8-word records of the same rows (augment=)")
+        if elastic is not None and affine is None:
+            raise ValueError("elastic records come with the affine records of the same rows (augment_affine=; augment.affine_records "
+                             "composes them from flips and shifts alone)")
         if augment is not None:          # (validated before the ring is touched: a refused step leaves no copy without its event)
-            aug = self._aug_blocks(GP, cohort, dev_idx, pin, augment, affine)
+            aug = self._aug_blocks(GP, cohort, dev_idx, pin, augment, affine, elastic, elastic_spacing)
         k = pin["k"]
         pin["k"] = (k + 1) % len(pin["bufs"])
         if pin["evs"][k] is not None:
@@ -337,9 +341,16 @@ class FoldGroupEngine:
         if affine is not None:
             aug["aff_pin"][k].copy_(affine)
             aug["aff_dev"].copy_(aug["aff_pin"][k], non_blocking=True)
+        if elastic is not None:
+            aug["ela_pin"][k].copy_(elastic)
+            aug["ela_dev"].copy_(aug["ela_pin"][k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         pin["evs"][k] = ev
+        if elastic is not None:
+            _lib.check(self.lib.mms_gather_elastic_group(aug["gather"], aug["aug"], aug["aff"], aug["ela"][elastic_spacing], GP.ng, ops.stream()),
+                       "mms_gather_elastic_group")
+            return
         if affine is not None:
             _lib.check(self.lib.mms_gather_affine_group(aug["gather"], aug["aug"], aug["aff"], GP.ng, ops.stream()), "mms_gather_affine_group")
             return
@@ -348,9 +359,10 @@ class FoldGroupEngine:
             return
         _lib.check(self.lib.mms_gather_rows_group(blocks, GP.ng, ops.stream()), "mms_gather_rows_group")
 
-    def _aug_blocks(self, GP, cohort, dev_idx, pin, augment, affine=None):
+    def _aug_blocks(self, GP, cohort, dev_idx, pin, augment, affine=None, elastic=None, elastic_spacing=16):
         """Per (plan, cohort): device + pinned record buffers and the (GatherP, AugP) arrays of mms_gather_aug_group -- with affine
-        records also theirs and the AffP array of mms_gather_affine_group; validates the step's records on the host (they are host
+        records also theirs and the AffP array of mms_gather_affine_group, with elastic records theirs and the ElaP array of
+        mms_gather_elastic_group (one per spacing); validates the step's records on the host (they are host
         data) so that the launch cannot be refused with a bare code."""
         from . import augment as A
         has_mask = all(P.gate is not None or P.moe is not None or P.mix is not None for P in GP.Ps)
@@ -364,6 +376,13 @@ class FoldGroupEngine:
                                  % (A.AFF_WORDS, tuple(affine.shape), len(GP.members), GP.B))
             A.check_affine_records(affine)
             mx = [0, 0, 0]               # (mms_gather_affine_group does not read the records' shifts)
+        if elastic is not None:
+            if tuple(elastic.shape) != (len(GP.members), GP.B, A.ELA_WORDS):
+                raise ValueError("augment_elastic must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
+                                 % (A.ELA_WORDS, tuple(elastic.shape), len(GP.members), GP.B))
+            ela_mx = A.check_elastic_records(elastic, spacing=elastic_spacing)
+            if GP.has_enc:
+                A._check_spacing(elastic_spacing, GP.dims)
         cache = GP.__dict__.setdefault("gather_aug", {})
         key = id(cohort)
         if key not in cache:
@@ -376,12 +395,23 @@ class FoldGroupEngine:
             aug["aff_dev"] = torch.zeros(len(GP.members), GP.B, A.AFF_WORDS, dtype=torch.int32, device=self.device)
             aug["aff_pin"] = [torch.zeros(aug["aff_dev"].shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]]
             aug["aff"] = _arr([A.aff_block(aug["aff_dev"][g]) for g in range(GP.ng)])
+        if elastic is not None:
+            if "ela_dev" not in aug:
+                aug["ela_dev"] = torch.zeros(len(GP.members), GP.B, A.ELA_WORDS, dtype=torch.int32, device=self.device)
+                aug["ela_pin"] = [torch.zeros(aug["ela_dev"].shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]]
+                aug["ela"] = {}
+            if elastic_spacing not in aug["ela"]:
+                aug["ela"][elastic_spacing] = _arr([A.ela_block(aug["ela_dev"][g], elastic_spacing, ela_mx) for g in range(GP.ng)])
+            for g in range(GP.ng):       # (one bound per launch: the largest amplitude of the step's records, every member)
+                for a in range(3):
+                    aug["ela"][elastic_spacing][g].max_amp[a] = ela_mx[a]
         for g in range(GP.ng):
             for a in range(3):
                 aug["aug"][g].max_shift[a] = mx[a]
         return aug
 
-    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None, augment_affine=None):
+    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None, augment_affine=None,
+                           augment_elastic=None, elastic_spacing=16):
         """Same step with the batches named by patient indices into a cohort that lives in HBM (data.cohort_to) or in pinned host
         memory (data.cohort_pin: the gather launch reads the rows over PCIe): indices: [len(members)][B] integer array-like (host).  The batch assembly of the whole group is one small
         host-to-device copy of the indices plus ONE gather launch (mms_gather_rows_group) instead of ~10 torch
@@ -389,7 +419,10 @@ class FoldGroupEngine:
         augment.sample_records, host int32): the gather launch applies them while it copies (mms_gather_aug_group: CT flips, shifts
         and intensity map, modality dropout); None: no augmentation, the plain gather.  augment_affine: [len(members)][B] affine records
         (augment.affine_records / augment.sample) of the same rows: the launch is mms_gather_affine_group (rotation / zoom resampling,
-        additive noise; the flip / shift fields of `augment` are not read, they are folded into the matrices)."""
+        additive noise; the flip / shift fields of `augment` are not read, they are folded into the matrices).  augment_elastic:
+        [len(members)][B] elastic records (augment.elastic_records / augment.sample_all) of the same rows over a control lattice of
+        elastic_spacing voxels, beside augment_affine: the launch is mms_gather_elastic_group (free-form deformation before the affine
+        map)."""
         members = self._members(members)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if idx.dim() != 2 or idx.shape[0] != len(members):
@@ -399,7 +432,8 @@ class FoldGroupEngine:
         self.engines[0].check_train_batch(B, dims)
         GP = self.plan(B, dims, members)
         self._gather_indexed(GP, cohort, idx, None if augment is None else torch.as_tensor(augment),
-                             None if augment_affine is None else torch.as_tensor(augment_affine))
+                             None if augment_affine is None else torch.as_tensor(augment_affine),
+                             None if augment_elastic is None else torch.as_tensor(augment_elastic), elastic_spacing)
         self._step(GP, skip_if_unusable, use_graph)
 
     def _eval_loss_body(self, GP):

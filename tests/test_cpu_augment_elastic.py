@@ -1,0 +1,233 @@
+"""CPU: the elastic key of the augmentation spec, its records and sampler, the loaders' third record, the C ABI of
+mms_gather_elastic_group / mms_elastic_field, and properties of the float64 test reference (augment_elastic_ref) -- no GPU."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import augment_elastic_ref as ER
+
+from multimodal_survival_prediction_amd import _build, _lib, augment as A, data
+
+FULL = "flip=0.5,shift=2:4:4,scale=0.9:1.1,offset=-0.05:0.05,moddrop=0.2"
+AFF = ",rot=10,zoom=0.9:1.1,noise=0:0.03"
+ELA = ",elastic=0.5:3:8"
+SHAPES = [((6, 12, 12), 1), ((6, 12, 12), 2), ((5, 7, 9), 1), ((5, 7, 9), 2), ((8, 24, 32), 1), ((8, 24, 32), 2), ((8, 24, 32), 3)]
+
+
+# ---- spec ---------------------------------------------------------------------------------------------------------------------------
+def test_spec_parse_and_round_trip():
+    s = A.AugmentSpec.parse(FULL + AFF + ELA)
+    assert s.elastic_range == (0.5, 3.0) and s.elastic_spacing == 8 and s.has_elastic and s.has_affine
+    assert A.AugmentSpec.parse(str(s)) == s and str(s).endswith(",elastic=0.5:3.0:8")
+    t = A.AugmentSpec.parse("elastic=0:3")
+    assert t.elastic_range == (0.0, 3.0) and t.elastic_spacing == 16 and t.has_elastic and not t.has_affine
+    assert A.AugmentSpec.parse(str(t)) == t
+    assert A.AugmentSpec.parse("rot=10,zoom=0.9:1.1,elastic=0:3:16").validate(dims=(64, 64, 32)).has_elastic
+    assert not A.AugmentSpec.parse("elastic=0:0").has_elastic and "elastic" not in str(A.AugmentSpec.parse("elastic=0:0:4"))
+    assert A.AugmentSpec().elastic_range == (0.0, 0.0) and A.AugmentSpec().elastic_spacing == 16
+
+
+@pytest.mark.parametrize("bad,word", [("elastic=0:3:12", "power of two"), ("elastic=0:3:1", "power of two"), ("elastic=0:3:128", "power of two"),
+                                      ("elastic=0:7:16", "fold"), ("elastic=0:0.9:2", "fold"), ("elastic=-1:1", ">= 0"),
+                                      ("elastic=2:1", "lo <= hi"), ("elastic=1", "cannot read"), ("elastic=0:1:8:2", "cannot read"),
+                                      ("elastic=0:x", "cannot read"), ("elastic=0:nan", "lo:hi"), ("elastic=0:1,elastic=0:1", "twice")])
+def test_spec_refusals(bad, word):
+    with pytest.raises(ValueError, match=word):
+        A.AugmentSpec.parse(bad).validate(dims=(8, 8, 8))
+
+
+def test_the_point_four_rule_is_exact_at_the_bound():
+    for sp in (2, 4, 8, 16, 32, 64):
+        A.AugmentSpec(elastic_range=(0.0, 0.4 * sp), elastic_spacing=sp)
+        with pytest.raises(ValueError, match="fold"):
+            A.AugmentSpec(elastic_range=(0.0, 0.4 * sp * 1.001), elastic_spacing=sp)
+
+
+def test_lattice_budget_names_the_smallest_spacing_that_fits():
+    """64 x 64 x 32: spacing 16 takes 3 * 7 * 7 * 5 = 735 floats, 8 takes 2541, 4 takes 3 * 19 * 19 * 11 = 11913 > 6144."""
+    assert A.lattice_max() == 6144
+    assert A.lattice_floats((64, 64, 32), 16) == 735 and A.lattice_floats((64, 64, 32), 8) == 2541 and A.lattice_floats((64, 64, 32), 4) == 11913
+    A.AugmentSpec.parse("elastic=0:1:8").validate(dims=(64, 64, 32))
+    with pytest.raises(ValueError, match="smallest spacing that fits is 8"):
+        A.AugmentSpec.parse("elastic=0:1:4").validate(dims=(64, 64, 32))
+    A.AugmentSpec.parse("elastic=0:1:4").validate()                     # without dims only the spec's own rules
+    A.AugmentSpec.parse("elastic=0:0:4").validate(dims=(64, 64, 32))     # not asked for: no lattice
+    for dims, l in SHAPES:
+        assert A.lattice_floats(dims, 1 << l) == 3 * int(np.prod(ER.lattice_shape(dims, (l, l, l)))) <= 6144
+
+
+# ---- sampling -----------------------------------------------------------------------------------------------------------------------
+def _cohort():
+    return data.make_cohort(n=48, dims=(8, 8, 8), rna_dim=8, seed=3, complete=False)
+
+
+@pytest.mark.parametrize("text", [FULL, FULL + AFF])
+def test_specs_without_the_key_print_and_sample_as_before(text):
+    c = _cohort()
+    spec = A.AugmentSpec.parse(text)
+    assert "elastic" not in str(spec) and not spec.has_elastic
+    g, h = torch.Generator().manual_seed(9), torch.Generator().manual_seed(9)
+    two, three = A.sample(spec, g, c["mask"], c["dims"], "partial"), A.sample_all(spec, h, c["mask"], c["dims"], "partial")
+    assert len(two) == 2 and len(three) == 3 and three[2] is None
+    assert torch.equal(two[0], three[0]) and (two[1] is None) == (three[1] is None) == (not spec.has_affine)
+    assert two[1] is None or torch.equal(two[1], three[1])
+    assert torch.equal(g.get_state(), h.get_state())                   # no third draw
+    k = torch.Generator().manual_seed(9)
+    torch.rand(48, 12, generator=k)
+    if spec.has_affine:
+        torch.rand(48, 8, generator=k)
+    assert torch.equal(g.get_state(), k.get_state())                   # exactly the draws of before
+
+
+def test_the_three_draws_are_independent_streams():
+    c = _cohort()
+    g = [torch.Generator().manual_seed(5) for _ in range(4)]
+    r0, a0 = A.sample(A.AugmentSpec.parse(FULL + AFF), g[0], c["mask"], c["dims"], "partial")
+    r1, a1, e1 = A.sample_all(A.AugmentSpec.parse(FULL + AFF + ELA), g[1], c["mask"], c["dims"], "partial")
+    assert torch.equal(r0, r1) and torch.equal(a0, a1)                 # earlier fields: the same with and without the key
+    assert e1.shape == (48, A.ELA_WORDS) and e1.dtype == torch.int32
+    # elastic without rot / zoom / noise: the matrices come from flips and shifts alone and the second draw is not consumed
+    r2, a2, e2 = A.sample_all(A.AugmentSpec.parse(FULL + ELA), g[2], c["mask"], c["dims"], "partial")
+    plain = A.sample_records(A.AugmentSpec.parse(FULL), g[3], c["mask"], c["dims"], "partial")
+    assert torch.equal(r2[:, A.SCALE:], plain[:, A.SCALE:]) and not bool(r2[:, A.FLIP:A.DX + 1].any())
+    assert torch.equal(a2, A.affine_records(plain, dims=c["dims"])) and not bool(a2.view(torch.float32)[:, A.AFF_SIGMA].any())
+    torch.rand(48, 4, generator=g[3])
+    assert torch.equal(g[2].get_state(), g[3].get_state())             # 12 wide, then 4 wide: no 8-wide draw in between
+    with pytest.raises(ValueError, match="sample_all"):
+        A.sample(A.AugmentSpec.parse(FULL + ELA), g[2], c["mask"], c["dims"], "partial")
+    amp = e1.view(torch.float32)[:, :3]
+    assert bool((amp[:, 0:1] == amp).all()) and float(amp.min()) >= 0.5 and float(amp.max()) <= 3.0
+    assert float(amp.max() - amp.min()) > 1.0 and len(set(e1[:, A.ELA_SEED].tolist())) > 40
+    assert A.check_elastic_records(e1, 48, 8) == [float(amp.max())] * 3
+
+
+def test_record_layout_and_host_check():
+    r = A.elastic_records(3, amp=[[1.0, 2.0, 3.0], [0.0, 0.0, 0.0], [0.5, 0.25, 0.125]], seed=[1, 0xDEADBEEF, 2 ** 32 + 5])
+    assert r.shape == (3, 4) and r.dtype == torch.int32
+    assert r.view(torch.float32)[:, :3].tolist() == [[1.0, 2.0, 3.0], [0.0, 0.0, 0.0], [0.5, 0.25, 0.125]]
+    assert [int(x) & 0xFFFFFFFF for x in r[:, A.ELA_SEED]] == [1, 0xDEADBEEF, 5]
+    assert torch.equal(A.elastic_records(2, [1.5, 2.5], 7).view(torch.float32)[:, :3], torch.tensor([[1.5] * 3, [2.5] * 3]))
+    assert torch.equal(A.elastic_records(2, 0.75, 7), A.elastic_records(2, [0.75, 0.75], [7, 7]))
+    assert A.check_elastic_records(r, 3, 8) == [1.0, 2.0, 3.0]
+    with pytest.raises(ValueError, match="fold"):
+        A.check_elastic_records(r, 3, 4)                               # 3 > 0.4 * 4
+    with pytest.raises(ValueError):
+        A.check_elastic_records(r, 4)
+    with pytest.raises(ValueError):
+        A.check_elastic_records(r.float())
+    with pytest.raises(ValueError):
+        A.check_elastic_records(r[:, :3])
+    with pytest.raises(ValueError, match="power of two"):
+        A.check_elastic_records(r, 3, 12)
+    for val in (float("nan"), float("inf"), -0.5, 65.0):
+        bad = r.clone()
+        bad.view(torch.float32)[1, 2] = val
+        with pytest.raises(ValueError):
+            A.check_elastic_records(bad)
+
+
+def test_a_lazy_loader_carries_the_third_record():
+    c = _cohort()
+    mk = lambda spec: data.BatchLoader(c, torch.arange(48), 4, shuffle=True, seed=5, lazy=True, augment=spec, augment_style="partial")
+    a, b, e = list(mk(FULL + AFF + ELA)), list(mk(FULL + AFF)), list(mk(FULL + ELA))
+    assert all(x["augment_elastic"].shape == (4, A.ELA_WORDS) and x["augment_elastic_spacing"] == 8 for x in a + e)
+    assert all("augment_affine" in x for x in a + e)                    # the elastic launch takes matrices
+    assert all("augment_elastic" not in x and "augment_elastic_spacing" not in x for x in b)
+    assert [x["index"].tolist() for x in a] == [x["index"].tolist() for x in b]
+    assert all(torch.equal(x["augment"], y["augment"]) and torch.equal(x["augment_affine"], y["augment_affine"]) for x, y in zip(a, b))
+    assert "augment_elastic" not in next(iter(mk(FULL + AFF + ELA).without_augment()))
+    with pytest.raises(ValueError, match="smallest spacing"):
+        data.BatchLoader(data.make_cohort(n=4, dims=(32, 32, 32), rna_dim=8, seed=3), torch.arange(4), 2, lazy=True, augment="elastic=0:0.5:2")
+
+
+# ---- ABI ----------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.lib_path()):
+        _build.build()
+    return _lib.load_library()
+
+
+def test_abi_exports_the_elastic_gather(lib):
+    for name in ("mms_gather_elastic_group", "mms_elastic_field"):
+        assert name in _lib.protos() and hasattr(lib, name)
+    assert len(_lib.protos()["mms_gather_elastic_group"]) == 6 and len(_lib.protos()["mms_elastic_field"]) == 7
+    S = _lib.structs()
+    for name in ("ElaRec", "ElaP"):
+        assert name in S and lib.mms_abi_sizeof(name.encode()) == ctypes.sizeof(S[name])
+    assert ctypes.sizeof(S["ElaRec"]) == 16 == 4 * A.ELA_WORDS
+    rec = S["ElaRec"].from_buffer_copy(A.elastic_records(1, [[1.0, 2.0, 3.5]], 0xDEADBEEF).numpy().tobytes())
+    assert (list(rec.amp), rec.seed) == ([1.0, 2.0, 3.5], 0xDEADBEEF)
+    assert _lib.defines("MMS_ELA_") == {"LATTICE_MAX": 6144}
+
+
+# ---- the reference's own properties ---------------------------------------------------------------------------------------------------
+def test_u_hits_multiples_of_2_pow_minus_23_in_the_half_open_interval():
+    v = ER.u(1234, np.arange(1 << 16))
+    assert v.min() >= -1.0 and v.max() < 1.0 and np.array_equal(v * 2.0 ** 23, np.round(v * 2.0 ** 23))
+    assert np.array_equal(v.astype(np.float32).astype(np.float64), v)   # exact in fp32
+    assert abs(v.mean()) <= 5.0 / np.sqrt(3 * 65536.0) and abs(v.var() - 1.0 / 3.0) <= 0.01     # uniform on [-1, 1): variance 1/3
+    assert v.min() < -0.999 and v.max() > 0.999
+    # salted: not the stream that the noise of the same seed reads (hash(k * golden + hash(seed)))
+    with np.errstate(over="ignore"):
+        hn = ER.R._hash(np.arange(1 << 16, dtype=np.uint32) * np.uint32(0x9E3779B9) + ER.R._hash(np.array([1234], dtype=np.uint32)))
+    vn = ((hn >> np.uint32(8)).astype(np.int64) - 8388608) * 2.0 ** -23
+    assert not np.array_equal(v, vn) and abs(float(np.corrcoef(v, vn)[0, 1])) <= 5.0 / 256.0
+
+
+def test_basis_is_a_partition_of_unity():
+    r = np.arange(64) / 64.0
+    b = ER.basis(r)
+    assert b.min() >= 0 and np.abs(b.sum(-1) - 1).max() <= 1e-15 and np.abs(ER.basis_prime(r).sum(-1)).max() <= 1e-15
+    assert np.allclose(ER.basis(0.0), [1 / 6, 4 / 6, 1 / 6, 0]) and np.allclose((ER.basis(r + 1e-6) - b) / 1e-6, ER.basis_prime(r), atol=1e-5)
+
+
+@pytest.mark.parametrize("dims,l", SHAPES)
+def test_field_is_bounded_by_amp_and_does_not_fold_at_the_bound(dims, l):
+    """amp = 0.4 * spacing on all three axes, the largest the host lets through and what the sampler draws at the top of a spec's
+    range: |d_a| <= amp_a, det(I + dd/dp) > 0 at every voxel for hashed lattices and for random +-amp lattices (every control point
+    at its extreme), and seeds give different fields."""
+    s = 1 << l
+    amp = [0.4 * s, 0.4 * s, 0.4 * s]
+    ll = (l, l, l)
+    rng = np.random.default_rng(l)
+    fields, dmin, worst = [], np.inf, np.inf
+    for seed in (0, 1, 0xFFFFFFFF, 12345):
+        c = ER.lattice(dims, ll, amp, seed)
+        assert c.shape == (3,) + ER.lattice_shape(dims, ll)
+        for a in range(3):
+            assert np.abs(c[a]).max() <= np.float32(amp[a])
+        d = ER.field(dims, ll, amp, seed)
+        assert d.shape == (3,) + tuple(dims)
+        for a in range(3):
+            assert np.abs(d[a]).max() <= float(np.float32(amp[a]))
+        assert np.abs(d).max() > 0.05 * s
+        dmin = min(dmin, float(ER.jacobian_det(dims, ll, c).min()))
+        sign = rng.choice([-1.0, 1.0], size=c.shape) * np.asarray(amp)[:, None, None, None]
+        worst = min(worst, float(ER.jacobian_det(dims, ll, sign).min()))
+        fields.append(d)
+    print("dims %s spacing %d: min det %.3f hashed, %.3f over +-amp lattices" % (dims, s, dmin, worst))
+    assert dmin > 0 and worst > 0
+    assert all(not np.array_equal(fields[0], f) for f in fields[1:])
+    assert not ER.field(dims, ll, [0.0, 0.0, 0.0], 5).any()
+
+
+def test_the_determinant_goes_negative_well_above_the_bound():
+    """The 0.4 rule is not vacuous: at amp = 1.2 * spacing an alternating lattice folds."""
+    dims, ll = (8, 24, 32), (2, 2, 2)
+    K = ER.lattice_shape(dims, ll)
+    jz, jy, jx = np.meshgrid(*[np.arange(k) for k in K], indexing="ij")
+    c = np.stack([4.8 * (-1.0) ** jz, 4.8 * (-1.0) ** jy, 4.8 * (-1.0) ** jx])
+    assert ER.jacobian_det(dims, ll, c).min() < 0
+
+
+def test_zero_amplitude_is_the_affine_reference():
+    rng = np.random.default_rng(0)
+    vol = rng.uniform(0, 1, (5, 7, 9))
+    m = np.eye(3, 4) + rng.uniform(-0.1, 0.1, (3, 4))
+    assert np.array_equal(ER.elastic_volume(vol, m, (1, 1, 1), [0, 0, 0], 3, 1.1, 0.1, 0.05, 9), ER.R.affine_volume(vol, m, 1.1, 0.1, 0.05, 9))
+    moved = ER.elastic_volume(vol, m, (1, 1, 1), [0.8, 0.8, 0.8], 3, 1.1, 0.1, 0.05, 9)
+    assert np.abs(moved - ER.R.affine_volume(vol, m, 1.1, 0.1, 0.05, 9)).max() > 0.01
