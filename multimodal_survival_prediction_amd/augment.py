@@ -43,6 +43,12 @@ AugmentSpec names the distribution, sample_records draws one epoch's records in 
 (turning augmentation on leaves the batch order of a seeded run unchanged; a spec with rot / zoom / noise makes a second call, after
 the first, so the first call's fields are the same with and without them; a spec with elastic makes a third, after those), apply() runs
 the kernel over an already materialised batch.
+
+Between the sampler and the launch the arrays travel as ONE bundle, Records: which arrays a row carries (KINDS: field, words per row,
+entry point, checker, launch block) is decided here and nowhere else.  data.BatchLoader builds a bundle per epoch and slices it per
+batch, training.train_epoch_lockstep groups and stacks the members' bundles (Records.key, Records.stack), FoldGroupEngine stages every
+array a bundle holds and apply() copies them; both validate with Records.check and launch through launch_gather, the one place
+that picks the entry point.
 """
 import ctypes
 import dataclasses
@@ -366,14 +372,20 @@ def affine_records(recs, angles=0.0, zoom=1.0, sigma=0.0, seed=0, dims=None):
     return torch.from_numpy(out)
 
 
+def _host_rows(x, words, what, maker, n=None):
+    """The opening of every check_*: x is a host int32 array of `words` per row (and of n rows) -> its [rows, words] view."""
+    x = torch.as_tensor(x)
+    if x.dtype != torch.int32 or x.shape[-1] != words or x.is_cuda:
+        raise ValueError("%s records must be a host int32 array of %d words per row (augment.%s)" % (what, words, maker))
+    rows = x.reshape(-1, words)
+    if n is not None and rows.shape[0] != n:
+        raise ValueError("augment: one %s record per row, got %d for %d rows" % (what, rows.shape[0], n))
+    return rows
+
+
 def check_affine_records(aff, n=None):
     """Host-side validation of affine records before they reach the kernel: shape, dtype, finite matrices, sigma >= 0."""
-    aff = torch.as_tensor(aff)
-    if aff.dtype != torch.int32 or aff.shape[-1] != AFF_WORDS or aff.is_cuda:
-        raise ValueError("affine records must be a host int32 array of %d words per row (augment.affine_records)" % AFF_WORDS)
-    if n is not None and aff.reshape(-1, AFF_WORDS).shape[0] != n:
-        raise ValueError("augment: one affine record per row, got %d for %d rows" % (aff.reshape(-1, AFF_WORDS).shape[0], n))
-    f = aff.reshape(-1, AFF_WORDS).view(torch.float32)
+    f = _host_rows(aff, AFF_WORDS, "affine", "affine_records", n).view(torch.float32)
     if not bool(torch.isfinite(f[:, :12]).all()):
         raise ValueError("augment: an affine record's matrix is not finite")
     if not bool((f[:, AFF_SIGMA] >= 0).all()) or not bool(torch.isfinite(f[:, AFF_SIGMA]).all()):
@@ -397,12 +409,7 @@ def elastic_records(n, amp=0.0, seed=0):
 def check_elastic_records(ela, n=None, spacing=None):
     """Host-side validation of elastic records before they reach the kernel (which clamps what it is given; the no-folding bound is
     checked HERE): shape, dtype, finite amplitudes in [0, min(64, 0.4 * spacing)] -> per-axis max amplitude (ElaP.max_amp)."""
-    ela = torch.as_tensor(ela)
-    if ela.dtype != torch.int32 or ela.shape[-1] != ELA_WORDS or ela.is_cuda:
-        raise ValueError("elastic records must be a host int32 array of %d words per row (augment.elastic_records)" % ELA_WORDS)
-    rows = ela.reshape(-1, ELA_WORDS)
-    if n is not None and rows.shape[0] != n:
-        raise ValueError("augment: one elastic record per row, got %d for %d rows" % (rows.shape[0], n))
+    rows = _host_rows(ela, ELA_WORDS, "elastic", "elastic_records", n)
     amp = rows.view(torch.float32)[:, :3]
     if not bool(torch.isfinite(amp).all()) or not bool((amp >= 0).all()):
         raise ValueError("augment: elastic amplitudes must be finite and >= 0")
@@ -418,17 +425,15 @@ def check_elastic_records(ela, n=None, spacing=None):
 
 def check_records(rec, dims=None, has_mask=True):
     """Host-side validation of a record array before it reaches the kernel -> per-axis max |shift|."""
-    rec = torch.as_tensor(rec)
-    if rec.dtype != torch.int32 or rec.shape[-1] != REC_WORDS or rec.is_cuda:
-        raise ValueError("augment records must be a host int32 array of %d words per row (augment.make_records)" % REC_WORDS)
-    mx = rec.reshape(-1, REC_WORDS)[:, DZ:DX + 1].abs().amax(0).tolist() if rec.numel() else [0, 0, 0]
+    rec = _host_rows(rec, REC_WORDS, "augment", "make_records")
+    mx = rec[:, DZ:DX + 1].abs().amax(0).tolist() if rec.numel() else [0, 0, 0]
     if dims is not None:
         for a, (s, d) in enumerate(zip(mx, dims)):
             if s >= d:
                 raise ValueError("augment: a record shifts axis %d by %d voxels, the volume's extent is %d" % (a, s, d))
-    if not has_mask and bool((rec.reshape(-1, REC_WORDS)[:, DROP] != 0).any()):
+    if not has_mask and bool((rec[:, DROP] != 0).any()):
         raise ValueError("augment: records drop modalities but the model takes no modality mask")
-    if bool(((rec.reshape(-1, REC_WORDS)[:, FLIP] & ~7) != 0).any()) or bool(((rec.reshape(-1, REC_WORDS)[:, DROP] & ~7) != 0).any()):
+    if bool(((rec[:, FLIP] & ~7) != 0).any()) or bool(((rec[:, DROP] & ~7) != 0).any()):
         raise ValueError("augment: flip and drop hold 3 bits each")
     return [int(x) for x in mx]
 
@@ -468,6 +473,99 @@ def ela_block(ela_dev, spacing, max_amp):
     return E
 
 
+@dataclasses.dataclass(frozen=True)
+class Kind:
+    """One record array a row may carry.  name: its field of Records; words: int32 words per row; entry: the gather entry point that
+    takes the arrays up to and including this one; check(array, dims, has_mask, spacing) -> the bound the launch block carries or
+    None; block(device rows, bound, roles, dims, spacing, stage_floats) -> the launch block; bound: the block's field that is
+    refreshed from the step's records; per_spacing: the block also depends on the lattice spacing."""
+    name: str
+    words: int
+    entry: str
+    check: object
+    block: object
+    bound: str = None
+    per_spacing: bool = False
+
+
+KINDS = (Kind("rec", REC_WORDS, "mms_gather_aug_group", lambda a, dims, has_mask, spacing: check_records(a, dims, has_mask),
+              lambda dev, bound, roles, dims, spacing, stage: aug_block(dev, roles, dims, bound), "max_shift"),
+         Kind("aff", AFF_WORDS, "mms_gather_affine_group", lambda a, dims, has_mask, spacing: check_affine_records(a),
+              lambda dev, bound, roles, dims, spacing, stage: aff_block(dev, stage)),
+         Kind("ela", ELA_WORDS, "mms_gather_elastic_group", lambda a, dims, has_mask, spacing: check_elastic_records(a, spacing=spacing),
+              lambda dev, bound, roles, dims, spacing, stage: ela_block(dev, spacing, bound), "max_amp", True))
+
+
+@dataclasses.dataclass(eq=False)
+class Records:
+    """The augmentation records of some rows, as they travel from the sampler to the gather launch: rec int32 [..., 8]
+    (make_records), aff int32 [..., 16] or None (affine_records), ela int32 [..., 4] or None (elastic_records) over a control lattice
+    of `spacing` voxels (read only with ela).  Leading axes: [B], or [members][B] for a fold group's step.  Which arrays are held
+    decides the launch (kind); every operation is a loop over KINDS."""
+    rec: torch.Tensor
+    aff: torch.Tensor = None
+    ela: torch.Tensor = None
+    spacing: int = 16
+
+    def __post_init__(self):
+        if self.aff is not None and self.rec is None:
+            raise ValueError("affine records come with the 8-word records of the same rows (augment=)")
+        if self.ela is not None and self.aff is None:
+            raise ValueError("elastic records come with the affine records of the same rows (Records.aff; augment.affine_records "
+                             "composes them from flips and shifts alone)")
+        for kd, a in self.held():
+            setattr(self, kd.name, torch.as_tensor(a))
+
+    @classmethod
+    def of(cls, x):
+        """x itself when it is a Records; a bare [..., 8] array or tensor as flips / shifts / intensity / drop only."""
+        return x if isinstance(x, cls) else cls(x)
+
+    @classmethod
+    def stack(cls, items):
+        """The bundles of a group's members, all of one kind and spacing -> one bundle with a new leading axis."""
+        if len({r.key for r in items}) != 1:
+            raise ValueError("augment: the members of one step carry records of one kind and spacing, got %s" % sorted({str(r.key) for r in items}))
+        return cls(*(torch.stack([getattr(r, kd.name) for r in items]) for kd, _ in items[0].held()), spacing=items[0].spacing)
+
+    def held(self):
+        """-> [(Kind, array)] of the arrays this bundle holds, in launch order."""
+        return [(kd, getattr(self, kd.name)) for kd in KINDS if getattr(self, kd.name) is not None]
+
+    def __getitem__(self, i):
+        return Records(*(a[i] for _, a in self.held()), spacing=self.spacing)
+
+    @property
+    def kind(self):
+        """The gather entry point that takes this bundle."""
+        return self.held()[-1][0].entry
+
+    @property
+    def key(self):
+        """What two bundles must share to ride one launch."""
+        return self.kind, (self.spacing if self.ela is not None else None)
+
+    def check(self, shape, dims=None, has_mask=True):
+        """Host-side validation before the records reach a kernel: every array's leading shape, then each kind's own rules and the
+        lattice's fit into dims -> (per-axis max |shift|, per-axis max elastic amplitude; zeros where absent)."""
+        for kd, a in self.held():
+            if tuple(a.shape) != tuple(shape) + (kd.words,):
+                raise ValueError("augment: %s must hold %s rows of %d words, got %r" % (kd.name, "x".join(str(n) for n in shape), kd.words, tuple(a.shape)))
+        bound = {kd.name: kd.check(a, dims, has_mask, self.spacing) for kd, a in self.held()}
+        if self.ela is not None:
+            _check_spacing(self.spacing, dims)
+        return bound["rec"], bound.get("ela", [0.0, 0.0, 0.0])
+
+
+def launch_gather(lib, G, A=None, F=None, E=None, ng=1):
+    """The batch-assembly launch over ng members: G their GatherP, A / F / E their AugP / AffP / ElaP (arrays or references) as far as
+    the rows carry records -- mms_gather_rows_group without any, else the entry point of the last kind given."""
+    from . import _lib, ops
+    blocks = [b for b in (A, F, E) if b is not None]
+    name = KINDS[len(blocks) - 1].entry if blocks else "mms_gather_rows_group"
+    _lib.check(getattr(lib, name)(G, *blocks, ng, ops.stream()), name)
+
+
 def displacement_field(records, dims, spacing):
     """The displacement field d of elastic records (mms_elastic_field: the device function the gather kernel calls) ->
     [n, 3, D, H, W] fp32 on the GPU; d[i, a] is the displacement along axis a (D / H / W) in voxels."""
@@ -486,30 +584,19 @@ def displacement_field(records, dims, spacing):
     return out
 
 
-def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0, elastic=None, elastic_spacing=16):
+def apply(batch, records, present_ok=(True, True), stage_floats=0):
     """The augmenting gather over an already materialised batch (device tensors image / rnaseq / clinical / mask as
-    data.BatchLoader yields them), out of place, identity indices: -> the batch dict with those four replaced.  present_ok: per
-    (image, rnaseq) whether rows whose mask column is 0 are known to be all-zero in the cohort (then they are not read, as in
-    SurvivalEngine.gather_block).  affine: [B, 16] affine records (affine_records): the launch is then mms_gather_affine_group, which
-    ignores the records' flip / shift.  elastic: [B, 4] elastic records (elastic_records) over a lattice of elastic_spacing voxels: the
-    launch is mms_gather_elastic_group; without `affine` the matrices are composed from the records' flips and shifts."""
+    data.BatchLoader yields them), out of place, identity indices: -> the batch dict with those four replaced.  records: the rows'
+    Records, or a bare [B, 8] array (flips / shifts / intensity / drop only); the arrays the bundle holds decide the launch
+    (Records.kind), and the affine and elastic launches ignore the 8-word records' flip / shift.  present_ok: per (image, rnaseq)
+    whether rows whose mask column is 0 are known to be all-zero in the cohort (data.absent_rows_zero; then they are not read).
+    stage_floats: AffP.stage_floats (aff_block)."""
     from . import _lib, ops
+    recs = Records.of(records)
     img, rna, clin, mask = batch["image"], batch["rnaseq"], batch["clinical"], batch["mask"]
     B, dims = img.shape[0], tuple(img.shape[-3:])
-    rec = torch.as_tensor(records)
-    if rec.shape != (B, REC_WORDS):
-        raise ValueError("augment.apply: one record per batch row, got %r for %d rows" % (tuple(rec.shape), B))
-    mx = check_records(rec, dims)
-    if affine is not None:
-        affine = torch.as_tensor(affine)
-        check_affine_records(affine, B)
-    if elastic is not None:
-        elastic = torch.as_tensor(elastic)
-        ela_mx = check_elastic_records(elastic, B, elastic_spacing)
-        _check_spacing(elastic_spacing, dims)
-        if affine is None:
-            affine = affine_records(rec, dims=dims)
-    S = _lib.structs()
+    mx, amp = recs.check((B,), dims)
+    bound = dict(rec=mx if recs.aff is None else (0, 0, 0), ela=amp)      # (only mms_gather_aug_group reads the records' shifts)
     dev = img.device
     mask = mask.contiguous()
     srcs = [(img.reshape(B, -1), ROLE_VOLUME, 0, mask if present_ok[0] else None),
@@ -517,32 +604,13 @@ def apply(batch, records, present_ok=(True, True), affine=None, stage_floats=0, 
             (clin.reshape(B, -1), ROLE_PLAIN, 2, None), (mask, ROLE_MASK, -1, None)]
     outs = [torch.empty_like(a) for a, _, _, _ in srcs]
     idx = torch.arange(B, dtype=torch.int64, device=dev)
-    rec_dev = rec.to(dev)
-    G = S["GatherP"]()
-    G.idx, G.B, G.nsrc = idx.data_ptr(), B, len(srcs)
-    roles = []
-    for i, ((a, role, bit, flag), o) in enumerate(zip(srcs, outs)):
-        if a.dtype != torch.float32 or not a.is_cuda:
-            raise TypeError("augment.apply works on fp32 device tensors: keep the cohort in HBM (data.cohort_to) or let a lazy loader name "
-                            "the batches of a pinned-host cohort (the gather launch then augments them)")
-        G.src[i], G.dst[i], G.src_ld[i], G.dst_ld[i], G.width[i] = a.data_ptr(), o.data_ptr(), a.stride(0), o.stride(0), a.shape[1]
-        if flag is not None:
-            G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
-        roles.append((role, bit))
-    A = aug_block(rec_dev, roles, dims, mx)
-    if affine is not None:
-        aff_dev = affine.reshape(B, AFF_WORDS).to(dev)
-        F = aff_block(aff_dev, stage_floats)
-    if elastic is not None:
-        ela_dev = elastic.reshape(B, ELA_WORDS).to(dev)
-        E = ela_block(ela_dev, elastic_spacing, ela_mx)
-        _lib.check(_lib.load_library().mms_gather_elastic_group(ctypes.byref(G), ctypes.byref(A), ctypes.byref(F), ctypes.byref(E), 1,
-                                                                ops.stream()), "mms_gather_elastic_group")
-    elif affine is not None:
-        _lib.check(_lib.load_library().mms_gather_affine_group(ctypes.byref(G), ctypes.byref(A), ctypes.byref(F), 1, ops.stream()),
-                   "mms_gather_affine_group")
-    else:
-        _lib.check(_lib.load_library().mms_gather_aug_group(ctypes.byref(G), ctypes.byref(A), 1, ops.stream()), "mms_gather_aug_group")
+    G = ops.gather_params(idx, B, [(a, o, None, flag) for (a, _, _, flag), o in zip(srcs, outs)],
+                          device_only="augment.apply works on fp32 device tensors: keep the cohort in HBM (data.cohort_to) or let a lazy "
+                                      "loader name the batches of a pinned-host cohort (the gather launch then augments them)")
+    roles = [(role, bit) for _, role, bit, _ in srcs]
+    devs = [a.to(dev) for _, a in recs.held()]
+    blocks = [kd.block(d, bound.get(kd.name), roles, dims, recs.spacing, stage_floats) for (kd, _), d in zip(recs.held(), devs)]
+    launch_gather(_lib.load_library(), ctypes.byref(G), *(ctypes.byref(b) for b in blocks))
     out = dict(batch)
     out["image"], out["rnaseq"], out["clinical"], out["mask"] = (outs[0].view(img.shape), outs[1], outs[2].view(clin.shape), outs[3])
     return out

@@ -90,6 +90,18 @@ def gather_view(cohort, with_valid):
     return cohort[key]
 
 
+def absent_rows_zero(cohort):
+    """Per (image, rnaseq): the rows of patients whose mask column is 0 are all-zero in the cohort, as the reference's dataset makes
+    them (partial_modality_training.py:96-141) -- a gather launch may then zero-fill them instead of reading them.  Checked once per
+    cohort dict."""
+    chk = cohort.setdefault("_absent_rows_zero", {})
+    for j, key in enumerate(("image", "rnaseq")):
+        if key not in chk:
+            gone = cohort["mask"][:, j] == 0
+            chk[key] = bool((cohort[key][gone] == 0).all()) if bool(gone.any()) else True
+    return chk["image"], chk["rnaseq"]
+
+
 class BatchLoader:
     """Minimal DataLoader stand-in over a tensor-resident cohort: yields the reference's batch dicts.
     shuffle uses its own seeded generator; drop_last=False like the reference's DataLoader calls.
@@ -98,13 +110,12 @@ class BatchLoader:
     ~8 indexing kernels + copies per fold and batch here.
     augment (an augment.AugmentSpec or its string; the reference dataset's unused `transform=` hook): every epoch draws one record
     per row from a generator of the loader's own -- the shuffle generator, hence the batch order, is the same with and without it.
-    A lazy loader adds augment=<records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them inside its
-    gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both yield the
-    same augmented batches.  A spec with rot / zoom / noise (AugmentSpec.has_affine) draws a second, 16-word record per row: a lazy loader
-    adds augment_affine=<rows> next to augment, a materialising one hands them to augment.apply(affine=).  A spec with elastic
-    (AugmentSpec.has_elastic) draws a third, 4-word record per row: a lazy loader adds augment_elastic=<rows> and
-    augment_elastic_spacing=<voxels> (and always augment_affine: the elastic launch takes matrices), a materialising one hands them to
-    augment.apply(elastic=).  augment_style: the model style ("partial", "final", ...) the spec is checked against.
+    A lazy loader adds augment=<augment.Records of this batch> to the named batch (FoldGroupEngine.train_step_indexed applies them
+    inside its gather launch); any other loader applies them to the batch it materialises (augment.apply: the same kernel), so both
+    yield the same augmented batches.  The bundle holds what the spec draws per row: the 8-word records always, 16-word affine records
+    (.aff) with rot / zoom / noise (AugmentSpec.has_affine), 4-word elastic records and their lattice spacing (.ela, .spacing) with
+    elastic (AugmentSpec.has_elastic; then always .aff too: the elastic launch takes matrices).
+    augment_style: the model style ("partial", "final", ...) the spec is checked against.
     fold: which cross-validation fold the loader belongs to.  Only read over a cohort that carries per-fold gene matrices
     (gene_select.GeneSelection.apply): the batches a loader materialises itself then take their rnaseq rows from that fold's [N, k]
     matrix (a lazy loader names rows only; the fold group's gather launch picks the matrix, FoldGroupEngine(folds=))."""
@@ -140,32 +151,20 @@ class BatchLoader:
         ld.augment = None
         return ld
 
-    def _present_ok(self):
-        """Per (image, rnaseq): rows whose mask column is 0 are all-zero in the cohort (checked once; SurvivalEngine.gather_block)."""
-        chk = self.c.setdefault("_absent_rows_zero", {})
-        for j, key in enumerate(("image", "rnaseq")):
-            if key not in chk:
-                gone = self.c["mask"][:, j] == 0
-                chk[key] = bool((self.c[key][gone] == 0).all()) if bool(gone.any()) else True
-        return chk["image"], chk["rnaseq"]
-
     def __iter__(self):
         idx = self.idx[torch.randperm(len(self.idx), generator=self.gen)] if self.shuffle else self.idx
         dev = self.c["image"].device
-        recs = aff = ela = None
+        recs = None
         if self.augment is not None:         # one vectorised draw per epoch (a second one for rot / zoom / noise, a third for elastic)
-            recs, aff, ela = _augment.sample_all(self.augment, self.aug_gen, self.mask_cpu[idx.long()], tuple(self.c["image"].shape[-3:]),
-                                                 self.augment_style)
+            recs = _augment.Records(*_augment.sample_all(self.augment, self.aug_gen, self.mask_cpu[idx.long()],
+                                                         tuple(self.c["image"].shape[-3:]), self.augment_style),
+                                    spacing=self.augment.elastic_spacing)
         for i in range(0, len(idx), self.bs):
             if self.lazy:
                 jj = idx[i:i + self.bs]
                 b = dict(index=jj, has_survival=[self.hs_cpu[int(k)] for k in jj], gather=self.view)
                 if recs is not None:
                     b["augment"] = recs[i:i + self.bs]
-                if aff is not None:
-                    b["augment_affine"] = aff[i:i + self.bs]
-                if ela is not None:
-                    b["augment_elastic"], b["augment_elastic_spacing"] = ela[i:i + self.bs], self.augment.elastic_spacing
                 yield b
                 continue
             j = idx[i:i + self.bs].to(dev)
@@ -176,8 +175,7 @@ class BatchLoader:
                 b["time"] = self.c["label"][j, 0:1]
                 b["event"] = self.c["label"][j, 1:2].long()
             if recs is not None:
-                kw = {} if ela is None else dict(elastic=ela[i:i + self.bs], elastic_spacing=self.augment.elastic_spacing)
-                b = _augment.apply(b, recs[i:i + self.bs], self._present_ok(), affine=None if aff is None else aff[i:i + self.bs], **kw)
+                b = _augment.apply(b, recs[i:i + self.bs], absent_rows_zero(self.c))
             yield b
 
 

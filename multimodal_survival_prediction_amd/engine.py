@@ -861,43 +861,20 @@ class SurvivalEngine:
             P.valid.copy_(valid.reshape(-1).to(torch.float32), non_blocking=True)
 
     def gather_block(self, P, cohort, idx_dev, fold=None):
-        """GatherP (include/mmsurv.h) that assembles this plan's batch from a cohort dict (data.make_cohort) that lives in HBM
+        """-> (GatherP (include/mmsurv.h) that assembles this plan's batch from a cohort dict (data.make_cohort) that lives in HBM
         (data.cohort_to) or in pinned host memory (data.cohort_pin: the gather launch then reads the rows over PCIe): image, rnaseq,
-        clinical, mask, label[time, event] and, when present, a float per-patient `valid` column.  idx_dev: [B] int64 device tensor
-        that the caller refills before each launch.  With a modality mask in the cohort, image / rnaseq rows of patients without that
-        modality are zero-filled instead of read -- after checking once that they are all-zero in the cohort, as the reference's
-        dataset makes them (partial_modality_training.py:96-141).  fold: over a cohort with per-fold gene matrices
+        clinical, mask, label[time, event] and, when present, a float per-patient `valid` column;  per source (role, drop bit): what it
+        is to augmentation records (augment.aug_block) -- the CT volume, a row that modality j's drop bit zero-fills, a mask whose
+        column j that bit clears, a plain copy).  idx_dev: [B] int64 device tensor that the caller refills before each launch.  With
+        a modality mask in the cohort, image / rnaseq rows of patients without that modality are zero-filled instead of read where
+        they are all-zero in the cohort (data.absent_rows_zero).  fold: over a cohort with per-fold gene matrices
         (gene_select.GeneSelection.apply) the rnaseq source -- pointer, pitch and width -- is that fold's [N, k] matrix."""
-        G, _ = self._gather_sources(P, cohort, idx_dev, fold)
-        return G
-
-    def gather_aug_blocks(self, P, cohort, idx_dev, rec_dev, aff_dev=None, fold=None):
-        """(GatherP, AugP) of mms_gather_aug_group: gather_block's sources plus what each of them is to the augmentation records
-        rec_dev ([B, 8] int32 device tensor, augment.make_records) -- the CT volume, a row that modality j's drop bit zero-fills,
-        a mask whose column j that bit clears.  time / event / valid are plain copies.  aff_dev ([B, 16] int32 device tensor,
-        augment.affine_records): -> (GatherP, AugP, AffP), the blocks of mms_gather_affine_group."""
-        from . import augment
-        G, roles = self._gather_sources(P, cohort, idx_dev, fold)
-        dims = tuple(P.ct.shape[-3:]) if P.has_enc else None
-        A = augment.aug_block(rec_dev, roles, dims, (0, 0, 0))
-        return (G, A) if aff_dev is None else (G, A, augment.aff_block(aff_dev))
-
-    def _gather_sources(self, P, cohort, idx_dev, fold=None):
-        """-> (GatherP, per source (augment role, drop bit)).  A source is (cohort tensor, destination, width or None = all columns,
-        availability flags or None, role, modality whose drop bit zero-fills it or -1)."""
         from .augment import ROLE_MASK, ROLE_PLAIN, ROLE_VOLUME
-        G = _S()["GatherP"]()
-        G.idx, G.B = idx_dev.data_ptr(), P.B
+        from .data import absent_rows_zero
         flags = {}
         if "mask" in cohort:
-            chk = cohort.setdefault("_absent_rows_zero", {})
-            for j, key in enumerate(("image", "rnaseq")):
-                if key not in chk:
-                    gone = cohort["mask"][:, j] == 0
-                    chk[key] = bool((cohort[key][gone] == 0).all()) if bool(gone.any()) else True
-                if chk[key]:
-                    flags[key] = cohort["mask"][:, j:]
-        srcs = []
+            flags = {key: cohort["mask"][:, j:] for j, (key, ok) in enumerate(zip(("image", "rnaseq"), absent_rows_zero(cohort))) if ok}
+        srcs = []        # (cohort tensor, destination, width or None = all columns, availability flags or None, role, drop bit or -1)
         if "rna" in P.buf:
             rna = cohort["rnaseq"]
             if "rnaseq_folds" in cohort:         # per-fold gene selection: this member's own [N, k] matrix (a zero row keeps zero columns)
@@ -919,16 +896,7 @@ class SurvivalEngine:
         srcs.append((lab[:, 1:], P.event.view(P.B, 1), 1, None, ROLE_PLAIN, -1))
         if "valid" in cohort:
             srcs.append((cohort["valid"].view(-1, 1), P.valid.view(P.B, 1), 1, None, ROLE_PLAIN, -1))
-        G.nsrc = len(srcs)
-        for i, (a, b, w, flag, _, _) in enumerate(srcs):
-            if a.dtype != torch.float32 or not (a.is_cuda or a.is_pinned()):
-                raise TypeError("gather sources must be fp32 tensors in device or pinned host memory")
-            G.src[i], G.dst[i] = a.data_ptr(), b.data_ptr()
-            G.src_ld[i], G.dst_ld[i] = a.stride(0), b.stride(0)
-            G.width[i] = w if w is not None else a.shape[1]
-            if flag is not None:
-                G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
-        return G, [(role, bit) for *_, role, bit in srcs]
+        return ops.gather_params(idx_dev, P.B, [s[:4] for s in srcs]), [s[4:] for s in srcs]
 
     def train_step(self, ct=None, rna=None, clinical=None, mask=None, time=None, event=None, valid=None, skip_if_unusable=True,
                    use_graph=True, ddp_world=1, global_cox=False, sync_bn=False):

@@ -17,7 +17,7 @@ import ctypes
 
 import torch
 
-from . import _lib, ops
+from . import _lib, augment as _augment, ops
 from .engine import SurvivalEngine, capture, check_attribute, gate_out, group_widths_ok
 
 _S = _lib.structs
@@ -301,128 +301,81 @@ class FoldGroupEngine:
             e.load_batch(P, **b)
         self._step(GP, skip_if_unusable, use_graph)
 
-    def _gather_indexed(self, GP, cohort, idx, augment=None, affine=None, elastic=None, elastic_spacing=16):
-        """Index copy (pinned ring -> device) + the ONE gather launch that assembles the group's batches in the plans' input buffers.
-        augment: [len(members)][B] records (augment.make_records) -- they ride the same pinned ring as the indices and the launch
-        is mms_gather_aug_group; affine: [len(members)][B] affine records (augment.affine_records) beside them -- the launch is
-        mms_gather_affine_group; elastic: [len(members)][B] elastic records (augment.elastic_records) over a lattice of
-        elastic_spacing voxels, a third ring beside those two -- the launch is mms_gather_elastic_group; None: today's path."""
-        members, B = GP.members, GP.B
-        key = id(cohort)
+    def _ring(self, GP, cohort):
+        """Per (plan, cohort): the members' GatherP array and the staging ring that feeds it.  A lane is one device buffer plus one
+        pinned buffer per slot; lane "idx" holds the indices, a lane per record kind is added on first use (_lane).  The async copy
+        reads a pinned buffer when the stream gets there, so a slot is only rewritten after the event recorded behind its previous
+        copies -- one event per slot covers all lanes."""
         cache = GP.__dict__.setdefault("gather", {})
-        if key not in cache:
-            dev_idx = torch.zeros(len(members), B, dtype=torch.int64, device=self.device)
-            # ring of pinned staging buffers: the async copy reads the buffer when the stream gets there, so a buffer is
-            # only rewritten after the event recorded behind its previous copy has completed
-            pin = dict(bufs=[torch.zeros(len(members), B, dtype=torch.int64).pin_memory() for _ in range(4)],
-                       evs=[None] * 4, k=0)
-            blocks = _arr([e.gather_block(P, cohort, dev_idx[g], fold=self.folds[GP.members[g]]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))])
-            for e, P in zip(GP.eng, GP.Ps):
-                if "valid" not in cohort:
+        if id(cohort) not in cache:
+            ring = dict(lanes={}, evs=[None] * 4, k=0, blocks={}, cohort=cohort)       # the cohort reference keeps the source pointers alive
+            dev_idx, _ = self._lane(ring, "idx", (GP.ng, GP.B), torch.int64)
+            pairs = [e.gather_block(P, cohort, dev_idx[g], fold=self.folds[GP.members[g]]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))]
+            ring["G"], ring["roles"] = _arr([G for G, _ in pairs]), [roles for _, roles in pairs]
+            if "valid" not in cohort:
+                for P in GP.Ps:
                     P.valid.fill_(1.0)
-            cache[key] = (dev_idx, pin, blocks, cohort)       # the cohort reference keeps the source pointers alive
-        dev_idx, pin, blocks, _ = cache[key]
-        if affine is not None and augment is None:
-            raise ValueError("affine records come with the 8-word records of the same rows (augment=)")
-        if elastic is not None and affine is None:
-            raise ValueError("elastic records come with the affine records of the same rows (augment_affine=; augment.affine_records "
-                             "composes them from flips and shifts alone)")
-        if augment is not None:          # (validated before the ring is touched: a refused step leaves no copy without its event)
-            aug = self._aug_blocks(GP, cohort, dev_idx, pin, augment, affine, elastic, elastic_spacing)
-        k = pin["k"]
-        pin["k"] = (k + 1) % len(pin["bufs"])
-        if pin["evs"][k] is not None:
-            pin["evs"][k].synchronize()
-        pin["bufs"][k].copy_(idx)
-        dev_idx.copy_(pin["bufs"][k], non_blocking=True)
-        if augment is not None:
-            aug["pin"][k].copy_(augment)               # (slot k's event above covers this buffer too)
-            aug["dev"].copy_(aug["pin"][k], non_blocking=True)
-        if affine is not None:
-            aug["aff_pin"][k].copy_(affine)
-            aug["aff_dev"].copy_(aug["aff_pin"][k], non_blocking=True)
-        if elastic is not None:
-            aug["ela_pin"][k].copy_(elastic)
-            aug["ela_dev"].copy_(aug["ela_pin"][k], non_blocking=True)
+            cache[id(cohort)] = ring
+        return cache[id(cohort)]
+
+    def _lane(self, ring, name, shape, dtype):
+        if name not in ring["lanes"]:
+            ring["lanes"][name] = (torch.zeros(shape, dtype=dtype, device=self.device),
+                                   [torch.zeros(shape, dtype=dtype).pin_memory() for _ in ring["evs"]])
+        return ring["lanes"][name]
+
+    def _gather_indexed(self, GP, cohort, idx, augment=None):
+        """Index copy (pinned ring -> device) + the ONE gather launch that assembles the group's batches in the plans' input buffers.
+        augment: [len(members)][B] augment.Records (or bare 8-word records): every array they hold rides the ring in a lane of its
+        own and decides the launch (augment.launch_gather); None: the plain gather."""
+        ring = self._ring(GP, cohort)
+        recs = None if augment is None else _augment.Records.of(augment)
+        # (validated before the ring is touched: a refused step leaves no copy without its event)
+        blocks = [] if recs is None else self._aug_blocks(GP, ring, recs)
+        k = ring["k"]
+        ring["k"] = (k + 1) % len(ring["evs"])
+        if ring["evs"][k] is not None:
+            ring["evs"][k].synchronize()
+        for name, src in [("idx", idx)] + ([] if recs is None else [(kd.name, a) for kd, a in recs.held()]):
+            dev, pin = ring["lanes"][name]
+            pin[k].copy_(src)
+            dev.copy_(pin[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        pin["evs"][k] = ev
-        if elastic is not None:
-            _lib.check(self.lib.mms_gather_elastic_group(aug["gather"], aug["aug"], aug["aff"], aug["ela"][elastic_spacing], GP.ng, ops.stream()),
-                       "mms_gather_elastic_group")
-            return
-        if affine is not None:
-            _lib.check(self.lib.mms_gather_affine_group(aug["gather"], aug["aug"], aug["aff"], GP.ng, ops.stream()), "mms_gather_affine_group")
-            return
-        if augment is not None:
-            _lib.check(self.lib.mms_gather_aug_group(aug["gather"], aug["aug"], GP.ng, ops.stream()), "mms_gather_aug_group")
-            return
-        _lib.check(self.lib.mms_gather_rows_group(blocks, GP.ng, ops.stream()), "mms_gather_rows_group")
+        ring["evs"][k] = ev
+        _augment.launch_gather(self.lib, ring["G"], *blocks, ng=GP.ng)
 
-    def _aug_blocks(self, GP, cohort, dev_idx, pin, augment, affine=None, elastic=None, elastic_spacing=16):
-        """Per (plan, cohort): device + pinned record buffers and the (GatherP, AugP) arrays of mms_gather_aug_group -- with affine
-        records also theirs and the AffP array of mms_gather_affine_group, with elastic records theirs and the ElaP array of
-        mms_gather_elastic_group (one per spacing); validates the step's records on the host (they are host
-        data) so that the launch cannot be refused with a bare code."""
-        from . import augment as A
+    def _aug_blocks(self, GP, ring, recs):
+        """Validates the step's records on the host (they are host data, so the launch cannot be refused with a bare code) -> the
+        members' launch block arrays [AugP, AffP, ElaP][:kinds held] over the ring's record lanes.  Lanes and arrays are created on
+        first use of a kind (ElaP: one array per spacing); the bounds the blocks carry are refreshed from this step's records."""
         has_mask = all(P.gate is not None or P.moe is not None or P.mix is not None for P in GP.Ps)
-        if tuple(augment.shape) != (len(GP.members), GP.B, A.REC_WORDS):
-            raise ValueError("augment must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
-                             % (A.REC_WORDS, tuple(augment.shape), len(GP.members), GP.B))
-        mx = A.check_records(augment, GP.dims if GP.has_enc else None, has_mask)
-        if affine is not None:
-            if tuple(affine.shape) != (len(GP.members), GP.B, A.AFF_WORDS):
-                raise ValueError("augment_affine must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
-                                 % (A.AFF_WORDS, tuple(affine.shape), len(GP.members), GP.B))
-            A.check_affine_records(affine)
-            mx = [0, 0, 0]               # (mms_gather_affine_group does not read the records' shifts)
-        if elastic is not None:
-            if tuple(elastic.shape) != (len(GP.members), GP.B, A.ELA_WORDS):
-                raise ValueError("augment_elastic must be [len(members)][B] records of %d words, got %r for %d members of %d rows"
-                                 % (A.ELA_WORDS, tuple(elastic.shape), len(GP.members), GP.B))
-            ela_mx = A.check_elastic_records(elastic, spacing=elastic_spacing)
-            if GP.has_enc:
-                A._check_spacing(elastic_spacing, GP.dims)
-        cache = GP.__dict__.setdefault("gather_aug", {})
-        key = id(cohort)
-        if key not in cache:
-            dev = torch.zeros(len(GP.members), GP.B, A.REC_WORDS, dtype=torch.int32, device=self.device)
-            pairs = [e.gather_aug_blocks(P, cohort, dev_idx[g], dev[g], fold=self.folds[GP.members[g]]) for g, (e, P) in enumerate(zip(GP.eng, GP.Ps))]
-            cache[key] = dict(dev=dev, pin=[torch.zeros(dev.shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]],
-                              gather=_arr([g for g, _ in pairs]), aug=_arr([a for _, a in pairs]))
-        aug = cache[key]
-        if affine is not None and "aff" not in aug:
-            aug["aff_dev"] = torch.zeros(len(GP.members), GP.B, A.AFF_WORDS, dtype=torch.int32, device=self.device)
-            aug["aff_pin"] = [torch.zeros(aug["aff_dev"].shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]]
-            aug["aff"] = _arr([A.aff_block(aug["aff_dev"][g]) for g in range(GP.ng)])
-        if elastic is not None:
-            if "ela_dev" not in aug:
-                aug["ela_dev"] = torch.zeros(len(GP.members), GP.B, A.ELA_WORDS, dtype=torch.int32, device=self.device)
-                aug["ela_pin"] = [torch.zeros(aug["ela_dev"].shape, dtype=torch.int32).pin_memory() for _ in pin["bufs"]]
-                aug["ela"] = {}
-            if elastic_spacing not in aug["ela"]:
-                aug["ela"][elastic_spacing] = _arr([A.ela_block(aug["ela_dev"][g], elastic_spacing, ela_mx) for g in range(GP.ng)])
-            for g in range(GP.ng):       # (one bound per launch: the largest amplitude of the step's records, every member)
-                for a in range(3):
-                    aug["ela"][elastic_spacing][g].max_amp[a] = ela_mx[a]
-        for g in range(GP.ng):
-            for a in range(3):
-                aug["aug"][g].max_shift[a] = mx[a]
-        return aug
+        dims = GP.dims if GP.has_enc else None
+        mx, amp = recs.check((GP.ng, GP.B), dims, has_mask)
+        bound = dict(rec=mx if recs.aff is None else [0, 0, 0], ela=amp)       # (only mms_gather_aug_group reads the records' shifts)
+        out = []
+        for kd, _ in recs.held():
+            dev, _ = self._lane(ring, kd.name, (GP.ng, GP.B, kd.words), torch.int32)
+            key = (kd.name, recs.spacing if kd.per_spacing else None)
+            if key not in ring["blocks"]:
+                ring["blocks"][key] = _arr([kd.block(dev[g], bound.get(kd.name), ring["roles"][g], dims, recs.spacing, 0) for g in range(GP.ng)])
+            if kd.bound:         # (one bound per launch: the largest of the step's records, every member)
+                for g in range(GP.ng):
+                    getattr(ring["blocks"][key][g], kd.bound)[:] = bound[kd.name]
+            out.append(ring["blocks"][key])
+        return out
 
-    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None, augment_affine=None,
-                           augment_elastic=None, elastic_spacing=16):
+    def train_step_indexed(self, cohort, indices, members=None, skip_if_unusable=True, use_graph=True, augment=None):
         """Same step with the batches named by patient indices into a cohort that lives in HBM (data.cohort_to) or in pinned host
         memory (data.cohort_pin: the gather launch reads the rows over PCIe): indices: [len(members)][B] integer array-like (host).  The batch assembly of the whole group is one small
         host-to-device copy of the indices plus ONE gather launch (mms_gather_rows_group) instead of ~10 torch
-        indexing/copy kernels per member.  augment: [len(members)][B] augmentation records (augment.make_records /
-        augment.sample_records, host int32): the gather launch applies them while it copies (mms_gather_aug_group: CT flips, shifts
-        and intensity map, modality dropout); None: no augmentation, the plain gather.  augment_affine: [len(members)][B] affine records
-        (augment.affine_records / augment.sample) of the same rows: the launch is mms_gather_affine_group (rotation / zoom resampling,
-        additive noise; the flip / shift fields of `augment` are not read, they are folded into the matrices).  augment_elastic:
-        [len(members)][B] elastic records (augment.elastic_records / augment.sample_all) of the same rows over a control lattice of
-        elastic_spacing voxels, beside augment_affine: the launch is mms_gather_elastic_group (free-form deformation before the affine
-        map)."""
+        indexing/copy kernels per member.  augment: the rows' augmentation records, an augment.Records with leading axes
+        [len(members)][B] (Records.stack of the members' bundles, as a lazy data.BatchLoader yields them) or a bare [len(members)][B]
+        array of 8-word records (augment.make_records / augment.sample_records, host int32): the gather launch applies them while it
+        copies -- CT flips, shifts and intensity map, modality dropout (mms_gather_aug_group); with affine records rotation / zoom
+        resampling and additive noise (mms_gather_affine_group; the flip / shift fields of the 8-word records are not read, they are
+        folded into the matrices); with elastic records a free-form deformation before the affine map (mms_gather_elastic_group).
+        None: no augmentation, the plain gather."""
         members = self._members(members)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         if idx.dim() != 2 or idx.shape[0] != len(members):
@@ -431,9 +384,7 @@ class FoldGroupEngine:
         dims = tuple(cohort["image"].shape[-3:]) if self.engines[0].prog["encoder"] is not None else None
         self.engines[0].check_train_batch(B, dims)
         GP = self.plan(B, dims, members)
-        self._gather_indexed(GP, cohort, idx, None if augment is None else torch.as_tensor(augment),
-                             None if augment_affine is None else torch.as_tensor(augment_affine),
-                             None if augment_elastic is None else torch.as_tensor(augment_elastic), elastic_spacing)
+        self._gather_indexed(GP, cohort, idx, augment)
         self._step(GP, skip_if_unusable, use_graph)
 
     def _eval_loss_body(self, GP):

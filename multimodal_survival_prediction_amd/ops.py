@@ -263,6 +263,22 @@ def zero_spans(tensors):
     return (S * len(tensors))(*[S(t.data_ptr(), t.numel() * t.element_size()) for t in tensors])
 
 
+def gather_params(idx_dev, B, srcs, device_only=None):
+    """GatherP (include/mmsurv.h) of B rows named by idx_dev over srcs = [(source, destination, width or None = all columns,
+    availability flags or None)]: fp32 rows in device or pinned host memory (the caller keeps them alive).  device_only: the message
+    that refuses pinned sources too."""
+    G = _S()["GatherP"]()
+    G.idx, G.B, G.nsrc = idx_dev.data_ptr(), B, len(srcs)
+    for i, (a, b, w, flag) in enumerate(srcs):
+        if a.dtype != torch.float32 or not (a.is_cuda or (device_only is None and a.is_pinned())):
+            raise TypeError(device_only or "gather sources must be fp32 tensors in device or pinned host memory")
+        G.src[i], G.dst[i], G.src_ld[i], G.dst_ld[i] = a.data_ptr(), b.data_ptr(), a.stride(0), b.stride(0)
+        G.width[i] = w if w is not None else a.shape[1]
+        if flag is not None:
+            G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
+    return G
+
+
 TIE_MODES = {"breslow": 0, "efron": 1}
 
 

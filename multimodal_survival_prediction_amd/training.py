@@ -388,6 +388,7 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
     (one sub-group's latency-bound kernels overlap the others').  Every member's loader is iterated under its sub-group's
     stream, so batch tensors are allocated and consumed on the same stream.
     -> per member, what train_epoch_<style> returns for that fold."""
+    from .augment import Records             # (augment imports this module's style table)
     row = _STYLES[style]
     members = tuple(range(len(group))) if members is None else tuple(members)
     for g in members:
@@ -406,16 +407,11 @@ def train_epoch_lockstep(group, loaders, style, members=None, concurrent=1):
             for g, b in lazy:
                 if row.pre_skip and _n_labelled(b) < 2:
                     continue                          # skipped before the forward
-                by.setdefault((len(b["index"]), id(b["gather"]), "augment" in b, "augment_affine" in b,
-                               b.get("augment_elastic_spacing")), []).append((g, b))
+                by.setdefault((len(b["index"]), id(b["gather"]), b["augment"].key if "augment" in b else None), []).append((g, b))
             for items in by.values():                 # (named batches that carry augmentation records: applied inside the gather launch)
-                aug = torch.stack([b["augment"] for _, b in items]) if "augment" in items[0][1] else None
-                kw = dict(augment_affine=torch.stack([b["augment_affine"] for _, b in items])) if "augment_affine" in items[0][1] else {}
-                if "augment_elastic" in items[0][1]:
-                    kw.update(augment_elastic=torch.stack([b["augment_elastic"] for _, b in items]),
-                              elastic_spacing=items[0][1]["augment_elastic_spacing"])
+                aug = Records.stack([b["augment"] for _, b in items]) if "augment" in items[0][1] else None
                 group.train_step_indexed(items[0][1]["gather"], torch.stack([torch.as_tensor(b["index"]) for _, b in items]),
-                                         members=tuple(g for g, _ in items), skip_if_unusable=row.skip_if_unusable, augment=aug, **kw)
+                                         members=tuple(g for g, _ in items), skip_if_unusable=row.skip_if_unusable, augment=aug)
             pos = {g: b for g, b in pos.items() if "gather" not in b}
         by_size = {}
         for g, batch in pos.items():

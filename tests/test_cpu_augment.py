@@ -51,9 +51,9 @@ def test_sampler_is_deterministic():
     # the loader's two epochs differ (the generator advances), two loaders with one seed agree
     mk = lambda: data.BatchLoader(c, torch.arange(48), 4, shuffle=True, seed=5, lazy=True, augment=spec, augment_style="partial")
     a, b = mk(), mk()
-    e1 = torch.cat([x["augment"] for x in a])
-    assert torch.equal(e1, torch.cat([x["augment"] for x in b]))
-    assert not torch.equal(e1, torch.cat([x["augment"] for x in a]))
+    e1 = torch.cat([x["augment"].rec for x in a])
+    assert torch.equal(e1, torch.cat([x["augment"].rec for x in b]))
+    assert not torch.equal(e1, torch.cat([x["augment"].rec for x in a]))
 
 
 def test_batch_order_is_unchanged_by_a_spec():

@@ -81,11 +81,11 @@ def test_loaders_carry_the_second_record():
     c = _cohort()
     mk = lambda spec: data.BatchLoader(c, torch.arange(48), 4, shuffle=True, seed=5, lazy=True, augment=spec, augment_style="partial")
     a, b = list(mk(FULL + NEW)), list(mk(FULL))
-    assert all("augment_affine" in x and x["augment_affine"].shape == (4, A.AFF_WORDS) for x in a)
-    assert all("augment_affine" not in x for x in b)
+    assert all(x["augment"].aff is not None and x["augment"].aff.shape == (4, A.AFF_WORDS) for x in a)
+    assert all(x["augment"].aff is None for x in b)
     assert [x["index"].tolist() for x in a] == [x["index"].tolist() for x in b]
-    assert all(torch.equal(x["augment"][:, A.SCALE:], y["augment"][:, A.SCALE:]) for x, y in zip(a, b))
-    assert "augment_affine" not in next(iter(mk(FULL + NEW).without_augment()))
+    assert all(torch.equal(x["augment"].rec[:, A.SCALE:], y["augment"].rec[:, A.SCALE:]) for x, y in zip(a, b))
+    assert "augment" not in next(iter(mk(FULL + NEW).without_augment()))
 
 
 def test_check_affine_records():

@@ -133,12 +133,12 @@ def test_a_lazy_loader_carries_the_third_record():
     c = _cohort()
     mk = lambda spec: data.BatchLoader(c, torch.arange(48), 4, shuffle=True, seed=5, lazy=True, augment=spec, augment_style="partial")
     a, b, e = list(mk(FULL + AFF + ELA)), list(mk(FULL + AFF)), list(mk(FULL + ELA))
-    assert all(x["augment_elastic"].shape == (4, A.ELA_WORDS) and x["augment_elastic_spacing"] == 8 for x in a + e)
-    assert all("augment_affine" in x for x in a + e)                    # the elastic launch takes matrices
-    assert all("augment_elastic" not in x and "augment_elastic_spacing" not in x for x in b)
+    assert all(x["augment"].ela.shape == (4, A.ELA_WORDS) and x["augment"].spacing == 8 for x in a + e)
+    assert all(x["augment"].aff is not None for x in a + e)             # the elastic launch takes matrices
+    assert all(x["augment"].ela is None and x["augment"].key[1] is None for x in b)
     assert [x["index"].tolist() for x in a] == [x["index"].tolist() for x in b]
-    assert all(torch.equal(x["augment"], y["augment"]) and torch.equal(x["augment_affine"], y["augment_affine"]) for x, y in zip(a, b))
-    assert "augment_elastic" not in next(iter(mk(FULL + AFF + ELA).without_augment()))
+    assert all(torch.equal(x["augment"].rec, y["augment"].rec) and torch.equal(x["augment"].aff, y["augment"].aff) for x, y in zip(a, b))
+    assert "augment" not in next(iter(mk(FULL + AFF + ELA).without_augment()))
     with pytest.raises(ValueError, match="smallest spacing"):
         data.BatchLoader(data.make_cohort(n=4, dims=(32, 32, 32), rna_dim=8, seed=3), torch.arange(4), 2, lazy=True, augment="elastic=0:0.5:2")
 

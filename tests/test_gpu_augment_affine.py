@@ -347,7 +347,7 @@ def _fallback_models(cls, G):
 
 @pytest.mark.parametrize("cls,style", [("PartialModalityNet", "partial"), ("MultiModalSurvivalNet", "final")])
 def test_indexed_augmented_step_equals_batch_step(cls, style):
-    """train_step_indexed(cohort, idx, augment=, augment_affine=) == train_step on the batches a materialising loader augmented
+    """train_step_indexed(cohort, idx, augment=Records with .aff) == train_step on the batches a materialising loader augmented
     beforehand (augment.apply: the same kernel over the same records, so both engines get bit-identical inputs -- what is compared is
     the plumbing of the two record arrays through the fold group; part 1 compares the kernel with the reference.  Tolerance of
     tests/test_gpu_fold_group.py::test_indexed_step_equals_batch_step).  The materialised CT is also held against the float64
@@ -368,8 +368,7 @@ def test_indexed_augmented_step_equals_batch_step(cls, style):
     for it, (mts, lzs) in enumerate(zip(zip(*mk(False)), zip(*mk(True)))):
         Ae.train_step([T._train_kwargs(style, mt) for mt in mts], skip_if_unusable=skip, use_graph=it > 0)
         Be.train_step_indexed(lzs[0]["gather"], torch.stack([lz["index"] for lz in lzs]), skip_if_unusable=skip, use_graph=it > 0,
-                              augment=torch.stack([lz["augment"] for lz in lzs]),
-                              augment_affine=torch.stack([lz["augment_affine"] for lz in lzs]))
+                              augment=A.Records.stack([lz["augment"] for lz in lzs]))
         torch.cuda.synchronize()
         if it == 0:
             for g in range(NG):
@@ -377,14 +376,14 @@ def test_indexed_augmented_step_equals_batch_step(cls, style):
                 print(cls, "member", g, "rel_err(gflat) =", e, "max |gflat| =", float(Ae.engines[g].gflat.abs().max()))
                 assert float(Ae.engines[g].gflat.abs().max()) > 0 and e <= 2e-5
             lz, mt = lzs[0], mts[0]
-            f8, f16 = lz["augment"].view(torch.float32), lz["augment_affine"].view(torch.float32)
+            f8, f16 = lz["augment"].rec.view(torch.float32), lz["augment"].aff.view(torch.float32)
             seen = 0
             for b, p in enumerate(lz["index"].tolist()):
-                if cpu["mask"][p, 0] == 0 or int(lz["augment"][b, A.DROP]) & 1:
+                if cpu["mask"][p, 0] == 0 or int(lz["augment"].rec[b, A.DROP]) & 1:
                     continue
                 ref = R.affine_volume(cpu["image"][p].reshape(DIMS).double().numpy(), f16[b, :12].double().numpy().reshape(3, 4),
                                       float(f8[b, A.SCALE]), float(f8[b, A.OFFSET]), float(f16[b, A.AFF_SIGMA]),
-                                      int(lz["augment_affine"][b, A.AFF_SEED]) & 0xFFFFFFFF)
+                                      int(lz["augment"].aff[b, A.AFF_SEED]) & 0xFFFFFFFF)
                 assert float(np.abs(mt["image"][b].reshape(DIMS).double().cpu().numpy() - ref).max()) <= 1e-5
                 seen += 1
             assert seen > 0
@@ -411,7 +410,7 @@ def test_lazy_and_materialising_loaders_agree(partial_group):
     P = GP.Ps[0]
     n = changed = 0
     for lz, mt in zip(mk(True), mk(False)):
-        ge._gather_indexed(GP, lz["gather"], lz["index"][None], lz["augment"][None], lz["augment_affine"][None])
+        ge._gather_indexed(GP, lz["gather"], lz["index"][None], lz["augment"][None])
         torch.cuda.synchronize()
         assert torch.equal(P.ct.view(mt["image"].shape), mt["image"]) and torch.equal(P.buf["rna"], mt["rnaseq"])
         assert torch.equal(P.buf["clin"].view(mt["clinical"].shape), mt["clinical"]) and torch.equal(P.mask, mt["mask"])

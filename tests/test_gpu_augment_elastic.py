@@ -455,7 +455,7 @@ def _fallback_models(cls, G):
 
 @pytest.mark.parametrize("cls,style", [("PartialModalityNet", "partial"), ("MultiModalSurvivalNet", "final")])
 def test_indexed_augmented_step_equals_batch_step(cls, style):
-    """train_step_indexed(cohort, idx, augment=, augment_affine=, augment_elastic=) == train_step on the batches a materialising loader
+    """train_step_indexed(cohort, idx, augment=Records with .aff and .ela) == train_step on the batches a materialising loader
     augmented beforehand (augment.apply: the same kernel over the same records; what is compared is the plumbing of the three record
     arrays through the fold group.  Tolerance of tests/test_gpu_fold_group.py::test_indexed_step_equals_batch_step).  The materialised
     CT is also held against the float64 reference, loosely (1e-5 on values in [-0.1, 1.3]): the loaders hand the kernel what they drew."""
@@ -475,10 +475,7 @@ def test_indexed_augmented_step_equals_batch_step(cls, style):
     for it, (mts, lzs) in enumerate(zip(zip(*mk(False)), zip(*mk(True)))):
         Ae.train_step([T._train_kwargs(style, mt) for mt in mts], skip_if_unusable=skip, use_graph=it > 0)
         Be.train_step_indexed(lzs[0]["gather"], torch.stack([lz["index"] for lz in lzs]), skip_if_unusable=skip, use_graph=it > 0,
-                              augment=torch.stack([lz["augment"] for lz in lzs]),
-                              augment_affine=torch.stack([lz["augment_affine"] for lz in lzs]),
-                              augment_elastic=torch.stack([lz["augment_elastic"] for lz in lzs]),
-                              elastic_spacing=lzs[0]["augment_elastic_spacing"])
+                              augment=A.Records.stack([lz["augment"] for lz in lzs]))
         torch.cuda.synchronize()
         if it == 0:
             for g in range(NG):
@@ -486,15 +483,15 @@ def test_indexed_augmented_step_equals_batch_step(cls, style):
                 print(cls, "member", g, "rel_err(gflat) =", e, "max |gflat| =", float(Ae.engines[g].gflat.abs().max()))
                 assert float(Ae.engines[g].gflat.abs().max()) > 0 and e <= 2e-5
             lz, mt = lzs[0], mts[0]
-            f8, f16, f4 = lz["augment"].view(torch.float32), lz["augment_affine"].view(torch.float32), lz["augment_elastic"].view(torch.float32)
+            f8, f16, f4 = lz["augment"].rec.view(torch.float32), lz["augment"].aff.view(torch.float32), lz["augment"].ela.view(torch.float32)
             seen = 0
             for b, p in enumerate(lz["index"].tolist()):
-                if cpu["mask"][p, 0] == 0 or int(lz["augment"][b, A.DROP]) & 1:
+                if cpu["mask"][p, 0] == 0 or int(lz["augment"].rec[b, A.DROP]) & 1:
                     continue
                 vol = cpu["image"][p].reshape(DIMS).double().numpy()
                 m32 = f16[b, :12].double().numpy().reshape(3, 4)
-                args = (float(f8[b, A.SCALE]), float(f8[b, A.OFFSET]), float(f16[b, A.AFF_SIGMA]), int(lz["augment_affine"][b, A.AFF_SEED]) & 0xFFFFFFFF)
-                ref = ER.elastic_volume(vol, m32, (2, 2, 2), f4[b, :3].double().numpy(), int(lz["augment_elastic"][b, A.ELA_SEED]) & 0xFFFFFFFF, *args)
+                args = (float(f8[b, A.SCALE]), float(f8[b, A.OFFSET]), float(f16[b, A.AFF_SIGMA]), int(lz["augment"].aff[b, A.AFF_SEED]) & 0xFFFFFFFF)
+                ref = ER.elastic_volume(vol, m32, (2, 2, 2), f4[b, :3].double().numpy(), int(lz["augment"].ela[b, A.ELA_SEED]) & 0xFFFFFFFF, *args)
                 have = mt["image"][b].reshape(DIMS).double().cpu().numpy()
                 assert float(np.abs(have - ref).max()) <= 1e-5
                 assert float(np.abs(have - ER.R.affine_volume(vol, m32, *args)).max()) > 1e-3        # ... and the field is in there
@@ -523,8 +520,7 @@ def test_lazy_and_materialising_loaders_agree(partial_group):
     P = GP.Ps[0]
     n = changed = 0
     for lz, mt in zip(mk(True), mk(False)):
-        ge._gather_indexed(GP, lz["gather"], lz["index"][None], lz["augment"][None], lz["augment_affine"][None], lz["augment_elastic"][None],
-                           lz["augment_elastic_spacing"])
+        ge._gather_indexed(GP, lz["gather"], lz["index"][None], lz["augment"][None])
         torch.cuda.synchronize()
         assert torch.equal(P.ct.view(mt["image"].shape), mt["image"]) and torch.equal(P.buf["rna"], mt["rnaseq"])
         assert torch.equal(P.buf["clin"].view(mt["clinical"].shape), mt["clinical"]) and torch.equal(P.mask, mt["mask"])
@@ -564,6 +560,28 @@ def test_an_elastic_spec_takes_the_elastic_gather_and_only_that(partial_group):
     finally:
         ge.lib = real
         torch.cuda.synchronize()
+
+
+def test_members_with_different_record_kinds_step_apart(partial_group):
+    """Two members whose loaders carry records of different kinds cannot share a gather launch: train_epoch_lockstep groups the named
+    batches by the records' key, so each position is two steps of one member each -- one launch of each kind's entry point, and
+    nothing else; both members still see both of their batches."""
+    from multimodal_survival_prediction_amd import data, training as T
+    from test_gpu_augment import _Spy
+    cohort, ge = partial_group
+    loaders = [data.BatchLoader(cohort, torch.arange(12 * f, 12 * f + 8), 4, shuffle=True, seed=f, lazy=True, augment=spec, augment_style="partial")
+               for f, spec in enumerate(("flip=0.5,scale=0.9:1.1", SPEC))]
+    real = ge.lib
+    try:
+        ge.lib = spy = _Spy(real)
+        stats = T.train_epoch_lockstep(ge, loaders, "partial")
+        gathers = {c for c in spy.calls if c.startswith("mms_gather")}
+        assert gathers == {"mms_gather_aug_group", "mms_gather_elastic_group"}, gathers
+    finally:
+        ge.lib = real
+        torch.cuda.synchronize()
+    assert len(stats) == 2
+    assert [e.epoch_stats()["n_batches"] for e in ge.engines] == [2, 2]
 
 
 def test_displacement_field_is_the_kernels_field():

@@ -304,7 +304,7 @@ def test_partial_modality_group_with_augmentation_records():
     gradients are fp32 atomic sums, so the gradients are compared at the tolerance of tests/test_gpu_augment.py's step test (2e-5 of the
     largest entry) instead of bit for bit; the inputs, which are what this change touches, must be identical."""
     from test_gpu_augment import _fallback_models
-    from multimodal_survival_prediction_amd import data
+    from multimodal_survival_prediction_amd import augment as A, data
     from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
     dims, k, K, B = (32, 32, 32), 8, 2, 4
     cohort, sel = _selected_cohort(24, 64, k, K, dims=dims, complete=False, seed=3)
@@ -317,7 +317,7 @@ def test_partial_modality_group_with_augmentation_records():
     for it in range(2):
         lz, mt = [next(i) for i in lazy], [next(i) for i in mat]
         assert all(b["gather"] is lz[0]["gather"] for b in lz)
-        idx, recs = torch.stack([b["index"] for b in lz]), torch.stack([b["augment"] for b in lz])
+        idx, recs = torch.stack([b["index"] for b in lz]), A.Records.stack([b["augment"] for b in lz])
         Be.train_step_indexed(lz[0]["gather"], idx, skip_if_unusable=False, use_graph=False, augment=recs)
         Ae.train_step([dict(ct=b["image"], rna=b["rnaseq"], clinical=b["clinical"], mask=b["mask"], time=b["label"][:, 0], event=b["label"][:, 1],
                             valid=torch.as_tensor(b["has_survival"], dtype=torch.float32)) for b in mt], skip_if_unusable=False, use_graph=False)

@@ -165,7 +165,6 @@ KERNELS = ("gather_rows_kernel", "gather_aug_kernel", "gather_affine_kernel", "g
 
 def cmd_kernel(args):
     torch, data, cpu, train_sets = _setup(os.path.dirname(HERE))
-    import ctypes
     from multimodal_survival_prediction_amd import _lib, augment as A, ops
     lib, S = _lib.load_library(), _lib.structs()
     dev = torch.device("cuda:0")
@@ -187,15 +186,9 @@ def cmd_kernel(args):
     ela_spec = A.AugmentSpec.parse(SPEC_ELA)
     keep, Gs, As = [], [], []
     for g in range(K):
-        G = S["GatherP"]()
-        G.idx, G.B, G.nsrc = idx_dev[g].data_ptr(), B, len(srcs)
-        for i, (a, w, flag, _) in enumerate(srcs):
-            o = torch.zeros(B, w, device=dev)
-            keep.append(o)
-            G.src[i], G.dst[i], G.src_ld[i], G.dst_ld[i], G.width[i] = a.data_ptr(), o.data_ptr(), a.stride(0), w, w
-            if flag is not None:
-                G.present[i], G.present_ld[i] = flag.data_ptr(), flag.stride(0)
-        Gs.append(G)
+        outs = [torch.zeros(B, w, device=dev) for _, w, _, _ in srcs]
+        keep += outs
+        Gs.append(ops.gather_params(idx_dev[g], B, [(a, o, w, flag) for (a, w, flag, _), o in zip(srcs, outs)]))
         As.append(A.aug_block(rec_dev[g], [r for *_, r in srcs], DIMS, (2, 4, 4)))
     Ga, Aa = (S["GatherP"] * K)(*Gs), (S["AugP"] * K)(*As)
     Fa = (S["AffP"] * K)(*[A.aff_block(aff_dev[g], DIRECT_STAGE if form == "direct" else STAGED_STAGE if args.elastic else 0) for g in range(K)])
@@ -215,7 +208,7 @@ def cmd_kernel(args):
         if any(len(b["index"]) != B for b in pos):
             break
         idx = torch.stack([b["index"] for b in pos])
-        rec = torch.stack([b["augment"] for b in pos])
+        rec = torch.stack([b["augment"].rec for b in pos])
         has = cpu["mask"][idx][..., [1, 0, 2]] != 0                                        # rna, image, clinical rows that exist
         drop = torch.stack([(rec[..., A.DROP] >> j) & 1 for j in (1, 0, 2)], -1) != 0
         written = K * B * (RNA + vol + 1 + 3 + 3) * 4
@@ -225,17 +218,17 @@ def cmd_kernel(args):
         idx_dev.copy_(idx)
         rec_dev.copy_(rec)
         if form != "none":
-            aff_dev.copy_(torch.stack([b["augment_affine"] for b in pos_aff]))
+            aff_dev.copy_(torch.stack([b["augment"].aff for b in pos_aff]))
         if args.elastic:
-            assert all(torch.equal(a["augment_affine"], e["augment_affine"]) for a, e in zip(pos_aff, pos_ela))      # the same matrices
-            ela_dev.copy_(torch.stack([b["augment_elastic"] for b in pos_ela]))
-        for _ in range(args.repeat):
-            _lib.check(lib.mms_gather_rows_group(Ga, K, ops.stream()), "mms_gather_rows_group")
-            _lib.check(lib.mms_gather_aug_group(Ga, Aa, K, ops.stream()), "mms_gather_aug_group")
+            assert all(torch.equal(a["augment"].aff, e["augment"].aff) for a, e in zip(pos_aff, pos_ela))      # the same matrices
+            ela_dev.copy_(torch.stack([b["augment"].ela for b in pos_ela]))
+        for _ in range(args.repeat):     # one launch per kind: the plain gather, then one more block array at a time
+            A.launch_gather(lib, Ga, ng=K)
+            A.launch_gather(lib, Ga, Aa, ng=K)
             if form != "none":      # (the 8-word records keep their flip / shift: this entry point does not read them)
-                _lib.check(lib.mms_gather_affine_group(Ga, Aa, Fa, K, ops.stream()), "mms_gather_affine_group")
+                A.launch_gather(lib, Ga, Aa, Fa, ng=K)
             if args.elastic:
-                _lib.check(lib.mms_gather_elastic_group(Ga, Aa, Fa, Ea, K, ops.stream()), "mms_gather_elastic_group")
+                A.launch_gather(lib, Ga, Aa, Fa, Ea, ng=K)
         torch.cuda.synchronize()
         n += 1
     per = {"gather_rows_kernel": bytes_plain // n, "gather_aug_kernel": bytes_aug // n}
