@@ -750,6 +750,30 @@ typedef struct AdamP {
     const long long* w2_off; float* const* w2_pack_b; float* const* w2_pack_f; int n_w2; uint64_t w2_fragmask;
 } AdamP;
 
+/* Fine-tuning form of the optimiser step (csrc/finetune.hip): the flat buffer in nseg SEGMENTS, segment s = elements
+ * [bounds[s], bounds[s + 1]) with lr_s = lr * lr_mult[s], wd_s = weight_decay * wd_mult[s] and an L2-SP pull of strength l2sp[s] towards
+ * anchor (the weights fine-tuning started from; Li et al. 2018) where weight decay is applied, after clipping:
+ *   Adam:  g <- coef * g + wd_s * w + l2sp_s * (w - anchor);   AdamW:  w <- w - lr_s * wd_s * w - lr_s * l2sp_s * (w - anchor), then Adam's step.
+ * lr_mult[s] = 0 FREEZES the segment: its p / m / v are neither read nor written, its gradient is not read and stays out of the global
+ * norm (torch: clip_grad_norm_ over the parameters that have a gradient).  One step counter; the skip_flag / acc / rng bookkeeping of
+ * mms_grad_sumsq.  bounds [nseg + 1], lr_mult / wd_mult / l2sp [nseg] live in DEVICE memory and are shared by all members of a group
+ * launch (the same pointers in every member); anchor [n] is per member, NULL when no trainable segment has l2sp > 0.
+ * A launch checks what it can without reading device memory (nseg in 1..MMS_TUNE_MAX_SEG, no NULL table, p / g / m / v / anchor 16-byte
+ * aligned, one table per group, n < 2^33); mms_tune_check reads the tables back (it synchronises: call it once, outside any capture)
+ * and checks the rest: bounds strictly ascending from 0 to n, no bound inside a packed conv2 tensor, multipliers finite and >= 0, a
+ * trainable segment, an anchor where one is needed.  Tables it would refuse make the launches wrong, not unsafe: a quad or packed tensor that
+ * does not lie inside [0, n) is skipped, never addressed.  A multiplier of 1 everywhere gives the bits of mms_clip_adam. */
+#define MMS_TUNE_MAX_SEG 512
+typedef struct TuneP {
+    AdamP a;
+    const long long* bounds;
+    const float* lr_mult;
+    const float* wd_mult;
+    const float* l2sp;
+    int nseg;
+    const float* anchor;
+} TuneP;
+
 /* Large-batch Linear (rows M > 32: BASELINE config 5, RNA-seq-only B = 2048; R/scripts/training/train_rnaseq_only.py:126-151).
  * y = P(x) W^T + bias [-> ReLU], P = Dropout(ReLU(BatchNorm1d(x))) of the PRECEDING nn.Sequential entries (has_bn = 0: P = identity
  * or dropout only).  fp32 MFMA GEMMs on the tile core; BatchNorm1d batch statistics travel like the BatchNorm3d ones: the
@@ -1071,6 +1095,11 @@ int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);        /* elastic-net Cox:
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */
+int mms_tune_check(const TuneP* p);                            /* contents of TuneP's device tables (TuneP above); synchronises */
+int mms_grad_sumsq_tuned(const TuneP* p, hipStream_t s);       /* mms_grad_sumsq over the trainable segments */
+int mms_clip_adam_tuned(const TuneP* p, hipStream_t s);        /* mms_clip_adam with per-segment settings; frozen segments untouched */
+int mms_grad_sumsq_tuned_group(const TuneP* p, int ng, hipStream_t s);     /* ng <= MMS_MAX_GROUP members, one segment table */
+int mms_clip_adam_tuned_group(const TuneP* p, int ng, hipStream_t s);
 int mms_w2_pack(const AdamP* p, hipStream_t s);                /* the derived conv2 packs alone, from the current weights (after load_state_dict / any external update) */
 
 /* ---- whole-encoder driver: replaces `self.ct_encoder(ct)` / `self.image_encoder(image)` and its autograd
@@ -1097,6 +1126,12 @@ int mms_dn121_forward(void* ws, int B, int D, int H, int W, const float* x, cons
                       const void* const* buffers, float* out, int ldo, int train, const MmsDnOpts* opts, hipStream_t s);
 int mms_dn121_backward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
                        const float* dout, int lddout, void* const* grads, const MmsDnOpts* opts, hipStream_t s);
+/* mms_dn121_backward that stops above dense block block_lo (0..3): stages 3 .. block_lo, where stage b = dense block b (denseblock{b+1})
+ * plus the transition below it (b = 0: the stem), and norm5 / class_layers ride with stage 3.  The gradients of the parameters below
+ * are not written (they stay as the caller zeroed them).  One unstaged call: skip_dead_bwd, the weight-gradient tables and the default
+ * launch forms stay in force; block_lo = 0 enqueues exactly what mms_dn121_backward enqueues.  block_lo outside 0..3: MMS_ERR_ARG. */
+int mms_dn121_backward_from(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
+                            const float* dout, int lddout, void* const* grads, int block_lo, const MmsDnOpts* opts, hipStream_t s);
 /* ---- data-parallel (one process per GPU) variants of the single-model drivers --------------------------------------------
  * The reference is single-process (R/scripts/training/final_multimodal.py:52,345); BASELINE config 4 shards a global batch over
  * ranks.  Two things then leave the rank: (a) the gradients, all-reduced bucket by bucket while the backward still runs -- the
@@ -1300,6 +1335,9 @@ int mms_dn121_forward_group(int ng, void* const* ws, int B, int D, int H, int W,
 int mms_dn121_backward_group(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
                              const void* const* const* params, const float* const* dout, int lddout,
                              void* const* const* grads, const MmsDnOpts* opts, hipStream_t s);
+int mms_dn121_backward_group_from(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
+                                  const void* const* const* params, const float* const* dout, int lddout,
+                                  void* const* const* grads, int block_lo, const MmsDnOpts* opts, hipStream_t s);      /* (mms_dn121_backward_from) */
 
 /* Fallback CT encoder in lock-step (csrc/fb_group.hip): fp32-MFMA group forms of the mms_fb_* ops on the same parameter blocks.  All
  * members share one shape.  Taken: Cin = 1 (has_bn = 0) or Cin a multiple of 16 in 16..128; Cout a multiple of 16 other than 48 + 64 n (a

@@ -875,6 +875,16 @@ extern "C" int mms_dn121_backward(void* ws, int B, int D, int H, int W, const fl
     Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
     return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr);
 }
+// The backward that stops above dense block block_lo (fine-tuning with frozen lower stages): stages 3 .. block_lo of ONE unstaged call, so
+// the head launch is this call's (skip_dead_bwd and the weight-gradient tables stay in force).  What dn121_backward_impl does per block --
+// the flush of its deferred weight-gradient launches, the conv2 gradient unpack range (l0, nl), block 1's batching rule (b == 0 only) -- does
+// not look below b_lo; the last stage's transition still writes the data gradient of the slab below it, which nothing reads.
+extern "C" int mms_dn121_backward_from(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
+                                       const float* dout, int lddout, void* const* grads, int block_lo, const MmsDnOpts* opts, hipStream_t s) {
+    Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
+    Dp dp; dp.b_lo = block_lo;
+    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
+}
 extern "C" int mms_dn121_backward_mt(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
                                      const float* dout, int lddout, void* const* grads, const MmsDnOpts* opts, hipStream_t s, hipStream_t side,
                                      hipEvent_t ev_fork, hipEvent_t ev_join) {
@@ -1039,4 +1049,13 @@ extern "C" int mms_dn121_backward_group(int ng, void* const* ws, int B, int D, i
     Ctx c[MMS_MAX_GROUP];
     FOR_G c[g] = Ctx{ws[g], x[g], (const float* const*)params[g], nullptr, nullptr, dout[g], (float* const*)grads[g]};
     return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr);
+}
+extern "C" int mms_dn121_backward_group_from(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
+                                             const void* const* const* params, const float* const* dout, int lddout,
+                                             void* const* const* grads, int block_lo, const MmsDnOpts* opts, hipStream_t s) {
+    if (ng < 1 || ng > MMS_MAX_GROUP || !ws || !x || !params || !dout || !grads) return MMS_ERR_ARG;
+    Ctx c[MMS_MAX_GROUP];
+    FOR_G c[g] = Ctx{ws[g], x[g], (const float* const*)params[g], nullptr, nullptr, dout[g], (float* const*)grads[g]};
+    Dp dp; dp.b_lo = block_lo;
+    return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
 }

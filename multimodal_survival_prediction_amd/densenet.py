@@ -53,6 +53,19 @@ def _build_features():
     return f, c
 
 
+def stage_table_ranges():
+    """[(lo, hi)] x 4: the entries of the drivers' 364-pointer parameter table (named_parameters() order) that backward stage b writes --
+    dense block b plus the transition below it (b = 0: conv0 and norm0); norm5 and class_layers, the table's last 4 entries, ride with
+    stage 3 (mms_dn121_backward_stage / _from, include/mmsurv.h).  The stages tile the table in order."""
+    out, lo = [], 0
+    for b, n in enumerate(_BLOCKS):
+        hi = lo + 3 + 6 * n          # 3 = the stem (conv0.weight, norm0.{weight, bias}) or a transition (norm.{weight, bias}, conv.weight)
+        out.append((lo, hi))
+        lo = hi
+    out[-1] = (out[-1][0], lo + 4)
+    return out
+
+
 class _Encode(torch.autograd.Function):
     """The activations and BatchNorm statistics of a forward live in the module's one workspace (`_eng`), not in the autograd graph:
     every forward of the module stamps a serial number on it (_run_forward), and a backward runs only while its forward is the latest

@@ -220,12 +220,15 @@ class _Plan:
 
 class SurvivalEngine:
     def __init__(self, model, adamw=None, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0,
-                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None, expert_weight=0.1, _slots=None):
+                 gate_entropy_weight=0.01, cox_ties=None, dn_opts=None, expert_weight=0.1, finetune=None, _slots=None):
         """expert_weight: lambda of SimMLM_SurvivalNet's training objective (project-defined)
         L = cox(ensemble; has_survival) + lambda * sum_m cox(h_m; has_survival and mask_m); ignored by the other models.
         dn_opts: launch-shape options of the encoder drivers (dict of MmsDnOpts fields, include/mmsurv.h; None = defaults).
+        finetune: None, a transfer.FineTunePlan or its string -- per-segment learning rates, frozen segments, L2-SP (the tuned optimiser
+        launches, csrc/finetune.hip), a backward that stops above the frozen DenseNet121 stages, the encoder in eval mode.  Fixed for
+        the engine's life.  None: the engine takes the launches it took before fine-tuning existed.
         _slots (used by FoldGroupEngine): dict(gflat=[n] fp32, sumsq=[1] fp64, entropy=[1] fp32) views of group-wide
-        buffers, so the per-step zeroing of a whole fold group is three memsets."""
+        buffers, so the per-step zeroing of a whole fold group is three memsets; tune_tab = the group's one segment table."""
         self.lib = _lib.load_library()
         self.model = model
         self.prog = head_program(model)
@@ -265,6 +268,7 @@ class SurvivalEngine:
         # device-side epoch accumulators: [sum loss*usable, n usable, sum entropy, n batches]
         self.acc = torch.zeros(4, device=self.device)
         self.acc_eval = torch.zeros(4, device=self.device)      # validation: [sum of batch losses, usable batches, -, batches]
+        self._set_finetune(finetune)
         model._mms_engine = self
 
     # ---- parameters ------------------------------------------------------------------------------
@@ -312,6 +316,41 @@ class SurvivalEngine:
                            pack_f=torch.tensor([base + (2 * i + 1) * step for i in range(len(self.w2_offsets))], dtype=torch.int64, device=self.device),
                            fragmask=None)
             self._packs_version = None
+
+    def _set_finetune(self, finetune):
+        """The plan's consequences for the launches (transfer.FineTunePlan): the segment table of the tuned optimiser pair, the L2-SP
+        anchor (a snapshot of the flat buffer, only where some trainable segment has l2sp > 0; constant, so not part of _state()),
+        whether the encoder backward runs and from which dense block, whether the encoder forward runs in eval mode."""
+        from . import transfer
+        self.finetune = transfer.as_plan(finetune)
+        self.tune_tab, self.anchor, self.enc_frozen, self.block_lo, self.enc_eval = None, None, False, 0, False
+        if self.finetune is None:
+            return
+        plan = self.finetune
+        seg = plan.resolve(self.model)
+        assert int(seg.bounds[-1]) == self.flat.numel()
+        self.segments = seg
+        self.tune_tab = self._slots.get("tune_tab") or ops.tune_table(seg.bounds.tolist(), seg.lr_mult.tolist(), seg.wd_mult.tolist(),
+                                                                      seg.l2sp.tolist(), self.device)
+        if bool(((seg.l2sp > 0) & (seg.lr_mult > 0)).any()):
+            self.anchor = self.flat.clone()          # (the weights at this moment; transfer.load_pretrained on a live engine calls reset_anchor)
+        self.enc_frozen = plan.encoder_frozen(self.model)
+        self.enc_eval = plan.encoder_eval
+        if self.enc_eval and not self.enc_frozen:
+            raise ValueError("encoder_eval: %s has no CT encoder to run in eval mode" % self.prog["kind"])
+        if self.packed and not self.enc_frozen:
+            self.block_lo = plan.freeze_stages
+
+    def reset_anchor(self):
+        """L2-SP pulls towards the weights as they are NOW (in place: the launches keep the anchor's address).  For weights loaded after the
+        engine was built; no-op without an anchor."""
+        if self.anchor is not None:
+            self.anchor.copy_(self.flat)
+
+    def _refuse_ddp(self):
+        if self.finetune is not None:
+            raise RuntimeError("fine-tuning plans are not implemented for the data-parallel steps (ddp_world > 1): their staged graphs "
+                               "take the plain optimiser launches; fine-tune on one GPU or as a fold group")
 
     def _check_params(self):
         if (self.params[0].data_ptr(), self.params[-1].data_ptr()) != self._key:
@@ -521,6 +560,9 @@ class SurvivalEngine:
                                  None, self.adamw, w2=w2, **book)
         P.adam_skip = ops.adam_params(self.flat, self.gflat, self.m, self.v, self.hyper, self.sumsq, self.step_count,
                                       P.cox_out[1:], self.adamw, w2=w2, **book)
+        if self.tune_tab is not None:
+            P.tune = ops.tune_params(P.adam, self.tune_tab, self.anchor)
+            P.tune_skip = ops.tune_params(P.adam_skip, self.tune_tab, self.anchor, check=False)
         P.graphs = {}
         self.plans[key] = P
         return P
@@ -668,13 +710,14 @@ class SurvivalEngine:
         if P.has_enc:
             feats = P.buf["feats"]
             out = feats[:, prog["ct_cols"]:]
+            enc_train = train and not self.enc_eval        # (FineTunePlan.encoder_eval: running statistics, not updated)
             if P.fallback:
                 self._check_scalar_path(P)
                 _lib.check(lib.mms_fb3_forward(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
-                                               feats.stride(0), 1 if train else 0, st), "mms_fb3_forward")
+                                               feats.stride(0), 1 if enc_train else 0, st), "mms_fb3_forward")
             else:
                 _lib.check(lib.mms_dn121_forward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, P.btab, out.data_ptr(),
-                                                 feats.stride(0), 1 if train else 0, enc_opts if enc_opts is not None else self._opts_arg(P), st),
+                                                 feats.stride(0), 1 if enc_train else 0, enc_opts if enc_opts is not None else self._opts_arg(P), st),
                            "mms_dn121_forward")
         if P.big:
             if train:
@@ -758,13 +801,21 @@ class SurvivalEngine:
         """Encoder backward from dbuf['feats'].  stage = (block_hi, block_lo): one stage of the DenseNet121 backward
         (mms_dn121_backward_stage; the data-parallel step all-reduces each stage's gradient bucket while the next stage runs);
         hook: SyncBN statistics all-reduce (P.bn_world ranks)."""
-        if not P.has_enc:
+        if not P.has_enc or self.enc_frozen:          # (a wholly frozen encoder: no gradient of it is wanted)
             return
         st = ops.stream()
         lib, prog = self.lib, self.prog
         B, (D, H, W) = P.B, P.dims
         dfe = P.dbuf["feats"]
         dct = dfe[:, prog["ct_cols"]:]
+        # frozen lower stages: the backward stops above them.  Batches above 32 rows and SimMLM_SurvivalNet take the plan as an
+        # optimiser-only feature: the full backward, whose frozen gradients nothing reads.
+        if self.block_lo > 0 and not P.big and P.moe is None:
+            if stage is not None or hook is not None or P.bn_world > 1:
+                self._refuse_ddp()
+            _lib.check(lib.mms_dn121_backward_from(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(), dfe.stride(0),
+                                                   P.gtab, self.block_lo, self._opts_arg(P), st), "mms_dn121_backward_from")
+            return
         if stage is not None or hook is not None or P.bn_world > 1:
             hi, lo = stage if stage is not None else (3, 0)
             _lib.check(lib.mms_dn121_backward_stage(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(), dfe.stride(0),
@@ -836,6 +887,11 @@ class SurvivalEngine:
                 return
         if part == "update":
             self.sumsq.zero_()                 # mms_grad_sumsq ADDS into it; the other parts that zero it are not in this graph
+        if self.tune_tab is not None:
+            tu = P.tune_skip if skip_if_unusable else P.tune
+            _lib.check(lib.mms_grad_sumsq_tuned(ctypes.byref(tu), st), "mms_grad_sumsq_tuned")
+            _lib.check(lib.mms_clip_adam_tuned(ctypes.byref(tu), st), "mms_clip_adam_tuned")
+            return
         ad = P.adam_skip if skip_if_unusable else P.adam
         _lib.check(lib.mms_grad_sumsq(ctypes.byref(ad), st), "mms_grad_sumsq")
         _lib.check(lib.mms_clip_adam(ctypes.byref(ad), st), "mms_clip_adam")
@@ -911,6 +967,8 @@ class SurvivalEngine:
         self.load_batch(P, ct, rna, clinical, mask, time, event, valid)
         self.sync_packs()
         P.fwd_serial += 1           # (a graph replay does not pass through _forward)
+        if ddp_world > 1:
+            self._refuse_ddp()
         if ddp_world > 1 and P.big and self.prog["encoder"] is not None:
             raise RuntimeError("the data-parallel steps of the imaging models are limited to 32 rows per rank (their staged graphs are "
                                "built and tested on the small-batch head kernels); got %d -- lower the per-rank batch (the global batch is "
@@ -960,6 +1018,7 @@ class SurvivalEngine:
         stage k+1 (torch.distributed enqueues an async collective behind the current stream's work and runs it on its own
         stream; the update waits for all of them).  Rank-local risk sets: gradients are averaged (1/world folded into the update
         graph).  global_cox: risk sets over the world*B patients (all-gather of hazard/time/event/valid), gradients summed."""
+        self._refuse_ddp()
         from . import distributed as D
         import torch.distributed as dist
         seq, buckets = self._ddp_sequence(P, global_cox)
@@ -1043,6 +1102,7 @@ class SurvivalEngine:
             feature gradient through its encoder;
           * gradients: encoder weights hold rank-local partial sums -> SUM; head parameters and BatchNorm3d gamma/beta hold the
             global value on every rank -> pre-scaled by 1/world so that the same SUM returns them; then clip + Adam."""
+        self._refuse_ddp()
         from . import distributed as D
         import torch.distributed as dist
         if not P.has_enc or P.fallback:
@@ -1235,4 +1295,9 @@ def engine_of(model, **kw):
     e = getattr(model, "_mms_engine", None)
     if e is None:
         e = SurvivalEngine(model, **kw)
+    elif "finetune" in kw:
+        from . import transfer
+        if transfer.as_plan(kw["finetune"]) != e.finetune:
+            raise RuntimeError("this model's engine was built with the fine-tuning plan %r; the plan of a live engine cannot be changed "
+                               "(to %r) -- build a fresh model and engine" % (e.finetune, kw["finetune"]))
     return e

@@ -66,6 +66,18 @@ class FoldGroupEngine:
         self.gflat_all = torch.zeros(G, n, device=dev)
         self.sumsq_all = torch.zeros(G, dtype=torch.float64, device=dev)
         self.entropy_all = torch.zeros(G, device=dev)
+        # fine-tuning (transfer.FineTunePlan): the tuned optimiser launches read ONE segment table for the whole group
+        tune_tab = None
+        if engine_kw.get("finetune") is not None:
+            from . import transfer
+            plan = engine_kw["finetune"] = transfer.as_plan(engine_kw["finetune"])
+            segs = [plan.resolve(m) for m in models]
+            if any(not all(torch.equal(a, b) for a, b in zip(sg[:4], segs[0][:4])) for sg in segs[1:]):
+                raise ValueError("the fine-tuning plan resolves to different segment tables on the group's models")
+            sg = segs[0]
+            tune_tab = ops.tune_table(sg.bounds.tolist(), sg.lr_mult.tolist(), sg.wd_mult.tolist(), sg.l2sp.tolist(), dev)
+            if plan.encoder_frozen(models[0]):        # (the fused ImageOnlyModel tail runs encoder and heads as one launch per pass)
+                self.fused_tail = False
         self.engines = []
         for g, m in enumerate(models):
             if getattr(m, "_mms_engine", None) is not None:
@@ -73,6 +85,8 @@ class FoldGroupEngine:
             if sum(p.numel() for p in m.parameters()) + (-sum(p.numel() for p in m.parameters())) % 4 != n:
                 raise ValueError("fold-group models must have identical shapes")
             slots = dict(gflat=self.gflat_all[g], sumsq=self.sumsq_all[g:g + 1], entropy=self.entropy_all[g:g + 1])
+            if tune_tab is not None:
+                slots["tune_tab"] = tune_tab
             self.engines.append(SurvivalEngine(m, _slots=slots, **engine_kw))
         kinds = {e.prog["kind"] for e in self.engines}
         if len(kinds) != 1:
@@ -133,6 +147,9 @@ class FoldGroupEngine:
         GP.cox = _arr([P.cox for P in Ps])
         GP.cox_eval = _arr([P.cox_eval for P in Ps])
         GP.adam = {True: _arr([P.adam_skip for P in Ps]), False: _arr([P.adam for P in Ps])}
+        GP.tune = None
+        if eng[0].tune_tab is not None:
+            GP.tune = {True: _arr([P.tune_skip for P in Ps]), False: _arr([P.tune for P in Ps])}
         GP.graphs = {}
         # zeroing: the whole group's buffers when the group is complete and contiguous, else per member
         GP.full = members == tuple(range(len(self.engines)))
@@ -155,12 +172,13 @@ class FoldGroupEngine:
                 _lib.check(lib.mms_img_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
                                                      1 if train else 0, lf[0], lf[1], st), "mms_img_forward_group")
                 return
+            enc_train = train and not GP.eng[0].enc_eval        # (FineTunePlan.encoder_eval)
             if GP.fallback:
                 _lib.check(lib.mms_fb3_forward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
-                                                     1 if train else 0, st), "mms_fb3_forward_group")
+                                                     1 if enc_train else 0, st), "mms_fb3_forward_group")
             else:
                 _lib.check(lib.mms_dn121_forward_group(ng, GP.ws, B, D, H, W, x, GP.params, GP.buffers, GP.out, GP.ld,
-                                                       1 if train else 0, enc_opts if enc_opts is not None else self._opts_arg(GP), st),
+                                                       1 if enc_train else 0, enc_opts if enc_opts is not None else self._opts_arg(GP), st),
                            "mms_dn121_forward_group")
         self._forward_heads(GP, train)
 
@@ -216,6 +234,11 @@ class FoldGroupEngine:
         else:
             _lib.check(lib.mms_cox_fwd_bwd_group(GP.cox, ng, st), "mms_cox_fwd_bwd_group")
         self._backward_from_dhz(GP)
+        if GP.tune is not None:
+            tu = GP.tune[bool(skip_if_unusable)]
+            _lib.check(lib.mms_grad_sumsq_tuned_group(tu, ng, st), "mms_grad_sumsq_tuned_group")
+            _lib.check(lib.mms_clip_adam_tuned_group(tu, ng, st), "mms_clip_adam_tuned_group")
+            return
         ad = GP.adam[bool(skip_if_unusable)]
         _lib.check(lib.mms_grad_sumsq_group(ad, ng, st), "mms_grad_sumsq_group")
         _lib.check(lib.mms_clip_adam_group(ad, ng, st), "mms_clip_adam_group")
@@ -242,9 +265,12 @@ class FoldGroupEngine:
             _lib.check(lib.mms_moe_bwd_group(GP.moe_bwd[0], ng, st), "mms_moe_bwd_group")
         for i in range(n_pre - 1, -1, -1):
             _lib.check(lib.mms_linear_bwd_group(GP.lin_bwd[i], ng, st), "mms_linear_bwd_group")
-        if GP.has_enc:
+        if GP.has_enc and not GP.eng[0].enc_frozen:
             B, (D, H, W) = GP.B, GP.dims
-            if GP.fallback:
+            if GP.eng[0].block_lo > 0 and GP.moe is None:        # (SimMLM_SurvivalNet: optimiser-only, as in SurvivalEngine._backward_encoder)
+                _lib.check(lib.mms_dn121_backward_group_from(ng, GP.ws, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads,
+                                                             GP.eng[0].block_lo, self._opts_arg(GP), st), "mms_dn121_backward_group_from")
+            elif GP.fallback:
                 _lib.check(lib.mms_fb3_backward_group(ng, GP.ws, GP.ws_bytes, GP.widths, B, D, H, W, GP.x, GP.params, GP.dout, GP.ld, GP.grads, st),
                            "mms_fb3_backward_group")
             else:

@@ -695,6 +695,30 @@ def adam_params(p_, g, m, v, hyper, sumsq, step, skip_flag=None, adamw=False, ac
     return a
 
 
+def tune_table(bounds, lr_mult, wd_mult, l2sp, device):
+    """The device tables of TuneP (include/mmsurv.h) from host sequences: one table serves every plan of an engine and every member of a
+    fold group."""
+    nseg = len(lr_mult)
+    if len(bounds) != nseg + 1 or len(wd_mult) != nseg or len(l2sp) != nseg:
+        raise ValueError("tune_table: bounds needs one entry more than the multipliers")
+    return dict(nseg=nseg, bounds=torch.tensor([int(b) for b in bounds], dtype=torch.int64, device=device),
+                lr_mult=torch.tensor([float(x) for x in lr_mult], dtype=torch.float32, device=device),
+                wd_mult=torch.tensor([float(x) for x in wd_mult], dtype=torch.float32, device=device),
+                l2sp=torch.tensor([float(x) for x in l2sp], dtype=torch.float32, device=device))
+
+
+def tune_params(adam, table, anchor=None, check=True):
+    """TuneP around an AdamP block (adam_params) and a tune_table.  check: mms_tune_check reads the tables back and validates them
+    against the block (it synchronises: not inside a graph capture)."""
+    t = _S()["TuneP"]()
+    t.a = adam
+    t.bounds, t.lr_mult, t.wd_mult, t.l2sp = ptr(table["bounds"]), ptr(table["lr_mult"]), ptr(table["wd_mult"]), ptr(table["l2sp"])
+    t.nseg, t.anchor = int(table["nseg"]), ptr(anchor)
+    if check:
+        _lib.check(_lib.load_library().mms_tune_check(ctypes.byref(t)), "mms_tune_check")
+    return t
+
+
 _WORKER_STREAMS = {}
 
 

@@ -75,6 +75,59 @@ def gene_hparams(sel):
     return {} if sel is None else {"select_genes": sel.k, "select_stability": sel.stability, "select_seed": sel.seed}
 
 
+class Transfer:
+    """Transfer learning of an entry point (multimodal_survival_prediction_amd.transfer), all unset by default -- the script then behaves
+    and writes exactly as before:
+      MMS_PRETRAINED=PATH        checkpoint each fold's model starts from (load_pretrained); `{fold}` in it is the fold's name (1, 2, ...)
+      MMS_PRETRAINED_GENES=FILE  the source panel's gene names in the source's column order (transfer.read_genes); with it a first RNA
+                                 layer of another width is aligned by gene name against the cohort's genes (its `gene_names`, else
+                                 transfer.default_gene_names; a fold's selected columns under MMS_SELECT_GENES)
+      MMS_FINETUNE=SPEC          FineTunePlan.parse: frozen stages / segments, learning-rate multipliers, L2-SP
+    apply(model, fold name, fold id) loads and logs; engine_kw goes to FusedOptimizer / FoldGroupEngine; record() is the `transfer` entry
+    of cv_results.json ({} when nothing is set)."""
+
+    def __init__(self, cohort=None, sel=None, rank=0):
+        from multimodal_survival_prediction_amd import transfer
+        self.path = os.environ.get("MMS_PRETRAINED") or None
+        gfile = os.environ.get("MMS_PRETRAINED_GENES") or None
+        self.genes_file = gfile
+        self.source_genes = transfer.read_genes(gfile) if gfile else None
+        spec = os.environ.get("MMS_FINETUNE") or None
+        self.plan = transfer.FineTunePlan.parse(spec) if spec else None
+        self.cohort, self.sel, self.rank, self.folds, self.described = cohort, sel, rank, [], False
+        self.engine_kw = {} if self.plan is None else {"finetune": self.plan}
+
+    def _target_genes(self, fold_id):
+        from multimodal_survival_prediction_amd import transfer
+        if self.source_genes is None or self.cohort is None or "rnaseq" not in self.cohort:
+            return None
+        names = self.cohort.get("gene_names") or transfer.default_gene_names(self.cohort["rnaseq"].shape[1])
+        if self.sel is not None:
+            names = [names[int(c)] for c in self.sel.columns_of(fold_id)]
+        return names
+
+    def apply(self, model, fold_name, fold_id=None):
+        from multimodal_survival_prediction_amd import transfer
+        if self.path is not None:
+            rep = transfer.load_pretrained(model, self.path.replace("{fold}", str(fold_name)), source_genes=self.source_genes,
+                                           target_genes=self._target_genes(fold_id))
+            print(f"[rank {self.rank}] fold {fold_name}: {rep}", flush=True)
+            self.folds.append(dict(fold=fold_name, **rep.as_dict()))
+        if self.plan is not None and not self.described:
+            print(f"[rank {self.rank}] fine-tuning plan {self.plan.spec()!r}:\n{self.plan.describe(model)}", flush=True)
+            self.described = True
+
+    def record(self):
+        if self.path is None and self.plan is None:
+            return {}
+        rec = {}
+        if self.path is not None:
+            rec.update(pretrained=self.path, pretrained_genes=self.genes_file, folds=self.folds)
+        if self.plan is not None:
+            rec["finetune"] = self.plan.spec()
+        return {"transfer": rec}
+
+
 def setup_device():
     from multimodal_survival_prediction_amd import distributed as D
     world, rank, local = D.init()
@@ -117,16 +170,21 @@ def lockstep_enabled(n_local_folds, batch_size=None):
 
 
 def cv_lockstep(style, models, loaders, group_kw, num_epochs, patience, make_scheduler, ckpt_path, device, rank, fold_names,
-                log_every=5, fold_ids=None):
+                log_every=5, fold_ids=None, transfer=None):
     """The per-fold epoch loop of the three scripts (train, validate, scheduler, best-checkpoint, early stopping) run for
     all local folds at once: one FoldGroupEngine advances every still-active fold by one batch per launch sequence.
     loaders: [(train_loader, val_loader)] per fold; make_scheduler(optimizer) -> object with step(metric) or step();
     patience None = no early stopping (simple_fusion.py).  fold_ids: the 0-based cross-validation fold of each model (None: model g is
-    fold g) -- which per-fold gene matrix its batches are gathered from (select_genes above).  -> per fold dict(best_c_index, best_epoch, patients_per_sec)."""
+    fold g) -- which per-fold gene matrix its batches are gathered from (select_genes above).  transfer: a Transfer (above) applied to every
+    model before the group is built.  -> per fold dict(best_c_index, best_epoch, patients_per_sec)."""
     import inspect
     import time
     from multimodal_survival_prediction_amd.fold_group import FoldGroupEngine
     from multimodal_survival_prediction_amd.training import FusedOptimizer, has_named_validation, train_epoch_lockstep, validate_lockstep
+    if transfer is not None:
+        for g, m in enumerate(models):
+            transfer.apply(m, fold_names[g], fold_ids[g] if fold_ids is not None else g)
+        group_kw = dict(group_kw, **transfer.engine_kw)
     group = FoldGroupEngine(models, folds=fold_ids, **group_kw)
     for tl, vl in loaders:                     # cohort in HBM (or pinned host memory): name the batches, let the group gather them
         for ld in ((tl, vl) if has_named_validation(style) else (tl,)):      # (validate_lockstep's named-batch path)

@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, lockstep_enabled, rna_width, save_json, select_genes, setup_device
+from _common import Transfer, augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, lockstep_enabled, rna_width, save_json, select_genes, setup_device
 
 from multimodal_survival_prediction_amd import data, distributed as D
 from multimodal_survival_prediction_amd.losses import calculate_cindex, cox_loss  # noqa: F401  (reference surface)
@@ -45,6 +45,7 @@ def main():
     os.makedirs("models/final", exist_ok=True)
     ckpt = lambda name: f"models/final/fold_{name}_best.pth"
     sel = select_genes(cohort, [tr for tr, _ in folds], ckpt, rank=rank)        # MMS_SELECT_GENES (unset: off)
+    xfer = Transfer(cohort, sel, rank)        # MMS_PRETRAINED / MMS_PRETRAINED_GENES / MMS_FINETUNE (unset: off)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
     if lockstep_enabled(len(my_folds), BATCH_SIZE):      # all local folds advance together, one launch sequence per batch position
@@ -53,7 +54,7 @@ def main():
         models = [MultiModalSurvivalNet(**rna_width(sel)).to(device) for _ in my_folds]
         res = cv_lockstep("final", models, loaders, dict(lr=LEARNING_RATE, weight_decay=1e-4, adamw=False), NUM_EPOCHS, PATIENCE,
                           lambda o: ReduceLROnPlateau(o, mode="max", factor=0.5, patience=5),
-                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds)
+                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds, transfer=xfer)
         local = [{"fold": f + 1, "best_c_index": r["best_c_index"], "patients_per_sec": r["patients_per_sec"], "epochs_run": r["epochs_run"]}
                  for f, r in zip(my_folds, res)]
         my_folds = []
@@ -63,7 +64,8 @@ def main():
                                         augment=AUGMENT, augment_style="final", fold=fold)
         val_loader = data.BatchLoader(cohort, val_idx, BATCH_SIZE, shuffle=False, fold=fold)
         model = MultiModalSurvivalNet(**rna_width(sel)).to(device)
-        optimizer = FusedOptimizer(model, lr=LEARNING_RATE, weight_decay=1e-4, adamw=False)      # optim.Adam (:350)
+        xfer.apply(model, fold + 1, fold)
+        optimizer = FusedOptimizer(model, lr=LEARNING_RATE, weight_decay=1e-4, adamw=False, **xfer.engine_kw)      # optim.Adam (:350)
         scheduler = ReduceLROnPlateau(optimizer, mode="max", factor=0.5, patience=5)             # (:351)
         best_c_index, patience_counter, t_train, n_train, epochs_run = 0, 0, 0.0, 0, 0
         for epoch in range(NUM_EPOCHS):
@@ -91,7 +93,7 @@ def main():
             "model": "MultiModalSurvivalNet (Late Fusion)", "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)),
             "fold_results": cv_results,
             "hyperparameters": {"batch_size": BATCH_SIZE, "learning_rate": LEARNING_RATE, "epochs": NUM_EPOCHS, "n_folds": N_FOLDS,
-                                **augment_hparams(AUGMENT), **gene_hparams(sel)}})
+                                **augment_hparams(AUGMENT), **gene_hparams(sel)}, **xfer.record()})
         print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f}; saved results/final/cv_results.json")
 
 

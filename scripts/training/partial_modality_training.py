@@ -15,7 +15,7 @@ import time
 import numpy as np
 import torch
 
-from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, load_or_make_cohort, lockstep_enabled, rna_width, save_json, select_genes, setup_device
+from _common import Transfer, augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, load_or_make_cohort, lockstep_enabled, rna_width, save_json, select_genes, setup_device
 
 from multimodal_survival_prediction_amd import data, distributed as D
 from multimodal_survival_prediction_amd.losses import calculate_cindex, cox_loss, gate_entropy_loss  # noqa: F401
@@ -47,6 +47,7 @@ def main():
     os.makedirs("models/partial_modality", exist_ok=True)
     ckpt = lambda name: f"models/partial_modality/fold_{name}_best.pth"
     sel = select_genes(cohort, [survival[tr] for tr, _ in folds], ckpt, rank=rank)        # MMS_SELECT_GENES (unset: off); labelled training patients
+    xfer = Transfer(cohort, sel, rank)        # MMS_PRETRAINED / MMS_PRETRAINED_GENES / MMS_FINETUNE (unset: off)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
     if lockstep_enabled(len(my_folds), BATCH_SIZE):
@@ -57,7 +58,7 @@ def main():
         res = cv_lockstep("partial", models, loaders,
                           dict(lr=LEARNING_RATE, weight_decay=1e-4, adamw=False, gate_entropy_weight=GATE_ENTROPY_WEIGHT),
                           NUM_EPOCHS, PATIENCE, lambda o: ReduceLROnPlateau(o, mode="max", factor=0.5, patience=5),
-                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds)
+                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds, transfer=xfer)
         local = [{"fold": f + 1, "best_c_index": r["best_c_index"], "train_size": int(len(tr_all)),
                   "train_survival_size": int(len(folds[f][0])), "val_size": int(len(va_s)), "patients_per_sec": r["patients_per_sec"],
                   "epochs_run": r["epochs_run"]}
@@ -71,8 +72,9 @@ def main():
                                         augment=AUGMENT, augment_style="partial", fold=fold)
         val_loader = data.BatchLoader(cohort, val_survival, BATCH_SIZE, shuffle=False, fold=fold)
         model = PartialModalityNet(**rna_width(sel)).to(device)
+        xfer.apply(model, fold + 1, fold)
         optimizer = FusedOptimizer(model, lr=LEARNING_RATE, weight_decay=1e-4, adamw=False,
-                                   gate_entropy_weight=GATE_ENTROPY_WEIGHT)
+                                   gate_entropy_weight=GATE_ENTROPY_WEIGHT, **xfer.engine_kw)
         scheduler = ReduceLROnPlateau(optimizer, mode="max", factor=0.5, patience=5)
         best_c_index, patience_counter, t_train, n_train, epochs_run = 0, 0, 0.0, 0, 0
         for epoch in range(NUM_EPOCHS):
@@ -103,7 +105,7 @@ def main():
             "c_index_std": float(np.std(c)), "fold_results": cv_results,
             "hyperparameters": {"batch_size": BATCH_SIZE, "learning_rate": LEARNING_RATE, "epochs": NUM_EPOCHS,
                                 "n_folds": N_FOLDS, "gate_entropy_weight": GATE_ENTROPY_WEIGHT,
-                                **augment_hparams(AUGMENT), **gene_hparams(sel)}})
+                                **augment_hparams(AUGMENT), **gene_hparams(sel)}, **xfer.record()})
         print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f}; saved results/partial_modality/cv_results.json")
 
 

@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from _common import augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, load_or_make_cohort, lockstep_enabled, rna_width, save_json, select_genes, setup_device
+from _common import Transfer, augment_hparams, augment_spec, cv_lockstep, env_dims, env_float, env_int, gene_hparams, load_or_make_cohort, lockstep_enabled, rna_width, save_json, select_genes, setup_device
 
 from multimodal_survival_prediction_amd import data, distributed as D
 from multimodal_survival_prediction_amd.models import SimMLM_SurvivalNet
@@ -51,6 +51,7 @@ def main():
     os.makedirs("models/simmim", exist_ok=True)
     ckpt = lambda name: f"models/simmim/fold_{name}_best.pth"
     sel = select_genes(cohort, [usable[tr] for tr, _ in folds], ckpt, rank=rank)        # MMS_SELECT_GENES (unset: off)
+    xfer = Transfer(cohort, sel, rank)        # MMS_PRETRAINED / MMS_PRETRAINED_GENES / MMS_FINETUNE (unset: off)
     kw = dict(lr=LEARNING_RATE, weight_decay=1e-4, adamw=False, expert_weight=EXPERT_LAMBDA)
     local = []
     my_folds = list(D.folds_of_rank(N_FOLDS, world, rank))
@@ -61,7 +62,7 @@ def main():
         models = [SimMLM_SurvivalNet(**rna_width(sel)).to(device) for _ in my_folds]
         res = cv_lockstep("simmlm", models, loaders, kw, NUM_EPOCHS, PATIENCE,
                           lambda o: ReduceLROnPlateau(o, mode="max", factor=0.5, patience=5),
-                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds)
+                          ckpt, device, rank, [f + 1 for f in my_folds], fold_ids=my_folds, transfer=xfer)
         local = [{"fold": f + 1, "best_c_index": r["best_c_index"], "train_size": int(len(tr)), "val_size": int(len(va)),
                   "patients_per_sec": r["patients_per_sec"], "epochs_run": r["epochs_run"]}
                  for f, r, (tr, va) in zip(my_folds, res, splits)]
@@ -71,7 +72,8 @@ def main():
         train_loader = data.BatchLoader(cohort, tr, BATCH_SIZE, shuffle=True, seed=SEED + fold, augment=AUGMENT, augment_style="simmlm", fold=fold)
         val_loader = data.BatchLoader(cohort, va, BATCH_SIZE, shuffle=False, fold=fold)
         model = SimMLM_SurvivalNet(**rna_width(sel)).to(device)
-        optimizer = FusedOptimizer(model, **kw)
+        xfer.apply(model, fold + 1, fold)
+        optimizer = FusedOptimizer(model, **kw, **xfer.engine_kw)
         scheduler = ReduceLROnPlateau(optimizer, mode="max", factor=0.5, patience=5)
         best_c_index, patience_counter, t_train, n_train, epochs_run = 0, 0, 0.0, 0, 0
         for epoch in range(NUM_EPOCHS):
@@ -101,7 +103,7 @@ def main():
             "patients": int(len(usable)), "patients_dropped": dropped,
             "hyperparameters": {"batch_size": BATCH_SIZE, "learning_rate": LEARNING_RATE, "epochs": NUM_EPOCHS, "n_folds": N_FOLDS,
                                 "expert_lambda": EXPERT_LAMBDA,
-                                **augment_hparams(AUGMENT), **gene_hparams(sel)}})
+                                **augment_hparams(AUGMENT), **gene_hparams(sel)}, **xfer.record()})
         print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f}; saved results/simmim/cv_results.json")
 
 
