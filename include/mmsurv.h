@@ -94,7 +94,7 @@ typedef struct MmsDnOpts {
                               mms_dn121_init wrote (mms_wgrad_tab_group; the parameter pointers of the call must be those given to
                               mms_dn121_init); -1 = launches of at most MMS_MAX_GROUP by-value members (rounds 2-5) */
     int skip_dead_bwd;     /* encoder backward of a model whose feature gradient is all zero (a batch without a CT under a modality mask):
-                              0 = the head launch of mms_dn121_backward / _mt / _group records in the workspace word "bwd_live" whether any
+                              0 = the head launch of mms_dn121_backward / _group records in the workspace word "bwd_live" whether any
                               element of dout compares unequal to 0.0f (NaN counts; -0.0f is zero), and every later launch of the call
                               returns at once for a model whose word is 0 -- every quantity they compute is linear in dout, so they would
                               add exact zeros to the gradients.  The word is data, not a launch parameter: one captured graph serves live
@@ -128,7 +128,7 @@ typedef struct MmsDnOpts {
                               from the first one's computation -- which is what the full computation yields too */
     int dup_zero_bwd;      /* the same in the backward of block 1's conv2.  The gradient rows of a model's zero samples are identical through the
                               whole backward iff their rows of dout are equal; under a modality mask an absent CT's row is exactly zero.  So the
-                              head launch of mms_dn121_backward / _mt / _group leaves in the workspace word "bwd_dup" the bit mask of
+                              head launch of mms_dn121_backward / _group leaves in the workspace word "bwd_dup" the bit mask of
                               D = { b : zero_words[b] == boxes per sample and row b of dout compares equal to 0.0f in every element } (NaN
                               counts as non-zero, -0.0f as zero), or 0 when |D| < 2, B > 32 or dout is too large for the live scan.  The
                               multi-tap backward-data kernel then computes the tiles of the lowest sample of D only, stores them to the same
@@ -1112,7 +1112,7 @@ int mms_ablation_build(void);      /* 1: the library was built with a timing-abl
 int mms_dn121_workspace_bytes(int B, int D, int H, int W, size_t* bytes);
 /* Named workspace regions (tests, diagnostics): byte offset and size.  "y0", "slab" / "dslab" [block], "y1" [layer], "tpool" [transition],
  * "stats" (the per-step zeroed region), "b4_err", "hx", and "bwd_live": ONE 32-bit word per workspace, written by the head launch of
- * every mms_dn121_backward / _mt / _group call with MmsDnOpts.skip_dead_bwd on -- 1 = this model's dout had an element unequal to 0.0f
+ * every mms_dn121_backward / _group call with MmsDnOpts.skip_dead_bwd on -- 1 = this model's dout had an element unequal to 0.0f
  * (or was too large to scan), 0 = the later launches of that call returned at once.  Outside the per-step zeroed region; undefined
  * before the first such call, not touched by the staged / SyncBN / input-gradient drivers.  "bwd_dup": ONE word likewise, written by
  * the same launch where MmsDnOpts.dup_zero_bwd is on: the bit mask of the samples whose gradient rows are identical, 0 = nothing to share. */
@@ -1153,11 +1153,6 @@ int mms_dn121_backward_stage(void* ws, int B, int D, int H, int W, const float* 
                              int bn_world, mms_sync_fn hook, void* user, const MmsDnOpts* opts, hipStream_t s);
 int mms_head_bwd_sums(const HeadBwdP* p, hipStream_t s);         /* SyncBN split of mms_head_bwd: masked gradient stash + local sums */
 int mms_head_bwd_apply(const HeadBwdP* p, hipStream_t s);        /* ... norm5 backward with the (all-reduced) sums + class_layers.out gradients */
-/* same, with the per-layer weight-gradient kernels forked onto `side` (caller-created stream and two events): they
- * are off the critical path dslab -> dbn2 -> dbn1 -> dslab, so under graph capture they become parallel branches. */
-int mms_dn121_backward_mt(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
-                          const float* dout, int lddout, void* const* grads, const MmsDnOpts* opts, hipStream_t s, hipStream_t side,
-                          hipEvent_t ev_fork, hipEvent_t ev_join);
 
 /* ---- preprocessing upstream of the path, on the GPU (replaces per-item numpy/scipy on the CPU) ----
  * mms_ct_preprocess: (x - min) / (max - min + 1e-8) and scipy.ndimage.zoom(order=1) to the network grid

@@ -579,13 +579,11 @@ static int dn121_forward_impl(const Ctx* cx, int ng, int B, int D, int H, int W,
 
 // Backward of the training-mode forward that last ran on these workspaces.  grads are ACCUMULATED into
 // (caller zeroes them, e.g. one hipMemsetAsync over a flat gradient buffer).  dout: [B][128] per model.
-static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W, int lddout, const MmsDnOpts* opts, hipStream_t s, hipStream_t side,
-                               hipEvent_t ev_fork, hipEvent_t ev_join, const Dp& dp = Dp()) {
+static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W, int lddout, const MmsDnOpts* opts, hipStream_t s,
+                               const Dp& dp = Dp()) {
     const MmsDnOpts o = mms_opts(opts);
     const int nout = out_features_of(o);
     if (nout > 4096 || lddout < nout) return MMS_ERR_ARG;
-    hipStream_t sw = side ? side : s;       // stream of the weight-gradient kernels
-    bool side_pending = false;
     Plan P;
     if (!make_plan(P, B, D, H, W) || ng < 1 || ng > MMS_MAX_GROUP) return MMS_ERR_ARG;
     FOR_G if (!cx[g].ws || !cx[g].x || !cx[g].prm || !cx[g].dout || !cx[g].grd) return MMS_ERR_ARG;
@@ -638,7 +636,7 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
     // Round 4: block 1 too.  Its launches do fill the chip, but at 1-2 models per launch badly (weight gradient 32 / 37 % of the MFMA
     // peak at 1 / 2 models, 48-53 % at 5-10): its six layers are issued as launches of 6 (one model), 3 + 3 layers x 2 (two models), ...
     // members.  MmsDnOpts.batch_w = -1 restores one launch pair per layer, 1 = blocks 2-4 only (rounds 2-3).
-    const bool batch_w = o.batch_w >= 0 && !side;      // (fine under SyncBN too: the sums the weight kernels read are all-reduced by then)
+    const bool batch_w = o.batch_w >= 0;      // (fine under SyncBN too: the sums the weight kernels read are all-reduced by then)
     Conv3BwdWP bwq[MMS_MAX_GROUP];
     Conv1BwdP c1q[MMS_MAX_GROUP];
     int nq = 0;
@@ -749,10 +747,6 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 ap[g] = BnBwdApplyP{at<float>(c.ws, P.dbn_in), CTOT[b], slab, CTOT[b], dslab, CTOT[b], M, C, bn1,
                                     bbsrc(c.ws, P.bb_in[l], 1024, P.R[b]), 1, c.grd[ip], c.grd[ip + 1], lv(c)};
             }
-            if (side && side_pending) {       // the previous layer's weight kernels read dbn_mid: join before overwriting it
-                if (hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return MMS_ERR_LAUNCH;
-                side_pending = false;
-            }
             if (!b4_bwd) {
                 TRYS(8 + b, mms_conv3_bwd_data_group(bd, ng, &o, s));
                 SYNC(at<double>(cx[0].ws, P.bb_y1[l]), P.R[b], 2 * 128, 128, 128);
@@ -772,15 +766,8 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
                 if (nq + ng > nq_limit) TRY(flush_w(b));
                 FOR_G { bwq[nq] = bw[g]; c1q[nq] = c1[g]; ++nq; }
             } else {
-                if (side) {
-                    if (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, ev_fork, 0) != hipSuccess) return MMS_ERR_LAUNCH;
-                }
-                TRYS(12 + b, mms_conv3_bwd_weight_group(bw, ng, &o, sw));
-                TRYS(16 + b, mms_conv1_bwd_weight_group(c1, ng, sw));
-                if (side) {
-                    if (hipEventRecord(ev_join, side) != hipSuccess) return MMS_ERR_LAUNCH;
-                    side_pending = true;
-                }
+                TRYS(12 + b, mms_conv3_bwd_weight_group(bw, ng, &o, s));
+                TRYS(16 + b, mms_conv1_bwd_weight_group(c1, ng, s));
             }
             if (b4_bwd) continue;
             TRYS(20 + b, mms_conv1_bwd_data_group(c1, ng, &o, s));
@@ -788,10 +775,6 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
             if (!fuse_apply) TRYS(24 + b, mms_bn_bwd_apply_group(ap, ng, s));
         }
         TRY(flush_w(b));
-        if (side && side_pending) {
-            if (hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return MMS_ERR_LAUNCH;
-            side_pending = false;
-        }
         if (b > 0) {   // transition b-1 -> b
             const int t = b - 1, ip = IDX.trans[t], Kp = CTOT[t], Mp = P.M[t];
             int ms1 = M / 256; if (ms1 < 1) ms1 = 1; if (ms1 > 32) ms1 = 32;
@@ -842,9 +825,6 @@ static int dn121_backward_impl(const Ctx* cx, int ng, int B, int D, int H, int W
             TRYS(29, mms_conv0_bwd_weight_group(cw, ng, &o, s));
         }
     }
-    if (side && side_pending) {
-        if (hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return MMS_ERR_LAUNCH;
-    }
     {   // tap-major scratch -> canonical conv2 gradients of the layers this call processed: one launch for the group
         // (the dwp regions are consecutive takes)
         static_assert(NLAYER == 58, "UnpackGroup is sized for DenseNet121");
@@ -873,7 +853,7 @@ extern "C" int mms_dn121_forward(void* ws, int B, int D, int H, int W, const flo
 extern "C" int mms_dn121_backward(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
                                   const float* dout, int lddout, void* const* grads, const MmsDnOpts* opts, hipStream_t s) {
     Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
-    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr);
+    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s);
 }
 // The backward that stops above dense block block_lo (fine-tuning with frozen lower stages): stages 3 .. block_lo of ONE unstaged call, so
 // the head launch is this call's (skip_dead_bwd and the weight-gradient tables stay in force).  What dn121_backward_impl does per block --
@@ -883,14 +863,7 @@ extern "C" int mms_dn121_backward_from(void* ws, int B, int D, int H, int W, con
                                        const float* dout, int lddout, void* const* grads, int block_lo, const MmsDnOpts* opts, hipStream_t s) {
     Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
     Dp dp; dp.b_lo = block_lo;
-    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
-}
-extern "C" int mms_dn121_backward_mt(void* ws, int B, int D, int H, int W, const float* x, const void* const* params,
-                                     const float* dout, int lddout, void* const* grads, const MmsDnOpts* opts, hipStream_t s, hipStream_t side,
-                                     hipEvent_t ev_fork, hipEvent_t ev_join) {
-    if (!side || !ev_fork || !ev_join) return MMS_ERR_ARG;
-    Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
-    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, side, ev_fork, ev_join);
+    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, dp);
 }
 
 // Input-gradient attribution (include/mmsurv.h): the DATA path of the backward with every BatchNorm frozen at its running statistics,
@@ -1030,7 +1003,7 @@ extern "C" int mms_dn121_backward_stage(void* ws, int B, int D, int H, int W, co
     if (bn_world < 1) return MMS_ERR_ARG;
     Ctx c{ws, x, (const float* const*)params, nullptr, nullptr, dout, (float* const*)grads};
     Dp dp; dp.bn_world = bn_world; dp.hook = hook; dp.user = user; dp.b_hi = block_hi; dp.b_lo = block_lo; dp.staged = true;
-    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
+    return dn121_backward_impl(&c, 1, B, D, H, W, lddout, opts, s, dp);
 }
 
 // Fold-group drivers: model g of the group is described by the g-th entry of each array (all models share B, D, H, W).
@@ -1048,7 +1021,7 @@ extern "C" int mms_dn121_backward_group(int ng, void* const* ws, int B, int D, i
     if (ng < 1 || ng > MMS_MAX_GROUP || !ws || !x || !params || !dout || !grads) return MMS_ERR_ARG;
     Ctx c[MMS_MAX_GROUP];
     FOR_G c[g] = Ctx{ws[g], x[g], (const float* const*)params[g], nullptr, nullptr, dout[g], (float* const*)grads[g]};
-    return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr);
+    return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s);
 }
 extern "C" int mms_dn121_backward_group_from(int ng, void* const* ws, int B, int D, int H, int W, const float* const* x,
                                              const void* const* const* params, const float* const* dout, int lddout,
@@ -1057,5 +1030,5 @@ extern "C" int mms_dn121_backward_group_from(int ng, void* const* ws, int B, int
     Ctx c[MMS_MAX_GROUP];
     FOR_G c[g] = Ctx{ws[g], x[g], (const float* const*)params[g], nullptr, nullptr, dout[g], (float* const*)grads[g]};
     Dp dp; dp.b_lo = block_lo;
-    return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s, nullptr, nullptr, nullptr, dp);
+    return dn121_backward_impl(c, ng, B, D, H, W, lddout, opts, s, dp);
 }

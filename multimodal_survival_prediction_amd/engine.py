@@ -17,7 +17,6 @@ PyTorch supplies device memory, streams and graph capture only; every numeric op
 include/mmsurv.h.  Nothing here falls back to torch math.
 """
 import ctypes
-import os
 
 import torch
 import torch.nn as nn
@@ -25,7 +24,6 @@ import torch.nn as nn
 from . import _lib, ops
 
 _S = _lib.structs
-
 
 
 def check_train_batch(B, bn_world=1):
@@ -260,9 +258,8 @@ class SurvivalEngine:
         self.expert_weight = float(expert_weight)
         from . import losses
         self.tie_mode = ops.TIE_MODES[cox_ties or losses.default_ties()]    # CoxP.tie_mode of the fused step's loss
-        self.side_stream = torch.cuda.Stream(device=self.device)
-        self.ev_fork, self.ev_join = torch.cuda.Event(), torch.cuda.Event()
-        self.ev_fork.record(); self.ev_join.record()          # materialise the handles
+        self.sync_collectives = 0    # all-reduces issued by the SyncBN hook (distributed.DataParallel; bench.py --mode ddp --sync-bn reports them)
+        self._dp = None              # distributed.DataParallel, created by the first data-parallel train_step
         self.plans = {}
         self.dropout_masks = {}      # parity mode: {lin index: [B, K] multiplicative mask}
         # device-side epoch accumulators: [sum loss*usable, n usable, sum entropy, n batches]
@@ -377,7 +374,7 @@ class SurvivalEngine:
         return [self.flat, self.m, self.v, self.step_count, self.rng, self.acc, self.acc_eval] + list(self.model.buffers())
 
     def snapshot(self):
-        """Copy of the engine's state for the roll-back around graph capture (`capture`, `_ddp_step`)."""
+        """Copy of the engine's state for the roll-back around graph capture (`capture`, `distributed.DataParallel.step`)."""
         return [t.clone() for t in self._state()]
 
     def restore(self, snap):
@@ -816,77 +813,30 @@ class SurvivalEngine:
             _lib.check(lib.mms_dn121_backward_from(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(), dfe.stride(0),
                                                    P.gtab, self.block_lo, self._opts_arg(P), st), "mms_dn121_backward_from")
             return
+        if P.fallback:
+            _lib.check(lib.mms_fb3_backward(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
+                                            dfe.stride(0), P.gtab, st), "mms_fb3_backward")
+            return
         if stage is not None or hook is not None or P.bn_world > 1:
             hi, lo = stage if stage is not None else (3, 0)
             _lib.check(lib.mms_dn121_backward_stage(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(), dfe.stride(0),
                                                     P.gtab, hi, lo, P.bn_world, hook, None, self._opts_arg(P), st), "mms_dn121_backward_stage")
             return
-        # The weight-gradient fork (mms_dn121_backward_mt) is off by default: measured, it neither helps a single chain
-        # (graph branches run mostly serially) nor concurrent fold models (it takes hardware queues away from them).
-        if os.environ.get("MMS_SIDE_STREAM") != "1" and not P.fallback:
-            _lib.check(lib.mms_dn121_backward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
-                                              dfe.stride(0), P.gtab, self._opts_arg(P), st), "mms_dn121_backward")
-            return
-        if P.fallback:
-            _lib.check(lib.mms_fb3_backward(P.ws.data_ptr(), P.ws_bytes, P.widths, B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
-                                            dfe.stride(0), P.gtab, st), "mms_fb3_backward")
-            return
-        _lib.check(lib.mms_dn121_backward_mt(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
-                                             dfe.stride(0), P.gtab, self._opts_arg(P), st, ctypes.c_void_p(self.side_stream.cuda_stream),
-                                             ctypes.c_void_p(self.ev_fork.cuda_event), ctypes.c_void_p(self.ev_join.cuda_event)),
-                   "mms_dn121_backward_mt")
+        _lib.check(lib.mms_dn121_backward(P.ws.data_ptr(), B, D, H, W, P.ct.data_ptr(), P.ptab, dct.data_ptr(),
+                                          dfe.stride(0), P.gtab, self._opts_arg(P), st), "mms_dn121_backward")
 
-    def _global_cox_buffers(self, P, world):
-        if getattr(P, "gcox", None) is None or P.gcox["world"] != world:
-            n, dev = world * P.B, self.device
-            G = dict(world=world, h=torch.zeros(n, device=dev), time=torch.zeros(n, device=dev), event=torch.zeros(n, device=dev),
-                     valid=torch.ones(n, device=dev), lse=torch.zeros(n, device=dev), dh=torch.zeros(n, device=dev), rank=0,
-                     frac=torch.zeros(n, device=dev))
-            G["cox"] = _S()["CoxP"](G["h"].data_ptr(), 1, G["time"].data_ptr(), G["event"].data_ptr(), G["valid"].data_ptr(), n, 1.0,
-                                    G["lse"].data_ptr(), G["dh"].data_ptr(), 1, P.cox_out.data_ptr(), self.tie_mode, G["frac"].data_ptr())
-            P.gcox = G
-        return P.gcox
+    def _train_body(self, P, skip_if_unusable):
+        """zero-grad -> forward -> Cox -> backward -> clip -> Adam, epoch accumulators: the single-GPU step (also what fold sharding runs)."""
+        self._zero_step()
+        self._forward(P, True, entropy_zeroed=True)
+        self._cox_step(P)
+        self._backward_from_dhz(P)
+        self._update(P, skip_if_unusable)
 
-    def _train_body(self, P, skip_if_unusable, part="all"):
-        """zero-grad -> forward -> Cox -> backward [-> gradient all-reduce outside] -> clip -> Adam, epoch accumulators.
-        part: "all" (single GPU / fold sharding), or "grad" / "update" = the two halves around the DDP all-reduce."""
+    def _update(self, P, skip_if_unusable):
+        """Global-norm clip + Adam over the flat buffers: the sum-of-squares launch and the update launch, tuned (fine-tuning plan) or plain."""
         st = ops.stream()
         lib = self.lib
-        if part == "fwd":                      # DDP with the global risk set: first third
-            self._zero_step()
-            self._forward(P, True, entropy_zeroed=True)
-            return
-        if part in ("coxbwd", "coxheads"):     # ... loss over the gathered world*B hazards, own slice of dL/dh [, heads only]
-            G = P.gcox
-            _lib.check(lib.mms_cox_fwd_bwd(ctypes.byref(G["cox"]), st), "mms_cox_fwd_bwd")
-            P.dbuf["hz"][:, 0].copy_(G["dh"][G["rank"] * P.B:(G["rank"] + 1) * P.B])
-            if part == "coxheads":
-                self._backward_heads(P)
-            else:
-                self._backward_from_dhz(P)
-            return
-        if part == "gradheads":                # rank-local risk set: zero-grad, forward, Cox, heads' backward
-            self._zero_step()
-            self._forward(P, True, entropy_zeroed=True)
-            _lib.check(lib.mms_cox_fwd_bwd(ctypes.byref(P.cox), st), "mms_cox_fwd_bwd")
-            self._backward_heads(P)
-            return
-        if isinstance(part, tuple) and part[0] == "enc":      # one stage of the encoder backward (None = all of it)
-            self._backward_encoder(P, stage=None if part[1] is None else (part[1], part[1]))
-            return
-        if isinstance(part, tuple) and part[0] == "update":   # gradients arrived as a SUM over ranks: scale (mean for rank-local losses)
-            if part[1] != 1.0:
-                self.gflat.mul_(part[1])
-            part = "update"
-        if part in ("all", "grad"):
-            self._zero_step()
-            self._forward(P, True, entropy_zeroed=True)
-            self._cox_step(P)
-            self._backward_from_dhz(P)
-            if part == "grad":
-                return
-        if part == "update":
-            self.sumsq.zero_()                 # mms_grad_sumsq ADDS into it; the other parts that zero it are not in this graph
         if self.tune_tab is not None:
             tu = P.tune_skip if skip_if_unusable else P.tune
             _lib.check(lib.mms_grad_sumsq_tuned(ctypes.byref(tu), st), "mms_grad_sumsq_tuned")
@@ -958,9 +908,9 @@ class SurvivalEngine:
                    use_graph=True, ddp_world=1, global_cox=False, sync_bn=False):
         """One optimisation step on one batch (inputs may live on host or device).  Returns nothing: losses are
         accumulated on the device (`epoch_stats()`), exactly one host sync per epoch instead of one per batch.
-        ddp_world > 1: data-parallel step on this rank's shard of the global batch (`_ddp_step`: bucketed gradient all-reduce
-        overlapped with the backward; rank-local BatchNorm; rank-local or global_cox risk sets), or with sync_bn=True the exact
-        global-batch step (`_ddp_step_syncbn`: SyncBN + replicated heads + global risk set; eager launches)."""
+        ddp_world > 1: data-parallel step on this rank's shard of the global batch (`distributed.DataParallel.step`: bucketed gradient
+        all-reduce overlapped with the backward; rank-local BatchNorm; rank-local or global_cox risk sets), or with sync_bn=True the
+        exact global-batch step (`DataParallel.step_syncbn`: SyncBN + replicated heads + global risk set; eager launches)."""
         B = (rna if rna is not None else ct).shape[0]
         self.check_train_batch(B, tuple(ct.shape[-3:]) if ct is not None else None, ddp_world if sync_bn else 1)
         P = self.plan(B, tuple(ct.shape[-3:]) if ct is not None else None, bn_world=ddp_world if (sync_bn and ddp_world > 1) else 1)
@@ -969,18 +919,20 @@ class SurvivalEngine:
         P.fwd_serial += 1           # (a graph replay does not pass through _forward)
         if ddp_world > 1:
             self._refuse_ddp()
-        if ddp_world > 1 and P.big and self.prog["encoder"] is not None:
-            raise RuntimeError("the data-parallel steps of the imaging models are limited to 32 rows per rank (their staged graphs are "
-                               "built and tested on the small-batch head kernels); got %d -- lower the per-rank batch (the global batch is "
-                               "ddp_world times it) or train large batches on one GPU" % B)
-        if ddp_world > 1 and P.moe is not None:
-            raise RuntimeError("SimMLM_SurvivalNet: the data-parallel step (ddp_world > 1) is not implemented for this model; "
-                               "train its folds as a fold group or one per process instead")
-        if ddp_world > 1 and sync_bn:
-            self._ddp_step_syncbn(P, ddp_world)
-            return
-        if ddp_world > 1:
-            self._ddp_step(P, ddp_world, global_cox, use_graph)
+            if P.big and self.prog["encoder"] is not None:
+                raise RuntimeError("the data-parallel steps of the imaging models are limited to 32 rows per rank (their staged graphs are "
+                                   "built and tested on the small-batch head kernels); got %d -- lower the per-rank batch (the global batch "
+                                   "is ddp_world times it) or train large batches on one GPU" % B)
+            if P.moe is not None:
+                raise RuntimeError("SimMLM_SurvivalNet: the data-parallel step (ddp_world > 1) is not implemented for this model; "
+                                   "train its folds as a fold group or one per process instead")
+            if self._dp is None:
+                from .distributed import DataParallel
+                self._dp = DataParallel(self)
+            if sync_bn:
+                self._dp.step_syncbn(P, ddp_world)
+            else:
+                self._dp.step(P, ddp_world, global_cox, use_graph)
             return
         if not use_graph:
             self._train_body(P, skip_if_unusable)
@@ -989,170 +941,6 @@ class SurvivalEngine:
         if key not in P.graphs:
             P.graphs[key] = capture([self], lambda: self._train_body(P, skip_if_unusable))
         P.graphs[key].replay()
-
-    # ---- data-parallel step (one process per GPU) --------------------------------------------------------
-    def _buckets(self, P):
-        """Gradient buckets in the order the backward finalises them (distributed.gradient_buckets) -> (staged, buckets)."""
-        if getattr(self, "_bucket_cache", None) is None:
-            from . import distributed as D
-            enc = self.prog["encoder"]
-            staged = enc is not None and not isinstance(enc, nn.Sequential)
-            self._bucket_cache = (staged, D.gradient_buckets(self.params, list(enc.parameters()) if enc is not None else [], staged))
-        return self._bucket_cache
-
-    def _ddp_sequence(self, P, global_cox):
-        """The step as a list of ("part", name) compute pieces (each one HIP graph) and communication points."""
-        staged, buckets = self._buckets(P)
-        seq = [("part", "fwd"), ("gather",), ("part", "coxheads")] if global_cox else [("part", "gradheads")]
-        if staged:
-            seq.append(("bucket", 0))
-            for k, b in enumerate((3, 2, 1, 0)):
-                seq += [("part", ("enc", b)), ("bucket", k + 1)]
-        else:
-            seq += [("part", ("enc", None)), ("bucket", 0)]
-        return seq + [("wait",)], buckets
-
-    def _ddp_step(self, P, world, global_cox, use_graph):
-        """Rank-local BatchNorm statistics.  The flat gradient buffer is all-reduced (SUM) bucket by bucket, each bucket launched as
-        soon as the backward stage that finalises it has been enqueued, so the collective of stage k runs beside the kernels of
-        stage k+1 (torch.distributed enqueues an async collective behind the current stream's work and runs it on its own
-        stream; the update waits for all of them).  Rank-local risk sets: gradients are averaged (1/world folded into the update
-        graph).  global_cox: risk sets over the world*B patients (all-gather of hazard/time/event/valid), gradients summed."""
-        self._refuse_ddp()
-        from . import distributed as D
-        import torch.distributed as dist
-        seq, buckets = self._ddp_sequence(P, global_cox)
-        upd = ("update", 1.0 if global_cox else 1.0 / world)
-        if global_cox:
-            G = self._global_cox_buffers(P, world)
-            G["rank"] = dist.get_rank() if dist.is_initialized() else 0
-
-        def run(run_part):
-            works = []
-            for item in seq:
-                if item[0] == "part":
-                    run_part(item[1])
-                elif item[0] == "gather":
-                    D.all_gather_into(G["h"], P.buf["hz"][:, 0], world)
-                    D.all_gather_into(G["time"], P.time, world); D.all_gather_into(G["event"], P.event, world)
-                    D.all_gather_into(G["valid"], P.valid, world)
-                elif item[0] == "bucket":
-                    works.append(D.allreduce_ranges_async(self.gflat, buckets[item[1]], world))
-                else:
-                    for w in works:
-                        w()
-            run_part(upd)
-        if not use_graph:
-            run(lambda part: self._train_body(P, False, part))
-            return
-        key0 = ("ddp", global_cox, world)
-        if key0 not in P.graphs:
-            # the parts depend on each other through the workspace (statistic accumulators are zeroed by the first part only), so
-            # they are warmed up as ONE eager step (on the current stream: the collectives stay where they are), rolled back, and then
-            # captured without being executed
-            snap = self.snapshot()
-            run(lambda part: self._train_body(P, False, part))
-            torch.cuda.synchronize()
-            self.restore(snap)
-            graphs = {}
-            for part in [it[1] for it in seq if it[0] == "part"] + [upd]:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._train_body(P, False, part)
-                graphs[part] = g
-            P.graphs[key0] = graphs
-        graphs = P.graphs[key0]
-        run(lambda part: graphs[part].replay())
-
-    def _sync_hook(self, P, world):
-        """mms_sync_fn (include/mmsurv.h) of a plan: all-reduce freshly written BatchNorm accumulator words over the ranks."""
-        if getattr(P, "sync_hook", None) is None:
-            from . import distributed as D
-            base0 = P.ws.data_ptr()
-            ws64 = P.ws[:P.ws.numel() // 8 * 8].view(torch.float64)
-
-            def hook(user, base, nrep, rstride, ncols, pstride, stream):
-                try:
-                    self.sync_collectives = getattr(self, "sync_collectives", 0) + 1      # (reported by bench.py --mode ddp --sync-bn)
-                    t = ws64.as_strided((nrep, 2, ncols), (rstride, pstride, 1), (base - base0) // 8)
-                    buf = t.contiguous()
-                    D.allreduce_sum_(buf, world)
-                    if buf.data_ptr() != t.data_ptr():
-                        t.copy_(buf)
-                    return 0
-                except Exception as e:      # never raise through the C frame
-                    print("mmsurv: SyncBN hook failed: %r" % (e,), flush=True)
-                    return -2
-            P.sync_hook = _lib.SYNC_FN(hook)
-        return P.sync_hook
-
-    def _ddp_step_syncbn(self, P, world):
-        """Exact single-process semantics for a global batch of world*B patients (SURVEY.md section 8e ii-iii), eager launches.
-        Collectives per step: ONE all-reduce per statistic-producing kernel (all replicas and both moments of its channels in one
-        message): 121 in the forward (conv0, pool0, conv1 + conv2 of the 58 dense layers, 3 transitions), 121 in the backward, + the
-        feature / label all-gathers and the gradient all-reduce -- 2 per BatchNorm layer and pass, the same count torch's SyncBatchNorm
-        issues.  It cannot be lower without changing the arithmetic: layer l's conv2 normalises with the statistics of ITS conv1's
-        output and layer l+1's conv1 with those of layer l's conv2 output, so the chain y1-stats(l) -> z-stats(l) -> y1-stats(l+1) is
-        strictly sequential (the slab's OLDER channels are reduced once, when they are produced, and reused by every later layer).
-        `self.sync_collectives` counts them; bench.py --mode ddp --sync-bn reports the count per step.
-          * encoder: every BatchNorm3d statistic (forward sums, backward sums) is all-reduced between the kernel that produces it
-            and the kernels that consume it (the drivers' hook);
-          * heads (BatchNorm1d over the batch, gate, Cox risk set): replicated -- the encoder features and the small per-patient
-            inputs are all-gathered and every rank runs the heads on the GLOBAL batch, then back-propagates its own patients'
-            feature gradient through its encoder;
-          * gradients: encoder weights hold rank-local partial sums -> SUM; head parameters and BatchNorm3d gamma/beta hold the
-            global value on every rank -> pre-scaled by 1/world so that the same SUM returns them; then clip + Adam."""
-        self._refuse_ddp()
-        from . import distributed as D
-        import torch.distributed as dist
-        if not P.has_enc or P.fallback:
-            raise RuntimeError("sync_bn: the DenseNet121-3D imaging models only")
-        st = ops.stream()
-        lib, prog = self.lib, self.prog
-        rank = dist.get_rank() if dist.is_initialized() else 0
-        B, (Dd, H, W) = P.B, P.dims
-        Pg = self.plan(world * B, P.dims, heads_only=True)
-        hook = self._sync_hook(P, world)
-        cc = prog["ct_cols"]
-        self.gflat.zero_(); self.sumsq.zero_()
-        feats = P.buf["feats"]
-        _lib.check(lib.mms_dn121_forward_sync(P.ws.data_ptr(), B, Dd, H, W, P.ct.data_ptr(), P.ptab, P.btab, feats[:, cc:].data_ptr(),
-                                              feats.stride(0), world, hook, None, self._opts_arg(P), st), "mms_dn121_forward_sync")
-
-        def gather(dst, src):
-            tmp = torch.empty(world * src.shape[0], *src.shape[1:], device=self.device)
-            D.all_gather_into(tmp.view(-1), src.contiguous().view(-1), world)
-            dst.copy_(tmp.view(dst.shape))
-        ew = prog.get("enc_width", 128)
-        gather(Pg.buf["feats"][:, cc:cc + ew], feats[:, cc:cc + ew])
-        for name in ("rna", "clin"):
-            if name in P.buf:
-                gather(Pg.buf[name], P.buf[name])
-        if P.gate is not None:
-            gather(Pg.mask, P.mask)
-        if P.mix is not None:
-            gather(Pg.mask2, P.mask2)
-        gather(Pg.time, P.time); gather(Pg.event, P.event); gather(Pg.valid, P.valid)
-        self._forward(Pg, True)                                   # heads only (Pg.has_enc is False)
-        _lib.check(lib.mms_cox_fwd_bwd(ctypes.byref(Pg.cox), st), "mms_cox_fwd_bwd")
-        self._backward_heads(Pg)
-        P.dbuf["feats"][:, cc:cc + ew].copy_(Pg.dbuf["feats"][rank * B:(rank + 1) * B, cc:cc + ew])
-        self._backward_encoder(P, hook=hook)
-        if getattr(self, "_share", None) is None or self._share[0] != world:
-            sh = torch.full_like(self.gflat, 1.0 / world)        # heads + BatchNorm3d parameters: global value on every rank
-            o = 0
-            bn_ids = {id(q) for m in prog["encoder"].modules() if isinstance(m, nn.BatchNorm3d) for q in m.parameters()}
-            eids = {id(q) for q in prog["encoder"].parameters()}
-            for q in self.params:
-                if id(q) in eids and id(q) not in bn_ids:
-                    sh[o:o + q.numel()] = 1.0                    # conv / class_layers weights: rank-local partial sums
-                o += q.numel()
-            self._share = (world, sh)
-        self.gflat.mul_(self._share[1])
-        D.allreduce_sum_(self.gflat, world)
-        ad = Pg.adam
-        _lib.check(lib.mms_grad_sumsq(ctypes.byref(ad), st), "mms_grad_sumsq")
-        _lib.check(lib.mms_clip_adam(ctypes.byref(ad), st), "mms_clip_adam")
 
     def forward_eval(self, ct=None, rna=None, clinical=None, mask=None, use_graph=True):
         """Eval-mode forward -> (hazard [B] view of a static buffer, gate [B,3] or None)."""

@@ -32,6 +32,21 @@ def stats(device, C):
     return torch.zeros(C, dtype=torch.float64, device=device), torch.zeros(C, dtype=torch.float64, device=device)
 
 
+class _Recorder:
+    """Stands in for an engine's library handle: records the entry points called."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*a):
+            self.calls.append(name)
+            return fn(*a)
+        return call
+
+
 def assert_conv2_packs_current(eng):
     """The derived conv2 packs of a SurvivalEngine with packed primary storage against the stand-alone pack kernels on the CURRENT weights,
     all 58 layers, bit for bit (the identities of tests/test_gpu_w2pack.py::test_w2_pack_equals_standalone_pack_kernels): the backward-data

@@ -85,7 +85,7 @@ def test_two_rank_gloo(tmp_path):
 
 
 def test_gradient_buckets_cover_flat_buffer_once():
-    """engine._buckets / distributed.gradient_buckets: heads first, then the DenseNet121 backward stages 3..0; contiguous ranges that
+    """distributed.gradient_buckets (DataParallel.buckets): heads first, then the DenseNet121 backward stages 3..0; contiguous ranges that
     cover the parameter-ordered flat buffer exactly once, each stage = the parameter tensors of its dense block (+ transition / stem / norm5)."""
     from multimodal_survival_prediction_amd import distributed as D, models
     m = models.MultiModalSurvivalNet(rna_dim=16)
@@ -114,6 +114,32 @@ def test_gradient_buckets_cover_flat_buffer_once():
     # single bucket for an encoder-less / fallback model
     one = D.gradient_buckets(params, [], False)
     assert one == [[(0, n)]]
+
+
+def test_step_sequence_orders_parts_and_buckets():
+    """distributed.step_sequence: the data-parallel step's compute parts and communication points, all four (staged, global_cox)
+    combinations; every gradient bucket is launched exactly once, after the part that finalises it (heads -> 0, stage b -> 4 - b)."""
+    from multimodal_survival_prediction_amd import distributed as D, models
+    part, bucket = (lambda name: ("part", name)), (lambda k: ("bucket", k))
+    stages = [bucket(0), part(("enc", 3)), bucket(1), part(("enc", 2)), bucket(2), part(("enc", 1)), bucket(3), part(("enc", 0)), bucket(4),
+              ("wait",)]
+    assert D.step_sequence(True, True) == [part("fwd"), ("gather",), part("coxheads")] + stages
+    assert D.step_sequence(True, False) == [part("gradheads")] + stages
+    assert D.step_sequence(False, True) == [part("fwd"), ("gather",), part("coxheads"), part(("enc", None)), bucket(0), ("wait",)]
+    assert D.step_sequence(False, False) == [part("gradheads"), part(("enc", None)), bucket(0), ("wait",)]
+    m = models.MultiModalSurvivalNet(rna_dim=16)
+    params, enc = list(m.parameters()), list(m.ct_encoder.parameters())
+    for staged in (True, False):
+        n = len(D.gradient_buckets(params, enc if staged else [], staged))
+        # the part whose end finalises bucket k: the heads' backward, then encoder stage 3, 2, 1, 0 (unstaged: the whole backward)
+        final = [("coxheads", "gradheads")] + [(("enc", b),) for b in (3, 2, 1, 0)] if staged else [(("enc", None),)]
+        for global_cox in (True, False):
+            seq = D.step_sequence(staged, global_cox)
+            assert [it[1] for it in seq if it[0] == "bucket"] == list(range(n))
+            assert seq[-1] == ("wait",) and seq.count(("wait",)) == 1
+            for k in range(n):
+                done = [i for i, it in enumerate(seq) if it[0] == "part" and it[1] in final[k]]
+                assert len(done) == 1 and done[0] < seq.index(bucket(k))
 
 
 def test_bench_launches_its_own_ranks(tmp_path):

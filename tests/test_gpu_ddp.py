@@ -122,6 +122,7 @@ import numpy as np, torch, torch.distributed as dist
 from multimodal_survival_prediction_amd import distributed as D, models as HM
 from multimodal_survival_prediction_amd.training import FusedOptimizer
 from oracle import models as OM, losses as OL
+from gpu_util import _Recorder
 from test_gpu_densenet import structured_volumes
 world, rank, local = D.init("gloo")
 dev = torch.device("cuda", 0)
@@ -267,6 +268,17 @@ def run_mode(MODE):
             sc_ = float(x.abs().max()) + 1e-30
             e_hip, e_f32 = float((c.cpu().double() - x).abs().max()) / sc_, float((b.double() - x).abs().max()) / sc_
             assert e_hip <= 4.0 * e_f32 + 1e-4, (MODE, k, e_hip, e_f32)
+    # Launch order of the mode: one more eager step on the last batch, the library handle wrapped in the recorder (both ranks: the
+    # collectives pair up).  The lists are what the step launched before the data-parallel steps moved to distributed.DataParallel.
+    fo.engine.lib = rec = _Recorder(fo.engine.lib)
+    fo.engine.train_step(ct[sl], rna[sl], clin[sl], time=t[sl], event=e[sl], skip_if_unusable=False, ddp_world=world,
+                         global_cox=MODE == "global_cox", sync_bn=MODE == "sync_bn", use_graph=False)
+    torch.cuda.synchronize()
+    fo.engine.lib = rec._lib
+    heads = ["mms_linear_fwd"] * 6 + ["mms_cox_fwd_bwd"] + ["mms_linear_bwd"] * 6
+    want = (["mms_dn121_forward_sync"] + heads + ["mms_dn121_backward_stage"] if MODE == "sync_bn" else
+            ["mms_zero_spans_group", "mms_dn121_forward"] + heads + ["mms_dn121_backward_stage"] * 4) + ["mms_grad_sumsq", "mms_clip_adam"]
+    assert rec.calls == want, (MODE, rec.calls)
     D.barrier()
     print("mode ok", rank, MODE, close / tot, flush=True)
 

@@ -13,7 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import finetune_ref as R
-from gpu_util import DEV, assert_close, rel_err
+from gpu_util import DEV, _Recorder, assert_close, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W2N = 32 * 27 * 128
@@ -392,21 +392,6 @@ def test_fold_group_with_plan_matches_oracle():
 
 
 # ---- refusals and the no-plan path ---------------------------------------------------------------------------
-class _Recorder:
-    """Stands in for an engine's library handle: records the entry points called."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def call(*a):
-            self.calls.append(name)
-            return fn(*a)
-        return call
-
-
 def _calls(finetune="absent"):
     from multimodal_survival_prediction_amd import models as HM
     from multimodal_survival_prediction_amd.engine import SurvivalEngine
@@ -423,6 +408,7 @@ def _calls(finetune="absent"):
 
 
 def test_no_plan_enqueues_the_same_launches_and_refusals():
+    from multimodal_survival_prediction_amd.distributed import DataParallel
     from multimodal_survival_prediction_amd.engine import engine_of
     from multimodal_survival_prediction_amd.transfer import FineTunePlan
     _, absent = _calls()
@@ -452,9 +438,9 @@ def test_no_plan_enqueues_the_same_launches_and_refusals():
     with pytest.raises(RuntimeError, match="data-parallel"):
         eng.train_step(ct, rna, clin, mask=mask, time=t, event=e, ddp_world=2)
     with pytest.raises(RuntimeError, match="data-parallel"):
-        eng._ddp_step(None, 2, False, False)
+        DataParallel(eng).step(None, 2, False, False)
     with pytest.raises(RuntimeError, match="data-parallel"):
-        eng._ddp_step_syncbn(None, 2)
+        DataParallel(eng).step_syncbn(None, 2)
 
 
 # ---- one entry point ---------------------------------------------------------------------------------------
