@@ -729,6 +729,89 @@ typedef struct CoxNewtonP {
     double* info;                       // [R * S][p][p] out, or NULL
 } CoxNewtonP;
 
+/* Random survival forest (csrc/rsf.hip; survival_forest.py): T trees grown level by level in lock-step over ONE feature-major matrix.
+ * The n patients stand in TIME-DESCENDING order (any order inside a group of equal times): event[i] = 0 / 1, tgroup[i] = the number of
+ * position i's group of equal times (equal inside a group, different between neighbouring groups).  xt[f][i] is feature f of position
+ * i.  A tree t is its multiplicity row mult[t][0..n) (0 = out of bag; a repeat counts as a separate subject) and its hash stream
+ * id = tree_id[t] (t when tree_id is NULL).  Trees are heap-indexed: node s has the children 2s + 1 and 2s + 2; the tables have nn
+ * nodes a tree.  node[t][i] is the current node of in-bag position i (all 0 before level 0).
+ *
+ * mms_rsf_split, one launch per level: workgroup = (tree, node s = 2^level - 1 + k).  It returns at once when s > 0 and its parent
+ * recorded no split, or when n_node[s] < 2 min_leaf (s > 0: the parent's launch wrote it).  Otherwise the node's m in-bag members are
+ * compacted in position order and C = mtry * nsplit candidates c = j * nsplit + q are scored.  With hash = csrc/common.h's hash_u32 and
+ * mulhi(h, k) = (h * k) >> 32 in 64 bits:
+ *     ht = hash(seed ^ (id * 0x85ebca6b));  hn = hash((s + 1) * 0x9E3779B9 + ht);  hf = hash((j + 1) * 0x9E3779B9 + hn);
+ *     feature f = mulhi(hf, p);   hq = hash((q + 1) * 0x85ebca6b + hf);   threshold = xt[f][position of member mulhi(hq, m)],
+ * all in 32-bit wrap-around arithmetic.  A member goes LEFT iff x <= threshold.  Over the node's tie groups with events, in time-
+ * descending order, with Y = the node's weighted members up to the group's end, d = the group's weighted events and Y_L the left
+ * child's weighted members up to there,
+ *     E <- fma(d / Y, Y_L, E),   V <- fma((d (Y - d) / (Y Y (Y - 1))) Y_L, Y - Y_L, V)   (the second coefficient 0 when Y = 1),
+ *     U = D_L - E  (D_L: the left child's weighted events),   chi2 = U U / V, 0 when V <= 0:
+ * the two-group log-rank statistic of survival_stats.logrank_test with every patient repeated mult times.  Counts are exact integers,
+ * the terms fp64.  A candidate is admissible when both children hold >= min_leaf weighted members; the largest chi2 > 0 among the
+ * admissible ones wins, the smallest c on ties: feat[s] = f, thr[s], stat[s] = chi2, n_node / d_node of both children are written and
+ * the node's members are routed (node[t][i] = 2s + 1 + [x > thr]) by the same workgroup.  Without a winner feat[s] = -1 (a leaf).
+ * Level 0 also writes n_node[0] / d_node[0].  The caller initialises feat = -1 and the other tables = 0.  U / V / n_left / d_left:
+ * optional tables [T][2^level][ldo] of every candidate, all four or none (a workgroup that returns at once writes nothing).
+ *
+ * mms_rsf_leaves, one launch after the last level: for every node with feat < 0 and n_node > 0 the Nelson-Aalen increments d / Y of its
+ * members' tie groups with events, in time-descending order, give mort = sum (d / Y) weight[w][i] (w = wset[t], 0 when wset is NULL; i
+ * a position of the group; weight[w][i] = the number of distinct event times of training set w that are >= time i, which makes mort
+ * the sum of H over those times) and H[h] = sum of d / Y over the groups at positions >= hpos[h] (hpos[h] = the number of positions
+ * with time > horizon h).
+ *
+ * mms_rsf_predict, one launch: workgroup = row of x [R][ldx]; it drops the row down every tree t with use[t][row] != 0 (all when use is
+ * NULL), thread j summing trees j, j + 256, ... in ascending order and the 256 partial sums folded in a fixed order:
+ * out_mort[row], out_H[row][h] = the means over the admitted trees, NaN when count[row] = 0.
+ *
+ * fp64 statistics, no atomics, plain stores; a tree's bits depend on its own multiplicities and hash stream only.  The launches cannot
+ * check the tables' contents: the CALLER guarantees the order of the positions, tgroup, feat < p and node values (ops.rsf_* check on
+ * the host).  A NULL required pointer, n outside 1..MMS_RSF_MAX_N, ld < n, p < 1, T < 0, T > MMS_RSF_MAX_T, level outside
+ * [0, MMS_RSF_MAX_DEPTH), nn < 2^(level + 2) - 1 (split) or nn outside 1..2^(MMS_RSF_MAX_DEPTH + 1) - 1, mtry < 1, nsplit < 1,
+ * mtry * nsplit > MMS_RSF_MAX_C, min_leaf < 1, some but not all of the tables, ldo < C with tables, nh outside 0..MMS_RSF_MAX_H, F < 1,
+ * R < 0, ldx < p, ldu < R with use, or a pointer not aligned to its element: MMS_ERR_ARG before any launch.  T = 0 (R = 0 for
+ * predict): MMS_OK without a launch. */
+#define MMS_RSF_MAX_N 2048       /* 28 bytes of LDS a member: 56 KB of the 64 KB a workgroup may declare */
+#define MMS_RSF_MAX_DEPTH 12
+#define MMS_RSF_MAX_C 65535
+#define MMS_RSF_MAX_T 65535      /* T * 2^11 workgroups at the deepest level stay below 2^31 */
+#define MMS_RSF_MAX_H 32
+typedef struct RsfSplitP {
+    int n; int ld; int p; int T;        // positions, pitch of xt / mult / node, features, trees
+    int level; int nn;                  // the level of this launch, nodes a tree in the tables
+    int mtry; int nsplit; int min_leaf; unsigned seed;
+    const float* xt;                    // [p][ld]
+    const unsigned char* mult;          // [T][ld]
+    const int* event; const int* tgroup;   // [n]
+    const int* tree_id;                 // [T] hash stream of each tree, or NULL: t
+    int* node;                          // [T][ld] in / out
+    int* feat; float* thr; double* stat; int* n_node; int* d_node;   // [T][nn]
+    double* U; double* V;               // [T][2^level][ldo] out or NULL
+    int* n_left; int* d_left;           // [T][2^level][ldo] out or NULL
+    int ldo;
+} RsfSplitP;
+typedef struct RsfLeavesP {
+    int n; int ld; int T; int nn; int nh; int F;   // F: weight rows
+    const unsigned char* mult;          // [T][ld]
+    const int* event; const int* tgroup;   // [n]
+    const int* node;                    // [T][ld]
+    const int* feat; const int* n_node; // [T][nn]
+    const double* weight;               // [F][ld]
+    const int* wset;                    // [T] weight row of each tree, or NULL: row 0
+    const int* hpos;                    // [nh]
+    double* mort;                       // [T][nn] out
+    double* H;                          // [T][nn][nh] out
+} RsfLeavesP;
+typedef struct RsfPredictP {
+    int R; int ldx; int p; int T; int nn; int nh;
+    const float* x;                     // [R][ldx]
+    const int* feat; const float* thr;  // [T][nn]
+    const double* mort; const double* H;   // [T][nn], [T][nn][nh]
+    const unsigned char* use; int ldu;  // [T][ldu] or NULL
+    double* out_mort; double* out_H;    // [R], [R][nh] out
+    int* count;                         // [R] out: admitted trees
+} RsfPredictP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -1091,7 +1174,10 @@ int mms_gene_screen(const GeneScreenP* p, hipStream_t s);     /* univariate Cox 
 int mms_logrank_scan(const LogrankScanP* p, hipStream_t s);   /* log-rank statistic of every cut of Q problems (LogrankScanP above) */
 int mms_td_metrics(const TdMetricsP* p, hipStream_t s);       /* IPCW Brier / dynamic AUC sums of M models x H horizons x R replicates (TdMetricsP above) */
 int mms_cox_newton(const CoxNewtonP* p, hipStream_t s);       /* Newton-Raphson Cox fits of R replicates x S covariate subsets (CoxNewtonP above) */
-int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);        /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
+int mms_rsf_split(const RsfSplitP* p, hipStream_t s);         /* random survival forest: one level of T trees (RsfSplitP above) */
+int mms_rsf_leaves(const RsfLeavesP* p, hipStream_t s);       /* ... mortality and H at the horizons of every leaf */
+int mms_rsf_predict(const RsfPredictP* p, hipStream_t s);     /* ... masked mean over the trees for R rows */
+int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);       /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */
 int mms_clip_adam(const AdamP* p, hipStream_t s);              /* clip by global norm + Adam/AdamW update (+ the derived conv2 packs, AdamP.w2_*) */

@@ -451,6 +451,105 @@ def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False,
     return _launch_or_plan("mms_logrank_scan", p, (t, out), res, plan_only)
 
 
+def _rsf_dev(t, dtype, what, dims=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (dims is not None and t.dim() != dims):
+        raise TypeError("%s must be a contiguous %s device tensor%s" % (what, dtype, "" if dims is None else " of %d dimensions" % dims))
+    return t
+
+
+def rsf_split(xt, mult, event, tgroup, node, tables, level, mtry, nsplit, min_leaf, seed, tree_id=None, candidates=False, plan_only=False):
+    """One level of T lock-step survival trees (RsfSplitP in mmsurv.h).  Device tensors: xt fp32 [p, n] feature-major in position order,
+    mult uint8 [T, n], event / tgroup int32 [n], node int32 [T, n] (updated), tables = dict(feat int32, thr fp32, stat fp64, n_node,
+    d_node int32), each [T, nn] (updated), tree_id int32 [T] or None.  candidates: also return dict(U, V float64, n_left, d_left int32)
+    [T, 2^level, C] of every candidate (zero where a node's workgroup returned at once)."""
+    _rsf_dev(xt, torch.float32, "xt", 2); _rsf_dev(mult, torch.uint8, "mult", 2); _rsf_dev(node, torch.int32, "node", 2)
+    _rsf_dev(event, torch.int32, "event", 1); _rsf_dev(tgroup, torch.int32, "tgroup", 1)
+    p_, n = xt.shape
+    T = mult.shape[0]
+    if mult.shape[1] != n or tuple(node.shape) != (T, n) or len(event) != n or len(tgroup) != n:
+        raise ValueError("mult / node must be [T, n] and event / tgroup [n] for xt [p, n]")
+    kinds = dict(feat=torch.int32, thr=torch.float32, stat=torch.float64, n_node=torch.int32, d_node=torch.int32)
+    nn = tables["feat"].shape[1] if T else 1
+    for k, dt in kinds.items():
+        _rsf_dev(tables[k], dt, k, 2)
+        if tuple(tables[k].shape) != (T, nn):
+            raise ValueError("the tree tables must all be [T, nn]")
+    if tree_id is not None:
+        _rsf_dev(tree_id, torch.int32, "tree_id", 1)
+        if len(tree_id) != T:
+            raise ValueError("tree_id must name one hash stream per tree")
+    C = int(mtry) * int(nsplit)
+    out = None
+    if candidates:
+        shape = (max(T, 1), 1 << int(level), max(C, 1))
+        out = dict(U=torch.zeros(shape, dtype=torch.float64, device=xt.device), V=torch.zeros(shape, dtype=torch.float64, device=xt.device),
+                   n_left=torch.zeros(shape, dtype=torch.int32, device=xt.device), d_left=torch.zeros(shape, dtype=torch.int32, device=xt.device))
+    if T == 0:                                                       # an empty forest: nothing to launch (and no pointer to give)
+        return None if out is None else {k: v[:0] for k, v in out.items()}
+    g = (lambda k: ptr(out[k])) if candidates else (lambda k: None)
+    p = _S()["RsfSplitP"](n, n, p_, T, int(level), nn, int(mtry), int(nsplit), int(min_leaf), int(seed) & 0xffffffff, ptr(xt), ptr(mult),
+                          ptr(event), ptr(tgroup), ptr(tree_id), ptr(node), ptr(tables["feat"]), ptr(tables["thr"]), ptr(tables["stat"]),
+                          ptr(tables["n_node"]), ptr(tables["d_node"]), g("U"), g("V"), g("n_left"), g("d_left"), max(C, 1) if candidates else 0)
+    res = None if out is None else {k: v[:T] for k, v in out.items()}
+    return _launch_or_plan("mms_rsf_split", p, (xt, mult, event, tgroup, node, tables, tree_id, out), res, plan_only)
+
+
+def rsf_leaves(mult, event, tgroup, node, feat, n_node, weight, wset, hpos, plan_only=False):
+    """Mortality and cumulative hazard at the horizons of every leaf of T trees (RsfLeavesP in mmsurv.h).  Device tensors: mult uint8
+    [T, n], event / tgroup int32 [n], node int32 [T, n], feat / n_node int32 [T, nn], weight float64 [F, n], wset int32 [T] or None (row
+    0), hpos int32 [nh].  -> (mort float64 [T, nn], H float64 [T, nn, nh]), zero at nodes that are no leaf."""
+    _rsf_dev(mult, torch.uint8, "mult", 2); _rsf_dev(node, torch.int32, "node", 2); _rsf_dev(event, torch.int32, "event", 1)
+    _rsf_dev(tgroup, torch.int32, "tgroup", 1); _rsf_dev(feat, torch.int32, "feat", 2); _rsf_dev(n_node, torch.int32, "n_node", 2)
+    _rsf_dev(weight, torch.float64, "weight", 2); _rsf_dev(hpos, torch.int32, "hpos", 1)
+    T, n = mult.shape
+    nn, F, nh = feat.shape[1], weight.shape[0], len(hpos)
+    if tuple(node.shape) != (T, n) or len(event) != n or len(tgroup) != n or weight.shape[1] != n or tuple(n_node.shape) != (T, nn):
+        raise ValueError("node must be [T, n], event / tgroup [n], weight [F, n], n_node like feat")
+    if wset is not None:
+        _rsf_dev(wset, torch.int32, "wset", 1)
+        if len(wset) != T or (T and (int(wset.min()) < 0 or int(wset.max()) >= F)):
+            raise ValueError("wset must name one of the %d weight rows for each tree" % F)
+    if nh and (int(hpos.min()) < 0 or int(hpos.max()) > n):
+        raise ValueError("hpos must lie in [0, n]")
+    mort = torch.zeros(T, nn, dtype=torch.float64, device=mult.device)
+    H = torch.zeros(T, nn, max(nh, 1), dtype=torch.float64, device=mult.device)
+    if T == 0:
+        return mort, H[:, :, :nh]
+    p = _S()["RsfLeavesP"](n, n, T, nn, nh, F, ptr(mult), ptr(event), ptr(tgroup), ptr(node), ptr(feat), ptr(n_node), ptr(weight), ptr(wset),
+                           ptr(hpos) if nh else None, ptr(mort), ptr(H))
+    return _launch_or_plan("mms_rsf_leaves", p, (mult, event, tgroup, node, feat, n_node, weight, wset, hpos), (mort, H[:, :, :nh]), plan_only)
+
+
+def rsf_predict(x, feat, thr, mort, H, use=None, plan_only=False):
+    """Masked forest means of R rows (RsfPredictP in mmsurv.h).  x fp32 [R, p] device (row pitch x.stride(0)); feat int32, thr fp32, mort
+    float64 [T, nn], H float64 [T, nn, nh] contiguous; use uint8 [T, R] or None (all trees).  feat is checked HERE against p (the launch
+    cannot).  -> (mortality float64 [R], H float64 [R, nh], count int32 [R]); NaN where count is 0."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise TypeError("x must be a float32 [R, p] device tensor with unit column stride")
+    _rsf_dev(feat, torch.int32, "feat", 2); _rsf_dev(thr, torch.float32, "thr", 2); _rsf_dev(mort, torch.float64, "mort", 2)
+    _rsf_dev(H, torch.float64, "H", 3)
+    R, p_ = x.shape
+    T, nn = feat.shape
+    nh = H.shape[2]
+    if tuple(thr.shape) != (T, nn) or tuple(mort.shape) != (T, nn) or tuple(H.shape[:2]) != (T, nn):
+        raise ValueError("thr, mort and H must match feat [T, nn]")
+    if T and int(feat.max()) >= p_:
+        raise ValueError("the forest splits on feature %d; x has %d columns" % (int(feat.max()), p_))
+    if use is not None:
+        _rsf_dev(use, torch.uint8, "use", 2)
+        if tuple(use.shape) != (T, R):
+            raise ValueError("use must be [T, R]")
+    dev = x.device
+    om = torch.zeros(max(R, 1), dtype=torch.float64, device=dev)
+    oh = torch.zeros(max(R, 1), max(nh, 1), dtype=torch.float64, device=dev)
+    cnt = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
+    d = torch.zeros(1, dtype=torch.float64, device=dev)            # never a NULL pointer for an empty table
+    pz = lambda t: ptr(t) if t.numel() else ptr(d)
+    p = _S()["RsfPredictP"](R, max(x.stride(0), p_) if R else p_, p_, T, max(nn, 1), nh, pz(x), pz(feat), pz(thr), pz(mort), pz(H), ptr(use),
+                            R if use is not None else 0, ptr(om), ptr(oh), ptr(cnt))
+    return _launch_or_plan("mms_rsf_predict", p, (x, feat, thr, mort, H, use, om, oh, cnt, d), (om[:R], oh[:R, :nh], cnt[:R]), plan_only)
+
+
 def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     """IPCW Brier / dynamic AUC sums of M models at H horizons under R multiplicity rows (TdMetricsP in mmsurv.h).  trank, event: [n] dense
     time ranks and event flags of the TIME-ASCENDING positions (events before censorings at equal times), hcut: [H] positions with

@@ -17,13 +17,16 @@ RESULTS_FILES = {          # display name -> file written by scripts/training/<e
     "SimMLM": "results/simmim/cv_results.json",              # scripts/training/simmlm_training.py
     "Image-Only": "results/image_only/cv_results.json",      # scripts/training/image_only_training.py
     "Cox elastic net": "results/cox_baseline/cv_results.json",   # scripts/training/cox_baseline.py
+    "Random survival forest": "results/rsf_baseline/cv_results.json",   # scripts/training/rsf_baseline.py
 }
 # The baseline's fold values are the OUTER validation C-index at a lambda chosen by inner cross-validation on the training patients (nested
 # CV); a network's best_c_index is its maximum over the epochs ON the validation fold.  The two are not on equal footing, and the baseline
-# is the one handicapped.
-NESTED = ("Cox elastic net",)
-NESTED_NOTE = ("(+) nested cross-validation: lambda chosen inside each fold's training patients, the validation fold not seen; the other "
-               "rows are maxima over epochs on the validation fold -- not on equal footing, the (+) row is the one handicapped")
+# is the one handicapped.  The forest's fold values are the validation C-index of the forest as specified: nothing is chosen on the
+# validation fold either.
+NESTED = ("Cox elastic net", "Random survival forest")
+NESTED_NOTE = ("(+) nested cross-validation: lambda chosen inside each fold's training patients, the validation fold not seen (the forest: "
+               "grown as specified, nothing tuned on the validation fold); the other rows are maxima over epochs on the validation fold -- "
+               "not on equal footing, the (+) rows are the ones handicapped")
 
 
 def collect(root="."):
