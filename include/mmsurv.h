@@ -812,6 +812,54 @@ typedef struct RsfPredictP {
     int* count;                         // [R] out: admitted trees
 } RsfPredictP;
 
+/* Permutation importance (ensemble VIMP, randomForestSRC importance = "permute") of a forest, mms_rsf_vimp: P problems (set f, gene g)
+ * times R repeats in ONE launch, workgroup = (problem q, repeat r), output index q R + r.
+ *
+ * A set f is some of the trees (a fold's) with the rows they admit: use[t][i] != 0 (the out-of-bag mask, or a validation mask), the
+ * base ensemble mortality M0[f][i] and tree count cnt[f][i] -- exactly what mms_rsf_predict returns for that mask over the set's trees.
+ * Rows with cnt = 0 are not part of the set's problems.  Rows are rows of x [n][ldx] as mms_rsf_predict takes it (NOT time positions).
+ *
+ * donor[r][t][i]: the row whose value of the problem's gene row i reads in tree t under repeat r.  The contract of the table
+ * (survival_forest.permutation_donors builds it; tests/rsf_vimp_ref.py restates it), all in 32-bit wrap-around arithmetic with
+ * hash = csrc/common.h's hash_u32 and ht = hash(seed ^ (id * 0x85ebca6b)) the tree key of RsfSplitP:
+ *     hp = hash((r + 1) * 0x85EBCA6B + hash(ht ^ 0x68E31DA4));    k_i = hash((i + 1) * 0x9E3779B9 + hp);
+ *     a_0 < a_1 < ... the rows tree t admits, s_0, s_1, ... the same rows sorted by (k, i) ascending:  donor[a_j] = s_j,
+ * and a row the tree does not admit is its own donor.  One permutation per (tree, repeat) serves every gene.
+ *
+ * Problem q = (pset[q], pgene[q]) lists the trees of its set that split on its gene at any node, ascending and without repeats:
+ * ptree[poff[q] .. poff[q + 1]).  For row i with cnt > 0, over those trees in that order that admit i, sequentially in fp64 from 0.0,
+ *     D_i += mort_t(leaf') - mort_t(leaf),
+ * leaf = the leaf of mms_rsf_predict's walk (stop: feat < 0 || 2 s + 2 >= nn), leaf' = the same walk reading x[donor[r][t][i]][g] in
+ * place of x[i][g] at EVERY node on g (a gene met twice on one path reads the substituted value both times).  Then
+ *     M_i = M0[f][i] + D_i / cnt[f][i]
+ * (IEEE fp64: one subtraction and one addition per tree, one division and one addition per row), and over the rows with cnt > 0 the
+ * pair counts of survival_stats.concordance_index(time, -M, event): the ordered pair (i, j) is comparable when i is an event and either
+ * tgroup[i] > tgroup[j] or tgroup[i] = tgroup[j] and j is censored -- tgroup[i] is the number of row i's group of equal times counted
+ * from the LATEST time (risk_sets.descending_groups' gid per row: a LARGER number is a SHORTER time), in 0 .. n - 1;
+ *     comparable[q R + r] = the comparable pairs,   conc2[q R + r] = sum over them of 2 [M_i > M_j] + [M_i = M_j],
+ * exact integers, so C = conc2 / (2 comparable).  A problem with an empty tree list counts M0 itself (the base C-index).  Optional
+ * outputs D and M [P R][ld]: D_i and M_i of every row (0.0 and M0 where cnt = 0).  No atomics; a problem's outputs do not depend on
+ * what shares its launch.  The launch cannot check table contents: the CALLER guarantees feat < p, genes in 0 .. p - 1, donors in
+ * 0 .. n - 1, trees in 0 .. T - 1, sets in 0 .. F - 1, tgroup in 0 .. n - 1, poff non-decreasing from 0 (ops.rsf_vimp checks on the
+ * host).  A NULL required pointer, n outside 1..MMS_RSF_MAX_N, ldu < n, ld < n, p < 1, ldx < p, T outside 0..MMS_RSF_MAX_T, nn outside
+ * 1..2^(MMS_RSF_MAX_DEPTH + 1) - 1, F < 1, R outside 1..MMS_RSF_VIMP_MAX_R, P < 0, P R >= 2^31 or a pointer not aligned to its element:
+ * MMS_ERR_ARG before any launch.  P = 0 or T = 0: MMS_OK without a launch. */
+#define MMS_RSF_VIMP_MAX_R 64
+typedef struct RsfVimpP {
+    int n; int ldx; int p; int T; int nn; int F; int R; int P;
+    int ldu; int ld;                    // pitch of use / donor rows; pitch of M0 / cnt / D / M rows
+    const float* x;                     // [n][ldx]
+    const int* feat; const float* thr; const double* mort;   // [T][nn]
+    const unsigned char* use;           // [T][ldu]
+    const int* donor;                   // [R][T][ldu]
+    const double* M0; const int* cnt;   // [F][ld]
+    const int* event; const int* tgroup;   // [n] per row of x
+    const int* pset; const int* pgene;  // [P]
+    const int* poff; const int* ptree;  // [P + 1], [poff[P]]
+    long long* conc2; long long* comparable;   // [P * R] out
+    double* D; double* M;               // [P * R][ld] out, or NULL
+} RsfVimpP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -1177,6 +1225,7 @@ int mms_cox_newton(const CoxNewtonP* p, hipStream_t s);       /* Newton-Raphson 
 int mms_rsf_split(const RsfSplitP* p, hipStream_t s);         /* random survival forest: one level of T trees (RsfSplitP above) */
 int mms_rsf_leaves(const RsfLeavesP* p, hipStream_t s);       /* ... mortality and H at the horizons of every leaf */
 int mms_rsf_predict(const RsfPredictP* p, hipStream_t s);     /* ... masked mean over the trees for R rows */
+int mms_rsf_vimp(const RsfVimpP* p, hipStream_t s);           /* ... permutation importance: P problems x R repeats (RsfVimpP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);       /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */

@@ -11,6 +11,9 @@
 // anything but a comparison with its own node number, which neither the old nor the new value equals.
 // mms_rsf_leaves -- workgroup = tree, lane = node: a leaf's lane walks the tree's positions (staged in LDS, broadcast reads) once.
 // mms_rsf_predict -- workgroup = row, lane = trees j, j + 256, ...
+// mms_rsf_vimp -- workgroup = (problem, repeat) of the permutation importance; lane = rows i, i + 256, ...: the row's delta sum over the
+// problem's trees (two walks a tree, the second reading the donor's value at the problem's gene), then M and the pair key
+// 2 tgroup + event into LDS and the pair count of the C-index from there (broadcast reads), folded in a fixed order.
 // No atomics, plain stores; a tree's bits depend on its own multiplicity row and hash stream only.
 #include "common.h"
 
@@ -288,6 +291,77 @@ __global__ __launch_bounds__(RSF_THREADS) void rsf_predict_kernel(const RsfPredi
     }
 }
 
+#define RSF_VIMP_OUT 0x7ffffffe                              // an even key no other key exceeds: such a row is in no comparable pair
+
+__device__ __forceinline__ int rsf_walk_with(const int* feat, const float* thr, int nn, const float* x, int g, float xg) {
+    int s = 0;
+    for (;;) {
+        const int f = feat[s];
+        if (f < 0 || 2 * s + 2 >= nn) break;
+        s = 2 * s + 1 + ((f == g ? xg : x[f]) <= thr[s] ? 0 : 1);
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(RSF_THREADS) void rsf_vimp_kernel(const RsfVimpP a) {
+    extern __shared__ __align__(16) unsigned char rsf_dyn[];
+    __shared__ long long sh_c[RSF_THREADS], sh_m[RSF_THREADS];
+    const int n = a.n, tid = threadIdx.x;
+    double* sh_M = (double*)rsf_dyn;                     // [n]
+    int* sh_k = (int*)(sh_M + n);                        // [n] 2 tgroup + event, RSF_VIMP_OUT for a row outside the problem
+    const int q = (int)(blockIdx.x / (unsigned)a.R), r = (int)(blockIdx.x - (unsigned)q * (unsigned)a.R);
+    const int f = a.pset[q], g = a.pgene[q], k0 = a.poff[q], k1 = a.poff[q + 1];
+    const double* M0 = a.M0 + (size_t)f * a.ld;
+    const int* cnt = a.cnt + (size_t)f * a.ld;
+    const int* donor = a.donor + (size_t)r * a.T * a.ldu;
+    for (int i = tid; i < n; i += RSF_THREADS) {
+        const int c = cnt[i];
+        double D = 0.0, M = M0[i];
+        int key = RSF_VIMP_OUT;
+        if (c > 0) {
+            const float* xi = a.x + (size_t)i * a.ldx;
+            const float xg = xi[g];
+            for (int k = k0; k < k1; ++k) {              // ascending trees, one sequential fp64 sum: the contract
+                const int t = a.ptree[k];
+                if (!a.use[(size_t)t * a.ldu + i]) continue;
+                const size_t tb = (size_t)t * a.nn;
+                const float xd = a.x[(size_t)donor[(size_t)t * a.ldu + i] * a.ldx + g];
+                const int l0 = rsf_walk_with(a.feat + tb, a.thr + tb, a.nn, xi, g, xg);
+                const int l1 = rsf_walk_with(a.feat + tb, a.thr + tb, a.nn, xi, g, xd);
+                D += a.mort[tb + l1] - a.mort[tb + l0];
+            }
+            M = M + D / (double)c;
+            key = 2 * a.tgroup[i] + (a.event[i] != 0 ? 1 : 0);
+        }
+        sh_M[i] = M; sh_k[i] = key;
+        if (a.D) a.D[(size_t)blockIdx.x * a.ld + i] = D;
+        if (a.M) a.M[(size_t)blockIdx.x * a.ld + i] = M;
+    }
+    __syncthreads();
+    // row i is the shorter time of the comparable pair (i, j) iff it is an event and key_i > key_j
+    long long c2 = 0, cm = 0;
+    for (int i = tid; i < n; i += RSF_THREADS) {
+        const int ki = sh_k[i];
+        if (!(ki & 1)) continue;
+        const double Mi = sh_M[i];
+        int c = 0, m = 0;                                // at most 2 n each
+        for (int j = 0; j < n; ++j) {
+            const double Mj = sh_M[j];
+            const bool cp = ki > sh_k[j];
+            m += cp ? 1 : 0;
+            c += cp ? (Mi > Mj ? 2 : Mi == Mj ? 1 : 0) : 0;
+        }
+        c2 += c; cm += m;
+    }
+    sh_c[tid] = c2; sh_m[tid] = cm;
+    __syncthreads();
+    for (int w = RSF_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { sh_c[tid] += sh_c[tid + w]; sh_m[tid] += sh_m[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) { a.conc2[blockIdx.x] = sh_c[0]; a.comparable[blockIdx.x] = sh_m[0]; }
+}
+
 static inline bool rsf_mis(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
 
 extern "C" int mms_rsf_split(const RsfSplitP* p, hipStream_t s) {
@@ -328,5 +402,20 @@ extern "C" int mms_rsf_predict(const RsfPredictP* p, hipStream_t s) {
     if (rsf_mis(p->out_mort, 7) || rsf_mis(p->out_H, 7) || rsf_mis(p->count, 3)) return MMS_ERR_ARG;
     if (p->R == 0) return MMS_OK;
     MMS_LAUNCH(rsf_predict_kernel, dim3(p->R), dim3(RSF_THREADS), 0, s, *p);
+    return mms_check_launch();
+}
+
+extern "C" int mms_rsf_vimp(const RsfVimpP* p, hipStream_t s) {
+    if (!p || !p->x || !p->feat || !p->thr || !p->mort || !p->use || !p->donor || !p->M0 || !p->cnt || !p->event || !p->tgroup) return MMS_ERR_ARG;
+    if (!p->pset || !p->pgene || !p->poff || !p->ptree || !p->conc2 || !p->comparable) return MMS_ERR_ARG;
+    if (p->n < 1 || p->n > MMS_RSF_MAX_N || p->ldu < p->n || p->ld < p->n || p->p < 1 || p->ldx < p->p) return MMS_ERR_ARG;
+    if (p->T < 0 || p->T > MMS_RSF_MAX_T || p->nn < 1 || p->nn > (2 << MMS_RSF_MAX_DEPTH) - 1 || p->F < 1) return MMS_ERR_ARG;
+    if (p->R < 1 || p->R > MMS_RSF_VIMP_MAX_R || p->P < 0 || (long long)p->P * p->R > 0x7fffffffLL) return MMS_ERR_ARG;
+    if (rsf_mis(p->x, 3) || rsf_mis(p->feat, 3) || rsf_mis(p->thr, 3) || rsf_mis(p->mort, 7) || rsf_mis(p->donor, 3) || rsf_mis(p->M0, 7)) return MMS_ERR_ARG;
+    if (rsf_mis(p->cnt, 3) || rsf_mis(p->event, 3) || rsf_mis(p->tgroup, 3) || rsf_mis(p->pset, 3) || rsf_mis(p->pgene, 3)) return MMS_ERR_ARG;
+    if (rsf_mis(p->poff, 3) || rsf_mis(p->ptree, 3) || rsf_mis(p->conc2, 7) || rsf_mis(p->comparable, 7) || rsf_mis(p->D, 7) || rsf_mis(p->M, 7)) return MMS_ERR_ARG;
+    if (p->P == 0 || p->T == 0) return MMS_OK;
+    const size_t lds = (size_t)p->n * (sizeof(double) + sizeof(int));
+    MMS_LAUNCH(rsf_vimp_kernel, dim3((unsigned)p->P * (unsigned)p->R), dim3(RSF_THREADS), lds, s, *p);
     return mms_check_launch();
 }

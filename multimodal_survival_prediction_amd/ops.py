@@ -550,6 +550,68 @@ def rsf_predict(x, feat, thr, mort, H, use=None, plan_only=False):
     return _launch_or_plan("mms_rsf_predict", p, (x, feat, thr, mort, H, use, om, oh, cnt, d), (om[:R], oh[:R, :nh], cnt[:R]), plan_only)
 
 
+def rsf_vimp(x, feat, thr, mort, use, donor, M0, cnt, event, tgroup, pset, pgene, poff, ptree, delta=False, plan_only=False):
+    """Permutation importance counts of P (set, gene) problems x R repeats in one launch (RsfVimpP in mmsurv.h).  Device tensors: x fp32
+    [n, p] (row pitch x.stride(0)); feat int32, thr fp32, mort float64 [T, nn]; use uint8 [T, n]; donor int32 [R, T, n] (both contiguous,
+    or views of one row pitch: donor.stride() == (T * use.stride(0), use.stride(0), 1)); M0 float64 and
+    cnt int32 [F, n]; event / tgroup int32 [n] per row of x (tgroup: a larger number is a shorter time); the problem table pset, pgene
+    [P], poff [P + 1], ptree [poff[P]] as int32 device tensors or host arrays.  The launch cannot check table contents, so they are checked
+    HERE: feat < p, genes in [0, p), donors in [0, n), trees in [0, T), sets in [0, F), tgroup in [0, n), poff non-decreasing from 0 to
+    len(ptree).  -> dict(conc2, comparable int64 [P, R]) and, with delta, D, M float64 [P, R, n].  P = 0 or T = 0 launches nothing."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise TypeError("x must be a float32 [n, p] device tensor with unit column stride")
+    _rsf_dev(feat, torch.int32, "feat", 2); _rsf_dev(thr, torch.float32, "thr", 2); _rsf_dev(mort, torch.float64, "mort", 2)
+    _rsf_dev(M0, torch.float64, "M0", 2)
+    for t, dt, dims, what in ((use, torch.uint8, 2, "use"), (donor, torch.int32, 3, "donor")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or t.dim() != dims:
+            raise TypeError("%s must be a %s device tensor of %d dimensions" % (what, dt, dims))
+    _rsf_dev(cnt, torch.int32, "cnt", 2); _rsf_dev(event, torch.int32, "event", 1); _rsf_dev(tgroup, torch.int32, "tgroup", 1)
+    dev = x.device
+    n, p_ = x.shape
+    T, nn = feat.shape
+    R, F = donor.shape[0], M0.shape[0]
+    lim = _lib.defines("MMS_RSF_")
+    ldu = use.stride(0) if use.dim() == 2 and use.shape[0] else n
+    if not (use.numel() and donor.numel() and ldu >= n and use.stride(1) == 1 and donor.stride() == (T * ldu, ldu, 1)):
+        use, donor, ldu = use.contiguous(), donor.contiguous(), n
+    P, nt = len(poff) - 1, len(ptree)
+    if P < 0 or len(pset) != P or len(pgene) != P:
+        raise ValueError("pset and pgene must be [P] and poff [P + 1]")
+    tab = [t.to(dev) if torch.is_tensor(t) else _upload(t, "int32", dev) for t in (pset, pgene, poff, ptree)]
+    if any(t.dtype != torch.int32 or t.dim() != 1 for t in tab):
+        raise TypeError("pset, pgene, poff and ptree must be one-dimensional int32")
+    pset, pgene, poff, ptree = (t.contiguous() for t in tab)
+    if not (1 <= n <= lim["MAX_N"]) or not (1 <= R <= lim["VIMP_MAX_R"]) or F < 1 or P < 0 or P * R >= 2 ** 31:
+        raise ValueError("n must be in 1..%d, repeats in 1..%d, sets >= 1, problems x repeats < 2^31" % (lim["MAX_N"], lim["VIMP_MAX_R"]))
+    if tuple(thr.shape) != (T, nn) or tuple(mort.shape) != (T, nn) or tuple(use.shape) != (T, n) or tuple(donor.shape) != (R, T, n):
+        raise ValueError("thr and mort must match feat [T, nn], use be [T, n] and donor [R, T, n]")
+    if tuple(cnt.shape) != (F, n) or len(event) != n or len(tgroup) != n:
+        raise ValueError("cnt must match M0 [F, n]; event and tgroup must be [n]")
+    if T and int(feat.max()) >= p_:
+        raise ValueError("the forest splits on feature %d; x has %d columns" % (int(feat.max()), p_))
+    if T and (int(donor.min()) < 0 or int(donor.max()) >= n):
+        raise ValueError("donors must lie in [0, %d)" % n)
+    if int(tgroup.min()) < 0 or int(tgroup.max()) >= n:
+        raise ValueError("tgroup must lie in [0, %d)" % n)
+    if int(poff[0]) != 0 or int(poff[P]) != nt or bool((poff[1:] < poff[:-1]).any()):
+        raise ValueError("poff must be non-decreasing from 0 to len(ptree)")
+    if P and (int(pset.min()) < 0 or int(pset.max()) >= F or int(pgene.min()) < 0 or int(pgene.max()) >= p_):
+        raise ValueError("sets must lie in [0, %d) and genes in [0, %d)" % (F, p_))
+    if nt and (int(ptree.min()) < 0 or int(ptree.max()) >= T):
+        raise ValueError("tree lists must lie in [0, %d)" % T)
+    out = dict(conc2=torch.zeros(max(P, 1), R, dtype=torch.int64, device=dev), comparable=torch.zeros(max(P, 1), R, dtype=torch.int64, device=dev))
+    if delta:
+        out.update(D=torch.zeros(max(P, 1), R, n, dtype=torch.float64, device=dev), M=torch.zeros(max(P, 1), R, n, dtype=torch.float64, device=dev))
+    res = {k: v[:P] for k, v in out.items()}
+    d = torch.zeros(1, dtype=torch.float64, device=dev)            # never a NULL pointer for an empty table
+    pz = lambda t: ptr(t) if t.numel() else ptr(d)
+    p = _S()["RsfVimpP"](n, max(x.stride(0), p_), p_, T, max(nn, 1), F, R, P, ldu, n, ptr(x), pz(feat), pz(thr), pz(mort), pz(use), pz(donor),
+                         ptr(M0), ptr(cnt), ptr(event), ptr(tgroup), pz(pset), pz(pgene), pz(poff), pz(ptree), ptr(out["conc2"]),
+                         ptr(out["comparable"]), ptr(out.get("D")), ptr(out.get("M")))
+    return _launch_or_plan("mms_rsf_vimp", p, (x, feat, thr, mort, use, donor, M0, cnt, event, tgroup, pset, pgene, poff, ptree, out, d), res,
+                           plan_only)
+
+
 def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     """IPCW Brier / dynamic AUC sums of M models at H horizons under R multiplicity rows (TdMetricsP in mmsurv.h).  trank, event: [n] dense
     time ranks and event flags of the TIME-ASCENDING positions (events before censorings at equal times), hcut: [H] positions with

@@ -15,14 +15,17 @@ mulhi(a, k) = (a * k) >> 32,
     draw k    of a bootstrap sample of m patients: member mulhi(h((k + 1) * 0x9E3779B9 + h(ht ^ 0xB5297A4D)), m), k = 0..m-1
     node key  hn = h((s + 1) * 0x9E3779B9 + ht),   feature j: hf = h((j + 1) * 0x9E3779B9 + hn), f = mulhi(hf, p)
     threshold q of feature j: x[f] of the node's in-bag member mulhi(h((q + 1) * 0x85ebca6b + hf), members), members counted without
-    repeats in time-descending order (the stable order of risk_sets.descending_groups)."""
+    repeats in time-descending order (the stable order of risk_sets.descending_groups).
+Permutation importance (include/mmsurv.h: RsfVimpP) adds, per tree and repeat r, over the ROWS i of the matrix handed in:
+    hp = h((r + 1) * 0x85EBCA6B + h(ht ^ 0x68E31DA4)),   k_i = h((i + 1) * 0x9E3779B9 + hp);
+    the rows the tree admits, ascending, receive the same rows sorted by (k, i) as donors; any other row is its own donor."""
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from .risk_sets import descending_groups, to_numpy
 
-GOLDEN, STREAM, DRAW = 0x9E3779B9, 0x85EBCA6B, 0xB5297A4D
+GOLDEN, STREAM, DRAW, PERMUTE = 0x9E3779B9, 0x85EBCA6B, 0xB5297A4D, 0x68E31DA4
 _M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -61,6 +64,58 @@ def bootstrap_mults(folds, n, n_trees, seed=0):
                 raise ValueError("a bootstrap multiplicity above 255")
             out[f * T + j] = cnt
     return out
+
+
+def _hash_t(x):
+    """hash_u32 on torch int64 tensors holding uint32 values (products wrap mod 2^64, which keeps the low 32 bits)"""
+    x = x & 0xFFFFFFFF
+    x = x ^ (x >> 16); x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x = x ^ (x >> 15); x = (x * 0x846CA68B) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def permutation_donors(seed, tree_ids, use, nperm):
+    """-> int32 [R, T, n] donor rows of R = nperm repeats (the contract: include/mmsurv.h, RsfVimpP): within each tree's admitted rows
+    (use [T, n] != 0) a permutation keyed by (seed, tree id, repeat), the identity elsewhere.  Computed with torch on use's device --
+    int64 arithmetic masked to 32 bits and two stable sorts; a device tensor when use is one, else a numpy array."""
+    import torch
+    as_numpy = not torch.is_tensor(use)
+    use = torch.as_tensor(np.ascontiguousarray(to_numpy(use)) != 0) if as_numpy else use != 0
+    T, n = use.shape
+    R = int(nperm)
+    ids = np.asarray(tree_ids, np.int64).reshape(-1)
+    if len(ids) != T or R < 1:
+        raise ValueError("one tree id per row of use, and at least one repeat")
+    hp = hash_u32(((np.arange(1, R + 1, dtype=np.uint64)[:, None] * np.uint64(STREAM)) & _M32)
+                  + hash_u32(tree_key(seed, ids) ^ np.uint64(PERMUTE))[None, :])                     # [R, T] (hash_u32 masks its input)
+    dev = use.device
+    hp = torch.from_numpy(hp.astype(np.int64)).to(dev)
+    k = _hash_t(torch.arange(1, n + 1, dtype=torch.int64, device=dev) * GOLDEN + hp[:, :, None])     # [R, T, n]
+    by_key = torch.sort(torch.where(use[None], k, torch.full_like(k, 1 << 32)), dim=2, stable=True).indices      # s_0, s_1, ..., then the rest
+    rows = torch.sort((~use).to(torch.uint8), dim=1, stable=True).indices                             # a_0, a_1, ..., then the rest
+    donor = torch.empty(R, T, n, dtype=torch.int64, device=dev)
+    donor.scatter_(2, rows[None].expand(R, T, n), by_key)
+    donor = donor.to(torch.int32)
+    return donor.numpy() if as_numpy else donor
+
+
+def problem_table(feat, sets=None, p=None):
+    """The (set, gene) problems of the forest tables feat [T, nn] (a tensor on any device, or an array): every pair for which some tree of
+    the set (sets [T], None: one set) splits on the gene at some node, sorted by (set, gene), with its trees ascending and without
+    repeats.  -> dict(set, gene [P], off [P + 1], tree [off[P]]) int32 tensors on feat's device."""
+    import torch
+    feat = torch.as_tensor(to_numpy(feat)) if not torch.is_tensor(feat) else feat
+    T = feat.shape[0]
+    dev = feat.device
+    p = int(p) if p is not None else (int(feat.max()) + 1 if feat.numel() else 1)
+    sets_t = torch.zeros(T, dtype=torch.int64, device=dev) if sets is None else torch.as_tensor(np.asarray(to_numpy(sets), np.int64)).to(dev)
+    t, s = torch.nonzero(feat >= 0, as_tuple=True)
+    key = torch.unique((sets_t[t] * max(p, 1) + feat[t, s].to(torch.int64)) * max(T, 1) + t)           # sorted, one per (set, gene, tree)
+    prob, count = torch.unique_consecutive(torch.div(key, max(T, 1), rounding_mode="floor"), return_counts=True)
+    off = torch.zeros(len(prob) + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(count, 0)
+    i32 = lambda a: a.to(torch.int32)
+    return dict(set=i32(torch.div(prob, max(p, 1), rounding_mode="floor")), gene=i32(prob % max(p, 1)), off=i32(off), tree=i32(key % max(T, 1)))
 
 
 def mortality_weights(time, event, masks):
@@ -111,6 +166,89 @@ class Forest:
             feat, stat = feat[np.asarray(trees)], stat[np.asarray(trees)]
         ok = feat >= 0
         return (np.bincount(feat[ok], minlength=self.p).astype(np.int64), np.bincount(feat[ok], weights=stat[ok], minlength=self.p))
+
+    def vimp(self, x, time, event, use, sets=None, nperm=1, return_delta=False, timings=None):
+        """Out-of-bag permutation importance (ensemble VIMP; include/mmsurv.h: RsfVimpP): the drop in the C-index of the rows `use` admits
+        when a gene's values are shuffled among each tree's admitted rows, all (set, gene, repeat) problems in ONE launch.
+        x: fp32 [n, p] device matrix; time / event: [n] of its rows; use: [T, n] mask (the out-of-bag rows of every tree, or a
+        validation mask); sets: [T] the set (fold) of each tree, None = one set: a set's C-index is over ITS trees' predictions.
+        -> dict(vimp [F, p] = c_base - the mean over repeats, vimp_reps [F, R, p], c_base [F], conc2 / comparable int64 [P, R] and
+        base_conc2 / base_comparable [F] (when a launch ran), problems = dict(set, gene [P], off [P + 1], tree), n_rows [F] rows some tree admits; with
+        return_delta also D and M float64 [P, R, n]).  A gene no tree of a set splits on has importance exactly 0.0 and no problem.
+        ValueError when a set has no comparable pair among its admitted rows.  timings: a list that receives (name, milliseconds)."""
+        import time as _time
+        import torch
+        from . import ops
+        from .survival_stats import concordance_index
+        dev = x.device
+        n, T, R = int(x.shape[0]), self.n_trees, int(nperm)
+        tm, ev = to_numpy(time, "time").astype(np.float64).reshape(-1), to_numpy(event).reshape(-1) != 0
+        use = torch.as_tensor(np.ascontiguousarray(to_numpy(use)).astype(np.uint8) if not torch.is_tensor(use) else use)
+        use = (use.to(dev) != 0).to(torch.uint8).contiguous()
+        sets = np.zeros(T, np.int64) if sets is None else np.asarray(to_numpy(sets), np.int64).reshape(-1)
+        if tuple(use.shape) != (T, n) or len(tm) != n or len(ev) != n or len(sets) != T or (T and sets.min() < 0):
+            raise ValueError("use must be [T, n], time / event [n] and sets [T] for x [n, p]")
+        F = int(sets.max()) + 1 if T else 1
+        sets_d = torch.from_numpy(sets).to(dev)
+        M0, cnt = torch.zeros(F, n, dtype=torch.float64, device=dev), torch.zeros(F, n, dtype=torch.int32, device=dev)
+        for f in range(F):                                          # what mms_rsf_predict returns for the set's trees and the mask
+            m, _, c = ops.rsf_predict(x, self.feat, self.thr, self.mort, self.H.contiguous(), use=use * (sets_d == f).to(torch.uint8)[:, None])
+            M0[f], cnt[f] = m, c
+        cnt_h = cnt.cpu().numpy()
+        order, _, gid, _, _ = descending_groups(tm)
+        tg = np.empty(n, np.int32); tg[order] = gid                 # per row; a larger number is a shorter time
+        t0 = _time.perf_counter()
+        prob = problem_table(self.feat, sets, self.p)
+        P = len(prob["set"])
+        out = dict(vimp=np.zeros((F, self.p)), vimp_reps=np.zeros((F, R, self.p)), n_rows=(cnt_h > 0).sum(1),
+                   problems={k: v.cpu().numpy() for k, v in prob.items()})
+        if P == 0:                                                  # stumps: nothing to permute and nothing to launch
+            M0_h = M0.cpu().numpy()
+            try:
+                out["c_base"] = np.array([concordance_index(tm[cnt_h[f] > 0], -M0_h[f][cnt_h[f] > 0], ev[cnt_h[f] > 0]) for f in range(F)])
+            except ZeroDivisionError:
+                raise ValueError("a set has no comparable pair among its admitted rows") from None
+            out.update(conc2=np.zeros((0, R), np.int64), comparable=np.zeros((0, R), np.int64))
+            if return_delta:
+                out.update(D=np.zeros((0, R, n)), M=np.zeros((0, R, n)))
+            return out
+        ids = self.tree_id if self.tree_id is not None else np.arange(T)
+        donor = permutation_donors(self.hyper.get("seed", 0), ids, use, R)
+        # the base C-index rides in the launch: F more problems with an empty tree list count M0 itself
+        i32 = lambda a: torch.as_tensor(a, dtype=torch.int32, device=dev)
+        pset, pgene = torch.cat([prob["set"], i32(np.arange(F))]), torch.cat([prob["gene"], i32(np.zeros(F))])
+        poff = torch.cat([prob["off"], prob["off"][-1:].expand(F)])
+        if timings is not None:
+            torch.cuda.synchronize()
+            timings.append(("tables", (_time.perf_counter() - t0) * 1e3))
+        args = (x, self.feat, self.thr, self.mort, use, donor, M0, cnt, i32(ev.astype(np.int32)), i32(tg), pset, pgene, poff, prob["tree"])
+        if timings is None:
+            got = ops.rsf_vimp(*args, delta=return_delta)
+        else:
+            plan = ops.rsf_vimp(*args, delta=return_delta, plan_only=True)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.call("mms_rsf_vimp", plan[0])
+            e1.record()
+            e1.synchronize()
+            timings.append(("launch", e0.elapsed_time(e1)))
+            got = plan[2]
+        got = {k: v.cpu().numpy() for k, v in got.items()}
+        conc2, comp = got["conc2"], got["comparable"]
+        if (comp[P:, 0] == 0).any():
+            raise ValueError("a set has no comparable pair among its admitted rows")
+        c_base = conc2[P:, 0] / (2.0 * comp[P:, 0])
+        ps, pg = out["problems"]["set"], out["problems"]["gene"]
+        total = np.zeros(P)
+        for r in range(R):                                          # the mean over repeats: a sequential sum, then one division
+            c_perm = conc2[:P, r] / (2.0 * comp[:P, r])
+            out["vimp_reps"][ps, r, pg] = c_base[ps] - c_perm
+            total = total + c_perm
+        out["vimp"][ps, pg] = c_base[ps] - total / R
+        out.update(c_base=c_base, conc2=conc2[:P], comparable=comp[:P], base_conc2=conc2[P:, 0], base_comparable=comp[P:, 0])
+        if return_delta:
+            out.update(D=got["D"][:P], M=got["M"][:P])
+        return out
 
     def save(self, path):
         np.savez(path, **{k: to_numpy(getattr(self, k)) for k in ("feat", "thr", "stat", "n_node", "d_node", "mort", "H")},
@@ -225,12 +363,14 @@ def default_horizons(time, event, k=3):
     return np.unique(np.quantile(t, np.arange(1, k + 1) / (k + 1.0))) if len(t) else np.zeros(0)      # (ties may merge two)
 
 
-def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf=15, max_depth=10, seed=0, horizons=None, x=None):
+def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf=15, max_depth=10, seed=0, horizons=None, x=None, vimp=0):
     """K-fold cross-validation of the forest: all K * n_trees trees grow in ONE launch sequence (one per fold when the cohort carries
     per-fold gene matrices, gene_select.fold_matrix; the trees keep their forest-wide hash streams).  Rows: coxnet.risk_rows(cohort),
     the eligible patients.  Higher mortality = higher risk: C = survival_stats.concordance_index(time, -mortality, event).
     -> list per fold of dict(fold, c_index, oob_c_index, oob_missing (training rows no tree left out), val_rows, val_mortality,
-    val_survival [n_val, nh], horizons, importance = (counts, chi2 sums) of the fold's trees, n_train, n_val, forest, trees)."""
+    val_survival [n_val, nh], horizons, importance = (counts, chi2 sums) of the fold's trees, n_train, n_val, forest, trees).
+    vimp = R > 0 adds the out-of-bag permutation importance of every fold over its own trees (Forest.vimp, R repeats; one launch for all
+    folds, one per fold with per-fold matrices): vimp float64 [p] and vimp_reps [R, p]."""
     import torch
     from . import coxnet, gene_select
     from .survival_stats import concordance_index
@@ -258,6 +398,7 @@ def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf
             val[i * T:(i + 1) * T, pos[f][1]] = 1
         oob = ((mults[trees] == 0) & masks[tree_fold[trees]]).astype(np.uint8)
         pv = forest.predict(xe, use=val)
+        vi = forest.vimp(xe, rr.time, rr.event, oob, sets=np.repeat(np.arange(len(grp)), T), nperm=int(vimp)) if int(vimp) > 0 else None
         for i, f in enumerate(grp):
             tr, va = pos[f]
             use = np.zeros_like(oob)                                # fold f's out-of-bag mean is over fold f's trees alone
@@ -269,4 +410,6 @@ def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf
                               oob_missing=int((~ok).sum()), val_rows=rr.rows[va], val_mortality=pv["mortality"][va],
                               val_survival=pv["survival"][va], horizons=horizons, importance=forest.importance(np.arange(i * T, (i + 1) * T)),
                               n_train=int(len(tr)), n_val=int(len(va)), forest=forest, trees=np.arange(i * T, (i + 1) * T))
+            if vi is not None:
+                results[f].update(vimp=vi["vimp"][i], vimp_reps=vi["vimp_reps"][i])
     return results

@@ -14,7 +14,10 @@ Writes results/rsf_baseline/cv_results.json in the RNA-only schema -- best_c_ind
 the fold's training patients; num_epochs / best_epoch have no meaning here and are 0 -- plus per fold fold_{k}_predictions.csv
 (patient_id, survival_time, event, risk_score = ensemble mortality: what evaluate_model.py --bootstrap --compare reads),
 fold_{k}_survival_curves.csv (the same columns and one S_<tau> column per horizon, the layout of evaluate_model.py's survival_curves.csv:
---compare-curves joins it) and fold_{k}_importance.csv (gene column, name, splits, summed chi2; the genes some tree split on)."""
+--compare-curves joins it) and fold_{k}_importance.csv (gene column, name, splits, summed chi2; the genes some tree split on).
+MMS_RSF_VIMP = R > 0 (default 0: nothing more is computed or written) adds the out-of-bag permutation importance with R repeats, one
+launch for all folds: fold_{k}_vimp.csv (index, column, gene, splits, chi2_sum, vimp = the drop in the fold's out-of-bag C-index when the
+gene is shuffled, vimp_sd over the repeats; the same genes, sorted by vimp) and "vimp_repeats" among the hyperparameters."""
 import os
 import time
 
@@ -33,6 +36,7 @@ NSPLIT = env_int("MMS_RSF_NSPLIT", 10)
 MIN_LEAF = env_int("MMS_RSF_MIN_LEAF", 15)
 DEPTH = env_int("MMS_RSF_DEPTH", 10)
 SEED = env_int("MMS_RSF_SEED", 0)
+VIMP = env_int("MMS_RSF_VIMP", 0)
 
 
 def curve_columns(horizons):
@@ -51,7 +55,7 @@ def main():
     sel = select_genes(cohort, [tr for tr, _ in folds], lambda name: os.path.join(RESULTS_DIR, f"best_model_fold{name}.pth"), rank=rank)
     t0 = time.perf_counter()
     res = survival_forest.cross_validate(cohort, folds, n_trees=TREES, mtry=MTRY or None, nsplit=NSPLIT, min_leaf=MIN_LEAF, max_depth=DEPTH,
-                                         seed=SEED)
+                                         seed=SEED, vimp=VIMP)
     dt = time.perf_counter() - t0
     names, ids = cohort.get("gene_names"), cohort.get("patient_id")
     label = cohort["label"].cpu().numpy()
@@ -70,6 +74,13 @@ def main():
         src = used if sel is None else np.asarray(sel.columns[f])[used]
         pd.DataFrame({"index": used, "column": src, "gene": [str(names[int(j)]) if names is not None else f"gene_{int(j)}" for j in src],
                       "splits": counts[used], "chi2_sum": chi2[used]}).to_csv(os.path.join(RESULTS_DIR, f"fold_{fold}_importance.csv"), index=False)
+        if VIMP > 0:
+            by = np.nonzero(counts)[0]
+            by = by[np.argsort(-r["vimp"][by], kind="stable")]
+            col = by if sel is None else np.asarray(sel.columns[f])[by]
+            pd.DataFrame({"index": by, "column": col, "gene": [str(names[int(j)]) if names is not None else f"gene_{int(j)}" for j in col],
+                          "splits": counts[by], "chi2_sum": chi2[by], "vimp": r["vimp"][by], "vimp_sd": r["vimp_reps"][:, by].std(0)}).to_csv(
+                os.path.join(RESULTS_DIR, f"fold_{fold}_vimp.csv"), index=False)
         print(f"fold {fold} | trees {TREES} | Val C-index: {r['c_index']:.4f} | OOB C-index: {r['oob_c_index']:.4f} "
               f"({r['oob_missing']} training patients never out of bag)", flush=True)
         fold_results.append({"fold": fold, "best_c_index": float(r["c_index"]), "best_epoch": 0, "train_size": int(len(folds[f][0])),
@@ -81,7 +92,7 @@ def main():
         "model": "Random survival forest", "n_folds": N_FOLDS, "num_epochs": 0,
         "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)), "fold_results": fold_results,
         "hyperparameters": {"n_trees": TREES, **hyper, "horizons": [float(h) for h in (res[0]["horizons"] if res else [])],
-                            **gene_hparams(sel)}})
+                            **({"vimp_repeats": VIMP} if VIMP > 0 else {}), **gene_hparams(sel)}})
     print(f"C-index: {np.mean(c):.4f} +/- {np.std(c):.4f} (validation folds, nothing tuned on them; {dt:.2f} s for all trees); "
           f"saved {RESULTS_DIR}/cv_results.json")
 
