@@ -860,6 +860,57 @@ typedef struct RsfVimpP {
     double* D; double* M;               // [P * R][ld] out, or NULL
 } RsfVimpP;
 
+/* Gene-set enrichment with a label-permutation null (multimodal_survival_prediction_amd/enrichment.py), two entry points.
+ *
+ * mms_gsea_scores: at beta = 0 the Cox score of gene g is linear in the null martingale residuals m (Breslow ties; sum m = 0), and
+ * relabelling the patients permutes m.  With the n analysed patients row[0 .. n) in list order and replicate r giving list position i
+ * the residual m[perm[r][i]] (row 0 of perm is the identity by convention of the caller),
+ *     Z[r][g] = scale[g] * sum_i m[perm[r][i]] x[row[i]][g],
+ *     scale[g] = 1 / sqrt( (sum m^2 / (n - 1)) * sum_i (x[row[i]][g] - mean_g)^2 ),
+ * the exact permutation variance of the sum; scale[g] = 0 (and Z[r][g] = +0.0 in every replicate) when the centred sum of squares or
+ * sum m^2 is 0.  Two launches.  Column pass: one thread per gene walks the rows in list order in fp64, the mean first, then the centred
+ * squares (and sum m^2 in the same order), so scale[g] depends on column g's values, row and m only.  Product: v_mfma_f64_16x16x4_f64,
+ * replicates on M, genes on N, list positions on K in a fixed order that depends on n only; no atomics, every Z[r][g] is owned by one
+ * lane, and the bits of replicate r do not depend on R1 or on r's place in the launch.  The launch cannot check table contents: the
+ * CALLER guarantees rows in [0, N) and every perm row inside [0, n) (ops.gsea_scores checks on the host).  A NULL pointer, n < 2, N < 1,
+ * G outside 1..MMS_GSEA_MAX_G, ld < G, ldz < G, R1 outside 0..MMS_GSEA_MAX_R1 or a pointer not aligned to its element: MMS_ERR_ARG
+ * before any launch.  R1 = 0: MMS_OK without a launch.
+ *
+ * mms_gsea_es: the enrichment score (Subramanian et al. 2005) of S gene sets (CSR: set s = set_gene[set_off[s] .. set_off[s + 1]),
+ * distinct genes, 1 <= k <= G - 1) in R1 replicates.  Replicate r ranks the keys z[g] = Z[r][g] -- or, with gperm (preranked mode: Z has
+ * ONE row), z[g] = Z[0][g] for r = 0 and Z[0][gperm[r - 1][g]] for r >= 1 -- by z descending, the lower g first on equal values (-0.0
+ * equals +0.0; the keys must be finite).  With w_g = |z_g| (weight 1) or 1 (weight 0; also taken for a set whose weights add up to 0)
+ * and NR their sum over the set, walking the ranking a member adds w_g / NR and a non-member subtracts 1 / (G - k); hi / lo are the
+ * largest / smallest value after a position; es = hi if hi >= -lo, else lo; peak = the first (0-based) position that attains it.  The value
+ * after a position is (hit weights so far) / NR - (misses so far) / (G - k), two true divisions; with unit weights it is the single
+ * division (hits (G - k) - misses k) / (k (G - k)) of an exact integer, so equal fractions are equal bits and real ties go to the first
+ * position.  One workgroup per replicate: the keys are sorted in LDS by a bitonic network over the next power of two (padding keys last), and each
+ * of the workgroup's waves then takes every fourth set: it flags the set's ranks in a byte strip of its own and walks the positions 64
+ * at a time with wave prefix sums (a chunk without a member in closed form).  fp64, no atomics, plain stores: every (replicate, set)
+ * is owned by one wave and does not depend on what shares the launch.  The launch cannot check table contents: the CALLER guarantees
+ * the CSR contract and that every gperm row is a permutation of 0 .. G - 1 (ops.gsea_es checks on the host).  A NULL required pointer,
+ * G outside 2..MMS_GSEA_MAX_G, S < 0, R1 outside 0..MMS_GSEA_MAX_R1, weight outside {0, 1}, ldz < G, lde < S or a pointer not aligned to
+ * its element: MMS_ERR_ARG before any launch.  R1 = 0 or S = 0: MMS_OK without a launch. */
+#define MMS_GSEA_MAX_G 8192         /* 16 bytes of LDS a gene (key 8, order 2, rank 2, 4 one-byte flag strips): 128 KB of the 160 KB a workgroup may declare on gfx950 */
+#define MMS_GSEA_MAX_R1 4194240     /* 65535 tiles of 64 replicates (grid y of the product) */
+typedef struct GseaScoreP {
+    int n; int N; int ld; int G; int R1; int ldz;   // list length; rows and row pitch of x; genes; replicates; row pitch of Z
+    const float* x;                     // [N][ld]
+    const int* row;                     // [n]
+    const double* m;                    // [n]
+    const int* perm;                    // [R1][n]
+    double* scale;                      // [G] out
+    double* Z;                          // [R1][ldz] out
+} GseaScoreP;
+typedef struct GseaEsP {
+    int G; int S; int R1; int weight; int ldz; int lde;   // genes; sets; replicates; 0 / 1; row pitch of Z; row pitch of es and peak
+    const double* Z;                    // [R1][ldz], or [1][ldz] with gperm
+    const int* gperm;                   // [R1 - 1][G], or NULL
+    const int* set_off; const int* set_gene;   // [S + 1], [set_off[S]]
+    double* es;                         // [R1][lde] out
+    int* peak;                          // [R1][lde] out, or NULL
+} GseaEsP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -1226,6 +1277,8 @@ int mms_rsf_split(const RsfSplitP* p, hipStream_t s);         /* random survival
 int mms_rsf_leaves(const RsfLeavesP* p, hipStream_t s);       /* ... mortality and H at the horizons of every leaf */
 int mms_rsf_predict(const RsfPredictP* p, hipStream_t s);     /* ... masked mean over the trees for R rows */
 int mms_rsf_vimp(const RsfVimpP* p, hipStream_t s);           /* ... permutation importance: P problems x R repeats (RsfVimpP above) */
+int mms_gsea_scores(const GseaScoreP* p, hipStream_t s);      /* gene-set enrichment: permutation Z of G genes x R1 relabellings (GseaScoreP above) */
+int mms_gsea_es(const GseaEsP* p, hipStream_t s);             /* ... enrichment score of S sets in R1 replicates (GseaEsP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);       /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */
 int mms_coxnet_iterate(const CoxnetP* p, int iters, hipStream_t s);   /* ... `iters` lock-step proximal-gradient rounds of P problems */
 int mms_grad_sumsq(const AdamP* p, hipStream_t s);             /* sum of squares of the flat gradient (fp64 atomics) */

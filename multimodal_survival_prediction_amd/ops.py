@@ -387,6 +387,124 @@ def gene_screen(x, off, row, coef, G=None, plan_only=False):
     return _launch_or_plan("mms_gene_screen", p, (x, off_d, row_d, coef_d), (U[:P], V[:P]), plan_only)
 
 
+def _check_permutations(perm, n, what):
+    """perm: int64 [R, n]; every row must hold each of 0 .. n - 1 once"""
+    import numpy as np
+    if perm.size and (perm.min() < 0 or perm.max() >= n):
+        raise ValueError("%s must hold values in [0, %d)" % (what, n))
+    seen = np.zeros(perm.shape, dtype=bool)
+    np.put_along_axis(seen, perm, True, axis=1)
+    if not seen.all():
+        raise ValueError("every row of %s must be a permutation of 0 .. %d" % (what, n - 1))
+
+
+def gsea_scores(x, row, m, perm, G=None, plan_only=False):
+    """Permutation Z of every gene under R1 relabellings (GseaScoreP in mmsurv.h).  x: fp32 [N, >= G] device matrix (row pitch
+    x.stride(0)); row: [n] patient rows in list order, m: [n] float64 null martingale residuals, perm: [R1, n] the residual each list
+    position gets per replicate -- host arrays.  The launch cannot check row / perm, so both are checked HERE, before the upload (as
+    ops.gene_screen checks its rows): rows in [0, N), every perm row a permutation of 0 .. n - 1, m finite.  -> (scale [G], Z [R1, G]):
+    float64 device tensors.  plan_only: upload and check, do not launch -> (GseaScoreP, the tensors it points to, scale, Z), for
+    call("mms_gsea_scores", p) by the caller (tools/bench_gsea.py times the launches alone)."""
+    import numpy as np
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise TypeError("x must be a 2-D fp32 device tensor with unit column stride")
+    N, G = x.shape[0], x.shape[1] if G is None else int(G)
+    row = np.asarray(row, dtype=np.int64).reshape(-1)
+    m = np.ascontiguousarray(np.asarray(m, dtype=np.float64)).reshape(-1)
+    n = len(row)
+    perm = np.asarray(perm, dtype=np.int64).reshape(-1, n) if n else np.zeros((0, 0), np.int64)
+    R1 = perm.shape[0]
+    lim = _lib.defines("MMS_GSEA_MAX_")
+    if N < 1 or not 1 <= G <= min(x.shape[1], lim["G"]):
+        raise ValueError("x must have N >= 1 rows and 1 <= G <= %d columns" % min(x.shape[1], lim["G"]))
+    if n < 2 or len(m) != n or not np.isfinite(m).all():
+        raise ValueError("row and m must hold the same n >= 2 entries, m finite")
+    if R1 > lim["R1"]:
+        raise ValueError("at most %d replicates a launch" % lim["R1"])
+    if row.min() < 0 or row.max() >= N:
+        raise ValueError("rows must lie in [0, %d)" % N)
+    _check_permutations(perm, n, "perm")
+    dev = x.device
+    row_d, m_d, perm_d = _upload(row, np.int32, dev), _upload(m, np.float64, dev), _upload(perm, np.int32, dev)
+    scale = torch.zeros(G, dtype=torch.float64, device=dev)
+    Z = torch.zeros(max(R1, 1), G, dtype=torch.float64, device=dev)
+    p = _S()["GseaScoreP"](n, N, x.stride(0), G, R1, G, ptr(x), ptr(row_d), ptr(m_d), ptr(perm_d), ptr(scale), ptr(Z))
+    return _launch_or_plan("mms_gsea_scores", p, (x, row_d, m_d, perm_d), (scale, Z[:R1]), plan_only)
+
+
+def check_gene_sets(set_off, set_gene, G):
+    """The CSR contract of GseaEsP on host arrays: set_off non-decreasing from 0 to len(set_gene), every set's genes distinct and in
+    [0, G), 1 <= k <= G - 1.  -> (set_off, set_gene) as int64."""
+    import numpy as np
+    off, gene = np.asarray(set_off, dtype=np.int64).reshape(-1), np.asarray(set_gene, dtype=np.int64).reshape(-1)
+    if len(off) < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != len(gene):
+        raise ValueError("set_off must be non-decreasing from 0 to len(set_gene)")
+    if len(gene) >= 2 ** 31:
+        raise ValueError("the sets together must stay below 2^31 members")
+    if len(gene) and (gene.min() < 0 or gene.max() >= G):
+        raise ValueError("set genes must lie in [0, %d)" % G)
+    k = np.diff(off)
+    if len(k) and (k.min() < 1 or k.max() > G - 1):
+        raise ValueError("every set must hold 1 .. G - 1 = %d genes" % (G - 1))
+    sid = np.repeat(np.arange(len(k)), k)
+    if len(np.unique(sid * G + gene)) != len(gene):
+        raise ValueError("a set lists a gene twice")
+    return off, gene
+
+
+def gsea_es(Z, set_off, set_gene, gperm=None, weight=1, peak=True, plan_only=False):
+    """Enrichment score of S gene sets in every replicate (GseaEsP in mmsurv.h).  Z: float64 [R1, G] gene statistics, a device tensor
+    (row pitch Z.stride(0); ops.gsea_scores' Z: finite by construction) or a host array (a non-finite value is refused HERE); set_off
+    [S + 1], set_gene: the sets in CSR form; gperm: None, or int [R, G] gene permutations (preranked mode: Z must have ONE row and
+    R1 = R + 1; replicate r >= 1 ranks z[gperm[r - 1][g]]); weight 0 / 1 -- host arrays, checked here before the upload
+    (check_gene_sets; every gperm row a permutation).  -> (es float64 [R1, S], peak int32 [R1, S] or None): device tensors.
+    plan_only: upload and check, do not launch -> (GseaEsP, the tensors it points to, es, peak), for call("mms_gsea_es", p)."""
+    import numpy as np
+    if torch.is_tensor(Z) and Z.is_cuda:
+        if Z.dtype != torch.float64 or Z.dim() != 2 or (Z.shape[1] > 1 and Z.stride(1) != 1):
+            raise TypeError("Z must be float64 [R1, G] with unit column stride")
+        if not bool(torch.isfinite(Z).all()):
+            raise ValueError("Z must be finite")
+        dev = Z.device
+    else:
+        Zh = np.asarray(Z.cpu() if torch.is_tensor(Z) else Z, dtype=np.float64)
+        Zh = Zh.reshape(1, -1) if Zh.ndim == 1 else Zh
+        if Zh.ndim != 2 or not np.isfinite(Zh).all():
+            raise ValueError("Z must be a finite float64 [R1, G] array")
+        dev = torch.device("cuda")
+        Z = torch.from_numpy(np.ascontiguousarray(Zh)).to(dev) if Zh.size else torch.zeros(Zh.shape, dtype=torch.float64, device=dev)
+    rows, G = Z.shape
+    if rows > 1 and Z.stride(0) < G:                 # (an expanded view: rows that overlap have no pitch)
+        Z = Z.contiguous()
+    lim = _lib.defines("MMS_GSEA_MAX_")
+    if weight not in (0, 1):
+        raise ValueError("weight must be 0 or 1")
+    if not 2 <= G <= lim["G"]:
+        raise ValueError("Z must have 2 .. %d gene columns" % lim["G"])
+    off, gene = check_gene_sets(set_off, set_gene, G)
+    S = len(off) - 1
+    gperm_d = None
+    if gperm is None:
+        R1 = rows
+    else:
+        gperm = np.asarray(gperm, dtype=np.int64).reshape(-1, G)
+        if rows != 1:
+            raise ValueError("preranked mode ranks ONE row of scores, got %d" % rows)
+        _check_permutations(gperm, G, "gperm")
+        R1 = gperm.shape[0] + 1
+        gperm_d = _upload(gperm, np.int32, dev)
+    if R1 > lim["R1"]:
+        raise ValueError("at most %d replicates a launch" % lim["R1"])
+    ldz = max(Z.stride(0), G) if rows > 1 else G
+    off_d, gene_d = _upload(off, np.int32, dev), _upload(gene, np.int32, dev)
+    lde = max(S, 1)
+    es = torch.zeros(max(R1, 1), lde, dtype=torch.float64, device=dev)
+    pk = torch.zeros(max(R1, 1), lde, dtype=torch.int32, device=dev) if peak else None
+    Zp = Z if Z.numel() else torch.zeros(1, dtype=torch.float64, device=dev)
+    p = _S()["GseaEsP"](G, S, R1, int(weight), ldz, lde, ptr(Zp), ptr(gperm_d), ptr(off_d), ptr(gene_d), ptr(es), ptr(pk))
+    return _launch_or_plan("mms_gsea_es", p, (Zp, gperm_d, off_d, gene_d), (es[:R1, :S], None if pk is None else pk[:R1, :S]), plan_only)
+
+
 def logrank_scan(rank, pflag, coef, coff, cut, cset=None, at=None, tables=False, plan_only=False):
     """Log-rank statistic of every cut of Q problems (LogrankScanP in mmsurv.h).  rank: int32 [Q, n] ranks over the shared time-descending
     positions -- a device tensor (row pitch rank.stride(0)) or a host array; pflag: [n], coef: [n, 2] float64 (h, c) from
