@@ -911,6 +911,128 @@ typedef struct GseaEsP {
     int* peak;                          // [R1][lde] out, or NULL
 } GseaEsP;
 
+/* Gradient-boosted trees on the Cox partial likelihood (csrc/gbm.hip; boosting.py): P problems advanced in lock-step, M rounds of one
+ * tree each, over ONE binned feature-major matrix.  The n patients stand in TIME-DESCENDING order as for the forest above: event[i],
+ * tgroup[i] (a larger number is a shorter time), rowid[i] = the row of the caller's matrix that stands at position i.  xb[f][i] in
+ * 0 .. B - 1 is the bin of feature f at position i: bin = the number of edges[f][0 .. B - 1) that are < x (searchsorted, side "left";
+ * the edges ascending, label-free quantiles, duplicates allowed).  The cut (f, b), b in 0 .. B - 2, sends bin <= b LEFT, which is
+ * x <= edges[f][b] on raw values: thr = edges[f][b].
+ *
+ * A problem q is its multiplicity row mult[q][0..n) (0 = held out; a repeat counts as a separate subject), an optional evaluation mask
+ * evalm[q][0..n), the scalars lr[q] (nu), depth[q] (D, 1 .. MMS_GBM_MAX_DEPTH), min_leaf[q] (weighted patients, >= 1), l2[q] (lambda
+ * >= 0), min_gain[q] (gamma >= 0), the thresholds subsample[q] / colsample[q] (0xFFFFFFFF = always) and its hash stream pid[q] (q when
+ * pid is NULL).  Everything a problem computes depends on its own row, scalars and id only, never on what shares its launches.  State
+ * per problem: F[q][0..n) fp64 (0 before round 0; kept for ALL positions, held-out ones included), node[q][i] the current node of
+ * position i in the round's tree, wt[q][i] = mult[q][i] where the position is in the round's sample, else 0.  Trees are heap-indexed
+ * (children of s: 2s + 1, 2s + 2); the tables are [P][M][nn], nn >= 2^(max depth + 1) - 1, and the CALLER initialises feat = -1 and
+ * every other table = 0.
+ *
+ * Hashes (hash = csrc/common.h's hash_u32, 32-bit wrap-around arithmetic):
+ *     hk = hash(seed ^ (id * 0x85ebca6b));   hm = hash((m + 1) * 0x85ebca6b + hk)   for round m;
+ *     position i is in the round's sample iff hash((rowid[i] + 1) * 0x9E3779B9 + hm) <= subsample;
+ *     feature j is admitted in the round  iff hash((j + 1) * 0x9E3779B9 + (hm ^ 0xB5297A4D)) <= colsample.
+ *
+ * mms_gbm_grad, one launch per round (workgroup = problem): over the TRAINING positions (mult > 0; all of them, sampled or not), with
+ * c = max F over them, e_i = exp(F_i - c), Breslow ties, fp64:
+ *     S_k = sum of mult_j e_j over the positions up to the end of tie group k   (a forward scan: time descending),
+ *     d_k = the weighted events of tie group k,   a_k = d_k / S_k,   b_k = a_k / S_k   (groups with d_k > 0),
+ *     Lambda_i = sum of a_k, Q_i = sum of b_k over the groups from i's own to the last   (a backward scan),
+ *     g_i = event_i - e_i Lambda_i,   h_i = e_i Lambda_i - (e_i e_i) Q_i,
+ *     qg_i = llrint(clamp(g_i, -2^8, 1) * 2^32),   qh_i = llrint(clamp(h_i, 0, 2^8) * 2^32)      (int64; 0 where mult = 0),
+ *     loglik[q][m] = sum over training events of mult_i (F_i - c) - sum_k d_k log S_k   (the log partial likelihood BEFORE round m's tree).
+ * The scans run in a fixed order: wave scans over chunks of 256 positions, wave totals in order, the chunks' carry in order.  The launch
+ * also writes wt, node = 0 and the root's n_node / G / H (weighted sums over the round's sample: G = sum wt_i qg_i, exact integers; with
+ * mult <= 255 and n <= MMS_GBM_MAX_N every sum stays below 2^59).  last != 0: only loglik[q][m] is written (m = M is allowed then:
+ * the likelihood after the last round; loglik is [P][M + 1]).
+ *
+ * mms_gbm_split, one call per level (two launches).  (1) grid = (tile of MMS_GBM_TILE features, problem): the workgroup returns at once
+ * when level >= depth[q] or no node s = 2^level - 1 + k of the level is live (s = 0 or the parent split; n_node[s] >= 2 min_leaf).
+ * Otherwise it builds, in LDS, the histograms {weighted count int32, sum wt qg int64, sum wt qh int64} per (feature of the tile, live
+ * node, bin) over the sampled members -- as many features a pass as MMS_GBM_LDS_CELLS cells of 20 bytes hold -- prefixes them over the
+ * bins and scores the B - 1 cuts of every admitted feature:
+ *     admissible iff n_L >= min_leaf and n - n_L >= min_leaf;      term(G, H) = (G G) / (H + lambda), 0 when H + lambda <= 0;
+ *     gain = term(G_L, H_L) + term(G_R, H_R) - term(G, H),   G_R = G - G_L, H_R = H - H_L in int64,
+ * every int64 sum converted to fp64 (round to nearest) and scaled by 2^-32 first; squares and quotients only, so no fused multiply-add
+ * can change a bit.  Its best cut per node (largest gain, then the smallest feature, then the smallest bin) goes to a partial table.
+ * form: 0 = the default (MMS_GBM_FORM_MEMBERS), MMS_GBM_FORM_MEMBERS = lanes over members with integer LDS atomic adds,
+ * MMS_GBM_FORM_PRIVATE = a lane per (feature, node) walking the members with a private LDS histogram; all sums are integers, so the
+ * forms give identical bits.  (2) grid = problem: per live node the partials of the tiles in ascending order (a fixed-order argmax);
+ * the winner splits iff gain > min_gain: feat / bin / thr / gain of s and n_node / G / H of both children are written; then every
+ * position of a node that split moves to 2s + 1 + [xb > bin] (ALL positions: held-out and unsampled ones follow the tree too).
+ * Optional trace tables t_n / t_G / t_H [P][2^level][p][B]: the prefixed (n_L, G_L, H_L) of every bin of every admitted feature of
+ * every live node (all three or none; untouched elsewhere).  No float atomics, no global atomics, no workgroup waits for another.
+ *
+ * mms_gbm_update, one launch per round (workgroup = problem): value[s] = lr * (G / (H + lambda)) (fp64 as above; 0 when H + lambda
+ * <= 0) for every leaf (s = 0 or the parent split, and feat[s] < 0), F_i += value[node_i] for ALL positions, and with evalm the pair
+ * counts of survival_stats.concordance_index(time, -F, event) over the masked positions by mms_rsf_vimp's pair rule:
+ * comparable[q][m], conc2[q][m] = 2 concordant + ties (int64, exact).
+ *
+ * mms_gbm_predict: thread = (problem, row of x [R][ldx] raw fp32): the row is dropped down the trees in round order (left iff
+ * x[feat] <= thr), its sum running sequentially from 0.0, and out[q][k][row] = the sum after at[k] rounds (at ascending, 0 .. M):
+ * on the training matrix that is F of the fit bit for bit.
+ *
+ * The launches cannot check table contents: the CALLER guarantees xb < B, tgroup, rowid, feat < p, node values and the order of the
+ * positions (ops.gbm_* check on the host).  A NULL required pointer, n outside 1..MMS_GBM_MAX_N, ld < n, p < 1, P outside
+ * 0..MMS_GBM_MAX_P, B outside 2..MMS_GBM_MAX_BINS, M < 1, round outside [0, M) ([0, M] with last), level outside [0,
+ * MMS_GBM_MAX_DEPTH), nn < 2^(level + 2) - 1 (split) or nn outside 1..2^(MMS_GBM_MAX_DEPTH + 1) - 1, form outside 0..2, some but not
+ * all of the trace tables, conc2 / comparable missing with evalm, R < 0, ldx < p, K < 1, or a pointer not aligned to its element:
+ * MMS_ERR_ARG before any launch.  P = 0 (R = 0 for predict): MMS_OK without a launch. */
+#define MMS_GBM_MAX_N 2048
+#define MMS_GBM_MAX_P 65535
+#define MMS_GBM_MAX_DEPTH 6
+#define MMS_GBM_MAX_BINS 64
+#define MMS_GBM_MAX_MULT 255        /* MAX_MULT * MAX_N * 2^8 * 2^32 < 2^59: every int64 sum of quantised gradients is exact */
+#define MMS_GBM_QBITS 32
+#define MMS_GBM_CLAMP_BITS 8
+#define MMS_GBM_TILE 32             /* features a workgroup of mms_gbm_split */
+#define MMS_GBM_LDS_CELLS 2880      /* histogram cells (20 bytes each, rows padded to B + 1) a pass: 57600 bytes of the 64 KB a workgroup may declare */
+#define MMS_GBM_FORM_MEMBERS 1
+#define MMS_GBM_FORM_PRIVATE 2
+typedef struct GbmGradP {
+    int n; int ld; int P; int round; int M; int nn; int last; unsigned seed;
+    const unsigned char* mult;          // [P][ld]
+    const int* event; const int* tgroup; const int* rowid;   // [n]
+    const int* pid;                     // [P] hash stream of each problem, or NULL: q
+    const unsigned* subsample;          // [P]
+    const double* F;                    // [P][ld]
+    long long* qg; long long* qh;       // [P][ld] out
+    unsigned char* wt;                  // [P][ld] out
+    int* node;                          // [P][ld] out
+    double* loglik;                     // [P][M + 1]: element [q][round] out
+    int* n_node; long long* G; long long* H;   // [P][M][nn]: the root of the round out
+} GbmGradP;
+typedef struct GbmSplitP {
+    int n; int ld; int p; int P; int B; int level; int round; int M; int nn; int form; unsigned seed; int ntiles;
+    const unsigned char* xb;            // [p][ld]
+    const unsigned char* wt;            // [P][ld]
+    const long long* qg; const long long* qh;   // [P][ld]
+    const float* edges;                 // [p][B - 1]
+    const int* depth; const int* min_leaf; const double* l2; const double* min_gain;   // [P]
+    const unsigned* colsample; const int* pid;   // [P]; pid or NULL
+    int* node;                          // [P][ld] in / out
+    int* feat; int* bin; float* thr; double* gain; int* n_node; long long* G; long long* H;   // [P][M][nn]
+    double* part_gain; int* part_cut; long long* part_sum;   // scratch [P][ntiles][2^level] x {1 double, 4 ints, 2 int64}; ntiles = ceil(p / MMS_GBM_TILE)
+    int* t_n; long long* t_G; long long* t_H;   // [P][2^level][p][B] out, or NULL
+} GbmSplitP;
+typedef struct GbmUpdateP {
+    int n; int ld; int P; int round; int M; int nn;
+    const int* node;                    // [P][ld]
+    const int* event; const int* tgroup;   // [n]
+    const unsigned char* evalm;         // [P][ld] or NULL
+    const double* lr; const double* l2; // [P]
+    const int* feat; const long long* G; const long long* H;   // [P][M][nn]
+    double* value;                      // [P][M][nn] out
+    double* F;                          // [P][ld] in / out
+    long long* conc2; long long* comparable;   // [P][M]: element [q][round] out; NULL without evalm
+} GbmUpdateP;
+typedef struct GbmPredictP {
+    int R; int ldx; int p; int P; int M; int nn; int K; int pad_;
+    const float* x;                     // [R][ldx]
+    const int* feat; const float* thr; const double* value;   // [P][M][nn]
+    const int* at;                      // [K] ascending round counts in 0 .. M
+    double* out;                        // [P][K][R]
+} GbmPredictP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -1277,6 +1399,10 @@ int mms_rsf_split(const RsfSplitP* p, hipStream_t s);         /* random survival
 int mms_rsf_leaves(const RsfLeavesP* p, hipStream_t s);       /* ... mortality and H at the horizons of every leaf */
 int mms_rsf_predict(const RsfPredictP* p, hipStream_t s);     /* ... masked mean over the trees for R rows */
 int mms_rsf_vimp(const RsfVimpP* p, hipStream_t s);           /* ... permutation importance: P problems x R repeats (RsfVimpP above) */
+int mms_gbm_grad(const GbmGradP* p, hipStream_t s);           /* gradient-boosted Cox trees: quantised gradients of a round (GbmGradP above) */
+int mms_gbm_split(const GbmSplitP* p, hipStream_t s);         /* ... one level: histograms, cuts, fixed-order argmax, routing */
+int mms_gbm_update(const GbmUpdateP* p, hipStream_t s);       /* ... leaf values, F, evaluation pair counts */
+int mms_gbm_predict(const GbmPredictP* p, hipStream_t s);     /* ... F of raw rows after each of K round counts */
 int mms_gsea_scores(const GseaScoreP* p, hipStream_t s);      /* gene-set enrichment: permutation Z of G genes x R1 relabellings (GseaScoreP above) */
 int mms_gsea_es(const GseaEsP* p, hipStream_t s);             /* ... enrichment score of S sets in R1 replicates (GseaEsP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);       /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */

@@ -730,6 +730,194 @@ def rsf_vimp(x, feat, thr, mort, use, donor, M0, cnt, event, tgroup, pset, pgene
                            plan_only)
 
 
+GBM_TABLES = dict(feat=torch.int32, bin=torch.int32, thr=torch.float32, gain=torch.float64, value=torch.float64, n_node=torch.int32,
+                  G=torch.int64, H=torch.int64)
+GBM_PARAMS = dict(lr=torch.float64, depth=torch.int32, min_leaf=torch.int32, l2=torch.float64, min_gain=torch.float64)
+_GBM_LIM = {}
+
+
+def _gbm_lim():
+    """the header's MMS_GBM_* limits, parsed once (these wrappers run five times a boosting round)"""
+    if not _GBM_LIM:
+        _GBM_LIM.update(_lib.defines("MMS_GBM_"))
+    return _GBM_LIM
+
+
+def gbm_tables(P, M, nn, device):
+    """The heap-indexed booster tables [P, M, nn] as mms_gbm_* expect them before round 0: feat = -1, every other table 0."""
+    return {k: (torch.full((P, M, nn), -1, dtype=dt, device=device) if k == "feat" else torch.zeros(P, M, nn, dtype=dt, device=device))
+            for k, dt in GBM_TABLES.items()}
+
+
+def gbm_state(P, n, M, device):
+    """The per-problem state of a fit: F (0), qg, qh, wt, node [P, n], loglik [P, M + 1], conc2 / comparable [P, M]."""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+    return dict(F=z((P, n), torch.float64), qg=z((P, n), torch.int64), qh=z((P, n), torch.int64), wt=z((P, n), torch.uint8),
+                node=z((P, n), torch.int32), loglik=z((P, M + 1), torch.float64), conc2=z((P, M), torch.int64),
+                comparable=z((P, M), torch.int64))
+
+
+def _gbm_common(mult, state, tables, params, n, need_tables=GBM_TABLES):
+    """Shapes and dtypes shared by the gbm wrappers -> (P, M, nn).  params: dict of [P] device tensors (GBM_PARAMS), each optional here."""
+    lim = _gbm_lim()
+    _rsf_dev(mult, torch.uint8, "mult", 2)
+    P = mult.shape[0]
+    if mult.shape[1] != n or not (1 <= n <= lim["MAX_N"]) or P > lim["MAX_P"]:
+        raise ValueError("mult must be [P, n] with n in 1..%d and P <= %d" % (lim["MAX_N"], lim["MAX_P"]))
+    kinds = dict(F=torch.float64, qg=torch.int64, qh=torch.int64, wt=torch.uint8, node=torch.int32)
+    for k, dt in kinds.items():
+        _rsf_dev(state[k], dt, k, 2)
+        if tuple(state[k].shape) != (P, n):
+            raise ValueError("state[%r] must be [P, n]" % k)
+    _rsf_dev(tables["feat"], torch.int32, "feat", 3)
+    _, M, nn = tables["feat"].shape
+    for k in need_tables:
+        _rsf_dev(tables[k], GBM_TABLES[k], k, 3)
+        if tuple(tables[k].shape) != (P, M, nn):
+            raise ValueError("the booster tables must all be [P, M, nn]")
+    if M < 1 or not (1 <= nn <= (2 << lim["MAX_DEPTH"]) - 1):
+        raise ValueError("M must be >= 1 and nn in 1..%d" % ((2 << lim["MAX_DEPTH"]) - 1))
+    for k, v in params.items():
+        _rsf_dev(v, GBM_PARAMS[k] if k in GBM_PARAMS else torch.int32, k, 1)
+        if len(v) != P:
+            raise ValueError("%s must be [P]" % k)
+    return P, M, nn
+
+
+def _gbm_u32(t):
+    """int64 values in 0 .. 2^32 - 1 -> the same bits as an int32 tensor (what a `const unsigned*` reads)"""
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+        raise ValueError("a hash threshold must lie in 0 .. 2^32 - 1")
+    return torch.where(t >= 2 ** 31, t - 2 ** 32, t).to(torch.int32).contiguous()
+
+
+def gbm_grad(mult, event, tgroup, rowid, subsample_u32, state, tables, round, seed, pid=None, last=False, plan_only=False):
+    """Quantised Cox gradients of one round of P lock-step boosters (GbmGradP in mmsurv.h).  Device tensors: mult uint8 [P, n], event /
+    tgroup / rowid int32 [n] in position (time-descending) order, subsample_u32 int32 [P] (the threshold's bits: _gbm_u32), state =
+    gbm_state(...), tables = gbm_tables(...), pid int32 [P] or None.  Writes state qg / qh / wt / node / loglik[:, round] and the root of
+    tables n_node / G / H [:, round]; last: only loglik[:, round] (round = M allowed)."""
+    n = mult.shape[1] if torch.is_tensor(mult) and mult.dim() == 2 else 0
+    params = dict(pid=pid) if pid is not None else {}
+    P, M, nn = _gbm_common(mult, state, tables, params, n, ("n_node", "G", "H"))
+    for t, what in ((event, "event"), (tgroup, "tgroup"), (rowid, "rowid"), (subsample_u32, "subsample")):
+        _rsf_dev(t, torch.int32, what, 1)
+    _rsf_dev(state["loglik"], torch.float64, "loglik", 2)
+    if len(event) != n or len(tgroup) != n or len(rowid) != n or len(subsample_u32) != P or tuple(state["loglik"].shape) != (P, M + 1):
+        raise ValueError("event / tgroup / rowid must be [n], subsample [P] and loglik [P, M + 1]")
+    round = int(round)
+    if not (0 <= round < M or (last and round == M)):
+        raise ValueError("round must lie in [0, M) ([0, M] with last)")
+    if P == 0:
+        return None
+    p = _S()["GbmGradP"](n, n, P, round, M, nn, 1 if last else 0, int(seed) & 0xffffffff, ptr(mult), ptr(event), ptr(tgroup), ptr(rowid), ptr(pid),
+                         ptr(subsample_u32), ptr(state["F"]), ptr(state["qg"]), ptr(state["qh"]), ptr(state["wt"]), ptr(state["node"]),
+                         ptr(state["loglik"]), ptr(tables["n_node"]), ptr(tables["G"]), ptr(tables["H"]))
+    return _launch_or_plan("mms_gbm_grad", p, (mult, event, tgroup, rowid, pid, subsample_u32, state, tables), None, plan_only)
+
+
+def gbm_scratch(P, p_, level, device):
+    """The partial tables of mms_gbm_split for one level: (part_gain, part_cut, part_sum)"""
+    nt = (int(p_) + _gbm_lim()["TILE"] - 1) // _gbm_lim()["TILE"]
+    c = max(P, 1) * nt * (1 << int(level))
+    return (torch.zeros(c, dtype=torch.float64, device=device), torch.zeros(4 * c, dtype=torch.int32, device=device),
+            torch.zeros(2 * c, dtype=torch.int64, device=device))
+
+
+def gbm_split(xb, edges, state, tables, params, colsample_u32, level, round, seed, pid=None, form=0, trace=False, scratch=None,
+              plan_only=False):
+    """One level of one round of P lock-step boosters: histograms, cuts, argmax, routing (GbmSplitP in mmsurv.h).  Device tensors: xb uint8
+    [p, n] bins, feature-major in position order (the CALLER guarantees xb < B: boosting.bin_matrix does; checked by fit once), edges fp32
+    [p, B - 1], state / tables as gbm_grad, params = dict(depth, min_leaf int32, l2, min_gain float64) [P], colsample_u32 int32 [P].
+    form: 0 default, 1 members, 2 private (header: MMS_GBM_FORM_*).  trace: also return dict(n, G, H) [P, 2^level, p, B], the prefixed
+    histograms of every admitted feature of every live node (zero elsewhere).  scratch: gbm_scratch(...) to reuse."""
+    lim = _gbm_lim()
+    _rsf_dev(xb, torch.uint8, "xb", 2); _rsf_dev(edges, torch.float32, "edges", 2)
+    p_, n = xb.shape
+    B = edges.shape[1] + 1
+    need = {k: params[k] for k in ("depth", "min_leaf", "l2", "min_gain")}
+    if pid is not None:
+        need["pid"] = pid
+    P, M, nn = _gbm_common(state["wt"], state, tables, need, n, ("feat", "bin", "thr", "gain", "n_node", "G", "H"))
+    _rsf_dev(colsample_u32, torch.int32, "colsample", 1)
+    level, round, form = int(level), int(round), int(form)
+    if edges.shape[0] != p_ or not (2 <= B <= lim["MAX_BINS"]) or len(colsample_u32) != P:
+        raise ValueError("edges must be [p, B - 1] with B in 2..%d and colsample [P]" % lim["MAX_BINS"])
+    if not (0 <= level < lim["MAX_DEPTH"]) or nn < (4 << level) - 1 or not (0 <= round < M) or form not in (0, 1, 2):
+        raise ValueError("level must lie in [0, %d) with nn >= 2^(level + 2) - 1, round in [0, M), form in 0..2" % lim["MAX_DEPTH"])
+    if (1 << level) * (B + 1) > lim["LDS_CELLS"]:
+        raise ValueError("the histograms of one feature at this level do not fit the workgroup's LDS")
+    dev = xb.device
+    out = None
+    if trace:
+        shape = (max(P, 1), 1 << level, p_, B)
+        out = dict(n=torch.zeros(shape, dtype=torch.int32, device=dev), G=torch.zeros(shape, dtype=torch.int64, device=dev),
+                   H=torch.zeros(shape, dtype=torch.int64, device=dev))
+    if P == 0:
+        return None if out is None else {k: v[:0] for k, v in out.items()}
+    sc = gbm_scratch(P, p_, level, dev) if scratch is None else scratch
+    nt = (p_ + lim["TILE"] - 1) // lim["TILE"]
+    if sc[0].dtype != torch.float64 or sc[1].dtype != torch.int32 or sc[2].dtype != torch.int64 or sc[0].numel() < P * nt * (1 << level) \
+            or sc[1].numel() < 4 * P * nt * (1 << level) or sc[2].numel() < 2 * P * nt * (1 << level):
+        raise ValueError("scratch too small for this level (gbm_scratch)")
+    g = (lambda k: ptr(out[k])) if trace else (lambda k: None)
+    p = _S()["GbmSplitP"](n, n, p_, P, B, level, round, M, nn, form, int(seed) & 0xffffffff, nt, ptr(xb), ptr(state["wt"]), ptr(state["qg"]),
+                          ptr(state["qh"]), ptr(edges), ptr(params["depth"]), ptr(params["min_leaf"]), ptr(params["l2"]), ptr(params["min_gain"]),
+                          ptr(colsample_u32), ptr(pid), ptr(state["node"]), ptr(tables["feat"]), ptr(tables["bin"]), ptr(tables["thr"]),
+                          ptr(tables["gain"]), ptr(tables["n_node"]), ptr(tables["G"]), ptr(tables["H"]), ptr(sc[0]), ptr(sc[1]), ptr(sc[2]),
+                          g("n"), g("G"), g("H"))
+    res = None if out is None else {k: v[:P] for k, v in out.items()}
+    return _launch_or_plan("mms_gbm_split", p, (xb, edges, state, tables, params, colsample_u32, pid, sc, out), res, plan_only)
+
+
+def gbm_update(event, tgroup, state, tables, params, round, evalm=None, plan_only=False):
+    """Leaf values, F of every position and the evaluation pair counts of one round (GbmUpdateP in mmsurv.h).  params = dict(lr, l2
+    float64 [P]); evalm uint8 [P, n] or None (no counts).  Writes tables value[:, round], state F and conc2 / comparable[:, round]."""
+    _rsf_dev(event, torch.int32, "event", 1); _rsf_dev(tgroup, torch.int32, "tgroup", 1)
+    n = len(event)
+    P, M, nn = _gbm_common(state["wt"], state, tables, {k: params[k] for k in ("lr", "l2")}, n, ("feat", "G", "H", "value"))
+    round = int(round)
+    if len(tgroup) != n or not (0 <= round < M):
+        raise ValueError("tgroup must be [n] and round lie in [0, M)")
+    if evalm is not None:
+        _rsf_dev(evalm, torch.uint8, "evalm", 2); _rsf_dev(state["conc2"], torch.int64, "conc2", 2); _rsf_dev(state["comparable"], torch.int64, "comparable", 2)
+        if tuple(evalm.shape) != (P, n) or tuple(state["conc2"].shape) != (P, M) or tuple(state["comparable"].shape) != (P, M):
+            raise ValueError("evalm must be [P, n] and conc2 / comparable [P, M]")
+    if P == 0:
+        return None
+    p = _S()["GbmUpdateP"](n, n, P, round, M, nn, ptr(state["node"]), ptr(event), ptr(tgroup), ptr(evalm), ptr(params["lr"]), ptr(params["l2"]),
+                           ptr(tables["feat"]), ptr(tables["G"]), ptr(tables["H"]), ptr(tables["value"]), ptr(state["F"]),
+                           ptr(state["conc2"]) if evalm is not None else None, ptr(state["comparable"]) if evalm is not None else None)
+    return _launch_or_plan("mms_gbm_update", p, (event, tgroup, state, tables, params, evalm), None, plan_only)
+
+
+def gbm_predict(x, feat, thr, value, at, plan_only=False):
+    """F of R raw rows after each of K round counts, for P boosters (GbmPredictP in mmsurv.h).  x fp32 [R, p] device (row pitch
+    x.stride(0)); feat int32, thr fp32, value float64 [P, M, nn]; at: K ascending round counts in 0..M (host sequence).  feat is checked
+    HERE against p.  -> float64 [P, K, R]."""
+    import numpy as np
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise TypeError("x must be a float32 [R, p] device tensor with unit column stride")
+    _rsf_dev(feat, torch.int32, "feat", 3); _rsf_dev(thr, torch.float32, "thr", 3); _rsf_dev(value, torch.float64, "value", 3)
+    R, p_ = x.shape
+    P, M, nn = feat.shape
+    at = np.asarray(at, np.int64).reshape(-1)
+    K = len(at)
+    lim = _gbm_lim()
+    if tuple(thr.shape) != (P, M, nn) or tuple(value.shape) != (P, M, nn) or M < 1 or not (1 <= nn <= (2 << lim["MAX_DEPTH"]) - 1):
+        raise ValueError("thr and value must match feat [P, M, nn]")
+    if K < 1 or at.min() < 0 or at.max() > M or (np.diff(at) < 0).any():
+        raise ValueError("at must hold ascending round counts in 0..%d" % M)
+    if P and int(feat.max()) >= p_:
+        raise ValueError("the booster splits on feature %d; x has %d columns" % (int(feat.max()), p_))
+    dev = x.device
+    out = torch.zeros(max(P, 1), K, max(R, 1), dtype=torch.float64, device=dev)
+    if P == 0 or R == 0:
+        return out[:P, :, :R]
+    at_d = _upload(at, "int32", dev)
+    p = _S()["GbmPredictP"](R, max(x.stride(0), p_), p_, P, M, nn, K, 0, ptr(x), ptr(feat), ptr(thr), ptr(value), ptr(at_d), ptr(out))
+    return _launch_or_plan("mms_gbm_predict", p, (x, feat, thr, value, at_d, out), out, plan_only)
+
+
 def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     """IPCW Brier / dynamic AUC sums of M models at H horizons under R multiplicity rows (TdMetricsP in mmsurv.h).  trank, event: [n] dense
     time ranks and event flags of the TIME-ASCENDING positions (events before censorings at equal times), hcut: [H] positions with

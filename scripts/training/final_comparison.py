@@ -18,15 +18,19 @@ RESULTS_FILES = {          # display name -> file written by scripts/training/<e
     "Image-Only": "results/image_only/cv_results.json",      # scripts/training/image_only_training.py
     "Cox elastic net": "results/cox_baseline/cv_results.json",   # scripts/training/cox_baseline.py
     "Random survival forest": "results/rsf_baseline/cv_results.json",   # scripts/training/rsf_baseline.py
+    "Gradient-boosted Cox trees": "results/gbm_baseline/cv_results.json",   # scripts/training/gbm_baseline.py
 }
 # The baseline's fold values are the OUTER validation C-index at a lambda chosen by inner cross-validation on the training patients (nested
 # CV); a network's best_c_index is its maximum over the epochs ON the validation fold.  The two are not on equal footing, and the baseline
 # is the one handicapped.  The forest's fold values are the validation C-index of the forest as specified: nothing is chosen on the
-# validation fold either.
-NESTED = ("Cox elastic net", "Random survival forest")
+# validation fold either.  The boosted trees' fold values are nested like the elastic net's: the learning rate, depth and number of rounds
+# are chosen on inner folds of the training patients.
+NESTED = ("Cox elastic net", "Random survival forest", "Gradient-boosted Cox trees")
 NESTED_NOTE = ("(+) nested cross-validation: lambda chosen inside each fold's training patients, the validation fold not seen (the forest: "
                "grown as specified, nothing tuned on the validation fold); the other rows are maxima over epochs on the validation fold -- "
                "not on equal footing, the (+) rows are the ones handicapped")
+# the clause the boosted trees add to the note; printed only when their row is there, so the other rows' output is what it was
+GBM_CLAUSE = "; the boosted trees: grid point and number of rounds chosen inside each fold's training patients"
 
 
 def collect(root="."):
@@ -74,7 +78,7 @@ def main(root="."):
     for name, r in sorted(res.items(), key=lambda kv: -kv[1]["mean"]):
         print(f"  {name + (' (+)' if name in NESTED else ''):22s} C-index {r['mean']:.4f} +/- {r['std']:.4f}  folds {['%.3f' % v for v in r['fold_values']]}")
     if any(name in NESTED for name in res):
-        print("  " + NESTED_NOTE)
+        print("  " + NESTED_NOTE + (GBM_CLAUSE if "Gradient-boosted Cox trees" in res else ""))
     best, tests = compare(res)
     print(f"best: {best} ({res[best]['mean']:.4f})")
     for name, t in tests.items():
