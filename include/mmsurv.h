@@ -1470,9 +1470,11 @@ int mms_head_bwd_apply(const HeadBwdP* p, hipStream_t s);        /* ... norm5 ba
 
 /* ---- preprocessing upstream of the path, on the GPU (replaces per-item numpy/scipy on the CPU) ----
  * mms_ct_preprocess: (x - min) / (max - min + 1e-8) and scipy.ndimage.zoom(order=1) to the network grid
- *   (R/scripts/training/partial_modality_training.py:94-109, simple_fusion.py:117-134); scratch >= 512 floats.
+ *   (R/scripts/training/partial_modality_training.py:94-109, simple_fusion.py:117-134); scratch >= 512 floats.  x - min is taken
+ *   BEFORE the interpolation (csrc/ct_resample.h, shared with mms_ct_preprocess_raw_batch): a constant volume gives exact zeros, no
+ *   output is below 0, and a float32 volume gives the bits mms_ct_preprocess_raw_batch gives for it as MMS_CT_F32, slope 1.
  * mms_rna_log_zscore: log2(count + 1), then per-gene StandardScaler over the n samples
- *   (R/scripts/preprocessing/preprocess_genomic.py:108-117). */
+ *   (R/scripts/preprocessing/preprocess_genomic.py:108-117); mean, two-pass variance and centring in fp64, one rounding to fp32. */
 int mms_ct_preprocess(const float* x, int inD, int inH, int inW, float* out, int oD, int oH, int oW, float* scratch, hipStream_t s);
 int mms_rna_log_zscore(const float* counts, float* out, int n, int g, hipStream_t s);
 

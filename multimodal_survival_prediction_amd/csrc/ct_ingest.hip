@@ -15,6 +15,7 @@
 // the output voxels they touch are NaN.
 // The element type and the byte order are per volume, i.e. uniform over a workgroup: the switches below are scalar branches.
 #include "common.h"
+#include "ct_resample.h"
 #include <float.h>
 #include <cmath>
 #include <string.h>
@@ -89,27 +90,21 @@ __global__ __launch_bounds__(256) void ct_raw_minmax_kernel(const unsigned char*
     }
 }
 
-// t = r - ref (sign +1) or ref - r (sign -1) of the eight neighbours, interpolated as ct_resample_norm_kernel (preproc.hip) does, times sc
+// t = r - ref (sign +1) or ref - r (sign -1) of the eight neighbours, interpolated and scaled by ct_interp_norm (ct_resample.h): the
+// arithmetic of ct_resample_norm_kernel (preproc.hip), so a float32 volume gives the same bits on either route
 template <class T, class U>
 __device__ __forceinline__ void resample_body(const unsigned char* __restrict__ xb, const VolK& d, bool swap, float ref, float sgn, float sc,
                                               float* __restrict__ out, Dims3 o) {
     const U* __restrict__ x = (const U*)xb;
     const int n = o.D * o.H * o.W;
-    const double sd = o.D > 1 ? (double)(d.D - 1) / (o.D - 1) : 0.0, sh = o.H > 1 ? (double)(d.H - 1) / (o.H - 1) : 0.0,
-                 sw = o.W > 1 ? (double)(d.W - 1) / (o.W - 1) : 0.0;
+    const Dims3 in{d.D, d.H, d.W};
+    const double sd = ct_axis_step(d.D, o.D), sh = ct_axis_step(d.H, o.H), sw = ct_axis_step(d.W, o.W);
+    auto at = [&](int dd, int hh, int ww) {
+        return (raw_val<T, U>(x[((unsigned)dd * (unsigned)d.H + (unsigned)hh) * (unsigned)d.W + (unsigned)ww], swap) - ref) * sgn;
+    };
     for (long long li = (long long)blockIdx.x * 256 + threadIdx.x; li < n; li += (long long)gridDim.x * 256) {
         const int idx = (int)li, ow = idx % o.W, oh = (idx / o.W) % o.H, od = idx / (o.W * o.H);
-        const double cd = od * sd, ch = oh * sh, cw = ow * sw;
-        const int d0 = (int)cd, h0 = (int)ch, w0 = (int)cw;
-        const int d1 = d0 + 1 < d.D ? d0 + 1 : d0, h1 = h0 + 1 < d.H ? h0 + 1 : h0, w1 = w0 + 1 < d.W ? w0 + 1 : w0;
-        const float fd = (float)(cd - d0), fh = (float)(ch - h0), fw = (float)(cw - w0);
-        auto at = [&](int dd, int hh, int ww) {
-            return (raw_val<T, U>(x[((unsigned)dd * (unsigned)d.H + (unsigned)hh) * (unsigned)d.W + (unsigned)ww], swap) - ref) * sgn;
-        };
-        const float c00 = at(d0, h0, w0) * (1 - fw) + at(d0, h0, w1) * fw, c01 = at(d0, h1, w0) * (1 - fw) + at(d0, h1, w1) * fw;
-        const float c10 = at(d1, h0, w0) * (1 - fw) + at(d1, h0, w1) * fw, c11 = at(d1, h1, w0) * (1 - fw) + at(d1, h1, w1) * fw;
-        const float v = (c00 * (1 - fh) + c01 * fh) * (1 - fd) + (c10 * (1 - fh) + c11 * fh) * fd;
-        out[idx] = v * sc;
+        out[idx] = ct_interp_norm(at, in, od, oh, ow, sd, sh, sw, sc);
     }
 }
 
@@ -127,8 +122,7 @@ __global__ __launch_bounds__(256) void ct_raw_resample_kernel(const unsigned cha
     }
     __syncthreads();
     const float rlo = mm[0], rhi = mm[1];
-    const float a = fabsf(d.slope);
-    const float sc = a / (a * (rhi - rlo) + 1e-8f);
+    const float sc = ct_norm_scale(fabsf(d.slope), rlo, rhi);
     const bool neg = d.slope < 0.f;
     const float ref = neg ? rhi : rlo, sgn = neg ? -1.f : 1.f;
     const unsigned char* x = base + d.off;

@@ -5,6 +5,7 @@
 //   * RNA-seq counts: log2(count + 1) then per-gene z-score over the cohort (sklearn StandardScaler, ddof 0)
 //     (R/scripts/preprocessing/preprocess_genomic.py:108-117).
 #include "common.h"
+#include "ct_resample.h"
 #include <float.h>
 
 // ---- per-volume min / max: stage 1 -> [blocks][2] partials, stage 2 (inside the resample kernel's prologue) ----
@@ -23,9 +24,9 @@ __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __rest
     }
 }
 
-// scipy.ndimage.zoom(order=1, grid_mode=False): output index o maps to input coordinate o * (in - 1) / (out - 1)
-// (0 when out == 1); linear interpolation between the two neighbours.  Normalisation (x - min) / (max - min + 1e-8) is
-// affine, so it commutes with the interpolation and is applied to the interpolated value.
+// Output voxel = ct_interp_norm (ct_resample.h) of x - min: the reference value is subtracted BEFORE the interpolation.  The
+// normalisation is affine and would commute with the interpolation in exact arithmetic; in fp32 it does not (a (1 - f) + a f is not
+// a), and normalising the interpolated value made a constant volume non-zero and lost low contrast on a large offset.
 __global__ __launch_bounds__(256) void ct_resample_norm_kernel(const float* __restrict__ x, Dims3 in, float* __restrict__ out, Dims3 o,
                                                                const float* __restrict__ part, int nparts) {
     __shared__ float mm[2];
@@ -37,21 +38,13 @@ __global__ __launch_bounds__(256) void ct_resample_norm_kernel(const float* __re
         if (threadIdx.x == 0) { mm[0] = lo; mm[1] = hi; }
     }
     __syncthreads();
-    const float lo = mm[0], inv = 1.0f / (mm[1] - mm[0] + 1e-8f);
+    const float lo = mm[0], sc = ct_norm_scale(1.0f, mm[0], mm[1]);
     const long long n = (long long)o.D * o.H * o.W;
-    const double sd = o.D > 1 ? (double)(in.D - 1) / (o.D - 1) : 0.0, sh = o.H > 1 ? (double)(in.H - 1) / (o.H - 1) : 0.0,
-                 sw = o.W > 1 ? (double)(in.W - 1) / (o.W - 1) : 0.0;
+    const double sd = ct_axis_step(in.D, o.D), sh = ct_axis_step(in.H, o.H), sw = ct_axis_step(in.W, o.W);
+    auto at = [&](int d, int h, int w) { return x[((size_t)d * in.H + h) * in.W + w] - lo; };
     for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long long)gridDim.x * 256) {
         const int ow = (int)(idx % o.W), oh = (int)((idx / o.W) % o.H), od = (int)(idx / ((long long)o.W * o.H));
-        const double cd = od * sd, ch = oh * sh, cw = ow * sw;
-        const int d0 = (int)cd, h0 = (int)ch, w0 = (int)cw;
-        const int d1 = d0 + 1 < in.D ? d0 + 1 : d0, h1 = h0 + 1 < in.H ? h0 + 1 : h0, w1 = w0 + 1 < in.W ? w0 + 1 : w0;
-        const float fd = (float)(cd - d0), fh = (float)(ch - h0), fw = (float)(cw - w0);
-        auto at = [&](int d, int h, int w) { return x[((size_t)d * in.H + h) * in.W + w]; };
-        const float c00 = at(d0, h0, w0) * (1 - fw) + at(d0, h0, w1) * fw, c01 = at(d0, h1, w0) * (1 - fw) + at(d0, h1, w1) * fw;
-        const float c10 = at(d1, h0, w0) * (1 - fw) + at(d1, h0, w1) * fw, c11 = at(d1, h1, w0) * (1 - fw) + at(d1, h1, w1) * fw;
-        const float v = (c00 * (1 - fh) + c01 * fh) * (1 - fd) + (c10 * (1 - fh) + c11 * fh) * fd;
-        out[idx] = (v - lo) * inv;
+        out[idx] = ct_interp_norm(at, in, od, oh, ow, sd, sh, sw, sc);
     }
 }
 
@@ -71,32 +64,34 @@ extern "C" int mms_ct_preprocess(const float* x, int inD, int inH, int inW, floa
 }
 
 // counts [n][g] row-major -> out [n][g] = zscore_over_rows(log2(count + 1)); zero-variance genes keep scale 1 (sklearn).
-// one workgroup per 64 genes: 4 row-groups x 64 columns, fp64 accumulation
+// one workgroup per 64 genes: 4 row-groups x 64 columns.  Everything up to the store is fp64, in three reads of the column: the mean,
+// then sum (v - mean)^2 (the one-pass E[v^2] - mean^2 cancels for a well-expressed stable gene: v ~ 17, sd ~ 1e-2 and below), then
+// (float)((v - mean) / sd) -- centring in fp32 would cost ulp(17) / sd.
 __global__ __launch_bounds__(256) void rna_log_zscore_kernel(const float* __restrict__ c, float* __restrict__ out, int n, int g) {
-    __shared__ double ssum[4][64], ssq[4][64];
-    __shared__ float smean[64], sinv[64];
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63), rg = threadIdx.x >> 6;
-    double s1 = 0, s2 = 0;
+    __shared__ double ssum[4][64];
+    __shared__ double smean[64], sinv[64];
+    const int lane = threadIdx.x & 63, col = blockIdx.x * 64 + lane, rg = threadIdx.x >> 6;
+    double s1 = 0;
     if (col < g)
-        for (int r = rg; r < n; r += 4) { const double v = log2((double)c[(size_t)r * g + col] + 1.0); s1 += v; s2 += v * v; }
-    ssum[rg][threadIdx.x & 63] = s1; ssq[rg][threadIdx.x & 63] = s2;
+        for (int r = rg; r < n; r += 4) s1 += log2((double)c[(size_t)r * g + col] + 1.0);
+    ssum[rg][lane] = s1;
+    __syncthreads();
+    if (rg == 0) smean[lane] = (ssum[0][lane] + ssum[1][lane] + ssum[2][lane] + ssum[3][lane]) / n;
+    __syncthreads();
+    const double m = smean[lane];
+    double s2 = 0;
+    if (col < g)
+        for (int r = rg; r < n; r += 4) { const double e = log2((double)c[(size_t)r * g + col] + 1.0) - m; s2 += e * e; }
+    ssum[rg][lane] = s2;                                       // (every read of the first sums is behind the barrier above)
     __syncthreads();
     if (rg == 0) {
-        const int j = threadIdx.x;
-        const double a = ssum[0][j] + ssum[1][j] + ssum[2][j] + ssum[3][j], b = ssq[0][j] + ssq[1][j] + ssq[2][j] + ssq[3][j];
-        const double m = a / n;
-        double var = b / n - m * m;
-        if (var < 0) var = 0;
-        const double sd = sqrt(var);
-        smean[j] = (float)m;
-        sinv[j] = sd < 1e-12 ? 1.0f : (float)(1.0 / sd);       // (sklearn: scale_ == 0 -> 1)
+        const double sd = sqrt((ssum[0][lane] + ssum[1][lane] + ssum[2][lane] + ssum[3][lane]) / n);
+        sinv[lane] = sd < 1e-12 ? 1.0 : 1.0 / sd;              // (sklearn: scale_ == 0 -> 1)
     }
     __syncthreads();
+    const double inv = sinv[lane];
     if (col < g)
-        for (int r = rg; r < n; r += 4) {
-            const float v = (float)log2((double)c[(size_t)r * g + col] + 1.0);
-            out[(size_t)r * g + col] = (v - smean[threadIdx.x & 63]) * sinv[threadIdx.x & 63];
-        }
+        for (int r = rg; r < n; r += 4) out[(size_t)r * g + col] = (float)((log2((double)c[(size_t)r * g + col] + 1.0) - m) * inv);
 }
 extern "C" int mms_rna_log_zscore(const float* counts, float* out, int n, int g, hipStream_t s) {
     if (!counts || !out || n <= 0 || g <= 0) return MMS_ERR_ARG;

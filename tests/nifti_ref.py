@@ -109,3 +109,52 @@ def ct_values(shape, datatype, seed):
     else:
         v = rng.integers(-1024, 3072, size=shape)
     return v.astype(np.dtype(letter))
+
+
+def full_range_values(shape, datatype, seed):
+    """values that reach the ends of the stored type, so that its signedness and width matter, as the datatype's numpy type:
+    u1 / i1 / i2 the whole range with both ends present; u2 [30000, 65535] with both ends (either side of 2^15); u4 2^31 + 256 k,
+    |k| < 2^20 (either side of 2^31 and exact in fp32: below 2^32 its spacing is at most 256); i4 integers of [-2^24, 2^24] with both
+    ends; f4 HU + U[0, 1) rounded to fp32, f8 the same fp32 values widened."""
+    rng = np.random.default_rng(seed)
+    letter = TYPES[datatype][0]
+    ends = None
+    if letter[0] == "f":
+        v = (rng.integers(-1024, 3072, size=shape) + rng.random(shape)).astype(np.float32)
+    elif letter == "u4":
+        v = 2 ** 31 + 256 * rng.integers(-2 ** 20 + 1, 2 ** 20, size=shape)
+        ends = (2 ** 31 - 256 * (2 ** 20 - 1), 2 ** 31 + 256 * (2 ** 20 - 1))
+    else:
+        ends = {"u1": (0, 255), "i1": (-128, 127), "u2": (30000, 65535), "i2": (-32768, 32767), "i4": (-2 ** 24, 2 ** 24)}[letter]
+        v = rng.integers(ends[0], ends[1] + 1, size=shape)
+    if ends is not None:
+        lo, hi = rng.choice(v.size, size=2, replace=False)
+        v.reshape(-1)[lo], v.reshape(-1)[hi] = ends
+    return v.astype(np.dtype(letter))
+
+
+def low_contrast_values(kind, shape, seed):
+    """float32 volumes whose contrast is tiny next to their offset -- where normalising AFTER interpolating cancels:
+    "two_level" {1000, 1001} (a mask-like scan), "sub_ulp" 1000 + U[0, 1e-3) rounded to fp32 (a few fp32 steps of 1000 apart),
+    "four_level" -1024 + {0, 1, 2, 3}"""
+    rng = np.random.default_rng(seed)
+    if kind == "two_level":
+        v = 1000.0 + rng.integers(0, 2, size=shape)
+    elif kind == "sub_ulp":
+        v = 1000.0 + rng.random(shape) * 1e-3
+    elif kind == "four_level":
+        v = -1024.0 + rng.integers(0, 4, size=shape)
+    else:
+        raise ValueError(kind)
+    return v.astype(np.float32)
+
+
+def scan_values(shape, letter, seed, min_at):
+    """integer HU values of [-1000, 3000) with the only -1024 at flat index min_at and the only 3071 in the last element: a pass over the
+    volume that drops a sweep or the tail gets an extreme wrong and with it every output voxel"""
+    rng = np.random.default_rng(seed)
+    v = rng.integers(-1000, 3000, size=shape)
+    flat = v.reshape(-1)
+    assert 0 <= min_at < flat.size - 1
+    flat[min_at], flat[-1] = -1024, 3071
+    return v.astype(np.dtype(letter))

@@ -3,7 +3,11 @@
 Yardstick: oracle.preproc.ct_preprocess(slope * raw.astype(float64) + inter, target) -- the reference's own numpy + scipy.zoom arithmetic on the
 values the file stands for -- at 1e-5, the tolerance tests/test_gpu_preproc.py uses for the same arithmetic after the load.  The raw values
 are integers of a CT-like range, so the int32 / uint32 / float64 cases are exact in fp32 as well.  Files come from tests/nifti_ref.py (the
-specification's byte offsets), not from the implementation's writer."""
+specification's byte offsets), not from the implementation's writer.
+
+Beyond that range: values at the ends of every stored type with a guard that the other signedness would fail (NR.full_range_values),
+fractional float elements, the documented rounding of float64 elements to fp32, low contrast on an offset, and one volume of scan size
+(pass 1 at its workgroup cap with a scalar tail, more than one sweep of pass 2's output loop, alone and next to small volumes)."""
 import importlib.util
 import os
 import sys
@@ -95,6 +99,106 @@ def test_constant_volume_is_exactly_zero(datatype):
     for slope, inter in ((1.0, 0.0), (2.5, -1024.0), (-1.0, 100.0)):
         got = run([(stored(vals, datatype, OTHER), slope, inter, True)], (8, 8, 4), fill=-3.0)
         assert torch.equal(got, torch.zeros_like(got))
+
+
+# the same bytes read with the other signedness: what a kernel that mixed up two MMS_CT_* cases would see
+SIGN_TWIN = {512: "i2", 4: "u2", 768: "i4", 8: "u4"}
+
+
+@pytest.mark.parametrize("datatype", sorted(NR.TYPES))
+def test_full_range_values_every_type_and_byte_order(datatype):
+    """values at the ends of the stored type (NR.full_range_values), fractional ones for the float types.  Guard, from the oracle alone:
+    for the 16- and 32-bit integers the oracle of the same bytes under the other signedness is at least 100 tolerances away, so reading
+    MMS_CT_U16 as int16 (or MMS_CT_U32 as int32, or the reverse) cannot pass"""
+    native, target = (3, 5, 7), (8, 8, 4)
+    vals = NR.full_range_values(native, datatype, seed=300 + datatype)
+    want = torch.tensor(oracle(("full", datatype), vals, 1.0, 0.0, target))
+    if datatype in SIGN_TWIN:
+        twin = np.ascontiguousarray(vals).view(np.dtype(SIGN_TWIN[datatype]))
+        assert twin.shape == vals.shape and not np.array_equal(twin.astype(np.float64), vals.astype(np.float64))
+        wrong = torch.tensor(oracle(("full twin", datatype), twin, 1.0, 0.0, target))
+        assert float((wrong - want).abs().max()) >= 100 * 1e-5
+    else:
+        assert datatype in (2, 256, 16, 64)
+    if datatype in (16, 64):
+        assert not np.array_equal(vals, np.rint(vals))              # fractional values
+    got = {}
+    for endian in (NATIVE, OTHER):
+        got[endian] = run([(stored(vals, datatype, endian), 1.0, 0.0, endian != NATIVE)], target, fill=-3.0)[0, 0]
+        assert_close(got[endian], want, 1e-5, "full range dtype %d %s" % (datatype, endian))
+    assert torch.equal(got[NATIVE], got[OTHER])
+    assert float(got[NATIVE].min()) >= 0.0 and float(got[NATIVE].max()) <= 1.0 + 1e-6
+
+
+def test_float64_elements_round_to_float32_at_the_load():
+    """The contract of csrc/ct_ingest.hip's header: a float64 element is rounded to the nearest fp32 at the load, as a host
+    astype(float32) rounds it.  So the yardstick here is the oracle of vals.astype(float32) -- NOT the oracle of the float64 values, which
+    is further than the tolerance away for 1000 + U[0, 1) (fp32 steps of 6e-5 on a range of 1): asserted below from the oracle alone"""
+    native, target = (5, 6, 7), (8, 8, 4)
+    vals = 1000.0 + np.random.default_rng(64).random(native)
+    assert vals.dtype == np.float64 and not np.array_equal(vals, vals.astype(np.float32))
+    want = torch.tensor(oracle("f8 rounded", vals.astype(np.float32), 1.0, 0.0, target))
+    unrounded = torch.tensor(oracle("f8 as stored", vals, 1.0, 0.0, target))
+    assert float((unrounded - want).abs().max()) > 1e-5
+    for endian in (NATIVE, OTHER):
+        got = run([(stored(vals, 64, endian), 1.0, 0.0, endian != NATIVE)], target, fill=-3.0)[0, 0]
+        assert_close(got, want, 1e-5, "float64 %s" % endian)
+
+
+@pytest.mark.parametrize("native,target", [((5, 6, 7), (8, 8, 4)), ((20, 45, 24), (32, 32, 16))])
+def test_stored_float32_low_contrast_on_an_offset(native, target):
+    """1000 + U[0, 1e-3): r - rmin is interpolated, so the error scales with the contrast and not with the offset"""
+    vals = NR.low_contrast_values("sub_ulp", native, seed=sum(native))
+    want = torch.tensor(oracle(("sub_ulp", native), vals, 1.0, 0.0, target))
+    for endian in (NATIVE, OTHER):
+        got = run([(stored(vals, 16, endian), 1.0, 0.0, endian != NATIVE)], target, fill=-3.0)[0, 0]
+        assert_close(got, want, 1e-5, "low contrast %s" % endian)
+        assert float(got.min()) >= 0.0 and float(got.max()) <= 1.0 + 1e-6
+
+
+# ---- scan size: pass 1 at its MMS_CT_RAW_PARTS cap, more than one sweep of the output loop of pass 2 ---------------------------------
+SCAN_NATIVE = (129, 127, 129)                # 2,113,407 int16 elements = 4.23 MB > 256 x 16 KiB; odd: a 7-element scalar tail
+SCAN_SWEEP = 256 * 256 * 8                   # int16 elements the capped grid of pass 1 reads in one sweep
+_SCAN = {}
+
+
+def scan_volume():
+    """shared, never modified: the only minimum where a second sweep of pass 1 reads it, the only maximum in the last element (the tail)"""
+    if not _SCAN:
+        v = NR.scan_values(SCAN_NATIVE, "i2", seed=11, min_at=SCAN_SWEEP + 300001)
+        assert v.size % 8 == 7 and v.nbytes > 256 * 16384 and int(v.argmin()) >= SCAN_SWEEP and int(v.argmax()) == v.size - 1
+        v.setflags(write=False)
+        _SCAN["v"] = v
+    return _SCAN["v"]
+
+
+@pytest.mark.parametrize("target", [(64, 64, 17), (64, 64, 32)])
+def test_scan_size_volume(target):
+    """(64, 64, 17) = 69,632 voxels: a ragged second sweep of the 256-workgroup output loop; (64, 64, 32): the production grid, two sweeps"""
+    from test_ingest_abi import _limit
+    assert _limit("MMS_CT_RAW_PARTS") == 256 and int(np.prod(target)) > 256 * 256
+    vals = scan_volume()
+    want = torch.tensor(oracle("scan", vals, 1.0, 0.0, target))
+    got = {}
+    for endian in (NATIVE, OTHER):
+        got[endian] = run([(stored(vals, 4, endian), 1.0, 0.0, endian != NATIVE)], target, fill=-3.0)[0, 0]
+        assert_close(got[endian], want, 1e-5, "scan %s->%s %s" % (SCAN_NATIVE, target, endian))
+        assert float(got[endian].min()) >= 0.0 and float(got[endian].max()) <= 1.0 + 1e-6
+    assert torch.equal(got[NATIVE], got[OTHER])
+
+
+def test_scan_size_volume_next_to_small_ones_in_one_launch():
+    """nb = 256 next to nb = 1 in one grid: the small volumes' workgroups b >= 1 of pass 1 return early.  Every row equals its own
+    single-volume launch bit for bit"""
+    target = (64, 64, 17)
+    small = [NR.ct_values((3, 5, 7), dt, seed=400 + dt) for dt in (4, 16)]
+    vols = [(stored(small[0], 4, OTHER), 1.0, 0.0, True), (stored(scan_volume(), 4, NATIVE), 1.0, 0.0, False),
+            (stored(small[1], 16, NATIVE), 1.0, 0.0, False)]
+    got = run(vols, target, n_rows=4, rows=[2, 0, 3], fill=-3.0)
+    assert torch.equal(got[1], torch.full_like(got[1], -3.0))
+    for vol, row in zip(vols, [2, 0, 3]):
+        assert torch.equal(got[row], run([vol], target, fill=-3.0)[0]), "row %d depends on its launch" % row
+    assert_close(got[0, 0], torch.tensor(oracle("scan", scan_volume(), 1.0, 0.0, target)), 1e-5, "scan volume in a mixed launch")
 
 
 MIX = [((3, 5, 7), 4, NATIVE, 1.0, 0.0), ((20, 45, 24), 512, OTHER, 1.0, -1024.0), ((5, 7, 1), 16, OTHER, 0.0, 0.0),

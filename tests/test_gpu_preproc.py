@@ -1,12 +1,59 @@
 """GPU preprocessing and the on-disk cohort contract against the reference's own library
-calls (scipy.ndimage.zoom order 1, sklearn StandardScaler)."""
+calls (scipy.ndimage.zoom order 1, sklearn StandardScaler).
+
+Yardstick: oracle.preproc on the float64 widening of the very values handed to the device, at 1e-5.
+
+mms_ct_preprocess (csrc/preproc.hip, the .npy route), beyond uniform random volumes of full HU range:
+  * constant volumes are zeros exactly; low contrast on a large offset ({1000, 1001}, 1000 + U[0, 1e-3), -1024 + {0..3}) meets the
+    oracle -- both fail when the kernel normalises AFTER interpolating, since in fp32 a (1 - f) + a f is not a;
+  * every output of this file lies in [0, 1 + 1e-6] (the bound of tests/test_gpu_ingest.py) with min == 0 on an identity grid;
+  * scan size: more elements than pass 1's capped grid takes in one sweep and more output voxels than pass 2's, with the extremes
+    where only a later sweep or the tail sees them; a unit axis in the target;
+  * a float32 volume gives the same bits through cohort_io.ct_preprocess and through cohort_io.ct_preprocess_batch (stored as
+    datatype 16): both kernels inline csrc/ct_resample.h;
+  * load_cohort on a constant .npy: mask 1 and an all-zero image, as the reference's __getitem__ gives;
+  * null pointers and non-positive extents are MMS_ERR_ARG and write nothing.
+mms_rna_log_zscore, per GENE (a whole-matrix bound hides a gene of small sd behind the largest z of the matrix): constant genes,
+near-constant genes on a large count, a well-expressed stable gene, full-range counts, n = 1 ... 600 samples, g on either side of the
+64-gene workgroup; sklearn's own constant-feature decision is checked against the kernel's rule on the inputs."""
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+import nifti_ref as NR
 from gpu_util import DEV, assert_close
+
+SENTINEL = -7.25
+LOW_CONTRAST = ["two_level", "sub_ulp", "four_level"]
+LOW_SHAPES = [((5, 6, 7), (8, 8, 4)), ((20, 45, 24), (32, 32, 16))]
+
+
+def assert_unit_range(got, identity=False):
+    """min >= 0 exactly (x - min >= 0 is interpolated with weights in [0, 1]); an interpolated value may round an ulp above 1"""
+    lo, hi = float(got.min()), float(got.max())
+    assert lo >= 0.0 and hi <= 1.0 + 1e-6, "range [%r, %r]" % (lo, hi)
+    if identity:
+        assert lo == 0.0
+
+
+def ct(vol, target):
+    """vol: float32 ndarray -> cohort_io.ct_preprocess into a store prefilled with a sentinel (CPU tensor)"""
+    from multimodal_survival_prediction_amd import cohort_io
+    assert vol.dtype == np.float32
+    out = torch.full(tuple(target), SENTINEL, device=DEV)
+    got = cohort_io.ct_preprocess(torch.tensor(vol, device=DEV), target, out=out)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out.data_ptr()
+    return got.cpu()
+
+
+def ct_oracle(vol, target):
+    from oracle import preproc as OP
+    want = OP.ct_preprocess(vol.astype(np.float64), target)
+    assert want.shape == tuple(target)
+    return torch.tensor(want)
 
 
 @pytest.mark.parametrize("native,target", [((40, 50, 23), (64, 64, 32)), ((128, 96, 70), (64, 64, 32)), ((64, 64, 32), (64, 64, 32)),
@@ -21,6 +68,105 @@ def test_ct_preprocess_matches_scipy_zoom(native, target):
     got = cohort_io.ct_preprocess(torch.tensor(vol, device=DEV), target)
     torch.cuda.synchronize()
     assert_close(got, torch.tensor(want), 1e-5, "ct preprocess")
+    assert_unit_range(got, identity=native == target)
+
+
+@pytest.mark.parametrize("native,value", [((5, 6, 7), -900.0), ((5, 6, 7), 100.0), ((5, 6, 7), 0.0), ((1, 1, 1), -900.0)])
+def test_constant_volume_is_exactly_zero(native, value):
+    """max == min: the reference divides 0 by 1e-8.  tests/test_gpu_ingest.py pins the same for the NIfTI route"""
+    got = ct(np.full(native, value, np.float32), (8, 8, 4))
+    assert torch.equal(got, torch.zeros(8, 8, 4)), "range [%r, %r]" % (float(got.min()), float(got.max()))
+
+
+@pytest.mark.parametrize("native,target", LOW_SHAPES)
+@pytest.mark.parametrize("kind", LOW_CONTRAST)
+def test_low_contrast_on_an_offset(kind, native, target):
+    vol = NR.low_contrast_values(kind, native, seed=sum(native))
+    assert float(vol.max()) > float(vol.min())
+    got = ct(vol, target)
+    assert_close(got, ct_oracle(vol, target), 1e-5, "%s %s->%s" % (kind, native, target))
+    assert_unit_range(got)
+
+
+# pass 1 runs at most 256 workgroups of 256 lanes x 16 elements, pass 2 at most 2048 workgroups x 256 voxels a sweep
+SCAN_NATIVE = (70, 128, 128)
+
+
+@pytest.mark.parametrize("target", [(128, 128, 33), (128, 128, 64)])
+def test_scan_size_takes_further_sweeps_in_both_passes(target):
+    """1,146,880 elements > 256 x 4096: every workgroup of pass 1 sweeps more than once; 540,672 output voxels > 2048 x 256: a ragged
+    second sweep of the output loop ((128, 128, 64) = 2 full sweeps, config 4's grid).  The minimum lies where only a second sweep of
+    pass 1 reads it, the maximum in the last element"""
+    n = int(np.prod(SCAN_NATIVE))
+    assert n > 256 * 4096 and int(np.prod(target)) > 2048 * 256
+    vol = NR.scan_values(SCAN_NATIVE, "f4", seed=7, min_at=256 * 4096 + 51427)
+    assert int(vol.argmin()) >= 256 * 4096 and int(vol.argmax()) == n - 1
+    got = ct(vol, target)
+    assert_close(got, ct_oracle(vol, target), 1e-5, "scan %s->%s" % (SCAN_NATIVE, target))
+    assert_unit_range(got)
+
+
+def test_unit_axis_in_the_target():
+    """out == 1 along an axis: scipy takes input coordinate 0 there"""
+    vol = NR.ct_values((9, 6, 5), 16, seed=3)
+    got = ct(vol, (1, 8, 4))
+    assert_close(got, ct_oracle(vol, (1, 8, 4)), 1e-5, "unit axis")
+    assert_unit_range(got)
+
+
+def _both_route_volumes():
+    yield "uniform", (20, 45, 24), (32, 32, 16), (np.random.default_rng(89).random((20, 45, 24), dtype=np.float32) * 2500 - 900).astype(np.float32)
+    for kind in LOW_CONTRAST:
+        for native, target in LOW_SHAPES:
+            yield kind, native, target, NR.low_contrast_values(kind, native, seed=sum(native))
+
+
+def test_both_routes_share_one_arithmetic():
+    """the same float32 volume as a device tensor (mms_ct_preprocess) and as stored float32 elements, native byte order, slope 1
+    (mms_ct_preprocess_raw_batch): bit for bit"""
+    from multimodal_survival_prediction_amd import cohort_io
+    for kind, native, target, vol in _both_route_volumes():
+        one = ct(vol, target)
+        store = torch.full((1, 1) + tuple(target), SENTINEL, device=DEV)
+        cohort_io.ct_preprocess_batch([(vol, 1.0, 0.0, False)], target, store, [0])
+        torch.cuda.synchronize()
+        assert torch.equal(one, store[0, 0].cpu()), "%s %s->%s: max difference %g" % (
+            kind, native, target, float((one - store[0, 0].cpu()).abs().max()))
+
+
+def test_ct_and_rna_refuse_bad_arguments_and_write_nothing():
+    from multimodal_survival_prediction_amd import _lib, ops
+    lib = _lib.load_library()
+    x = torch.ones(3, 5, 7, device=DEV)
+    out = torch.full((8, 8, 4), SENTINEL, device=DEV)
+    scratch = torch.empty(512, device=DEV)
+
+    def ct_call(x=x.data_ptr(), out=out.data_ptr(), scratch=scratch.data_ptr(), i=(3, 5, 7), o=(8, 8, 4)):
+        return lib.mms_ct_preprocess(x, i[0], i[1], i[2], out, o[0], o[1], o[2], scratch, ops.stream())
+
+    bad = dict(no_x=ct_call(x=None), no_out=ct_call(out=None), no_scratch=ct_call(scratch=None))
+    for axis in range(3):
+        for v in (0, -1):
+            ext = [3, 5, 7]; ext[axis] = v
+            bad["in%d=%d" % (axis, v)] = ct_call(i=tuple(ext))
+            ext = [8, 8, 4]; ext[axis] = v
+            bad["out%d=%d" % (axis, v)] = ct_call(o=tuple(ext))
+    counts = torch.ones(5, 8, device=DEV)
+    zs = torch.full((5, 8), SENTINEL, device=DEV)
+
+    def rna_call(c=counts.data_ptr(), z=zs.data_ptr(), n=5, g=8):
+        return lib.mms_rna_log_zscore(c, z, n, g, ops.stream())
+
+    bad.update(no_counts=rna_call(c=None), no_z=rna_call(z=None), n0=rna_call(n=0), n_neg=rna_call(n=-1), g0=rna_call(g=0),
+               g_neg=rna_call(g=-1))
+    torch.cuda.synchronize()
+    assert len(bad) == 21
+    for what, rc in bad.items():
+        assert rc == -1, what                                # MMS_ERR_ARG
+    assert torch.equal(out, torch.full_like(out, SENTINEL)) and torch.equal(zs, torch.full_like(zs, SENTINEL))
+    assert ct_call() == 0 and rna_call() == 0                # the same calls with nothing wrong go through
+    torch.cuda.synchronize()
+    assert float(out.min()) == 0.0 and float(zs.abs().max()) == 0.0
 
 
 def test_rna_log_zscore_matches_sklearn():
@@ -34,6 +180,57 @@ def test_rna_log_zscore_matches_sklearn():
     torch.cuda.synchronize()
     assert_close(got, torch.tensor(want), 1e-5, "rna log2 + zscore")
     assert float(got[:, 5].abs().max()) == 0.0
+
+
+RNA_SPECIAL = ["const 6", "const 1e6", "const 0", "1e6, one sample 1e6 + 1", "65535, last sample 65536", "stable [99000, 101000)",
+               "full range [0, 2^24)"]
+
+
+def rna_counts(n, g, seed):
+    """(n, g) float32 counts: Poisson genes, then -- as the LAST columns, so that at g = 65 they straddle two workgroups -- the genes of
+    RNA_SPECIAL; g < 7 keeps the first g of those alone.  -> (counts, names by column)"""
+    rng = np.random.default_rng(seed)
+    sp = np.empty((n, 7), np.float64)
+    sp[:, 0], sp[:, 1], sp[:, 2] = 6.0, 1e6, 0.0
+    sp[:, 3] = 1e6; sp[n // 2, 3] = 1e6 + 1
+    sp[:, 4] = 65535.0; sp[-1, 4] = 65536.0
+    sp[:, 5] = rng.integers(99000, 101000, size=n)
+    sp[:, 6] = rng.integers(0, 2 ** 24, size=n)
+    if g < 7:
+        return sp[:, :g].astype(np.float32), RNA_SPECIAL[:g]
+    po = rng.poisson(rng.gamma(2.0, 50.0, size=(1, g - 7)), size=(n, g - 7))
+    return np.concatenate([po, sp], axis=1).astype(np.float32), ["poisson %d" % j for j in range(g - 7)] + RNA_SPECIAL
+
+
+@pytest.mark.parametrize("g", [1, 63, 64, 65, 300])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 97, 600])
+def test_rna_log_zscore_per_gene(n, g):
+    """every gene on its own scale: |got - want| <= 1e-5 max(1, |want|) per column.  The kernel's error is one fp32 rounding of an fp64
+    quotient, so the file's 1e-5 holds per gene too"""
+    from sklearn.preprocessing import StandardScaler
+    from oracle import preproc as OP
+    from multimodal_survival_prediction_amd import cohort_io
+    counts, names = rna_counts(n, g, seed=1000 * n + g)
+    assert counts.shape == (n, g) and np.array_equal(counts, np.rint(counts))           # fp32 holds every count exactly
+    want = OP.rna_log_zscore(counts)
+    # conditions on the inputs, from the reference side alone: sklearn's constant-feature decision is the kernel's sd < 1e-12 rule
+    logs = np.log2(counts.astype(np.float64) + 1)
+    sd = np.sqrt(((logs - logs.mean(axis=0)) ** 2).mean(axis=0))
+    fit = StandardScaler().fit(logs)
+    for j in range(g):                                   # (scale_ == 1 where sklearn replaced sqrt(var_); a gene's sd may also BE 1)
+        replaced = fit.scale_[j] == 1.0 and np.sqrt(fit.var_[j]) != 1.0
+        assert replaced == (sd[j] < 1e-12), "%s: sklearn scale_ %r var_ %r, two-pass sd %r" % (names[j], fit.scale_[j], fit.var_[j], sd[j])
+    assert not np.isnan(want).any()
+    got = cohort_io.rna_log_zscore(torch.tensor(counts, device=DEV))
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    assert not np.isnan(got).any()
+    err = np.abs(got.astype(np.float64) - want.astype(np.float64)).max(axis=0)
+    bound = 1e-5 * np.maximum(1.0, np.abs(want).max(axis=0))
+    worst = int(np.argmax(err / bound))
+    print("n %d g %d: worst gene %r err %.3e bound %.3e" % (n, g, names[worst], err[worst], bound[worst]))
+    bad = ["%s: err %.3e > %.3e" % (names[j], err[j], bound[j]) for j in range(g) if not err[j] <= bound[j]]
+    assert not bad, "; ".join(bad)
 
 
 def test_cohort_roundtrip_through_disk(tmp_path):
@@ -51,6 +248,9 @@ def test_cohort_roundtrip_through_disk(tmp_path):
     assert_close(got["rnaseq"], c["rnaseq"], 1e-6, "rnaseq"); assert_close(got["clinical"], c["clinical"], 1e-6, "clinical")
     assert_close(got["label"], c["label"], 1e-6, "label")
     assert_close(got["image"], c["image"], 2e-5, "image (stored at the network grid: min-max undoes the HU-like scaling)")
+    for i in range(14):
+        if float(c["mask"][i, 0]):
+            assert_unit_range(got["image"][i], identity=True)
     # stored at another resolution: the loader must equal scipy.zoom of what is on disk
     cohort_io.write_cohort(str(tmp_path / "b"), c, native_dims=(20, 45, 24), seed=3)
     got = cohort_io.load_cohort(str(tmp_path / "b"), DEV, target_size=dims)
@@ -59,5 +259,29 @@ def test_cohort_roundtrip_through_disk(tmp_path):
         if isinstance(p, str):
             want = OP.ct_preprocess(np.load(p).astype(np.float64), dims)
             assert_close(got["image"][i, 0], torch.tensor(want), 1e-5, "image %d" % i)
+            assert_unit_range(got["image"][i])
         else:
             assert float(got["image"][i].abs().max()) == 0.0
+
+
+def test_load_cohort_constant_npy_volume(tmp_path):
+    """a constant scan that exists and loads is a present modality: mask 1 and an all-zero image ((x - min) / 1e-8 = 0, what the
+    reference's __getitem__ makes of it); every other patient keeps its bits"""
+    from multimodal_survival_prediction_amd import cohort_io, data
+    dims = (32, 32, 16)
+    c = data.make_cohort(n=14, dims=dims, rna_dim=40, seed=9, complete=False, counts=dict(n=14, imaging=9, rnaseq=10, clinical=12, survival=8))
+    cohort_io.write_cohort(str(tmp_path), c, native_dims=(20, 45, 24), seed=3)
+    before = cohort_io.load_cohort(str(tmp_path), DEV, target_size=dims)
+    mt, _ = cohort_io.read_tables(str(tmp_path))
+    have = [i for i, p in enumerate(mt["nifti_path"]) if isinstance(p, str)]
+    victim = have[4]
+    assert float(before["image"][victim].abs().max()) > 0
+    np.save(mt["nifti_path"][victim], np.full((20, 45, 24), -900.0, np.float32))
+    after = cohort_io.load_cohort(str(tmp_path), DEV, target_size=dims)
+    torch.cuda.synchronize()
+    assert float(after["mask"][victim, 0]) == 1.0
+    assert torch.equal(after["image"][victim], torch.zeros_like(after["image"][victim]))
+    keep = [i for i in range(14) if i != victim]
+    assert torch.equal(after["image"][keep], before["image"][keep]) and torch.equal(after["mask"], before["mask"])
+    for k in ("rnaseq", "clinical", "label", "has_survival"):
+        assert torch.equal(after[k], before[k]), k
