@@ -1033,6 +1033,43 @@ typedef struct GbmPredictP {
     double* out;                        // [P][K][R]
 } GbmPredictP;
 
+/* Path-dependent TreeSHAP (Lundberg et al. 2018/2020, Algorithm 2's value function) of heap-indexed tree tables: which features pushed
+ * a row's prediction up or down, and by how much (csrc/tree_shap.hip; tree_shap.py, Booster.shap, Forest.shap; tests/tree_shap_ref.py
+ * restates all of this in numpy).  The tables are the boosters' and the forest's: feat (< 0: a leaf or absent), thr, a leaf value and
+ * the cover (n_node), [T][nn]; a row goes LEFT at split node s iff x[feat[s]] <= thr[s]; a node is a leaf iff feat < 0 or
+ * 2s + 2 >= nn (mms_gbm_predict's rule).
+ *
+ * A tree, and a leaf l reached from the root by the edges e_1 .. e_d; edge k leaves split node s_k for child c_k and carries the
+ * feature f_k = feat[s_k], the zero fraction z_k = cover[c_k] / cover[s_k] (fp64) and the one indicator o_k = [the row goes to c_k at
+ * s_k] = ((x[f_k] <= thr[s_k]) == (c_k is the left child)).  Edges of a path that share a feature merge: z is the product in path
+ * order, o the conjunction; that leaves u <= d unique features (z_j, o_j) in order of first occurrence.  With v the leaf's value:
+ *     base  += v prod_k z_k                                  (v alone when the root is the leaf)
+ *     phi_j += v (o_j - z_j) sum_{k=0}^{u-1} w_k e_k^(j),    w_k = k! (u - k - 1)! / u!,
+ *              e_k^(j) = the coefficient of t^k in prod_{m != j} (z_m + o_m t)
+ * A group's result is the SUM over its trees goff[g] .. goff[g+1) in table order, leaves depth-first and left-first, a leaf's
+ * features in order of first occurrence; with `use` a row skips the trees that do not admit it (use[t][row] == 0).  Local accuracy:
+ * base + sum_j phi_j = the sum of the leaf values the row reaches.  The only division is cover[c] / cover[s] at split nodes: the
+ * CALLER guarantees cover[2s+1] + cover[2s+2] == cover[s] with both children > 0 there, feat < p and slot in [0, U)
+ * (ops.tree_shap checks all of it on the host).
+ *
+ * mms_tree_shap, one launch: workgroup = (group, 64 rows), lane = row; phi [G][U][ldr] is SLOT-major (slot[t][s] = the output column
+ * of feat[t][s]).  The launch writes every element of phi[g][0..U)[0..R) and base[g][0..R) itself (zeros where nothing contributes)
+ * and nothing at columns >= R.  No atomics, no workgroup waits for another; a group's bits depend only on its own trees and rows.
+ * The kernel is instantiated on the depth bound (6 when nn <= 127, else MMS_SHAP_MAX_DEPTH).  A NULL required pointer, R < 0,
+ * ldx < p, p < 1, T < 0, G < 0, U < 1, nn outside 1..2^(MMS_SHAP_MAX_DEPTH + 1) - 1, ldr < R, ldu < R with use, ceil(R / 64) G >= 2^31
+ * or a pointer not aligned to its element: MMS_ERR_ARG before any launch.  R = 0 or G = 0: MMS_OK without a launch. */
+#define MMS_SHAP_MAX_DEPTH 12          /* = MMS_RSF_MAX_DEPTH >= MMS_GBM_MAX_DEPTH */
+typedef struct TreeShapP {
+    int R; int ldx; int p; int T; int nn; int G; int U; int ldr; int ldu; int pad_;
+    const float* x;                     // [R][ldx] raw rows
+    const int* feat; const float* thr; const double* value; const int* cover;   // [T][nn]
+    const int* goff;                    // [G + 1] ascending: group g owns trees goff[g] .. goff[g+1)
+    const int* slot;                    // [T][nn] output column (0 .. U-1) of feat at split nodes
+    const unsigned char* use;           // [T][ldu] or NULL: tree t admits row r
+    double* phi;                        // [G][U][ldr] out, SLOT-major
+    double* base;                       // [G][ldr] out
+} TreeShapP;
+
 /* clip_grad_norm_(max_norm) + Adam/AdamW over one flat fp32 parameter buffer (R/...final_multimodal.py:259-260,350;
  * simple_fusion.py:273-274,391).  hyper (device): {lr, beta1, beta2, eps, weight_decay, max_norm}; state (device):
  * {step (as float), sumsq scratch (double as 2 floats)}; skip: optional device flag, 0 => no-op (degenerate batch). */
@@ -1403,6 +1440,7 @@ int mms_gbm_grad(const GbmGradP* p, hipStream_t s);           /* gradient-booste
 int mms_gbm_split(const GbmSplitP* p, hipStream_t s);         /* ... one level: histograms, cuts, fixed-order argmax, routing */
 int mms_gbm_update(const GbmUpdateP* p, hipStream_t s);       /* ... leaf values, F, evaluation pair counts */
 int mms_gbm_predict(const GbmPredictP* p, hipStream_t s);     /* ... F of raw rows after each of K round counts */
+int mms_tree_shap(const TreeShapP* p, hipStream_t s);         /* path-dependent TreeSHAP of tree tables, G groups of trees in one launch */
 int mms_gsea_scores(const GseaScoreP* p, hipStream_t s);      /* gene-set enrichment: permutation Z of G genes x R1 relabellings (GseaScoreP above) */
 int mms_gsea_es(const GseaEsP* p, hipStream_t s);             /* ... enrichment score of S sets in R1 replicates (GseaEsP above) */
 int mms_coxnet_eval(const CoxnetP* p, hipStream_t s);       /* elastic-net Cox: eta, residual, loss and gradient of P problems at beta (CoxnetP above) */

@@ -117,6 +117,27 @@ class Booster:
         ok = feat >= 0
         return (np.bincount(feat[ok], minlength=self.p).astype(np.int64), np.bincount(feat[ok], weights=gain[ok], minlength=self.p))
 
+    def shap(self, x, problems=None, rounds=None, timings=None):
+        """Path-dependent TreeSHAP of the listed problems (an index sequence, None = all) after their first `rounds` rounds (None: all;
+        an int, or one round count per listed problem -- nested_cv's chosen counts differ per fold) for the RAW rows x: fp32 [R, p]
+        device.  The trees are gathered into contiguous [T, nn] tables, one group per problem; the cover is n_node, the round's sample.
+        -> tree_shap.ShapValues with one group per listed problem: base[g] + phi[g].sum(1) == predict(x, rounds)[problem] to rounding,
+        and exp(phi) is a gene's hazard-ratio multiplier for that patient.  timings: receives ("launch", milliseconds)."""
+        import torch
+        from . import tree_shap
+        P, M = self.n_problems, self.rounds
+        probs = np.arange(P, dtype=np.int64) if problems is None else np.asarray(problems, np.int64).reshape(-1)
+        rds = _per_problem(M if rounds is None else rounds, len(probs), np.int64, "rounds") if len(probs) else np.zeros(0, np.int64)
+        if len(probs) and (probs.min() < 0 or probs.max() >= P or rds.min() < 0 or rds.max() > M):
+            raise ValueError("problems must lie in 0..%d and rounds in 0..%d" % (P - 1, M))
+        goff = np.concatenate([[0], np.cumsum(rds)])
+        dev = self.tables["feat"].device
+        pi = torch.from_numpy(np.repeat(probs, rds)).to(dev)
+        ri = torch.from_numpy(np.concatenate([np.arange(r) for r in rds]).astype(np.int64) if len(rds) else np.zeros(0, np.int64)).to(dev)
+        tab = [self.tables[k][pi, ri].contiguous() for k in ("feat", "thr", "value", "n_node")]
+        phi, base, genes = tree_shap.launch(x, *tab, goff, timings=timings)
+        return tree_shap.from_launch(phi, base, genes)
+
     def save(self, path):
         keys = sorted(self.hyper)
         np.savez(path, **{k: to_numpy(self.tables[k]) for k in TABLES}, edges=to_numpy(self.edges), p=np.int64(self.p),
@@ -247,7 +268,7 @@ def default_grid(learning_rate=(0.1,), max_depth=(2,)):
 
 
 def nested_cv(cohort, folds, inner=5, rounds=300, grid=None, seed=0, *, min_leaf=10, l2=1.0, min_gain=0.0, subsample=1.0, colsample=1.0,
-              bins=32, x=None, timings=None):
+              bins=32, x=None, timings=None, shap=False):
     """Nested cross-validation of the boosted Cox trees: all K (J + 1) |grid| problems in ONE fit (one fit per outer fold when the cohort
     carries per-fold gene matrices, gene_select.fold_matrix: one matrix per call; the problems keep their ids).  grid: a list of dicts
     overriding learning_rate / max_depth / min_leaf / l2 / min_gain / subsample / colsample (None: one point, the defaults).  Problem
@@ -257,7 +278,8 @@ def nested_cv(cohort, folds, inner=5, rounds=300, grid=None, seed=0, *, min_leaf
     the validation fold is recorded (outer_curve) and never consulted.
     -> list per fold of dict(fold, grid_index, grid_point, rounds, c_index, inner [G, J, M], inner_mean [G, M], outer_curve [G, M],
     val_rows, val_F, train_rows, train_F, importance = (counts, gain sums) of the chosen booster's first `rounds` rounds, n_train, n_val,
-    booster, problem)."""
+    booster, problem).  shap=True adds `shap`: the TreeSHAP values (Booster.shap -> tree_shap.ShapValues, one group) of the chosen booster
+    at the chosen round count on that fold's VALIDATION rows only, in val_rows' order: out-of-fold, so honest."""
     import torch
     from . import coxnet, gene_select
     from .survival_stats import concordance_index
@@ -297,4 +319,6 @@ def nested_cv(cohort, folds, inner=5, rounds=300, grid=None, seed=0, *, min_leaf
             results[f] = dict(fold=f, grid_index=g, grid_point=pts[g], rounds=r, c_index=c, inner=inner_c, inner_mean=mean,
                               outer_curve=cidx[i, J], val_rows=plan[f]["val"], val_F=Fp[va], train_rows=plan[f]["train"], train_F=Fp[tr],
                               importance=bst.importance([prob], r), n_train=int(len(tr)), n_val=int(len(va)), booster=bst, problem=prob)
+            if shap:
+                results[f]["shap"] = bst.shap(xe[torch.as_tensor(va, device=xe.device)].contiguous(), problems=[prob], rounds=r)
     return results

@@ -918,6 +918,64 @@ def gbm_predict(x, feat, thr, value, at, plan_only=False):
     return _launch_or_plan("mms_gbm_predict", p, (x, feat, thr, value, at_d, out), out, plan_only)
 
 
+def tree_shap(x, feat, thr, value, cover, goff, slot, U, use=None, plan_only=False, out=None):
+    """Path-dependent TreeSHAP of G groups of trees for R raw rows (TreeShapP in mmsurv.h).  x fp32 [R, p] device (row pitch
+    x.stride(0)); feat int32, thr fp32, value float64, cover int32, slot int32 [T, nn] device; goff: G + 1 ascending tree offsets from 0
+    to T (host sequence); U >= 1 output columns; use uint8 [T, R] device (row pitch use.stride(0)) or None (every tree admits every
+    row).  What the launch cannot check is checked HERE: feat < p, slot in [0, U) and the cover rule (tree_shap.check_tables: at every
+    split node the children's covers are > 0 and sum to the node's).  out = (phi float64 [G, U, ldr], base float64 [G, ldr]) device
+    tensors to write into (ldr >= R; columns >= R are left alone), None: fresh ones with ldr = R.
+    -> (phi [G, U, R], base [G, R]) float64 device tensors, SLOT-major: phi[g][slot][row]."""
+    import numpy as np
+    from . import tree_shap as _ts
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise TypeError("x must be a float32 [R, p] device tensor with unit column stride")
+    _rsf_dev(feat, torch.int32, "feat", 2); _rsf_dev(thr, torch.float32, "thr", 2); _rsf_dev(value, torch.float64, "value", 2)
+    _rsf_dev(cover, torch.int32, "cover", 2); _rsf_dev(slot, torch.int32, "slot", 2)
+    R, p_ = x.shape
+    T, nn = feat.shape
+    U = int(U)
+    goff = np.asarray(goff, np.int64).reshape(-1)
+    G = len(goff) - 1
+    lim = _lib.defines("MMS_SHAP_")
+    if any(tuple(t.shape) != (T, nn) for t in (thr, value, cover, slot)) or not (1 <= nn <= (2 << lim["MAX_DEPTH"]) - 1):
+        raise ValueError("thr, value, cover and slot must match feat [T, nn], nn in 1..%d" % ((2 << lim["MAX_DEPTH"]) - 1))
+    if G < 0 or p_ < 1 or U < 1 or (G >= 0 and len(goff) and (goff[0] != 0 or goff[-1] != T or (np.diff(goff) < 0).any())):
+        raise ValueError("goff must ascend from 0 to T = %d, U >= 1 and x have a column" % T)
+    if T:
+        if int(feat.max()) >= p_:
+            raise ValueError("a tree splits on feature %d; x has %d columns" % (int(feat.max()), p_))
+        split = _ts.split_nodes(feat)
+        sl = slot[:, :split.shape[1]][split]
+        if sl.numel() and (int(sl.min()) < 0 or int(sl.max()) >= U):
+            raise ValueError("slot must lie in [0, U) at every split node")
+        _ts.check_tables(feat, cover)
+    ldu = 0
+    if use is not None:
+        if not torch.is_tensor(use) or not use.is_cuda or use.dtype != torch.uint8 or use.dim() != 2 or tuple(use.shape) != (T, R) \
+                or (R > 1 and use.stride(1) != 1) or (T > 1 and use.stride(0) < R):
+            raise TypeError("use must be a uint8 [T, R] device tensor with unit column stride")
+        ldu = max(int(use.stride(0)), R) if T > 1 else R
+    dev = x.device
+    if out is None:
+        phi, base = torch.empty(max(G, 1), U, max(R, 1), dtype=torch.float64, device=dev), torch.empty(max(G, 1), max(R, 1), dtype=torch.float64, device=dev)
+    else:
+        phi, base = out
+        _rsf_dev(phi, torch.float64, "phi", 3); _rsf_dev(base, torch.float64, "base", 2)
+        if phi.shape[0] != max(G, 1) or phi.shape[1] != U or base.shape[0] != max(G, 1) or phi.shape[2] != base.shape[1] or base.shape[1] < max(R, 1):
+            raise ValueError("out must be (phi [G, U, ldr], base [G, ldr]) with ldr >= R")
+    ldr = int(base.shape[1])
+    res = (phi[:G, :, :R], base[:G, :R])
+    if T == 0:                                                      # groups without a tree: zeros, and nothing to launch
+        res[0].zero_(); res[1].zero_()
+    if G == 0 or R == 0 or T == 0:
+        return ((None, ()) + res) if plan_only else res
+    goff_d = _upload(goff, "int32", dev)
+    p = _S()["TreeShapP"](R, max(x.stride(0), p_), p_, T, nn, G, U, ldr, ldu, 0, ptr(x), ptr(feat), ptr(thr), ptr(value), ptr(cover), ptr(goff_d),
+                          ptr(slot), ptr(use), ptr(phi), ptr(base))
+    return _launch_or_plan("mms_tree_shap", p, (x, feat, thr, value, cover, goff_d, slot, use, phi, base), res, plan_only)
+
+
 def td_metrics(trank, event, hcut, rord, surv, w, plan_only=False):
     """IPCW Brier / dynamic AUC sums of M models at H horizons under R multiplicity rows (TdMetricsP in mmsurv.h).  trank, event: [n] dense
     time ranks and event flags of the TIME-ASCENDING positions (events before censorings at equal times), hcut: [H] positions with

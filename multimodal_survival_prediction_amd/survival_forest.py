@@ -250,6 +250,41 @@ class Forest:
             out.update(D=got["D"][:P], M=got["M"][:P])
         return out
 
+    def shap(self, x, use=None, sets=None, trees=None, timings=None):
+        """Path-dependent TreeSHAP of the ensemble mortality for the rows x: fp32 [R, p] device.  use: [T, R] mask as in predict (None:
+        every tree); sets: [T] the set (fold) of each tree, None = one set: one group per set 0..max, over ITS trees; trees: an index
+        array of the trees that take part (None = all, as in importance; use and sets stay indexed by the forest's trees).  A
+        contiguous run of trees is read in place, anything else is gathered.  The kernel's sums are divided by the admitted-tree
+        count (the set's tree count, or use.sum(0) over its trees); NaN where that is 0, as in predict.
+        -> tree_shap.ShapValues with one group per set: base[g] + phi[g].sum(1) == predict(x, use)["mortality"] to rounding when the
+        set holds all trees.  timings: receives ("launch", milliseconds)."""
+        import torch
+        from . import tree_shap
+        T, R, dev = self.n_trees, int(x.shape[0]), x.device
+        sets = np.zeros(T, np.int64) if sets is None else np.asarray(to_numpy(sets), np.int64).reshape(-1)
+        idx = np.arange(T) if trees is None else np.asarray(trees, np.int64).reshape(-1)
+        if len(sets) != T or (T and sets.min() < 0) or (len(idx) and (idx.min() < 0 or idx.max() >= T)):
+            raise ValueError("sets must name one set >= 0 per tree and trees lie in 0..%d" % (T - 1))
+        G = int(sets[idx].max()) + 1 if len(idx) else 1
+        order = idx[np.argsort(sets[idx], kind="stable")]
+        goff = np.concatenate([[0], np.cumsum(np.bincount(sets[idx], minlength=G))])
+        if len(order) and (order == np.arange(order[0], order[0] + len(order))).all():
+            take = slice(int(order[0]), int(order[0]) + len(order))                     # a view: nothing is copied or uploaded
+        else:
+            take = torch.from_numpy(order).to(dev)
+        tab = [t[take].contiguous() for t in (self.feat, self.thr, self.mort, self.n_node)]
+        if use is not None:
+            use = torch.as_tensor(np.ascontiguousarray(to_numpy(use)).astype(np.uint8) if not torch.is_tensor(use) else use)
+            use = (use.to(dev) != 0).to(torch.uint8)
+            if tuple(use.shape) != (T, R):
+                raise ValueError("use must be [T, R]")
+            use = use[take].contiguous()
+            count = torch.stack([use[goff[g]:goff[g + 1]].sum(0, dtype=torch.int64) for g in range(G)]).cpu().numpy()
+        else:
+            count = np.repeat(np.diff(goff)[:, None], R, axis=1)
+        phi, base, genes = tree_shap.launch(x, *tab, goff, use=use, timings=timings)
+        return tree_shap.from_launch(phi, base, genes, count=count)
+
     def save(self, path):
         np.savez(path, **{k: to_numpy(getattr(self, k)) for k in ("feat", "thr", "stat", "n_node", "d_node", "mort", "H")},
                  horizons=np.asarray(self.horizons, np.float64), p=np.int64(self.p),
@@ -363,14 +398,16 @@ def default_horizons(time, event, k=3):
     return np.unique(np.quantile(t, np.arange(1, k + 1) / (k + 1.0))) if len(t) else np.zeros(0)      # (ties may merge two)
 
 
-def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf=15, max_depth=10, seed=0, horizons=None, x=None, vimp=0):
+def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf=15, max_depth=10, seed=0, horizons=None, x=None, vimp=0, shap=False):
     """K-fold cross-validation of the forest: all K * n_trees trees grow in ONE launch sequence (one per fold when the cohort carries
     per-fold gene matrices, gene_select.fold_matrix; the trees keep their forest-wide hash streams).  Rows: coxnet.risk_rows(cohort),
     the eligible patients.  Higher mortality = higher risk: C = survival_stats.concordance_index(time, -mortality, event).
     -> list per fold of dict(fold, c_index, oob_c_index, oob_missing (training rows no tree left out), val_rows, val_mortality,
     val_survival [n_val, nh], horizons, importance = (counts, chi2 sums) of the fold's trees, n_train, n_val, forest, trees).
     vimp = R > 0 adds the out-of-bag permutation importance of every fold over its own trees (Forest.vimp, R repeats; one launch for all
-    folds, one per fold with per-fold matrices): vimp float64 [p] and vimp_reps [R, p]."""
+    folds, one per fold with per-fold matrices): vimp float64 [p] and vimp_reps [R, p].
+    shap=True adds `shap`: the TreeSHAP values (Forest.shap -> tree_shap.ShapValues, one group) of the fold's own trees on that fold's
+    VALIDATION rows only (Forest.shap(trees=the fold's)), in val_rows' order: out-of-fold, so honest; one launch per fold."""
     import torch
     from . import coxnet, gene_select
     from .survival_stats import concordance_index
@@ -412,4 +449,6 @@ def cross_validate(cohort, folds, n_trees=500, *, mtry=None, nsplit=10, min_leaf
                               n_train=int(len(tr)), n_val=int(len(va)), forest=forest, trees=np.arange(i * T, (i + 1) * T))
             if vi is not None:
                 results[f].update(vimp=vi["vimp"][i], vimp_reps=vi["vimp_reps"][i])
+            if shap:
+                results[f]["shap"] = forest.shap(xe[torch.as_tensor(va, device=xe.device)].contiguous(), trees=np.arange(i * T, (i + 1) * T))
     return results

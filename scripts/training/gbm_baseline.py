@@ -18,7 +18,12 @@ evaluate_model.py --bootstrap --compare reads), fold_{k}_survival_curves.csv (th
 absolute_risk.breslow_baseline on the training patients' F: --compare-curves joins it), fold_{k}_importance.csv (index, column, gene,
 splits, gain_sum of the chosen booster's chosen rounds: gene_set_enrichment.py --scores ... --score-column gain_sum reads it) and
 fold_{k}_curves.csv (per grid point and round count: every inner fold's C-index, their mean, and the validation fold's own C-index,
-which is recorded and never consulted)."""
+which is recorded and never consulted).
+MMS_GBM_SHAP=1 (default 0: nothing more is computed or written) adds the TreeSHAP values (Booster.shap) of every fold's chosen booster at
+its chosen round count on that fold's VALIDATION patients: fold_{k}_shap.npz (patient_id, genes = source columns, phi [patients, genes],
+base; F = base + phi.sum(1), exp(phi) a gene's hazard-ratio multiplier for that patient), fold_{k}_shap_importance.csv (index, column,
+gene, mean_abs_shap, mean_shap) and the pooled shap_importance.csv (gene, score = the mean |phi| over all out-of-fold patients, 0 for a
+gene never split on: gene_set_enrichment.py --scores reads it by its default column)."""
 import os
 import time
 
@@ -39,6 +44,7 @@ COLSAMPLE = env_float("MMS_GBM_COLSAMPLE", 1.0)
 BINS = env_int("MMS_GBM_BINS", 32)
 INNER = env_int("MMS_GBM_INNER", 5)
 SEED = env_int("MMS_GBM_SEED", 0)
+SHAP = env_int("MMS_GBM_SHAP", 0)
 
 
 def curve_columns(horizons):
@@ -65,9 +71,9 @@ def write_outputs(results, label, folds, horizons, out_dir=RESULTS_DIR, gene_nam
     """results: boosting.nested_cv's list (with `grid`: the grid points, added by main); label: [N, 2] (time, event) of the cohort.
     Writes every file of the module docstring -> the cv_results.json dict."""
     import pandas as pd
-    from multimodal_survival_prediction_amd import absolute_risk
+    from multimodal_survival_prediction_amd import absolute_risk, tree_shap
     os.makedirs(out_dir, exist_ok=True)
-    fold_results = []
+    fold_results, shap_folds = [], []
     for f, r in enumerate(results):
         fold = f + 1
         rows = np.asarray(r["val_rows"])
@@ -86,12 +92,16 @@ def write_outputs(results, label, folds, horizons, out_dir=RESULTS_DIR, gene_nam
         pd.DataFrame({"index": used, "column": src, "gene": [str(gene_names[int(j)]) if gene_names is not None else f"gene_{int(j)}" for j in src],
                       "splits": counts[used], "gain_sum": gain[used]}).to_csv(os.path.join(out_dir, f"fold_{fold}_importance.csv"), index=False)
         curves_frame(r).to_csv(os.path.join(out_dir, f"fold_{fold}_curves.csv"), index=False)
+        if "shap" in r:
+            shap_folds.append(tree_shap.write_fold(out_dir, fold, r["shap"], base["patient_id"], None if sel is None else sel.columns[f], gene_names))
         print(f"fold {fold} | grid point {r['grid_index']} {r['grid_point']['learning_rate']}/{r['grid_point']['max_depth']} | rounds {r['rounds']} | "
               f"Val C-index: {r['c_index']:.4f} | inner mean C-index: {r['inner_mean'][r['grid_index'], r['rounds'] - 1]:.4f}", flush=True)
         fold_results.append({"fold": fold, "best_c_index": float(r["c_index"]), "best_epoch": int(r["rounds"]), "train_size": int(len(folds[f][0])),
                              "val_size": int(len(folds[f][1])), "grid_index": int(r["grid_index"]),
                              "learning_rate": float(r["grid_point"]["learning_rate"]), "max_depth": int(r["grid_point"]["max_depth"]),
                              "inner_c_index": float(r["inner_mean"][r["grid_index"], r["rounds"] - 1]), "genes_split_on": int(len(used))})
+    if shap_folds:
+        tree_shap.write_pooled(out_dir, shap_folds, results[0]["booster"].p if sel is None else sel.n_genes, gene_names)
     c = [r["best_c_index"] for r in fold_results]
     cv = {"model": "Gradient-boosted Cox trees", "n_folds": len(results), "num_epochs": int(results[0]["inner"].shape[2]) if results else 0,
           "c_index_mean": float(np.mean(c)), "c_index_std": float(np.std(c)), "fold_results": fold_results,
@@ -114,7 +124,7 @@ def main():
     grid = boosting.default_grid(LR, DEPTH)
     t0 = time.perf_counter()
     res = boosting.nested_cv(cohort, folds, inner=INNER, rounds=ROUNDS, grid=grid, seed=SEED, min_leaf=MIN_LEAF, l2=L2, subsample=SUBSAMPLE,
-                             colsample=COLSAMPLE, bins=BINS)
+                             colsample=COLSAMPLE, bins=BINS, shap=SHAP > 0)
     dt = time.perf_counter() - t0
     for r in res:
         r["grid"] = grid

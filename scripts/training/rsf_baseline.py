@@ -17,7 +17,12 @@ fold_{k}_survival_curves.csv (the same columns and one S_<tau> column per horizo
 --compare-curves joins it) and fold_{k}_importance.csv (gene column, name, splits, summed chi2; the genes some tree split on).
 MMS_RSF_VIMP = R > 0 (default 0: nothing more is computed or written) adds the out-of-bag permutation importance with R repeats, one
 launch for all folds: fold_{k}_vimp.csv (index, column, gene, splits, chi2_sum, vimp = the drop in the fold's out-of-bag C-index when the
-gene is shuffled, vimp_sd over the repeats; the same genes, sorted by vimp) and "vimp_repeats" among the hyperparameters."""
+gene is shuffled, vimp_sd over the repeats; the same genes, sorted by vimp) and "vimp_repeats" among the hyperparameters.
+MMS_RSF_SHAP=1 (default 0: nothing more is computed or written) adds the TreeSHAP values (Forest.shap) of every fold's trees on that
+fold's VALIDATION patients: fold_{k}_shap.npz (patient_id, genes = source columns, phi [patients, genes], base; mortality = base +
+phi.sum(1)), fold_{k}_shap_importance.csv (index, column, gene, mean_abs_shap, mean_shap) and the pooled shap_importance.csv (gene, score =
+the mean |phi| over all out-of-fold patients, 0 for a gene never split on: gene_set_enrichment.py --scores reads it by its default
+column)."""
 import os
 import time
 
@@ -25,7 +30,7 @@ import numpy as np
 
 from _common import env_int, gene_hparams, save_json, select_genes, setup_device
 
-from multimodal_survival_prediction_amd import data, survival_forest
+from multimodal_survival_prediction_amd import data, survival_forest, tree_shap
 
 RESULTS_DIR = "results/rsf_baseline"
 N_FOLDS = env_int("MMS_FOLDS", 3)
@@ -37,6 +42,7 @@ MIN_LEAF = env_int("MMS_RSF_MIN_LEAF", 15)
 DEPTH = env_int("MMS_RSF_DEPTH", 10)
 SEED = env_int("MMS_RSF_SEED", 0)
 VIMP = env_int("MMS_RSF_VIMP", 0)
+SHAP = env_int("MMS_RSF_SHAP", 0)
 
 
 def curve_columns(horizons):
@@ -55,11 +61,11 @@ def main():
     sel = select_genes(cohort, [tr for tr, _ in folds], lambda name: os.path.join(RESULTS_DIR, f"best_model_fold{name}.pth"), rank=rank)
     t0 = time.perf_counter()
     res = survival_forest.cross_validate(cohort, folds, n_trees=TREES, mtry=MTRY or None, nsplit=NSPLIT, min_leaf=MIN_LEAF, max_depth=DEPTH,
-                                         seed=SEED, vimp=VIMP)
+                                         seed=SEED, vimp=VIMP, shap=SHAP > 0)
     dt = time.perf_counter() - t0
     names, ids = cohort.get("gene_names"), cohort.get("patient_id")
     label = cohort["label"].cpu().numpy()
-    fold_results = []
+    fold_results, shap_folds = [], []
     for f, r in enumerate(res):
         fold = f + 1
         rows = r["val_rows"]
@@ -81,11 +87,15 @@ def main():
             pd.DataFrame({"index": by, "column": col, "gene": [str(names[int(j)]) if names is not None else f"gene_{int(j)}" for j in col],
                           "splits": counts[by], "chi2_sum": chi2[by], "vimp": r["vimp"][by], "vimp_sd": r["vimp_reps"][:, by].std(0)}).to_csv(
                 os.path.join(RESULTS_DIR, f"fold_{fold}_vimp.csv"), index=False)
+        if "shap" in r:
+            shap_folds.append(tree_shap.write_fold(RESULTS_DIR, fold, r["shap"], base["patient_id"], None if sel is None else sel.columns[f], names))
         print(f"fold {fold} | trees {TREES} | Val C-index: {r['c_index']:.4f} | OOB C-index: {r['oob_c_index']:.4f} "
               f"({r['oob_missing']} training patients never out of bag)", flush=True)
         fold_results.append({"fold": fold, "best_c_index": float(r["c_index"]), "best_epoch": 0, "train_size": int(len(folds[f][0])),
                              "val_size": int(len(folds[f][1])), "oob_c_index": float(r["oob_c_index"]), "oob_missing": int(r["oob_missing"]),
                              "genes_split_on": int(len(used))})
+    if shap_folds:
+        tree_shap.write_pooled(RESULTS_DIR, shap_folds, res[0]["forest"].p if sel is None else sel.n_genes, names)
     c = [r["best_c_index"] for r in fold_results]
     hyper = res[0]["forest"].hyper if res else {}
     save_json(os.path.join(RESULTS_DIR, "cv_results.json"), {
